@@ -23,7 +23,12 @@ per GPU; rank 0 builds the proofs and ONE broadcast moves the proof block over R
     collective, so this IS the per-GPU rate of a W-GPU run.
 value = cells of all ranks / max-rank time.
 
-The CPU oracle (oracle/) is imported by the `cpu_baseline` leg only (rank 0, N = 1), never by the measured path.
+A plain run sets up, warms up, times `--steps` steps and prints the line: the headline figure and nothing that needs runs of its own.
+`--full` adds the other legs: per-kernel roofline figures from isolated launches (`--calib`), the one-proof latency, the Goldilocks-caps
+secondary, the eager boundary and its replay, the committed PMC traffic, and the CPU baselines.  `--dump-outputs DIR` writes what the
+last timed step computed to DIR/*.npy (float64) so that two builds can be compared output for output on the same seeded inputs.
+
+The CPU oracle (oracle/) is imported by the `cpu_baseline` leg only (`--full`, rank 0, N = 1), never by the measured path.
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -36,9 +41,6 @@ import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-# several launches are in flight on separate HIP streams (+ the library's side streams); ROCm maps streams onto 4 hardware queues
-# by default, which would serialise them pairwise.  Must be set before the HIP runtime initialises.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 CONFIGS = {
     # name: (degree_bits, num_queries, rate_bits, description)
@@ -131,6 +133,40 @@ def kernel_source_sha16():
     return h.hexdigest()[:16]
 
 
+DUMP_SAMPLE_CELLS = 1 << 19     # --dump-outputs: advice cells in the seeded sample (8 float64 limbs each: 32 MB)
+
+
+def dump_outputs(dirname, plan, adv, ws, n_proofs, blocks, stream):
+    """--dump-outputs: what one launch of the timed path hands its caller, as float64 arrays (every value exact) in dirname:
+    status.npy: the device status word of each proof;
+    advice_digest.npy: h2w_advice_digest of each of `blocks` equal blocks of the advice buffer (a proof each, unless sharded), its 4 u64 words as 8 u32 limbs;
+    advice_sample.npy: a fixed, seeded sample of the buffer's 32-byte cells, each as 8 u32 limbs (little-endian), at the indices in advice_sample_cells.npy."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    n = adv.numel() // 32
+    per = n // blocks
+    dig = torch.zeros(blocks * 4, dtype=torch.int64, device=adv.device)
+    for j in range(blocks):
+        plan.advice_digest(adv.data_ptr() + j * per * 32, per, dig.data_ptr() + j * 32, stream)
+    torch.cuda.synchronize()
+    idx = np.unique(np.random.default_rng(0xD0B5).integers(0, n, min(DUMP_SAMPLE_CELLS, n)))
+    cells = adv.view(torch.int32).view(n, 8)
+    chunk = 1 << 26      # cells per gather: the element indices inside one gather stay below 2^31
+    parts = []
+    for lo in range(0, n, chunk):
+        sel = idx[np.searchsorted(idx, lo):np.searchsorted(idx, lo + chunk)] - lo
+        if len(sel):
+            parts.append(cells[lo:lo + chunk].index_select(0, torch.from_numpy(sel).to(adv.device)).cpu())
+
+    def limbs(t):
+        return t.numpy().view(np.uint32).astype(np.float64)
+    np.save(os.path.join(dirname, "status.npy"), np.array(plan.status(ws.data_ptr(), n_proofs, stream), dtype=np.float64))
+    np.save(os.path.join(dirname, "advice_digest.npy"), limbs(dig.cpu()).reshape(blocks, 8))
+    np.save(os.path.join(dirname, "advice_sample.npy"), limbs(torch.cat(parts)).reshape(-1, 8))
+    np.save(os.path.join(dirname, "advice_sample_cells.npy"), idx.astype(np.float64))
+
+
 def _spawn_ranks(n):
     """`--gpus N` without a launcher: start N fresh rank processes (one per GPU) BEFORE anything touches the GPU here, relay rank 0's
     line, exit with the worst rank's code."""
@@ -184,13 +220,16 @@ def _main():
     ap.add_argument("--launches-per-step", type=int, default=24)
     ap.add_argument("--lookup-bits", type=int, default=21)
     ap.add_argument("--advice-cap-gb", type=float, default=262.0, help="upper bound on the advice buffers of all launches in flight (the stream count is reduced to fit)")
-    ap.add_argument("--calib", type=int, default=3, help="isolated launches after the timed region (one at a time, chain kernel on the caller's stream) for the per-kernel roofline numbers")
+    ap.add_argument("--calib", type=int, default=3, help="--full: isolated launches after the timed region (one at a time, chain kernel on the caller's stream) for the per-kernel roofline numbers")
     ap.add_argument("--proofs", default="valid", choices=["valid", "random"], help="synthetic inputs: valid FRI instances generated on the GPU by the ingest rank (h2w_prove_fri_batch, SURVEY 8d variant A) or uniform random words (variant B)")
     ap.add_argument("--shard-queries", action="store_true", help="N > 1: shard the (proof, query) units of the SAME proofs over the ranks (strong scaling; default for cfg5)")
     ap.add_argument("--layout", default="flat", choices=["flat", "columns"], help="columns: every kernel writes the FlexGate column layout directly (h2w_fri_witness_batch_columns, SURVEY 8f row 1)")
     ap.add_argument("--k", type=int, default=22, help="--layout columns: rows per column = 2^k")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the legs beside the primary metric (one-proof latency, Goldilocks-caps secondary, eager boundary)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the legs beside the primary metric (one-proof latency, Goldilocks-caps secondary, eager boundary)")
+    ap.add_argument("--full", action="store_true", help="also run the legs beside the headline figure (per-kernel roofline, latency, secondary, eager and replay, CPU baselines); "
+                                                        "a plain run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last step computed to DIR/*.npy (float64; see dump_outputs)")
     ap.add_argument("--compact", action="store_true", help="--shard-queries: every rank writes a packed buffer of its own blocks (h2w_fri_witness_batch_shard_compact; the default there)")
     ap.add_argument("--flat-shards", action="store_true", help="--shard-queries: every rank keeps a full-size advice buffer and writes its blocks at their global offsets")
     ap.add_argument("--no-fork", action="store_true", help="experiment: PoseidonBN254 chain kernels on the caller's stream (H2W_OPT_FORK_CHAINS = 0)")
@@ -202,6 +241,10 @@ def _main():
     ap.add_argument("--world", type=int, default=0, help="--emulate-rank: the world being emulated (default 8)")
     ap.add_argument("--gen-budget-s", type=float, default=300.0, help="rank 0 stops generating valid proofs after this many seconds and repeats the ones it has (the other ranks wait in the broadcast)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:       # a plain run: the headline figure only
+        args.calib = 0; args.no_extras = args.no_cpu_baseline = True
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return _spawn_ranks(args.gpus)          # (nothing has touched the GPU yet)
 
@@ -326,7 +369,8 @@ def _main():
         my_proofs = all_proofs[lo * words:hi * words]
 
     adv_bytes = plan.shard_cells(B, sh_rank, sh_world) * 32 if (shard_queries and args.compact) else B * cell_bytes
-    advices = [torch.empty(adv_bytes, dtype=torch.uint8, device=dev) for _ in range(S)]
+    # (zeroed for --dump-outputs: cells a mode leaves unwritten, such as other ranks' blocks, are then the same in every run)
+    advices = [(torch.zeros if args.dump_outputs else torch.empty)(adv_bytes, dtype=torch.uint8, device=dev) for _ in range(S)]
     wss = [torch.empty(plan.shard_workspace_bytes(B, sh_rank, sh_world) if shard_queries else plan.workspace_bytes(B), dtype=torch.uint8, device=dev) for _ in range(S)]
     streams = [torch.cuda.Stream(device=dev) for _ in range(S)]
     torch.cuda.synchronize()
@@ -365,6 +409,9 @@ def _main():
     for i in range(S):
         status = plan.status(wss[i].data_ptr(), B, streams[i].cuda_stream)
         assert status == [0] * B, f"device status {status}"
+    if args.dump_outputs and rank == 0:       # every launch of a step runs on the same proofs: the buffers of the step's last launch
+        last = (counter[0] - 1) % S
+        dump_outputs(args.dump_outputs, plan, advices[last], wss[last], B, 1 if shard_queries else B, streams[last].cuda_stream)
 
     # per-kernel timing from the HIP events the library records on the streams it launches on
     # (a) over the timed region (launches overlap each other there, so these intervals include time-sharing);
@@ -607,8 +654,8 @@ def _main():
         # counts a wide streaming read at half its bytes, MI355X_MICROARCH.md) are a committed file - used only for the workload they were taken on
         traffic, traffic_src, valu = None, None, None
         pmc_file = os.path.join(ROOT, "profiles", "r04_pmc_cfg3_bn254_b64.json")
-        src_sha = kernel_source_sha16()
         if isol and args.config == "cfg3" and hash_mode == 1 and B == 64 and world == 1 and not shard_queries and bps is None and args.lookup_bits == 21:
+            src_sha = kernel_source_sha16()
             if not os.path.exists(pmc_file):
                 traffic_src = {"file": None, "why_null": "no committed PMC pass for this workload"}
             else:
