@@ -26,9 +26,7 @@
 namespace h2w {
 
 
-struct PlanSink {
-    static constexpr bool kCoop = false, kSplitOnly = false, kBnUnits = false, kDevSponge = false; static constexpr int kHashMode = -1;
-    void coop_poseidon_permute(uint64_t *, const h2w_poseidon_consts_t *) {}
+struct PlanSink : SinkBase {
     std::vector<uint64_t> *meta; const TemplateTable *tt; StrandTable *st;
     uint64_t nrec = 0, cell_off = 0, cur_q_rec = 0, cur_q_cell = 0, mk_rec0 = 0, mk_cell0 = 0; bool mk_zc = false;
     std::vector<uint64_t> *unit_cell = nullptr; uint64_t nunit = 0, cur_q_unit = 0, mk_unit0 = 0; bool pu_zc = false;
@@ -36,8 +34,6 @@ struct PlanSink {
     std::vector<LoadItem> *items = nullptr, *cap_items = nullptr;
     void note_load(uint64_t w, int kind) { LoadItem it; it.word = (uint32_t)w; it.kind = (uint32_t)kind; it.rec = nrec; it.cell = cell_off; items->push_back(it); }
     void note_cap_hash(uint64_t w) { if (cap_items) { LoadItem it; it.word = (uint32_t)w; it.kind = 4; it.rec = nrec; it.cell = cell_off; cap_items->push_back(it); } }
-    bool coop_load_proof(const ValCfg &) { return false; }
-    bool bn_emit_inline(fr_t *, const ValCfg &, bool &) { return false; }
     void bn_perm_begin(bool zc) { unit_cell->push_back(cell_off); pu_zc = zc; }
     void bn_perm_end(bool zc) { if (!pu_zc && zc) st->first_zero_unit = (int64_t)nunit; nunit++; }
     void glp_note() { nglp++; }
@@ -169,8 +165,7 @@ template <bool COLS> __global__ __launch_bounds__(QUAD_BLOCK) H2W_QUAD_ATTR void
     unsigned idx = (blockIdx.x * QUAD_BLOCK + threadIdx.x) >> 2;
     if (idx >= total) idx = total - 1;
     int p, q; own_unit_at(A, idx, p, q);
-    const int n_or = A.shape.n_perm_z > 0 ? 3 : 2;
-    const int slot = blockIdx.y, kind = slot < n_or ? slot : 3 + (slot - n_or);
+    const int kind = merkle_kind(A.shape.n_perm_z, blockIdx.y);
     Sink sink;
     quad_strand<QuadB>(A, sink, idx, p, q, kind);
 }
@@ -250,10 +245,9 @@ h2w_plan *h2w_plan_compile(const h2w_shape_t *shape, const h2w_poseidon_consts_t
         if (s.hash_mode == 1) pl->st.q_nglp = 0;
         if ((uint64_t)pl->st.pro_nglp + (uint64_t)s.num_queries * pl->st.q_nglp != sink.nglp) { set_error("h2w_plan_compile: internal: permutation list layout"); delete pl; return nullptr; }
         uint32_t it = 0;
-        for (int k2 = 0; k2 < MK_KINDS; k2++) {
+        for (int k2 = 0, slot = 0; k2 < MK_KINDS; k2++) {      // (kinds a shape does not have own no items)
             pl->st.mk_item0[k2] = it;
-            const bool exists = k2 < 3 ? k2 < pl->d.n_oracles : k2 - 3 < pl->d.n_steps;
-            if (exists) it += pl->st.mk_nunit[k2] ? pl->st.mk_nunit[k2] : 1;
+            if (slot < pl->d.n_oracles + pl->d.n_steps && merkle_kind(s.n_perm_z, slot) == k2) { it += pl->st.mk_nunit[k2] ? pl->st.mk_nunit[k2] : 1; slot++; }
         }
         pl->st.mk_item0[MK_KINDS] = it;
         pl->small_mds = glp_small_mds(*consts);
@@ -347,7 +341,6 @@ uint64_t h2w_plan_num_chain_cells(const h2w_plan *p) {      // cells of the Merk
     for (int k = 0; k < MK_KINDS; k++) n += p->st.mk_ncell[0][k] + (uint64_t)(p->shape.num_queries - 1) * p->st.mk_ncell[1][k];
     return n;
 }
-struct ShardSpec { int rank = 0, world = 1, compact = 0; };
 static uint64_t own_count(uint64_t total, int rank, int world) { return total > (uint64_t)rank ? (total - (uint64_t)rank + (uint64_t)world - 1) / (uint64_t)world : 0; }
 static uint32_t unit_slot_of(const h2w_plan *p) { return (uint32_t)(p->st.q_nunit[0] > p->st.q_nunit[1] ? p->st.q_nunit[0] : p->st.q_nunit[1]); }
 // Per-proof pieces first (their offsets do not depend on the sharding: h2w_plan_status finds the status words whatever call filled them), then the
@@ -462,6 +455,19 @@ static void fill_expand_shard(const h2w_plan *p, ExpandArgs &E, const ShardSpec 
     if (p->shape.num_queries == 1) E.q_rec0_rest = ~0ull;
     E.pro_ncell = p->st.pro_ncell; E.q_cell0_first = p->st.q_cell0[0]; E.q_cell0_rest = p->st.q_cell0[1]; E.q_ncell_rest = p->st.q_ncell[1]; E.q_slot = shard_q_slot(p);
 }
+}  // extern "C"
+int h2w::launch_plan_expand(const h2w_plan *p, uint64_t n_proofs, const rec_t *recs, uint32_t *tile_ctr, fr_t *out, uint64_t cell_stride, ColMap cm,
+                            const ShardSpec *sh, uint32_t roam_per_cu, hipStream_t stream) {
+    ExpandArgs E;
+    E.meta = p->d_meta; E.recs = recs; E.nrec = p->nrec; E.rec_stride = p->nrec; E.out = out; E.cell_stride = cell_stride; E.pool = nullptr; E.cm = cm;
+    if (sh) fill_expand_shard(p, E, *sh); else expand_unsharded(E);
+    p->dt.fill(E);
+    E.tile_ctr = tile_ctr; E.roam_per_cu = roam_per_cu;
+    H2W_HIP(hipMemsetAsync(tile_ctr, 0, n_proofs * sizeof(uint32_t), stream));
+    int gx = (int)(2048 / (n_proofs < 2048 ? n_proofs : 2048)); if (gx < 8) gx = 8;
+    return launch_expand(E, n_proofs, gx, stream);
+}
+extern "C" {
 static int run_batch(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void *advice_dev, void *workspace_dev, void *stream_, void *emit_stream_, ColMap cm, uint64_t cell_stride, ShardSpec sh) {
     if (!p) { set_error("h2w_fri_witness_batch: null plan"); return -1; }
     if (p->device < 0) { set_error("h2w_fri_witness_batch: no HIP device — the hot path only runs on the GPU (no CPU fallback)"); return -1; }
@@ -503,11 +509,11 @@ static int run_batch(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs,
     const unsigned nkinds = (unsigned)(p->d.n_oracles + p->d.n_steps);
     bool forked = false;
     auto body = [&]() -> int {
-        H2W_HIP(hipEventRecord(ev[0], stream));
+        H2W_HIP(hipEventRecord(ev[H2W_EV_CALL_START], stream));
         // 1. prologue strands, values: one wavefront per proof (witness load, Fiat-Shamir sponge, PoW, reduced openings) -> challenge blocks.  FIRST: everything
         //    else of the launch waits for the challenges, nothing for the load cells
         launch_prologue_values(A, stream);
-        H2W_HIP(hipEventRecord(ev[9], stream));
+        H2W_HIP(hipEventRecord(ev[h2w_plan::EV_PROLOGUE_VALUES_END], stream));
         // 0. witness load + cap-hash limb decompositions: one lane per (proof, item).  Cells and a flag word only (nobody's input): behind the prologue, beside the
         //    Merkle chains that fork off at this point
         H2W_HIP(hipMemsetAsync(A.load_flag, 0, n_proofs * sizeof(uint32_t), stream));
@@ -519,19 +525,19 @@ static int run_batch(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs,
         //    together with the Merkle strands' (below)
         const unsigned n_pro_perms = A.sh.n_own_proofs * p->st.pro_nglp, n_mk_perms = nunits * p->st.q_nglp;
         auto glp_emit = [&](unsigned n) -> int {
-            H2W_HIP(hipEventRecord(ev[11], stream));
+            H2W_HIP(hipEventRecord(ev[h2w_plan::EV_GLP_START], stream));
             if (n) { if (cm.starts) hipLaunchKernelGGL(k_glp_emit<true>, dim3(n), dim3(64), 0, stream, A); else hipLaunchKernelGGL(k_glp_emit<false>, dim3(n), dim3(64), 0, stream, A); }
-            H2W_HIP(hipEventRecord(ev[12], stream));
+            H2W_HIP(hipEventRecord(ev[h2w_plan::EV_GLP_END], stream));
             return 0;
         };
         if (p->shape.hash_mode == 1) { if (glp_emit(n_pro_perms) != 0) return -1; }
-        H2W_HIP(hipEventRecord(ev[1], stream));
+        H2W_HIP(hipEventRecord(ev[H2W_EV_PROLOGUE_END], stream));
         // 3. PoseidonBN254 Merkle chains (hash_mode 1): values, then one quad per permutation unit.  They write their cells themselves and no
         //    block records, so nothing but the challenge blocks orders them against the other kernels of the batch: they run on a side
         //    stream of the plan and rejoin at the end of the call.
         if (p->shape.hash_mode == 1) {
-            if (cstream != stream) { H2W_HIP(hipStreamWaitEvent(cstream, ev[9], 0)); forked = true; }
-            H2W_HIP(hipEventRecord(ev[4], cstream));
+            if (cstream != stream) { H2W_HIP(hipStreamWaitEvent(cstream, ev[h2w_plan::EV_PROLOGUE_VALUES_END], 0)); forked = true; }
+            H2W_HIP(hipEventRecord(ev[H2W_EV_CHAINS_START], cstream));
             const dim3 sgrid((nunits * 4 + QUAD_BLOCK - 1) / QUAD_BLOCK, nkinds);
             // one pass or two (include/h2w.h H2W_OPT_CHAIN_PASSES): a launch whose paths do not fill the chip is bound by the depth of a path - split it
             const int passes = p->chain_passes ? p->chain_passes : (nunits <= 512 ? 2 : 1);
@@ -553,52 +559,45 @@ static int run_batch(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs,
                     if (nval) hipLaunchKernelGGL(k_sbox_canon, dim3((unsigned)((nval + 255) / 256)), dim3(256), 0, cstream, A, upq);
                 }
             }
-            H2W_HIP(hipEventRecord(ev[10], cstream));
+            H2W_HIP(hipEventRecord(ev[h2w_plan::EV_CHAIN_VALUES_END], cstream));
             const unsigned long long items = passes == 1 ? 0ull : (unsigned long long)((nunits + 15u) & ~15u) * p->st.mk_item0[MK_KINDS];
             if (items) {
                 const dim3 egrid((unsigned)((items * 4 + QUAD_BLOCK - 1) / QUAD_BLOCK));
                 launch_merkle_bn_emit(A, egrid, cstream);
             }
-            H2W_HIP(hipEventRecord(ev[5], cstream));
+            H2W_HIP(hipEventRecord(ev[H2W_EV_CHAINS_END], cstream));
         }
         // 4. query glue strands (FriChip::verify_query_round minus its Merkle proofs): one lane per owned (proof, query);
         //    Goldilocks-Poseidon Merkle strands (hash_mode 0), values: one cooperating wavefront per (proof, query, tree)
         //    The two read the challenge blocks and write disjoint records (and list entries): with Goldilocks caps the Merkle strands run on the
         //    plan's side stream beside the glue strands and rejoin before the permutations' records are emitted.
-        H2W_HIP(hipEventRecord(ev[7], stream));
+        H2W_HIP(hipEventRecord(ev[H2W_EV_GLUE_START], stream));
         if (p->shape.hash_mode == 0) {
-            if (cstream != stream) { H2W_HIP(hipStreamWaitEvent(cstream, ev[9], 0)); forked = true; }
-            H2W_HIP(hipEventRecord(ev[4], cstream));
+            if (cstream != stream) { H2W_HIP(hipStreamWaitEvent(cstream, ev[h2w_plan::EV_PROLOGUE_VALUES_END], 0)); forked = true; }
+            H2W_HIP(hipEventRecord(ev[H2W_EV_CHAINS_START], cstream));
             if (nunits) launch_merkle_gl_values(A, nunits, nkinds, cstream);
-            H2W_HIP(hipEventRecord(ev[10], cstream)); H2W_HIP(hipEventRecord(ev[5], cstream));
+            H2W_HIP(hipEventRecord(ev[h2w_plan::EV_CHAIN_VALUES_END], cstream)); H2W_HIP(hipEventRecord(ev[H2W_EV_CHAINS_END], cstream));
         }
         if (nunits) launch_glue_strands(A, stream);
         if (p->shape.hash_mode == 0) {
-            if (forked) { H2W_HIP(hipStreamWaitEvent(stream, ev[5], 0)); forked = false; }
+            if (forked) { H2W_HIP(hipStreamWaitEvent(stream, ev[H2W_EV_CHAINS_END], 0)); forked = false; }
             if (glp_emit(n_pro_perms + n_mk_perms) != 0) return -1;
         }
-        H2W_HIP(hipEventRecord(ev[2], stream));
+        H2W_HIP(hipEventRecord(ev[H2W_EV_GLUE_END], stream));
         // 5. expansion of the block records (HBM-write-bound)
-        ExpandArgs E;
-        E.meta = p->d_meta; E.recs = A.recs; E.nrec = p->nrec; E.rec_stride = p->nrec; E.out = A.out; E.cell_stride = cell_stride; E.pool = nullptr; E.cm = cm;
-        fill_expand_shard(p, E, sh);
-        p->dt.fill(E);
-        E.tile_ctr = (uint32_t *)(ws + wl.ctr);
-        E.roam_per_cu = p->shape.hash_mode == 0 ? 2 : 1;      // (profiles/r02_expand_grid.txt)
-        int gx = (int)(2048 / (n_proofs < 2048 ? n_proofs : 2048)); if (gx < 8) gx = 8;
-        if (estream != stream) H2W_HIP(hipStreamWaitEvent(estream, ev[2], 0));    // value strands done -> expansion on the emit stream
-        H2W_HIP(hipMemsetAsync(E.tile_ctr, 0, n_proofs * sizeof(uint32_t), estream));
+        if (estream != stream) H2W_HIP(hipStreamWaitEvent(estream, ev[H2W_EV_GLUE_END], 0));    // value strands done -> expansion on the emit stream
         // One expansion kernel at a time over all the streams a plan is driven on: its blocks are persistent and hold their CUs until the
         // launch is written, so two of them side by side keep the latency-bound strands of the other launches in flight off the chip
         // (measured: +8..12 % for the whole job with PoseidonBN254 caps, profiles/r02_sweep5.txt; +5 % with Goldilocks caps since that kernel
         // runs on a grid of resident blocks there and reaches its rate alone, profiles/r02_expand_grid.txt).
-        if (p->serial_expand != 0 && prev_ev) H2W_HIP(hipStreamWaitEvent(estream, prev_ev[3], 0));
-        H2W_HIP(hipEventRecord(ev[8], estream));
-        if (launch_expand(E, n_proofs, gx, estream) != 0) return -1;
-        H2W_HIP(hipEventRecord(ev[3], estream));
-        if (estream != stream) H2W_HIP(hipStreamWaitEvent(stream, ev[3], 0));    // the caller's stream completes when the advice is complete
-        if (forked) { H2W_HIP(hipStreamWaitEvent(stream, ev[5], 0)); forked = false; }
-        H2W_HIP(hipEventRecord(ev[6], stream));
+        if (p->serial_expand != 0 && prev_ev) H2W_HIP(hipStreamWaitEvent(estream, prev_ev[H2W_EV_EXPAND_END], 0));
+        H2W_HIP(hipEventRecord(ev[H2W_EV_EXPAND_START], estream));
+        if (launch_plan_expand(p, n_proofs, A.recs, (uint32_t *)(ws + wl.ctr), A.out, cell_stride, cm, &sh,
+                               p->shape.hash_mode == 0 ? 2 : 1, estream) != 0) return -1;      // roam_per_cu: profiles/r02_expand_grid.txt
+        H2W_HIP(hipEventRecord(ev[H2W_EV_EXPAND_END], estream));
+        if (estream != stream) H2W_HIP(hipStreamWaitEvent(stream, ev[H2W_EV_EXPAND_END], 0));    // the caller's stream completes when the advice is complete
+        if (forked) { H2W_HIP(hipStreamWaitEvent(stream, ev[H2W_EV_CHAINS_END], 0)); forked = false; }
+        H2W_HIP(hipEventRecord(ev[H2W_EV_CALL_END], stream));
         H2W_HIP(hipGetLastError());
         return 0;
     };
@@ -622,16 +621,9 @@ int h2w_fri_expand_records(h2w_plan *p, uint64_t n_proofs, void *advice_dev, voi
     hipStream_t stream = (hipStream_t)stream_;
     const WsLayout wl = ws_layout(p, n_proofs);
     char *ws = (char *)workspace_dev;
-    ExpandArgs E;
-    E.meta = p->d_meta; E.recs = (rec_t *)(ws + wl.recs); E.nrec = p->nrec; E.rec_stride = p->nrec; E.out = (fr_t *)advice_dev; E.cell_stride = p->ncells; E.pool = nullptr;
-    E.cm = ColMap{nullptr, 0, 0};
-    fill_expand_shard(p, E, ShardSpec());
-    p->dt.fill(E);
-    E.tile_ctr = (uint32_t *)(ws + wl.ctr);
-    E.roam_per_cu = p->shape.hash_mode == 0 ? 2 : 1;      // (profiles/r02_expand_grid.txt)
-    H2W_HIP(hipMemsetAsync(E.tile_ctr, 0, n_proofs * sizeof(uint32_t), stream));
-    int gx = (int)(2048 / (n_proofs < 2048 ? n_proofs : 2048)); if (gx < 8) gx = 8;
-    if (launch_expand(E, n_proofs, gx, stream) != 0) return -1;
+    const ShardSpec one_rank{};
+    if (launch_plan_expand(p, n_proofs, (rec_t *)(ws + wl.recs), (uint32_t *)(ws + wl.ctr), (fr_t *)advice_dev, p->ncells, ColMap{nullptr, 0, 0}, &one_rank,
+                           p->shape.hash_mode == 0 ? 2 : 1, stream) != 0) return -1;      // (as run_batch)
     H2W_HIP(hipGetLastError());
     return 0;
 }
@@ -896,36 +888,35 @@ int h2w_plan_timing(h2w_plan *p, uint64_t back, float ms[5]) {   // `back` batch
     if (!p || !p->ev_recorded || back >= p->n_batches || back >= (uint64_t)h2w_plan::EV_RING) { set_error("h2w_plan_timing: no such batch"); return -1; }
     hipEvent_t *ev = p->evr[(p->n_batches - 1 - back) % h2w_plan::EV_RING];
     DeviceGuard dg(p->device);
-    H2W_HIP(hipEventSynchronize(ev[6]));
-    H2W_HIP(hipEventElapsedTime(&ms[0], ev[0], ev[1]));   // prologue strands: values (+ with PoseidonBN254 caps: their permutations' records)
-    H2W_HIP(hipEventElapsedTime(&ms[1], ev[7], ev[2]));   // query glue strands (+ Goldilocks caps: Merkle strands, values, and every listed permutation's records)
-    H2W_HIP(hipEventElapsedTime(&ms[2], ev[4], ev[5]));   // PoseidonBN254 Merkle chains: values + emission (on their side stream; 0 for Goldilocks-Poseidon Merkle)
-    H2W_HIP(hipEventElapsedTime(&ms[3], ev[8], ev[3]));   // expansion kernel
-    H2W_HIP(hipEventElapsedTime(&ms[4], ev[0], ev[6]));   // whole call
+    H2W_HIP(hipEventSynchronize(ev[H2W_EV_CALL_END]));
+    H2W_HIP(hipEventElapsedTime(&ms[0], ev[H2W_EV_CALL_START], ev[H2W_EV_PROLOGUE_END]));   // prologue strands: values (+ with PoseidonBN254 caps: their permutations' records)
+    H2W_HIP(hipEventElapsedTime(&ms[1], ev[H2W_EV_GLUE_START], ev[H2W_EV_GLUE_END]));   // query glue strands (+ Goldilocks caps: Merkle strands, values, and every listed permutation's records)
+    H2W_HIP(hipEventElapsedTime(&ms[2], ev[H2W_EV_CHAINS_START], ev[H2W_EV_CHAINS_END]));   // PoseidonBN254 Merkle chains: values + emission (on their side stream; 0 for Goldilocks-Poseidon Merkle)
+    H2W_HIP(hipEventElapsedTime(&ms[3], ev[H2W_EV_EXPAND_START], ev[H2W_EV_EXPAND_END]));   // expansion kernel
+    H2W_HIP(hipEventElapsedTime(&ms[4], ev[H2W_EV_CALL_START], ev[H2W_EV_CALL_END]));   // whole call
     return 0;
 }
 int h2w_plan_timing_ex(h2w_plan *p, uint64_t back, float ms[8]) {
     if (!p || !p->ev_recorded || back >= p->n_batches || back >= (uint64_t)h2w_plan::EV_RING) { set_error("h2w_plan_timing_ex: no such batch"); return -1; }
     hipEvent_t *ev = p->evr[(p->n_batches - 1 - back) % h2w_plan::EV_RING];
     DeviceGuard dg(p->device);
-    H2W_HIP(hipEventSynchronize(ev[6]));
-    H2W_HIP(hipEventElapsedTime(&ms[0], ev[0], ev[9]));    // k_prologue_values
-    H2W_HIP(hipEventElapsedTime(&ms[1], ev[11], ev[12]));  // k_glp_emit
-    H2W_HIP(hipEventElapsedTime(&ms[2], ev[7], p->shape.hash_mode == 0 ? ev[11] : ev[2]));   // k_strands (+ k_merkle_gl_values)
-    H2W_HIP(hipEventElapsedTime(&ms[3], ev[4], ev[10]));   // k_merkle_bn_values
-    H2W_HIP(hipEventElapsedTime(&ms[4], ev[10], ev[5]));   // k_merkle_bn_emit
-    H2W_HIP(hipEventElapsedTime(&ms[5], ev[8], ev[3]));    // expansion kernel
-    H2W_HIP(hipEventElapsedTime(&ms[6], ev[0], ev[6]));    // whole call
+    H2W_HIP(hipEventSynchronize(ev[H2W_EV_CALL_END]));
+    H2W_HIP(hipEventElapsedTime(&ms[0], ev[H2W_EV_CALL_START], ev[h2w_plan::EV_PROLOGUE_VALUES_END]));    // k_prologue_values
+    H2W_HIP(hipEventElapsedTime(&ms[1], ev[h2w_plan::EV_GLP_START], ev[h2w_plan::EV_GLP_END]));  // k_glp_emit
+    H2W_HIP(hipEventElapsedTime(&ms[2], ev[H2W_EV_GLUE_START], p->shape.hash_mode == 0 ? ev[h2w_plan::EV_GLP_START] : ev[H2W_EV_GLUE_END]));   // k_strands (+ k_merkle_gl_values)
+    H2W_HIP(hipEventElapsedTime(&ms[3], ev[H2W_EV_CHAINS_START], ev[h2w_plan::EV_CHAIN_VALUES_END]));   // k_merkle_bn_values
+    H2W_HIP(hipEventElapsedTime(&ms[4], ev[h2w_plan::EV_CHAIN_VALUES_END], ev[H2W_EV_CHAINS_END]));   // k_merkle_bn_emit
+    H2W_HIP(hipEventElapsedTime(&ms[5], ev[H2W_EV_EXPAND_START], ev[H2W_EV_EXPAND_END]));    // expansion kernel
+    H2W_HIP(hipEventElapsedTime(&ms[6], ev[H2W_EV_CALL_START], ev[H2W_EV_CALL_END]));    // whole call
     ms[7] = p->shape.hash_mode == 1 ? (float)p->passes_of[(p->n_batches - 1 - back) % h2w_plan::EV_RING] : 0.f;
     return 0;
 }
 int h2w_plan_last_timing(h2w_plan *p, float ms[5]) { return h2w_plan_timing(p, 0, ms); }
 int h2w_plan_event_gap(h2w_plan *p, uint64_t back_a, int which_a, uint64_t back_b, int which_b, float *ms) {
-    static const int idx[H2W_EV_COUNT] = {0, 1, 7, 2, 4, 5, 8, 3, 6};
     if (!p || !ms || !p->ev_recorded || back_a >= p->n_batches || back_b >= p->n_batches || back_a >= (uint64_t)h2w_plan::EV_RING || back_b >= (uint64_t)h2w_plan::EV_RING ||
         which_a < 0 || which_a >= H2W_EV_COUNT || which_b < 0 || which_b >= H2W_EV_COUNT) { set_error("h2w_plan_event_gap: no such batch / event"); return -1; }
     if (p->shape.hash_mode == 0 && (which_a == H2W_EV_CHAINS_START || which_a == H2W_EV_CHAINS_END || which_b == H2W_EV_CHAINS_START || which_b == H2W_EV_CHAINS_END)) { set_error("h2w_plan_event_gap: no chain kernel with Goldilocks-Poseidon caps"); return -1; }
-    hipEvent_t a = p->evr[(p->n_batches - 1 - back_a) % h2w_plan::EV_RING][idx[which_a]], b = p->evr[(p->n_batches - 1 - back_b) % h2w_plan::EV_RING][idx[which_b]];
+    hipEvent_t a = p->evr[(p->n_batches - 1 - back_a) % h2w_plan::EV_RING][which_a], b = p->evr[(p->n_batches - 1 - back_b) % h2w_plan::EV_RING][which_b];
     DeviceGuard dg(p->device);
     H2W_HIP(hipEventSynchronize(a)); H2W_HIP(hipEventSynchronize(b));
     H2W_HIP(hipEventElapsedTime(ms, a, b));

@@ -98,11 +98,7 @@ template <class QuadB, class Sink> __device__ __forceinline__ void quad_strand(c
     QuadB be(sink, mc, !(q == 0 && kind == A.st->first_zero_kind));
     const h2w_shape_t shp = A.shape;      // (a reference into the kernel arguments would put all of them on every lane's stack)
     Verifier<QuadB> V(be, shp, A.consts);
-    const uint64_t x = A.cbs[p].fri_query_indices[q];
-    const int lde = V.d.lde_bits; int lo = 0;
-    if (kind >= 3) for (int i = 0; i <= kind - 3; i++) lo += V.d.arity[i];
-    const uint64_t cap_index = (x >> (lde - A.shape.cap_height)) & ((1ull << A.shape.cap_height) - 1);
-    V.merkle_strand(q, kind, PackedBits{x, lo}, lde - lo, cap_index);
+    V.merkle_strand_at(q, kind, A.cbs[p].fri_query_indices[q]);
     if ((threadIdx.x & 3) == 0 && be.status) atomicCAS(&A.status[p], 0u, be.status);
 }
 void launch_glue_strands(const BatchArgs &A, hipStream_t stream);      // glue.hip

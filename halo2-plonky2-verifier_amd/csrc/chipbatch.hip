@@ -12,13 +12,10 @@
 
 namespace h2w {
 
-struct CountSink {       // host: lays out the instance (record metas, cell count)
-    static constexpr bool kCoop = false, kSplitOnly = false, kBnUnits = false, kDevSponge = false; static constexpr int kHashMode = -1;
+struct CountSink : SinkBase {       // host: lays out the instance (record metas, cell count)
     const TemplateTable *tt; std::vector<uint64_t> meta; uint64_t cell_off = 0;
     void rec(int t, uint64_t, uint64_t, uint64_t, uint64_t) { meta.push_back(meta_pack((uint32_t)t, cell_off)); cell_off += (uint64_t)tt->ncells(t); }
     void cell(const fr_t &) { cell_off++; }
-    void gate() {}
-    void lookup() {}
 };
 
 // operands: GL ops take 2 (add, sub, mul, div), 3 (mul_add) or 1 (inv) words; extension ops 2 words per element

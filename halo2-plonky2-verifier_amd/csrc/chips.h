@@ -1,9 +1,10 @@
 // chips.h — the verifier gadget stack (layers L2-L5 of the reference), written once and instantiated over a
 // backend `B` that stands in for NativeChip / halo2-base:
 //
-//   * ValBackend<DevSink>  (device)  — computes Goldilocks / Fr values natively and emits block records + direct cells
-//   * ValBackend<PlanSink> (host)    — same code with a counting sink: the shape compiler (cell layout, record metas)
-//   * AbiBackend           (host)    — drives the eager C-ABI of include/h2w.h (the drop-in boundary itself)
+//   * ValBackend<Sink>     (device and host) — computes Goldilocks / Fr values natively and hands block records + direct cells to a sink:
+//                                              device memory (DevSink, the strand kernels' sinks) or the shape compiler's counting PlanSink
+//                                              (the sinks, their flags and hooks: valbackend.h SinkBase)
+//   * AbiBackend           (host)            — drives the eager C-ABI of include/h2w.h (the drop-in boundary itself)
 //
 // Each class mirrors one reference chip: names, argument meaning and call order follow the Rust source so the
 // advice stream is cell-for-cell the reference's.  File:line citations are to /root/reference/verifier/src.

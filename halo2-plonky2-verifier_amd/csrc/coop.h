@@ -90,8 +90,8 @@ namespace h2w {
 constexpr int GLP_LIST_WORDS = 1 + SPONGE_WIDTH;            // one listed permutation: {index of its first record, input state}
 
 // VALPH: the values phase of a strand (see the top of the file); false: the record-emitting permutation (k_glp_emit)
-template <bool COLS, bool VALPH = false, int HASH_MODE = -1> struct CoopSinkT {
-    static constexpr bool kCoop = true, kSplitOnly = false, kBnUnits = false, kDevSponge = VALPH; static constexpr int kHashMode = HASH_MODE;
+template <bool COLS, bool VALPH = false, int HASH_MODE = -1> struct CoopSinkT : SinkBase {
+    static constexpr bool kCoop = true, kDevSponge = VALPH; static constexpr int kHashMode = HASH_MODE;
     rec_t *recs; uint64_t nrec; fr_t *out; uint64_t cell_off; const uint16_t *ncells; int lane; ColPolicy<COLS> cc;
     lds64_t *lk = nullptr, *la = nullptr, *lb = nullptr, *lm = nullptr, *lx = nullptr;      // s_glp_k, s_glp_a, s_glp_b, s_glp_m (s_glp_x: values phase) of the running kernel (set by bind_lds)
     uint64_t *glp = nullptr; uint32_t glp_slot = 0; bool small_mds = false;   // values phase: this proof's permutation list, the next slot of this strand
@@ -102,28 +102,13 @@ template <bool COLS, bool VALPH = false, int HASH_MODE = -1> struct CoopSinkT {
         nrec++; cell_off += ncells[t];
     }
     __device__ __forceinline__ void cell(const fr_t &v) { if (lane == 0 && emit) g_store_fr(out + cc.map(cell_off), v); cell_off++; }
-    __device__ __forceinline__ void gate() {}
-    __device__ __forceinline__ void lookup() {}
     __device__ __forceinline__ void skip(uint64_t nr, uint64_t nc) { nrec += nr; cell_off += nc; }
-    __device__ void merkle_begin(int, int, bool, uint64_t) {}
-    __device__ void merkle_end(int, int, bool) {}
-    __device__ void query_begin(int, uint64_t) {}
-    __device__ void query_end(int, uint64_t) {}
-    __device__ void bn_perm_begin(bool) {}
-    __device__ void bn_perm_end(bool) {}
-    __device__ void glp_note() {}
-    __device__ void note_load(uint64_t, int) {}
-    __device__ bool bn_emit_inline(fr_t *, const ValCfg &, bool &) { return false; }
-    __device__ void note_cap_hash(uint64_t) {}
     // WitnessChip::load_proof_with_pis (witness/mod.rs:267-294) and the limb decompositions of the caps' BN254 hashes are k_prologue_load's
     // (every item is independent: one lane each); the strand only steps over their records and cells
     __device__ __forceinline__ bool coop_load_proof(const ValCfg &cfg) { nrec += cfg.load_nrec; cell_off += cfg.load_ncell; return true; }
     // ---- the Fiat-Shamir sponge of the values phase (ChallengerChip, challenger/mod.rs:19-126; overwrite-mode duplex, rate 8): the state
     // lives on the lanes (lane l: element l), the input buffer in LDS; every permutation is listed for k_glp_emit
     uint64_t sx = 0; int sp_in = 0, sp_out = 0; lds64_t *lin = nullptr;
-#ifdef H2W_EXP_GLP_CLOCK
-    long long dbg_cycles = 0, dbg_t[24], dbg_c[24]; int dbg_n = 0, dbg_k = 0, dbg_m[24];
-#endif
     __device__ __forceinline__ void sponge_init() { sx = 0; sp_in = sp_out = 0; lin = (lds64_t *)s_glp_in; }
     __device__ __forceinline__ bool sponge_observe(uint64_t t) { sp_out = 0; if (sp_in >= CH_BUF) return false; lin[sp_in++] = t; return true; }
     template <class WordFn> __device__ __forceinline__ bool sponge_observe_words(const uint64_t *proof, int n, WordFn word) {      // n proof words, one lane each
@@ -161,13 +146,7 @@ template <bool COLS, bool VALPH = false, int HASH_MODE = -1> struct CoopSinkT {
         const uint64_t up = row_shr64<1>(sx), w = lane == 0 ? nrec : up;
         uint64_t *at = emit && lane < GLP_LIST_WORDS ? glp + (uint64_t)glp_slot * GLP_LIST_WORDS + lane : nullptr;
         glp_slot++;
-#ifdef H2W_EXP_GLP_CLOCK      // experiment: the cycles of the strand's sponge permutations (printed by k_prologue_values)
-        const long long c0 = clock64();
-#endif
         sx = glp_permute_lanes(sx, lk, lm, lx, lane, small_mds, at, w);
-#ifdef H2W_EXP_GLP_CLOCK
-        dbg_cycles += clock64() - c0; dbg_n++;
-#endif
         nrec += GLP_RECS;
         cell_off += perm_cell_count();
     }
@@ -460,8 +439,8 @@ constexpr BnSrc bn_map_partial(int c) {
 }
 
 enum { QUAD_VALUES = 1, QUAD_EMIT = 2, QUAD_FUSED = 3 };      // QUAD_FUSED: one quad walks its strand AND emits every unit of it (one pass, serial in the path's depth)
-template <bool COLS, int MODE> struct QuadSinkT {
-    static constexpr bool kCoop = false, kSplitOnly = false, kBnUnits = true, kDevSponge = false; static constexpr int kHashMode = 1;
+template <bool COLS, int MODE> struct QuadSinkT : SinkBase {
+    static constexpr bool kBnUnits = true; static constexpr int kHashMode = 1;
     rec_t *recs; uint64_t nrec; fr_t *out; uint64_t cell_off; const uint16_t *ncells; int l4; ColPolicy<COLS> cc;
     fr_t *ustate;                  // output states of this strand's permutation units, [unit][4] (written by QUAD_VALUES, read by QUAD_EMIT)
     fr_t *sbx;                     // the S-box chains of their partial rounds, [unit][BN_PARTIAL_ROUNDS][3] = canonical x^2, x^4, x^5 (QUAD_VALUES -> QUAD_EMIT)
@@ -474,20 +453,7 @@ template <bool COLS, int MODE> struct QuadSinkT {
         nrec++; cell_off += ncells[t];
     }
     __device__ __forceinline__ void cell(const fr_t &v) { if (MODE != QUAD_VALUES && l4 == 0 && act) g_store_fr(out + cc.map(cell_off), v); cell_off++; }
-    __device__ __forceinline__ void gate() {}
-    __device__ __forceinline__ void lookup() {}
-    __device__ void note_cap_hash(uint64_t) {}
     __device__ __forceinline__ void skip(uint64_t nr, uint64_t nc) { nrec += nr; cell_off += nc; }
-    __device__ void merkle_begin(int, int, bool, uint64_t) {}
-    __device__ void merkle_end(int, int, bool) {}
-    __device__ void query_begin(int, uint64_t) {}
-    __device__ void query_end(int, uint64_t) {}
-    __device__ void bn_perm_begin(bool) {}
-    __device__ void bn_perm_end(bool) {}
-    __device__ void glp_note() {}
-    __device__ void note_load(uint64_t, int) {}
-    __device__ bool coop_load_proof(const ValCfg &) { return false; }
-    __device__ void coop_poseidon_permute(uint64_t *, const h2w_poseidon_consts_t *) {}
     // The emitter's working set, by value (a member read behind an opaque call is a FLAT load of the sink object, and flat loads
     // wait for every cell store in flight).
     struct Em {

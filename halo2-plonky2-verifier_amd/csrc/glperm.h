@@ -149,9 +149,6 @@ __device__ __forceinline__ void glq_dense12(uint32_t limb, const uint32_t (&wl)[
 // has the whole permutation to complete in; issued by the caller, the entry of this function would wait for it.
 __device__ __noinline__ uint64_t glp_permute_lanes(uint64_t x, lds64_t *K, lds64_t *M, lds64_t *X, int l, bool small, uint64_t *list_at = nullptr, uint64_t list_word = 0) {
     if (list_at) H2W_GSTORE64(reinterpret_cast<unsigned long long *>(list_at), list_word);
-#ifdef H2W_EXP_GLP_STUB      // experiment (tools/experiments/variant.sh): what the values phase costs WITHOUT its permutations - the values are garbage
-    return x + K[KO_ARC + (l & 7)];
-#endif
     const int l15 = l & 15, lc = l15 < SPONGE_WIDTH ? l15 : SPONGE_WIDTH - 1;
     const bool odd_row = (l >> 4) & 1;
     // this lane's row of the dense MDS matrix sits in registers for all eight full rounds (small entries: one dword each); every round's table words

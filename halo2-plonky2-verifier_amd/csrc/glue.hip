@@ -23,27 +23,14 @@ namespace h2w {
 // ---- the row-cooperative values pass (rowfr.h, rowperm.h): ONE wavefront per Merkle path, the four rows of the wavefront = the four elements of the
 // PoseidonBN254 state, one 29-bit limb per lane.  The wavefront walks its strand wave-uniformly (every lane runs the same gadget code on the same
 // values and writes nothing: the walk between two permutation units is a few selects); a permutation unit is rowperm.h bn_permute_rows.
-struct RowSink {
-    static constexpr bool kCoop = false, kSplitOnly = false, kBnUnits = true, kDevSponge = false; static constexpr int kHashMode = 1;
+struct RowSink : SinkBase {
+    static constexpr bool kBnUnits = true; static constexpr int kHashMode = 1;
     fr_t *ustate;                  // output states of this strand's permutation units, [unit][4]
     uint32_t *sbx9;                // their partial rounds' S-box values in limb form, [unit][56][3][12]
     const rf::RowConst *rowk; int unit_local = 0;
     __device__ __forceinline__ void rec(int, uint64_t, uint64_t, uint64_t, uint64_t) {}
     __device__ __forceinline__ void cell(const fr_t &) {}
-    __device__ __forceinline__ void gate() {}
-    __device__ __forceinline__ void lookup() {}
-    __device__ void note_cap_hash(uint64_t) {}
     __device__ __forceinline__ void skip(uint64_t, uint64_t) {}
-    __device__ void merkle_begin(int, int, bool, uint64_t) {}
-    __device__ void merkle_end(int, int, bool) {}
-    __device__ void query_begin(int, uint64_t) {}
-    __device__ void query_end(int, uint64_t) {}
-    __device__ void bn_perm_begin(bool) {}
-    __device__ void bn_perm_end(bool) {}
-    __device__ void glp_note() {}
-    __device__ void note_load(uint64_t, int) {}
-    __device__ bool coop_load_proof(const ValCfg &) { return false; }
-    __device__ void coop_poseidon_permute(uint64_t *, const h2w_poseidon_consts_t *) {}
     __device__ __forceinline__ bool level_skip(fr_t &, bool &) { return false; }
     __device__ __forceinline__ bool tail_skip() const { return true; }      // the cap lookup: cells only (no value anyone uses)
     __device__ __forceinline__ void permute_unit(fr_t *st) {
@@ -68,8 +55,7 @@ __global__ __launch_bounds__(QUAD_BLOCK) __attribute__((flatten)) void k_merkle_
     const unsigned idx = blockIdx.x * QUAD_WAVES + (threadIdx.x >> 6);      // this wavefront's (proof, query) unit
     int p, q;
     if (!own_unit_at(A, idx, p, q)) return;
-    const int n_or = A.shape.n_perm_z > 0 ? 3 : 2;
-    const int slot = blockIdx.y, kind = slot < n_or ? slot : 3 + (slot - n_or);
+    const int kind = merkle_kind(A.shape.n_perm_z, blockIdx.y);
     const int sq = q == 0 ? 0 : 1;
     RowSink sink;
     const uint64_t unit0 = (uint64_t)idx * A.sh.unit_slot + A.st->mk_unit_rel[sq][kind];
@@ -78,11 +64,7 @@ __global__ __launch_bounds__(QUAD_BLOCK) __attribute__((flatten)) void k_merkle_
     RowB be(sink, mc, !(q == 0 && kind == A.st->first_zero_kind));
     const h2w_shape_t shp = A.shape;
     Verifier<RowB> V(be, shp, A.consts);
-    const uint64_t x = A.cbs[p].fri_query_indices[q];
-    const int lde = V.d.lde_bits; int lo = 0;
-    if (kind >= 3) for (int i = 0; i <= kind - 3; i++) lo += V.d.arity[i];
-    const uint64_t cap_index = (x >> (lde - A.shape.cap_height)) & ((1ull << A.shape.cap_height) - 1);
-    V.merkle_strand(q, kind, PackedBits{x, lo}, lde - lo, cap_index);
+    V.merkle_strand_at(q, kind, A.cbs[p].fri_query_indices[q]);
     if ((threadIdx.x & 63) == 0 && be.status) atomicCAS(&A.status[p], 0u, be.status);
 }
 void launch_merkle_bn_values_row(const BatchArgs &A, unsigned nkinds, hipStream_t stream) {
@@ -112,22 +94,12 @@ template <bool COLS> __global__ __launch_bounds__(64) __attribute__((flatten)) v
     __builtin_amdgcn_s_setprio(3);   // latency-bound serial strand: win issue arbitration against co-resident streaming waves
     stage_glp_consts<true>(A.consts, threadIdx.x, 64);
     const int p = blockIdx.x;
-#ifdef H2W_EXP_GLP_CLOCK
-    const long long k0 = clock64();
-#endif
     Sink sink; coop_sink_init(sink, A, p, -1); sink.nrec = 0; sink.cell_off = 0; sink.glp_slot = 0;
     sink.emit = own_prologue(A, p);
     CoopB be(sink, make_cfg(A, p), true);
     const h2w_shape_t shp = A.shape;      // (a reference into the kernel arguments would put all of them on every lane's stack)
     Verifier<CoopB> V(be, shp, A.consts);
     V.prologue(*reinterpret_cast<ChallengeBlock<CoopB> *>(&A.cbs[p]));
-#ifdef H2W_EXP_GLP_CLOCK
-    if (p == 0 && threadIdx.x == 0) {      // marks (verifier.h prologue): load_proof | caps and alphas | zeta and openings | fri alpha and betas | final poly and pow | query indices | reduced openings
-        const long long total = (long long)clock64() - k0;
-        for (int i = 0; i < sink.dbg_k; i++) printf("mark %d at %lld cycles %lld in %d permutations\n", i, sink.dbg_t[i], sink.dbg_c[i], sink.dbg_m[i]);
-        printf("kernel %lld cycles\n", total);
-    }
-#endif
     if (threadIdx.x == 0) A.status[p] = be.status;
 }
 
@@ -163,8 +135,7 @@ __global__ __launch_bounds__(QUAD_BLOCK) __attribute__((flatten)) void k_merkle_
     unsigned idx = (blockIdx.x * QUAD_BLOCK + threadIdx.x) >> 2;
     if (idx >= total) idx = total - 1;                  // tail quads redo the last strand (identical bytes)
     int p, q; own_unit_at(A, idx, p, q);
-    const int n_or = A.shape.n_perm_z > 0 ? 3 : 2;
-    const int slot = blockIdx.y, kind = slot < n_or ? slot : 3 + (slot - n_or);
+    const int kind = merkle_kind(A.shape.n_perm_z, blockIdx.y);
     Sink sink;
     quad_strand<QuadB>(A, sink, idx, p, q, kind);
 }
@@ -184,19 +155,14 @@ template <bool COLS> __global__ __launch_bounds__(64) __attribute__((flatten)) v
     int p, q;
     if (!own_unit_at(A, blockIdx.x, p, q)) return;
     const int sq = q == 0 ? 0 : 1;
-    const int n_or = A.shape.n_perm_z > 0 ? 3 : 2;
-    const int slot = blockIdx.y, kind = slot < n_or ? slot : 3 + (slot - n_or);
+    const int kind = merkle_kind(A.shape.n_perm_z, blockIdx.y);
     Sink sink; coop_sink_init(sink, A, p, q); sink.emit = true;
     sink.nrec = strand_q_rec(*A.st, q) + A.st->mk_rec_rel[sq][kind]; sink.cell_off = strand_q_cell(*A.st, q) + A.st->mk_cell_rel[sq][kind];
     sink.glp_slot = A.st->pro_nglp + (uint32_t)q * A.st->q_nglp + A.st->mk_glp_rel[kind];
     CoopB be(sink, make_cfg(A, p), true);
     const h2w_shape_t shp = A.shape;      // (a reference into the kernel arguments would put all of them on every lane's stack)
     Verifier<CoopB> V(be, shp, A.consts);
-    const uint64_t x = A.cbs[p].fri_query_indices[q];
-    const int lde = V.d.lde_bits; int lo = 0;
-    if (kind >= 3) for (int i = 0; i <= kind - 3; i++) lo += V.d.arity[i];
-    const uint64_t cap_index = (x >> (lde - A.shape.cap_height)) & ((1ull << A.shape.cap_height) - 1);
-    V.merkle_strand(q, kind, PackedBits{x, lo}, lde - lo, cap_index);
+    V.merkle_strand_at(q, kind, A.cbs[p].fri_query_indices[q]);
     if (threadIdx.x == 0 && be.status) atomicCAS(&A.status[p], 0u, be.status);
 }
 

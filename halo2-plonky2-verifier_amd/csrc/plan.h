@@ -3,7 +3,10 @@
 #include "common.h"
 #include "batchargs.h"
 
-namespace h2w { struct TracedPlan; }
+namespace h2w {
+struct TracedPlan;
+struct ShardSpec { int rank = 0, world = 1, compact = 0; };
+}
 using namespace h2w;      // (included by batch.hip and replay.hip only, which live in that namespace's vocabulary)
 struct h2w_plan {
     h2w_shape_t shape; int device;
@@ -19,9 +22,10 @@ struct h2w_plan {
     StrandTable *d_st = nullptr;                      // device copy of st
     bool small_mds = false;                           // Goldilocks-Poseidon MDS entries are tiny (coop.h glp_small_mds)
     uint64_t *d_meta = nullptr; h2w_poseidon_consts_t *d_consts = nullptr; uint16_t *d_ncells = nullptr; fr_t *d_inv = nullptr;
-    static constexpr int EV_RING = 64, N_EV = 13, N_SIDE = 16;
-    // per call: 0 start, 9 prologue values done, 11 / 12 permutation-record kernel start / end, 1 prologue block complete, 7 / 2 glue (+ Goldilocks Merkle
-    // strands) start / done, 8 / 3 expansion start / done, 4 / 10 / 5 chain kernels start / values done / end, 6 end of call
+    static constexpr int EV_RING = 64, N_SIDE = 16;
+    // event slots of a call: slot i < H2W_EV_COUNT is the public H2W_EV_* i (include/h2w.h: call start / end, prologue block complete, glue (+ Goldilocks
+    // Merkle strands) start / end, chain kernels start / end, expansion start / end), then the internal ones
+    enum { EV_PROLOGUE_VALUES_END = H2W_EV_COUNT, EV_CHAIN_VALUES_END, EV_GLP_START, EV_GLP_END, N_EV };
     hipEvent_t evr[EV_RING][N_EV]; int passes_of[EV_RING] = {0};
     hipStream_t side[N_SIDE]; hipStream_t side_of[N_SIDE]; int n_side = 0;   // PoseidonBN254 chain kernels run beside the glue + expansion kernels
     int chain_passes = 0;            // H2W_OPT_CHAIN_PASSES (0: by the size of the launch)
@@ -32,4 +36,11 @@ struct h2w_plan {
     h2w::TracedPlan *traced = nullptr;      // set: the plan replays a recorded tape (replay.hip); the strand tables above are unused
     explicit h2w_plan(int L) : tt(L) {}
 };
+namespace h2w {
+// The expansion launch of a plan's call (batch.hip run_batch, h2w_fri_expand_records; replay.hip traced_run): records[n_proofs][p->nrec] -> cells
+// out[n_proofs][cell_stride] through cm.  sh: the (proof, query) sharding of the record ranges; null: every proof is one block (a traced plan has
+// no strand table).  tile_ctr: n_proofs words of workspace, zeroed here.  roam_per_cu: ExpandArgs.
+int launch_plan_expand(const h2w_plan *p, uint64_t n_proofs, const rec_t *recs, uint32_t *tile_ctr, fr_t *out, uint64_t cell_stride, ColMap cm,
+                       const ShardSpec *sh, uint32_t roam_per_cu, hipStream_t stream);
+}
 

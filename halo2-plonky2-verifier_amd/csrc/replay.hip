@@ -92,18 +92,12 @@ struct TracedPlan {
 
 // ------------------------------------------------------------------------------------------------------------------- device
 // (its own sink type: the flattened value backend of this unit is instantiated nowhere else - field.h HNI)
-struct ReplaySink {
-    static constexpr bool kCoop = false, kSplitOnly = false, kBnUnits = false, kDevSponge = false; static constexpr int kHashMode = -1;
-    HF void coop_poseidon_permute(uint64_t *, const h2w_poseidon_consts_t *) {}
+struct ReplaySink : SinkBase {
     rec_t *recs; uint64_t nrec; fr_t *out; uint64_t cell_off; const uint32_t *ncells;      // ncells: an LDS table (a global load per record would wait for the record stores in flight)
     ColCursor cc;      // the FlexGate column layout of a direct cell (flat stream: the identity, never located)
     HF void rec(int t, uint64_t a, uint64_t b, uint64_t c, uint64_t d) { g_store_rec(recs + nrec, a, b, c, d); nrec++; cell_off += ncells[t]; }
     HF void cell(const fr_t &v) { g_store_fr(out + cc.map(cell_off), v); cell_off++; }
-    HF void gate() {} HF void lookup() {}
     HF void skip(uint64_t nr, uint64_t nc) { nrec += nr; cell_off += nc; }
-    HF void merkle_begin(int, int, bool, uint64_t) {} HF void merkle_end(int, int, bool) {} HF void query_begin(int, uint64_t) {} HF void query_end(int, uint64_t) {}
-    HF void bn_perm_begin(bool) {} HF void bn_perm_end(bool) {} HF void glp_note() {} HF void note_load(uint64_t, int) {} HF void note_cap_hash(uint64_t) {}
-    HF bool coop_load_proof(const ValCfg &) { return false; } HF bool bn_emit_inline(fr_t *, const ValCfg &, bool &) { return false; }
 };
 typedef ValBackend<ReplaySink> RB;
 __shared__ uint64_t s_lds[LDS_WORDS];      // [ring | pool64 | poolfr]
@@ -301,13 +295,7 @@ int traced_run(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void 
         if (nb) hipLaunchKernelGGL(k_replay, dim3(nb), dim3(64), 0, stream, R);
     }
     // expansion of the block records
-    ExpandArgs E;
-    E.meta = p->d_meta; E.recs = R.recs; E.nrec = p->nrec; E.rec_stride = p->nrec; E.out = R.out; E.cell_stride = cell_stride; E.pool = nullptr; E.cm = cm;
-    expand_unsharded(E); p->dt.fill(E);
-    E.tile_ctr = (uint32_t *)(ws + wl.ctr); E.roam_per_cu = 2;
-    H2W_HIP(hipMemsetAsync(E.tile_ctr, 0, n_proofs * 4, stream));
-    int gx = (int)(2048 / (n_proofs < 2048 ? n_proofs : 2048)); if (gx < 8) gx = 8;
-    if (launch_expand(E, n_proofs, gx, stream) != 0) return -1;
+    if (launch_plan_expand(p, n_proofs, R.recs, (uint32_t *)(ws + wl.ctr), R.out, cell_stride, cm, nullptr, 2, stream) != 0) return -1;
     H2W_HIP(hipGetLastError());
     return 0;
 }

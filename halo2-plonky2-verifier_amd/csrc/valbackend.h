@@ -4,7 +4,7 @@
 // are not part of the advice stream.  Every op computes its result natively (Goldilocks mul/reduce on 64-bit
 // integer MADs, Montgomery Fr) and hands the *cells* to a Sink either as a 32-byte block record (the big
 // Goldilocks templates, expanded later by expand.hip) or as direct cells (small irregular templates and BN254
-// Poseidon).  Sinks: DevSink (device memory) and PlanSink (host, counts + metas = the shape compiler).
+// Poseidon).  The sinks and their hooks: SinkBase below.
 // Cell templates: SURVEY.md Appendix A; reduce block: field/goldilocks/base.rs:346-368.
 #pragma once
 #include "records.h"
@@ -45,6 +45,45 @@ struct ValCfg {
     bool split_bn;                   // true: the sink emits a PoseidonBN254 permutation's cells itself (QuadSink::bn_emit_inline)
     const LoadItem *load_items; uint32_t n_load_items; uint64_t load_nrec, load_ncell;
     uint32_t n_cap_items;            // ... followed by n_cap_items items of kind 4
+};
+
+// ---- Sinks.  ValBackend<Sink> decides WHAT is emitted; the sink decides where it goes.  A sink derives from SinkBase and keeps only its fields,
+// the hooks it really implements and the flags it overrides: a hook or flag redeclared in the sink hides the base's.
+// Every sink provides (its cursor over the stream of records and direct cells):
+//   rec(t, a, b, c, d)   a block record of template t (cells: ncells[t])            ValBackend: every Goldilocks template
+//   cell(v)              one direct cell                                            ValBackend: small native templates, BN254 Poseidon
+//   skip(nrec, ncells)   step over a Merkle strand that is another kernel's          ValBackend::merkle_split (cfg.split)
+// Flags (SinkBase: all off) and the hooks a flag makes the sink provide:
+//   kCoop        one wavefront cooperates on a Goldilocks permutation: coop_poseidon_permute(st, k)          (chips.h PoseidonChip)
+//   kSplitOnly   the backend only runs strands whose Merkle proofs are other strands (verifier.h merkle_call)
+//   kBnUnits     every PoseidonBN254 permutation is a unit of the sink (bn_emit_inline); level_skip(node, zc), tail_skip()
+//                step over Merkle levels / the cap lookup that are another quad's                         (chips.h MerkleTreeChip)
+//   kDevSponge   the Fiat-Shamir sponge is the sink's: sponge_init / _observe / _observe_words / _observe_cap / _challenge,
+//                stage_words, staged_word                                                                  (verifier.h prologue)
+//   kHashMode    >= 0: the only hash mode the backend is ever run with (-1: the shape's)
+// Optional hooks (SinkBase: no-ops; the shape compiler's PlanSink implements most of them to lay the stream out):
+//   gate(), lookup()                        keygen markers for the NEXT direct cell (ValBackend G() / LK())
+//   merkle_begin / merkle_end(q, kind, ..)  around a Merkle strand; query_begin / query_end(q, unit) around a query round   (verifier.h)
+//   bn_perm_begin / bn_perm_end(zc)         around a PoseidonBN254 permutation that is not a sink unit                       (chips.h)
+//   glp_note()                              a Goldilocks-Poseidon permutation starts                                         (chips.h)
+//   note_load(word, kind), note_cap_hash(w) a witness load / a cap hash's limb decomposition, for the load kernel's items    (verifier.h)
+//   coop_load_proof(cfg) -> bool            true: the sink took WitnessChip::load_proof_with_pis over (cursor stepped past it)
+//   bn_emit_inline(st, cfg, zc) -> bool     true: the sink computed / emitted this PoseidonBN254 permutation (cfg.split_bn)
+struct SinkBase {
+    static constexpr bool kCoop = false, kSplitOnly = false, kBnUnits = false, kDevSponge = false; static constexpr int kHashMode = -1;
+    HF void gate() {}
+    HF void lookup() {}
+    HF void merkle_begin(int, int, bool, uint64_t) {}
+    HF void merkle_end(int, int, bool) {}
+    HF void query_begin(int, uint64_t) {}
+    HF void query_end(int, uint64_t) {}
+    HF void bn_perm_begin(bool) {}
+    HF void bn_perm_end(bool) {}
+    HF void glp_note() {}
+    HF void note_load(uint64_t, int) {}
+    HF void note_cap_hash(uint64_t) {}
+    HF bool coop_load_proof(const ValCfg &) { return false; }
+    HF bool bn_emit_inline(fr_t *, const ValCfg &, bool &) { return false; }
 };
 
 template <class Sink> struct ValBackend {
@@ -235,26 +274,12 @@ template <class Sink> struct ValBackend {
 };
 
 // device sink: records into this proof's record array, direct cells into this proof's advice range
-template <bool COLS, bool SPLIT_ONLY = false> struct DevSinkT {
-    static constexpr bool kCoop = false, kSplitOnly = SPLIT_ONLY, kBnUnits = false, kDevSponge = false; static constexpr int kHashMode = -1;
-    HF void coop_poseidon_permute(uint64_t *, const h2w_poseidon_consts_t *) {}
+template <bool COLS, bool SPLIT_ONLY = false> struct DevSinkT : SinkBase {
+    static constexpr bool kSplitOnly = SPLIT_ONLY;
     rec_t *recs; uint64_t nrec; fr_t *out; uint64_t cell_off; const uint16_t *ncells; ColPolicy<COLS> cc;
     HF void rec(int t, uint64_t a, uint64_t b, uint64_t c, uint64_t d) { g_store_rec(recs + nrec, a, b, c, d); nrec++; cell_off += ncells[t]; }
     HF void cell(const fr_t &v) { g_store_fr(out + cc.map(cell_off), v); cell_off++; }
-    HF void gate() {}
-    HF void lookup() {}
     HF void skip(uint64_t nr, uint64_t nc) { nrec += nr; cell_off += nc; }
-    HF void merkle_begin(int, int, bool, uint64_t) {}
-    HF void merkle_end(int, int, bool) {}
-    HF void query_begin(int, uint64_t) {}
-    HF void query_end(int, uint64_t) {}
-    HF void bn_perm_begin(bool) {}
-    HF void bn_perm_end(bool) {}
-    HF void glp_note() {}
-    HF void note_load(uint64_t, int) {}
-    HF void note_cap_hash(uint64_t) {}
-    HF bool coop_load_proof(const ValCfg &) { return false; }
-    HF bool bn_emit_inline(fr_t *, const ValCfg &, bool &) { return false; }
 };
 typedef DevSinkT<false> DevSink;
 

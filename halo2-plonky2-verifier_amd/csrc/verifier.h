@@ -15,6 +15,9 @@ namespace h2w {
 constexpr int MAX_QUERIES = 128;
 constexpr int CH_BUF = (5 * MAX_CAP > 2 * MAX_FINAL_POLY ? 5 * MAX_CAP : 2 * MAX_FINAL_POLY) + 16;      // the sponge's input buffer: a cap of BN254 hashes (5 limbs each) or the final polynomial + the PoW witness
 constexpr int MK_KINDS = 3 + MAX_STEPS;   // merkle strand kinds: initial oracle o (0..2), fold step i (3+i)
+// the kind of Merkle-strand slot `slot` (blockIdx.y of the strand kernels; the plan's emission items): the shape's initial oracles - two without
+// permutation Zs (trace, quotient), three with them - then its fold steps
+HF int merkle_kind(int n_perm_z, int slot) { const int n_or = n_perm_z > 0 ? 3 : 2; return slot < n_or ? slot : 3 + (slot - n_or); }
 
 // wires produced by the prologue and consumed by the query strands (fri/mod.rs:64-69 FriChallengesWire + instance points)
 template <class B> struct ChallengeBlock {
@@ -134,19 +137,10 @@ template <class B> struct Verifier {
         i -= s.n_cols; return o + 2ull * (2 * s.n_cols + s.n_perm_z + i);
     }
     // ---- prologue strand
-#if defined(H2W_EXP_GLP_CLOCK) && defined(__HIP_DEVICE_COMPILE__)      // experiment: where the prologue wavefront's cycles go (proof 0, lane 0 prints)
-#define H2W_CLK_MARK(what) do { if constexpr (B::kDevSponge) { if (be.sink.dbg_k < 24) { be.sink.dbg_t[be.sink.dbg_k] = (long long)clock64() - clk0; be.sink.dbg_c[be.sink.dbg_k] = be.sink.dbg_cycles; be.sink.dbg_m[be.sink.dbg_k++] = be.sink.dbg_n; } } } while (0)
-#else
-#define H2W_CLK_MARK(what) do { } while (0)
-#endif
     HF void prologue(ChallengeBlock<B> &cb) {
-#if defined(H2W_EXP_GLP_CLOCK) && defined(__HIP_DEVICE_COMPILE__)
-        const long long clk0 = clock64();
-#endif
         ChallengerChip<B> ch(be, hs, k);
         ch.load_zero_state();                                        // stark/mod.rs:497-499
         load_proof_with_pis();                                       // stark/mod.rs:506
-        H2W_CLK_MARK("load_proof");
         // ChallengerChip::get_stark_challenges (challenger/mod.rs:167-222)
         observe_cap(ch, pl.trace_cap);
         if (s.n_perm_z > 0) {
@@ -155,22 +149,17 @@ template <class B> struct Verifier {
         }
         for (int i = 0; i < s.num_challenges; i++) ch.get_challenge();                               // stark_alphas (:203)
         observe_cap(ch, pl.quotient_cap);
-        H2W_CLK_MARK("caps and alphas");
         const Ex zeta = ch.get_extension_challenge(); cb.zeta = zeta;                               // :206 (what the strand goes on to use is kept in locals: the block is device memory behind a generic reference - every read of it a flat load behind the record stores)
         const int nz = s.n_cols + s.n_perm_z + s.n_quotient, nzn = s.n_cols + s.n_perm_z;
         ch.observe_ext_words(nz, [&](int i) { return zeta_word(i); });                               // observe_openings (:208)
         ch.observe_ext_words(nzn, [&](int i) { return zeta_next_word(i); });
-        H2W_CLK_MARK("zeta and openings");
         // get_fri_challenges (:128-165)
         const Ex fri_alpha = ch.get_extension_challenge(); cb.fri_alpha = fri_alpha;
-        for (int i = 0; i < d.n_steps; i++) { observe_cap(ch, pl.commit_caps + (uint64_t)i * d.cap_size * 4); H2W_CLK_MARK("commit cap observed"); cb.fri_betas[i] = ch.get_extension_challenge(); H2W_CLK_MARK("beta"); }
-        H2W_CLK_MARK("fri alpha and betas");
+        for (int i = 0; i < d.n_steps; i++) { observe_cap(ch, pl.commit_caps + (uint64_t)i * d.cap_size * 4); cb.fri_betas[i] = ch.get_extension_challenge(); }
         ch.observe_ext_words(d.final_poly_len, [&](int i) { return pl.final_poly + 2ull * i; });
         ch.observe_element(be.proof_gl(pl.pow_witness));
         const Gl pow_response = ch.get_challenge(); cb.fri_pow_response = pow_response;
-        H2W_CLK_MARK("final poly and pow");
         for (int i = 0; i < s.num_queries; i++) cb.fri_query_indices[i] = ch.get_challenge();
-        H2W_CLK_MARK("query indices");
         // verify_proof_with_challenges: fri_instance_info (stark/mod.rs:144-200): zeta_next = g * zeta
         {   // (the generator of the trace domain is the LDE domain's, squared rate_bits times: with the shape's table at hand that replaces an exponentiation - 33 k cycles of the prologue wavefront)
             const FriTab *ft = be.fri_tab();
@@ -179,22 +168,18 @@ template <class B> struct Verifier {
             else gd = gl_primitive_root_of_unity(s.degree_bits);
             gle_t gv; gv.c[0] = gd; gv.c[1] = 0; Ex g = ext.load_constant(gv); cb.zeta_next = ext.mul(g, zeta);
         }
-        H2W_CLK_MARK("zeta_next");
         // FriChip::verify_fri_proof (fri/mod.rs:446-502): PoW (:130-145), from_os_and_alpha (:45-62)
         be.range_check(pow_response, 64 - s.pow_bits);
-        H2W_CLK_MARK("pow range check");
         if constexpr (B::kDevSponge) {      // (the device prologue wavefront: the opening words side by side into the idle input buffer, not one dependent load each)
             static_assert(CH_BUF >= 4 * MAX_BATCH_POLYS, "the openings fit the sponge's input buffer");
             be.stage_words(0, 2 * nz, [&](int j) { return zeta_word(j >> 1) + (uint64_t)(j & 1); });
             be.stage_words(2 * nz, 2 * nzn, [&](int j) { return zeta_next_word(j >> 1) + (uint64_t)(j & 1); });
             cb.reduced_openings[0] = ext.reduce_with_powers(nz, [&](int i) { Ex e; e.e[0] = be.staged_word(2 * i); e.e[1] = be.staged_word(2 * i + 1); return e; }, fri_alpha);
-            H2W_CLK_MARK("reduced openings 0");
             cb.reduced_openings[1] = ext.reduce_with_powers(nzn, [&](int i) { Ex e; e.e[0] = be.staged_word(2 * nz + 2 * i); e.e[1] = be.staged_word(2 * nz + 2 * i + 1); return e; }, fri_alpha);
         } else {
             cb.reduced_openings[0] = ext.reduce_with_powers(nz, [&](int i) { return proof_ext(zeta_word(i)); }, fri_alpha);
             cb.reduced_openings[1] = ext.reduce_with_powers(nzn, [&](int i) { return proof_ext(zeta_next_word(i)); }, fri_alpha);
         }
-        H2W_CLK_MARK("reduced openings");
     }
     // ---- merkle strand: kind < 3: initial oracle `kind`; kind >= 3: fold step kind-3.  bits/cap_index are wires of the query.
     HF uint64_t query_word(int q) const { return pl.queries + (uint64_t)q * pl.query_words; }
@@ -217,6 +202,13 @@ template <class B> struct Verifier {
             mk.verify_proof_to_cap_with_cap_index(ProofGl{&be, base}, ne, bits, n_bits, cap_index, d.cap_size,
                 [&](int i) { return be.proof_hash(capw + 4ull * i); }, pl.step_sibs[st], [&](int i) { return be.proof_hash(sibw + 4ull * i); });
         }
+    }
+    // one Merkle strand on its own (the device strand kernels), from the query index x: the index bits and cap index query_round hands it
+    HF void merkle_strand_at(int q, int kind, uint64_t x) {
+        const int lde = d.lde_bits; int lo = 0;
+        if (kind >= 3) for (int i = 0; i <= kind - 3; i++) lo += d.arity[i];      // the bits the fold steps up to this one have taken
+        const uint64_t cap_index = (x >> (lde - s.cap_height)) & ((1ull << s.cap_height) - 1);
+        merkle_strand(q, kind, PackedBits{x, lo}, lde - lo, cap_index);
     }
     template <class BitsT> HF void merkle_call(int q, int kind, const BitsT &bits, int n_bits, Gl cap_index) {
         if constexpr (B::kSplitOnly) { be.merkle_split(q, kind); return; }      // glue strands: the cells of this call belong to a merkle strand
