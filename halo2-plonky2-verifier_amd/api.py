@@ -251,7 +251,9 @@ class Plan:
     def from_trace(cls, ctx, proof_words, parallel_scopes=("verify_query_round", "verify_proof_to_cap_with_cap_index"), device_id=0):
         """h2w_plan_from_trace: the tape `ctx` recorded (Context.trace_begin, then ONE run through the level-1 / level-2 calls) as a plan that
         h2w_fri_witness_batch replays on other proofs of the shape.  parallel_scopes: the #[count] scopes whose instances are independent
-        (fri/mod.rs:488-501, merkle/mod.rs:57-78); the library checks the claim on the tape."""
+        (fri/mod.rs:488-501, merkle/mod.rs:57-78); the library checks the claim on the tape.  The depth-1 instances (the query rounds) are the
+        units of the sharded calls; a context created with witness_gen_only=False also gives the plan its keygen metadata (selectors(),
+        lookup_cells(), equalities(), const_equalities(), break_points(), check_constraints())."""
         L = lib()
         names = (C.c_char_p * len(parallel_scopes))(*[s.encode() for s in parallel_scopes])
         h = L.h2w_plan_from_trace(ctx.p, proof_words, names, len(parallel_scopes), device_id)
@@ -351,7 +353,12 @@ class Plan:
         _ck(self.L.h2w_fri_witness_batch_shard_compact(self.p, proofs_ptr, n, shard_advice_ptr, workspace_ptr, stream, rank, world), "h2w_fri_witness_batch_shard_compact")
 
     def shard_cells(self, n, rank, world):
-        return int(self.L.h2w_plan_shard_cells(self.p, n, rank, world))
+        """Cells of rank's packed buffer.  A traced plan shards by its depth-1 parallel instances (the query rounds); one that cannot be
+        sharded raises H2WError here and in every other shard call."""
+        v = int(self.L.h2w_plan_shard_cells(self.p, n, rank, world))
+        if v == 0 and n > 0 and self.shape is None:      # a traced plan: no cells is a refusal or a rank without blocks; shard_block tells which
+            self.shard_block(rank, world, 0, -1)
+        return v
 
     def shard_workspace_bytes(self, n, rank, world):
         """Scratch bytes of a sharded call of this rank (the unit buffers hold the rank's own units only)."""

@@ -216,6 +216,7 @@ static int plan_replay(h2w_plan *p, const std::vector<uint64_t> &words, std::vec
 static int plan_equalities_build(h2w_plan *p) {
     PlanEqualities &E = plan_equalities(p);
     if (E.ready) return 0;
+    if (plan_traced(p)) { set_error("h2w_plan_equalities: the plan was traced on a context with witness_gen_only != 0, which records no keygen lists (trace with witness_gen_only = 0)"); return -1; }
     const h2w_shape_t &sh = plan_shape(p);
     Derived d = derive_shape(sh); ProofLayout pl = proof_layout(sh, d);
     std::vector<uint64_t> wa(pl.total), wb(pl.total);

@@ -189,9 +189,11 @@ namespace h2w {
 // a traced plan (replay.hip)
 uint64_t traced_workspace_bytes(const h2w_plan *p, uint64_t n);
 uint64_t traced_status_offset(const h2w_plan *p, uint64_t n, bool flags);
-int traced_run(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void *advice_dev, void *workspace_dev, void *stream_, ColMap cm, uint64_t cell_stride);
+int traced_run(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void *advice_dev, void *workspace_dev, void *stream_, ColMap cm, uint64_t cell_stride, const ShardSpec &sh);
 void traced_free(h2w_plan *p);
+const char *traced_shard_refusal(const h2w_plan *p);      // null: the traced plan shards by its depth-1 parallel instances
 PlanEqualities &plan_equalities(h2w_plan *p) { return p->eqs; }
+bool plan_traced(const h2w_plan *p) { return p->traced != nullptr; }
 const h2w_shape_t &plan_shape(const h2w_plan *p) { return p->shape; }
 const h2w_poseidon_consts_t &plan_consts(const h2w_plan *p) { return p->h_consts; }
 uint64_t plan_cells(const h2w_plan *p) { return p->ncells; }
@@ -364,6 +366,8 @@ static WsLayout ws_layout(const h2w_plan *p, uint64_t n, const ShardSpec &sh = S
 uint64_t h2w_plan_workspace_bytes(const h2w_plan *p, uint64_t n_proofs) { return !p ? 0 : p->traced ? traced_workspace_bytes(p, n_proofs) : ws_layout(p, n_proofs).total; }
 uint64_t h2w_plan_shard_workspace_bytes(const h2w_plan *p, uint64_t n_proofs, int rank, int world) {
     if (!p || world < 1 || rank < 0 || rank >= world) return 0;
+    if (const char *why = traced_shard_refusal(p)) { set_error(std::string("h2w_plan_shard_workspace_bytes: ") + why); return 0; }
+    if (p->traced) return traced_workspace_bytes(p, n_proofs);      // (value store and records per proof: the unsharded size)
     ShardSpec sh; sh.rank = rank; sh.world = world;
     return ws_layout(p, n_proofs, sh).total;
 }
@@ -417,6 +421,7 @@ int h2w_fri_witness_batch_columns(h2w_plan *p, const uint64_t *proofs_dev, uint6
 // challenges) - at their global offsets in advice_dev[n_proofs][num_cells]; the other blocks are left untouched.
 int h2w_fri_witness_batch_shard(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void *advice_dev, void *workspace_dev, void *stream_, int rank, int world) {
     if (world < 1 || rank < 0 || rank >= world) { set_error("h2w_fri_witness_batch_shard: bad rank / world"); return -1; }
+    if (const char *why = p ? traced_shard_refusal(p) : nullptr) { set_error(std::string("h2w_fri_witness_batch_shard: ") + why); return -1; }
     ColMap flat; flat.starts = nullptr; flat.ncols = 0; flat.k = 0;
     ShardSpec sh; sh.rank = rank; sh.world = world;
     return run_batch(p, proofs_dev, n_proofs, advice_dev, workspace_dev, stream_, stream_, flat, p ? p->ncells : 0, sh);
@@ -425,10 +430,12 @@ int h2w_fri_witness_batch_shard(h2w_plan *p, const uint64_t *proofs_dev, uint64_
 static uint64_t shard_q_slot(const h2w_plan *p) { return p->st.q_ncell[0] > p->st.q_ncell[1] ? p->st.q_ncell[0] : p->st.q_ncell[1]; }
 uint64_t h2w_plan_shard_cells(const h2w_plan *p, uint64_t n_proofs, int rank, int world) {
     if (!p || world < 1 || rank < 0 || rank >= world) return 0;
+    if (const char *why = traced_shard_refusal(p)) { set_error(std::string("h2w_plan_shard_cells: ") + why); return 0; }
     return own_count(n_proofs, rank, world) * p->st.pro_ncell + own_count(n_proofs * (uint64_t)p->shape.num_queries, rank, world) * shard_q_slot(p);
 }
 int h2w_plan_shard_block(const h2w_plan *p, int rank, int world, uint64_t proof, int query, uint64_t *local_cell, uint64_t *n_cells, uint64_t *global_cell) {
     if (!p || world < 1 || rank < 0 || rank >= world || query >= p->shape.num_queries) { set_error("h2w_plan_shard_block: bad argument"); return -1; }
+    if (const char *why = traced_shard_refusal(p)) { set_error(std::string("h2w_plan_shard_block: ") + why); return -1; }
     const uint64_t W = (uint64_t)world, r = (uint64_t)rank, nq = (uint64_t)p->shape.num_queries, u0 = proof * nq;
     const bool owned = query < 0 ? proof % W == r : (u0 + (uint64_t)query) % W == r;
     if (!owned) return 1;
@@ -444,6 +451,7 @@ int h2w_plan_shard_block(const h2w_plan *p, int rank, int world, uint64_t proof,
 }
 int h2w_fri_witness_batch_shard_compact(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void *shard_advice_dev, void *workspace_dev, void *stream_, int rank, int world) {
     if (world < 1 || rank < 0 || rank >= world) { set_error("h2w_fri_witness_batch_shard_compact: bad rank / world"); return -1; }
+    if (const char *why = p ? traced_shard_refusal(p) : nullptr) { set_error(std::string("h2w_fri_witness_batch_shard_compact: ") + why); return -1; }
     if (p && !(p->shape.lookup_bits == 21 || p->shape.lookup_bits == 13 || p->shape.lookup_bits == 8)) { set_error("h2w_fri_witness_batch_shard_compact: lookup_bits must be 21, 13 or 8 (the packed layout is written by expand_fast)"); return -1; }
     ColMap flat; flat.starts = nullptr; flat.ncols = 0; flat.k = 0;
     ShardSpec sh; sh.rank = rank; sh.world = world; sh.compact = 1;
@@ -473,9 +481,9 @@ static int run_batch(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs,
     if (p->device < 0) { set_error("h2w_fri_witness_batch: no HIP device — the hot path only runs on the GPU (no CPU fallback)"); return -1; }
     if (!proofs_dev || !advice_dev || !workspace_dev) { set_error("h2w_fri_witness_batch: null buffer"); return -1; }
     if (n_proofs == 0) return 0;
-    if (p->traced) {      // a recorded run (replay.hip): the flat stream or the FlexGate columns, unsharded
-        if (sh.world > 1 || emit_stream_ != stream_) { set_error("h2w_fri_witness_batch: a traced plan runs on one stream, unsharded"); return -1; }
-        return traced_run(p, proofs_dev, n_proofs, advice_dev, workspace_dev, stream_, cm, cell_stride);
+    if (p->traced) {      // a recorded run (replay.hip): the flat stream, the FlexGate columns, or this rank's (proof, query) units
+        if (emit_stream_ != stream_) { set_error("h2w_fri_witness_batch: a traced plan runs on one stream"); return -1; }
+        return traced_run(p, proofs_dev, n_proofs, advice_dev, workspace_dev, stream_, cm, cell_stride, sh);
     }
     if (n_proofs * (uint64_t)p->shape.num_queries * (p->st.mk_item0[MK_KINDS] ? p->st.mk_item0[MK_KINDS] : 1) > 0x3fffffffull) { set_error("h2w_fri_witness_batch: batch too large"); return -1; }
     if (n_proofs > 65535) { set_error("h2w_fri_witness_batch: more than 65535 proofs per call (the proof index is a grid dimension of the load and expansion kernels); split the batch"); return -1; }
@@ -630,8 +638,8 @@ int h2w_fri_expand_records(h2w_plan *p, uint64_t n_proofs, void *advice_dev, voi
 // ---- keygen-side metadata of the cell stream: static per shape, computed by a second host replay
 int h2w_plan_metadata(h2w_plan *pl) {
     if (!pl) { set_error("h2w_plan_metadata: null plan"); return -1; }
-    if (pl->traced) { set_error("h2w_plan_metadata: a traced plan has no shape to replay on the host (the tracing context recorded the keygen lists: h2w_ctx_* with witness_gen_only = 0)"); return -1; }
-    if (pl->meta_ready) return 0;
+    if (pl->meta_ready) return 0;      // (a traced plan: the tracing context's lists, h2w_plan_from_trace)
+    if (pl->traced) { set_error("h2w_plan_metadata: the plan was traced on a context with witness_gen_only != 0, which records no keygen lists (trace with witness_gen_only = 0)"); return -1; }
     if (pl->shape.lookup_bits >= 48) { set_error("h2w_plan_metadata: lookup_bits >= 48 makes a single-limb range check look up its SOURCE cell; not tracked"); return -1; }
     std::vector<fr_t> inv(2 * INV_TAB, fr_zero());
     for (int k2 = 1; k2 < INV_TAB; k2++) { inv[k2] = fr_inv(fr_from_u64((uint64_t)k2), pl->P); inv[INV_TAB + k2] = fr_neg(inv[k2]); }

@@ -40,6 +40,7 @@ PlanEqualities &plan_equalities(h2w_plan *);                       // batch.hip
 const h2w_shape_t &plan_shape(const h2w_plan *);
 const h2w_poseidon_consts_t &plan_consts(const h2w_plan *);
 uint64_t plan_cells(const h2w_plan *);
+bool plan_traced(const h2w_plan *);
 
 // arguments of the expansion kernel (expand.hip)
 struct ExpandArgs {

@@ -603,4 +603,5 @@ namespace h2w {
 Trace *ctx_trace(h2w_ctx *c) { return c ? c->trace : nullptr; }
 int ctx_lookup_bits(const h2w_ctx *c) { return c->L; }
 uint64_t ctx_num_cells(const h2w_ctx *c) { return c->ncells; }
+const MetaRecorder *ctx_meta(const h2w_ctx *c) { return c->keygen ? &c->mr : nullptr; }      // the keygen lists (witness_gen_only == 0), else null
 }

@@ -29,10 +29,11 @@
 #include <cstdlib>
 #include "plan.h"
 #include "trace.h"
+#include "keygen.h"
 
 struct h2w_ctx;
 namespace h2w {
-Trace *ctx_trace(h2w_ctx *); int ctx_lookup_bits(const h2w_ctx *); uint64_t ctx_num_cells(const h2w_ctx *);      // eager.cpp
+Trace *ctx_trace(h2w_ctx *); int ctx_lookup_bits(const h2w_ctx *); uint64_t ctx_num_cells(const h2w_ctx *); const MetaRecorder *ctx_meta(const h2w_ctx *);      // eager.cpp
 
 enum { W64 = 0, W128 = 1, WFR = 2 };
 enum { RK_LOCAL = 0, RK_IMPORT = 1, RK_LIT64 = 2, RK_INPUT = 3, RK_LITFR = 4, RK_RING = 5 };
@@ -70,7 +71,8 @@ HD void operand_span(uint32_t op, uint32_t n, uint32_t &first, uint32_t &count) 
 constexpr int MAX_TMPL = 48;
 constexpr uint32_t NO_SLOT = 0xffffffffu;
 
-struct InstD { uint64_t cell0, rec0; uint32_t imp0, in0; };
+// unit: the depth-1 parallel instance (shard unit) the instance is or lies in, NO_SLOT for the root; ucell0: that unit's first cell (root: 0)
+struct InstD { uint64_t cell0, rec0, ucell0; uint32_t imp0, in0, unit, pad; };
 struct ImpD { uint32_t tmpl, inst, slot; };
 struct TmplD { uint32_t tape0, nslots, ninst, inst0, depth; };
 
@@ -81,6 +83,10 @@ struct ReplayArgs {
     uint32_t depth, ntmpl, npool64, npoolfr;
     const TmplD *tm; const uint64_t *prefix;      // per template (device tables of the plan): its description; the u64 elements per proof of the value stores before it
     uint32_t blk0[MAX_TMPL + 1];                  // first block of each template among the blocks of this launch (templates of `depth` only)
+    uint32_t *lflag;                              // per proof: 4 when a proof word is outside its field (h2w_plan_status)
+    // (proof, query) sharding (ShardSpec): lanes != null lists the lanes of this rank, template t's at [lane0[t], lane0[t + 1]) (lane_table)
+    const uint32_t *lanes; uint32_t lane0[MAX_TMPL + 1];
+    uint32_t sh_world, sh_rank, sh_compact, nq; uint64_t pro_ncell, q_slot;      // the packed layout (batchargs.h block_out)
 };
 
 struct TracedPlan {
@@ -88,6 +94,9 @@ struct TracedPlan {
     TmplD *d_tm = nullptr; uint64_t *d_prefix = nullptr; uint32_t npool64 = 0, npoolfr = 0;
     uint32_t *d_tape = nullptr; InstD *d_insts = nullptr; ImpD *d_imps = nullptr; uint32_t *d_inputs = nullptr; uint64_t *d_pool64 = nullptr; fr_t *d_poolfr = nullptr;
     uint64_t n_ops = 0, n_segments = 0;
+    // sharding: the depth-1 instances are the units (query q = the q-th in tape order); why_unshardable empty: they tile the stream behind the root's block
+    std::string why_unshardable; std::vector<uint32_t> h_unit;      // h_unit: the unit of every instance (InstD order)
+    std::vector<uint32_t> h_lanes, lane0; uint32_t *d_lanes = nullptr; uint64_t lanes_n = 0; int lanes_rank = -1, lanes_world = 0;      // the lane table of the last (n, rank, world)
 };
 
 // ------------------------------------------------------------------------------------------------------------------- device
@@ -95,8 +104,9 @@ struct TracedPlan {
 struct ReplaySink : SinkBase {
     rec_t *recs; uint64_t nrec; fr_t *out; uint64_t cell_off; const uint32_t *ncells;      // ncells: an LDS table (a global load per record would wait for the record stores in flight)
     ColCursor cc;      // the FlexGate column layout of a direct cell (flat stream: the identity, never located)
-    HF void rec(int t, uint64_t a, uint64_t b, uint64_t c, uint64_t d) { g_store_rec(recs + nrec, a, b, c, d); nrec++; cell_off += ncells[t]; }
-    HF void cell(const fr_t &v) { g_store_fr(out + cc.map(cell_off), v); cell_off++; }
+    uint32_t emit;     // 0: a root lane of a proof another rank emits (sharded) - values only; uniform over the wavefront (the lane table groups them)
+    HF void rec(int t, uint64_t a, uint64_t b, uint64_t c, uint64_t d) { if (emit) g_store_rec(recs + nrec, a, b, c, d); nrec++; cell_off += ncells[t]; }
+    HF void cell(const fr_t &v) { if (emit) g_store_fr(out + cc.map(cell_off), v); cell_off++; }
     HF void skip(uint64_t nr, uint64_t nc) { nrec += nr; cell_off += nc; }
 };
 typedef ValBackend<ReplaySink> RB;
@@ -133,12 +143,27 @@ __global__ __launch_bounds__(64) __attribute__((flatten)) void k_replay(ReplayAr
     t = (uint32_t)__builtin_amdgcn_readfirstlane((int)t);
     const TmplD T = R.tm[t];
     const uint32_t ninst = (uint32_t)__builtin_amdgcn_readfirstlane((int)T.ninst), tape0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)T.tape0), inst0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)T.inst0);
-    const uint32_t g = (blockIdx.x - R.blk0[t]) * 64 + lane;
-    if (g >= R.nproofs * ninst) return;
+    const uint32_t gl = (blockIdx.x - R.blk0[t]) * 64 + lane;
+    uint32_t g, emit = 1u;      // g = p * ninst + inst: the lane's place in the value store
+    if (R.lanes) {              // sharded: the lanes this rank owns; bit 31: a root lane of a proof it does not own; NO_SLOT: padding
+        const uint32_t base = R.lane0[t];
+        if (gl >= R.lane0[t + 1] - base) return;
+        const uint32_t e = R.lanes[base + gl];
+        if (e == NO_SLOT) return;
+        g = e & 0x7fffffffu; emit = (uint32_t)__builtin_amdgcn_readfirstlane((int)((e >> 31) ^ 1u));
+    } else { g = gl; if (g >= R.nproofs * ninst) return; }
     const uint32_t p = g / ninst, inst = g % ninst;
     const InstD *const I = R.insts + inst0 + inst;
     const uint32_t imp0 = I->imp0, in0 = I->in0;
-    ReplaySink sink; sink.recs = R.recs + (uint64_t)p * R.rec_stride; sink.out = R.out + (uint64_t)p * R.cell_stride; sink.ncells = s_nc; sink.cc.init(R.cm);
+    fr_t *outb = R.out + (uint64_t)p * R.cell_stride;
+    if (R.sh_compact) {         // the packed buffer: the lane's block (the root's: the prologue block) at its local start, its cells at their global offsets
+        const uint64_t W = R.sh_world, r = R.sh_rank, u0 = (uint64_t)p * R.nq, unit = I->unit;
+        const uint64_t units_before = (u0 + W - 1 - r) / W;
+        uint64_t local = (((uint64_t)p + W - 1 - r) / W) * R.pro_ncell + units_before * R.q_slot;
+        if (unit != NO_SLOT) local += ((uint64_t)p % W == r ? R.pro_ncell : 0) + ((u0 + unit + W - 1 - r) / W - units_before) * R.q_slot;
+        outb = R.out + local - I->ucell0;
+    }
+    ReplaySink sink; sink.recs = R.recs + (uint64_t)p * R.rec_stride; sink.out = outb; sink.ncells = s_nc; sink.cc.init(R.cm); sink.emit = emit;
     sink.nrec = I->rec0; sink.cell_off = I->cell0;
     ValCfg cfg; cfg.proof = R.proofs + (uint64_t)p * R.proof_words; cfg.mode = 1; cfg.L = R.L; cfg.P = R.P; cfg.inv_pos = R.inv_pos; cfg.inv_neg = R.inv_neg; cfg.st = nullptr;
     cfg.split = false; cfg.split_bn = false; cfg.load_items = nullptr; cfg.n_load_items = 0; cfg.load_nrec = cfg.load_ncell = 0; cfg.n_cap_items = 0; cfg.fri = nullptr;
@@ -165,6 +190,7 @@ __global__ __launch_bounds__(64) __attribute__((flatten)) void k_replay(ReplayAr
     auto put64 = [&](uint32_t slot, uint64_t v) { if (slot != NO_SLOT) st1(slot, v); };
     auto putfr = [&](uint32_t slot, const fr_t &v) { if (slot != NO_SLOT) { st1(slot, v.l[0]); st1(slot + 1, v.l[1]); st1(slot + 2, v.l[2]); st1(slot + 3, v.l[3]); } };
     uint64_t ta[64], tb[64];
+    bool bad_word = false;
     // The op at pc sits in eight scalar registers (a window of the tape); the window of the NEXT op is requested before this one runs: a scalar load
     // waited for where it is used was ~200 cycles, five times per op.  (Ops with operand lists read the words beyond the window themselves.)
     uint32_t pc = tape0;
@@ -221,18 +247,28 @@ __global__ __launch_bounds__(64) __attribute__((flatten)) void k_replay(ReplayAr
                     q += 4;
                     const uint32_t na = tw(tape, q), nb = tw(tape, q + 1), nc = tw(tape, q + 2), no = tw(tape, q + 3);      // (past the last op: the next op's first words, unused)
                     const uint64_t A = get64(a, 0), B = get64(b, 0), C = get64(c, 0);
-                    g_store_rec(rp, A, B, C, 0); rp++; st1(o & 0xffffffu, gl_reduce128((u128)A * B + C));
+                    if (sink.emit) g_store_rec(rp, A, B, C, 0);
+                    rp++; st1(o & 0xffffffu, gl_reduce128((u128)A * B + C));
                     a = na; b = nb; c = nc; o = no;
                 }
                 sink.nrec += n; sink.cell_off += w1;
                 break;
             }
-            case DOP_FETCH: { for (uint32_t j = 0; j < n; j++) ring_put(w2 + j, slow_get64(w1, j, vals_g, Lt, p, imp0, in0, proof)); break; }      // a far operand into the ring (no write-through: a copy)
+            case DOP_FETCH: {      // a far operand into the ring (no write-through: a copy)
+                bool ge = true;        // a proof word (every one enters here): at least the modulus of its field (one word: Goldilocks, four: BN254)?
+                for (uint32_t j = 0; j < n; j++) {
+                    const uint64_t x = slow_get64(w1, j, vals_g, Lt, p, imp0, in0, proof), m = n == 1 ? GL_P : fr_mod_limb((int)j);
+                    ring_put(w2 + j, x); ge = x > m || (x == m && ge);
+                }
+                if (ref_kind(w1) == RK_INPUT && ge) bad_word = true;      // status 4 (as k_prologue_load); the cells still come from the raw value
+                break;
+            }
             default: be.fail(99); break;      // (unreachable: the lowering emits nothing else)
         }
         pc = pcn; w0 = n0; w1 = n1; w2 = n2; w3 = n3; w4 = n4;
     }
     if (be.status) atomicCAS(&R.status[p], 0u, be.status);
+    if (bad_word) atomicOr(&R.lflag[p], 4u);
 }
 
 // ------------------------------------------------------------------------------------------------------------------- host: lowering
@@ -241,7 +277,8 @@ struct SegInfo {
     int parent = -1, depth = 0; uint32_t name = 0;
     std::vector<uint32_t> tape; uint32_t nslots = 0; std::vector<ImpD> imps /* tmpl field holds the producer SEGMENT until templates exist */; std::vector<uint32_t> inputs;
     std::map<std::pair<uint32_t, uint32_t>, uint32_t> imp_of;
-    uint64_t cell0 = 0, rec0 = 0, ncells = 0, nrecs = 0; bool started = false;
+    uint64_t cell0 = 0, rec0 = 0, ncells = 0, nrecs = 0, all_recs = 0; bool started = false;      // all_recs: with the nested segments' (ncells includes them)
+    uint32_t unit = NO_SLOT;      // the depth-1 instance (shard unit) this segment is or lies in
     int tmpl = -1; uint32_t inst = 0;
     long last_const_at = -1; uint64_t last_const_cell = 0;      // the op emitted last is a static CONST1 (its tape position, its cell): a GLOP right behind it that takes it as operand A fuses with it
 };
@@ -253,8 +290,9 @@ using namespace h2w;
 
 namespace h2w {
 uint64_t traced_workspace_bytes(const h2w_plan *p, uint64_t n);
-int traced_run(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void *advice_dev, void *workspace_dev, void *stream_, ColMap cm, uint64_t cell_stride);
+int traced_run(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void *advice_dev, void *workspace_dev, void *stream_, ColMap cm, uint64_t cell_stride, const ShardSpec &sh);
 void traced_free(h2w_plan *p);
+const char *traced_shard_refusal(const h2w_plan *p) { return p->traced && !p->traced->why_unshardable.empty() ? p->traced->why_unshardable.c_str() : nullptr; }
 struct TracedWs { size_t recs, status, lflag, ctr, vals, total; };
 static size_t al(size_t x) { return (x + 255) / 256 * 256; }
 static TracedWs traced_ws(const h2w_plan *p, uint64_t n) {
@@ -271,31 +309,71 @@ void traced_free(h2w_plan *p) {
     if (t->d_tm) (void)hipFree(t->d_tm); if (t->d_prefix) (void)hipFree(t->d_prefix);
     if (t->d_tape) (void)hipFree(t->d_tape); if (t->d_insts) (void)hipFree(t->d_insts); if (t->d_imps) (void)hipFree(t->d_imps);
     if (t->d_inputs) (void)hipFree(t->d_inputs); if (t->d_pool64) (void)hipFree(t->d_pool64); if (t->d_poolfr) (void)hipFree(t->d_poolfr);
+    if (t->d_lanes) (void)hipFree(t->d_lanes);
     delete t; p->traced = nullptr;
 }
-int traced_run(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void *advice_dev, void *workspace_dev, void *stream_, ColMap cm, uint64_t cell_stride) {
+// The lanes a rank launches (sharded calls), template by template: the root lane of every proof - those of the proofs the rank owns first, then, from
+// the next wavefront on, the others marked with bit 31 (they compute the values the units import, and store nothing else) -, and of every deeper
+// template only the (proof, instance) pairs whose unit (proof * nq + q) % world == rank (h2w_plan_shard_block, distributed.py unit_owner).
+static int lane_table(h2w_plan *p, uint64_t n, const ShardSpec &sh) {
+    TracedPlan *t = p->traced;
+    if (t->d_lanes && t->lanes_n == n && t->lanes_rank == sh.rank && t->lanes_world == sh.world) return 0;
+    const uint64_t W = (uint64_t)sh.world, r = (uint64_t)sh.rank, nq = (uint64_t)p->shape.num_queries;
+    std::vector<uint32_t> &L = t->h_lanes; L.clear(); t->lane0.assign(t->tmpls.size() + 1, 0);
+    for (size_t i = 0; i < t->tmpls.size(); i++) {
+        const TmplD &T = t->tmpls[i]; t->lane0[i] = (uint32_t)L.size();
+        if (n * T.ninst >= 0x80000000ull) { set_error("h2w_fri_witness_batch_shard: too many (proof, instance) lanes in one call"); return -1; }
+        if (T.depth == 0) {
+            for (uint64_t pr = r; pr < n; pr += W) L.push_back((uint32_t)pr);
+            while ((L.size() - t->lane0[i]) % 64) L.push_back(NO_SLOT);
+            for (uint64_t pr = 0; pr < n; pr++) if (pr % W != r) L.push_back((uint32_t)pr | 0x80000000u);
+        } else
+            for (uint64_t pr = 0; pr < n; pr++)
+                for (uint32_t k = 0; k < T.ninst; k++) if ((pr * nq + t->h_unit[T.inst0 + k]) % W == r) L.push_back((uint32_t)(pr * T.ninst + k));
+    }
+    t->lane0[t->tmpls.size()] = (uint32_t)L.size();
+    H2W_HIP(hipDeviceSynchronize());      // a previous call may still read the old table (plans are single-threaded handles, include/h2w.h)
+    if (t->d_lanes) { (void)hipFree(t->d_lanes); t->d_lanes = nullptr; }
+    H2W_HIP(hipMalloc((void **)&t->d_lanes, (L.empty() ? 1 : L.size()) * 4));
+    if (!L.empty()) H2W_HIP(hipMemcpy(t->d_lanes, L.data(), L.size() * 4, hipMemcpyHostToDevice));
+    t->lanes_n = n; t->lanes_rank = sh.rank; t->lanes_world = sh.world;
+    return 0;
+}
+int traced_run(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void *advice_dev, void *workspace_dev, void *stream_, ColMap cm, uint64_t cell_stride, const ShardSpec &sh) {
     TracedPlan *t = p->traced;
     if (n_proofs > 65535) { set_error("h2w_fri_witness_batch: more than 65535 proofs per call"); return -1; }
+    const bool sharded = sh.world > 1;
+    if ((sharded || sh.compact) && !t->why_unshardable.empty()) { set_error("h2w_fri_witness_batch_shard: " + t->why_unshardable); return -1; }
+    if (sh.compact && !sharded) { set_error("h2w_fri_witness_batch_shard_compact: world 1 on a traced plan: use h2w_fri_witness_batch (the packed form of one rank is the flat stream)"); return -1; }
     DeviceGuard dg(p->device);
+    if (sharded && lane_table(p, n_proofs, sh) != 0) return -1;
     hipStream_t stream = (hipStream_t)stream_;
     const TracedWs wl = traced_ws(p, n_proofs); char *ws = (char *)workspace_dev;
     ReplayArgs R; memset(&R, 0, sizeof(R));
     R.tape = t->d_tape; R.insts = t->d_insts; R.imps = t->d_imps; R.inputs = t->d_inputs; R.pool64 = t->d_pool64; R.poolfr = t->d_poolfr;
     R.proofs = proofs_dev; R.proof_words = p->pl.total; R.recs = (rec_t *)(ws + wl.recs); R.rec_stride = p->nrec; R.out = (fr_t *)advice_dev; R.cell_stride = cell_stride; R.cm = cm;      // (cm.starts: the FlexGate columns of every proof, cell_stride = ncols << k; else the flat stream)
     R.vals = (uint64_t *)(ws + wl.vals); R.status = (uint32_t *)(ws + wl.status); R.ncells = p->d_ncells; R.inv_pos = p->d_inv; R.inv_neg = p->d_inv + INV_TAB; R.P = p->P; R.L = p->shape.lookup_bits;
-    R.nproofs = (uint32_t)n_proofs;
+    R.nproofs = (uint32_t)n_proofs; R.lflag = (uint32_t *)(ws + wl.lflag);
     R.ntmpl = (uint32_t)t->tmpls.size(); R.tm = t->d_tm; R.prefix = t->d_prefix; R.npool64 = t->npool64; R.npoolfr = t->npoolfr;
+    if (sharded) {
+        R.lanes = t->d_lanes; for (size_t i = 0; i < t->lane0.size(); i++) R.lane0[i] = t->lane0[i];
+        R.sh_world = (uint32_t)sh.world; R.sh_rank = (uint32_t)sh.rank; R.sh_compact = (uint32_t)sh.compact; R.nq = (uint32_t)p->shape.num_queries;
+        R.pro_ncell = p->st.pro_ncell; R.q_slot = std::max(p->st.q_ncell[0], p->st.q_ncell[1]);
+    }
     H2W_HIP(hipMemsetAsync(ws + wl.status, 0, n_proofs * 4, stream));
     H2W_HIP(hipMemsetAsync(ws + wl.lflag, 0, n_proofs * 4, stream));
     uint32_t maxd = 0; for (const TmplD &T : t->tmpls) if (T.depth > maxd) maxd = T.depth;
     for (uint32_t d = 0; d <= maxd; d++) {      // a segment reads its ancestors' values: depth by depth; the templates of one depth in one launch
         uint32_t nb = 0;
-        for (size_t i = 0; i < t->tmpls.size(); i++) { R.blk0[i] = nb; if (t->tmpls[i].depth == d) nb += (uint32_t)((n_proofs * t->tmpls[i].ninst + 63) / 64); }
+        for (size_t i = 0; i < t->tmpls.size(); i++) {
+            R.blk0[i] = nb;
+            if (t->tmpls[i].depth == d) nb += (uint32_t)(((sharded ? t->lane0[i + 1] - t->lane0[i] : n_proofs * t->tmpls[i].ninst) + 63) / 64);
+        }
         R.blk0[t->tmpls.size()] = nb; R.depth = d;
         if (nb) hipLaunchKernelGGL(k_replay, dim3(nb), dim3(64), 0, stream, R);
     }
     // expansion of the block records
-    if (launch_plan_expand(p, n_proofs, R.recs, (uint32_t *)(ws + wl.ctr), R.out, cell_stride, cm, nullptr, 2, stream) != 0) return -1;
+    if (launch_plan_expand(p, n_proofs, R.recs, (uint32_t *)(ws + wl.ctr), R.out, cell_stride, cm, sharded ? &sh : nullptr, 2, stream) != 0) return -1;
     H2W_HIP(hipGetLastError());
     return 0;
 }
@@ -375,7 +453,7 @@ extern "C" h2w_plan *h2w_plan_from_trace(h2w_ctx *ctx, uint64_t proof_words, con
                 SegInfo &C = segs[(size_t)prev_seg]; C.ncells = o.cell0 - C.cell0; C.tape.push_back(DOP_END | (1u << 24));
                 // the child's totals include its own children's (they are nested in its cell and record ranges)
                 const uint64_t nr = nrec - C.rec0; uint32_t *w = S.tape.data() + open_child[(size_t)prev_seg];
-                w[0] = (uint32_t)nr; w[1] = (uint32_t)(nr >> 32); w[2] = (uint32_t)C.ncells; w[3] = (uint32_t)(C.ncells >> 32);
+                w[0] = (uint32_t)nr; w[1] = (uint32_t)(nr >> 32); w[2] = (uint32_t)C.ncells; w[3] = (uint32_t)(C.ncells >> 32); C.all_recs = nr;
             }
             prev_seg = s; continue;
         }
@@ -529,6 +607,28 @@ extern "C" h2w_plan *h2w_plan_from_trace(h2w_ctx *ctx, uint64_t proof_words, con
     }
     if (!err.empty()) { set_error("h2w_plan_from_trace: " + err); return nullptr; }
     segs[0].tape.push_back(DOP_END | (1u << 24)); segs[0].cell0 = 0; segs[0].rec0 = 0;
+    // ---- shard units: the depth-1 instances in tape order (unit q: the q-th; "verify_query_round" instance q of the standard trace, where the
+    // compiled plan's query block q starts: AbiBackend::query_begin).  Shardable: the root's block [0, unit 0) and the units back to back to the end
+    // of the stream and of the records, units 1.. all of one size (the compiled plan's StrandTable: query 0, a later query).
+    std::vector<int> units;
+    for (size_t si = 1; si < segs.size(); si++) {      // (a segment comes after its parent)
+        SegInfo &S = segs[si];
+        if (S.depth == 1) { S.unit = (uint32_t)units.size(); units.push_back((int)si); }
+        else S.unit = segs[(size_t)S.parent].unit;
+    }
+    std::string why_unshardable;
+    {
+        uint64_t c = units.empty() ? 0 : segs[(size_t)units[0]].cell0, r = units.empty() ? 0 : segs[(size_t)units[0]].rec0;
+        for (size_t q = 0; q < units.size() && why_unshardable.empty(); q++) {
+            const SegInfo &U = segs[(size_t)units[q]], &U1 = segs[(size_t)units[q > 1 ? 1 : q]];
+            if (U.cell0 != c || U.rec0 != r) why_unshardable = "the root has cells or records between parallel instances " + std::to_string(q ? q - 1 : 0) + " and " + std::to_string(q) + " at depth 1";
+            else if (U.ncells != U1.ncells || U.all_recs != U1.all_recs) why_unshardable = "the parallel instances at depth 1 differ in size (instance " + std::to_string(q) + ")";
+            c += U.ncells; r += U.all_recs;
+        }
+        if (units.empty()) why_unshardable = "no parallel scope instance at depth 1 (trace the query rounds as parallel: \"verify_query_round\")";
+        else if (why_unshardable.empty() && (c != ctx_num_cells(ctx) || r != nrec)) why_unshardable = "the root has cells or records after the last parallel instance at depth 1";
+        if (!why_unshardable.empty()) why_unshardable = "the traced plan is not shardable: " + why_unshardable;
+    }
     // ---- consecutive Goldilocks-level ops -> runs (DOP_GLOPRUN)
     for (SegInfo &S : segs) {
         if (S.nslots >= (1u << 24)) continue;
@@ -571,6 +671,7 @@ extern "C" h2w_plan *h2w_plan_from_trace(h2w_ctx *ctx, uint64_t proof_words, con
             for (int si : members[t]) {
                 const SegInfo &S = segs[(size_t)si];
                 InstD I; I.cell0 = S.cell0; I.rec0 = S.rec0; I.imp0 = (uint32_t)imps.size(); I.in0 = (uint32_t)inputs.size();
+                I.unit = S.unit; I.ucell0 = S.unit == NO_SLOT ? 0 : segs[(size_t)units[S.unit]].cell0; I.pad = 0; tp->h_unit.push_back(S.unit);
                 for (const ImpD &m : S.imps) { const SegInfo &Pn = segs[(size_t)m.tmpl]; imps.push_back(ImpD{(uint32_t)Pn.tmpl, Pn.inst, m.slot}); }
                 inputs.insert(inputs.end(), S.inputs.begin(), S.inputs.end());
                 insts.push_back(I);
@@ -634,7 +735,7 @@ extern "C" h2w_plan *h2w_plan_from_trace(h2w_ctx *ctx, uint64_t proof_words, con
     }
     if (!err.empty()) { set_error("h2w_plan_from_trace: " + err); delete tp; return nullptr; }
     for (uint32_t w : inputs) if (w >= proof_words) { set_error("h2w_plan_from_trace: an input tag beyond proof_words"); delete tp; return nullptr; }
-    tp->n_ops = tr->ops.size(); tp->n_segments = segs.size();
+    tp->n_ops = tr->ops.size(); tp->n_segments = segs.size(); tp->why_unshardable = why_unshardable;
 
     // ---- the plan handle
     h2w_plan *pl = new h2w_plan(L);
@@ -642,6 +743,33 @@ extern "C" h2w_plan *h2w_plan_from_trace(h2w_ctx *ctx, uint64_t proof_words, con
     pl->device = device_id; pl->P = fr_params_init(); memset(&pl->st, 0, sizeof(pl->st)); memset(&pl->pl, 0, sizeof(pl->pl)); memset(&pl->d, 0, sizeof(pl->d));
     pl->pl.total = proof_words; pl->nrec = nrec; pl->ncells = ctx_num_cells(ctx); pl->traced = tp;
     for (uint64_t m : meta) pl->rec_cells += (uint64_t)pl->tt.ncells((int)meta_tmpl(m));
+    // the block structure (StrandTable: what h2w_plan_strand_layout / _shard_cells / _shard_block and the sharded expansion read): unshardable, one block
+    StrandTable &st = pl->st; st.first_zero_kind = -1; st.first_zero_unit = -1; st.total_rec = nrec; st.total_cell = pl->ncells;
+    if (why_unshardable.empty()) {
+        const SegInfo &U0 = segs[(size_t)units[0]], &U1 = segs[(size_t)units[units.size() > 1 ? 1 : 0]];
+        pl->shape.num_queries = (uint32_t)units.size();
+        st.pro_ncell = U0.cell0; st.pro_nrec = U0.rec0;
+        st.q_cell0[0] = U0.cell0; st.q_rec0[0] = U0.rec0; st.q_ncell[0] = U0.ncells; st.q_nrec[0] = U0.all_recs;
+        st.q_cell0[1] = U1.cell0; st.q_rec0[1] = U1.rec0; st.q_ncell[1] = U1.ncells; st.q_nrec[1] = U1.all_recs;
+    } else { st.pro_ncell = pl->ncells; st.pro_nrec = nrec; }
+    // keygen metadata (witness_gen_only = 0): the tracing context's own lists (keygen.h), as h2w_plan_metadata / h2w_plan_equalities hand them out
+    if (const MetaRecorder *mr = ctx_meta(ctx)) {
+        pl->sel_bits.assign((size_t)(pl->ncells + 7) / 8, 0); pl->lk_bits.assign(pl->sel_bits.size(), 0);
+        for (uint64_t c : mr->sel) if (c < pl->ncells) pl->sel_bits[c / 8] |= (uint8_t)(1u << (c & 7));
+        for (uint64_t c : mr->lookups) if (c < pl->ncells) pl->lk_bits[c / 8] |= (uint8_t)(1u << (c & 7));
+        for (uint8_t b : pl->sel_bits) pl->n_gates += (uint64_t)__builtin_popcount(b);
+        for (uint8_t b : pl->lk_bits) pl->n_lookups += (uint64_t)__builtin_popcount(b);
+        pl->meta_ready = true;
+        PlanEqualities &E = pl->eqs; E.pairs = mr->eq; E.const_cells = mr->ceq_cell; E.const_values = mr->ceq_val; E.const_word.assign(E.const_cells.size(), -1);
+        // proof words loaded as constants (Goldilocks-Poseidon hash wires, hash/poseidon/hash.rs:86-96): their constant equality takes the given proof's word
+        std::unordered_map<uint64_t, const TraceOp *> word_const;
+        for (const TraceOp &o : tr->ops) if (o.code == TR_LOAD_CONSTANT && o.tag.kind == 1) word_const[o.cell0] = &o;
+        for (size_t i = 0; i < E.const_cells.size(); i++) {
+            auto it = word_const.find(E.const_cells[i]);
+            if (it != word_const.end() && fr_eq(E.const_values[i], tr->consts[(size_t)it->second->imm])) E.const_word[i] = (int64_t)it->second->tag.word;
+        }
+        E.ready = true;
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { pl->device = -1; return pl; }      // layout queries only
     if (device_id < 0 || device_id >= ndev) { set_error("h2w_plan_from_trace: device_id out of range"); h2w_plan_free(pl); return nullptr; }

@@ -176,7 +176,17 @@ int h2w_chip_verify_stark(h2w_ctx *, const h2w_shape_t *, const h2w_poseidon_con
  * "verify_query_round", fri/mod.rs:488-501, and "verify_proof_to_cap_with_cap_index", merkle/mod.rs:57-78): each instance becomes a lane of the
  * device program.  The library VERIFIES the claim on the tape (an instance may read what its enclosing scopes computed before it and nothing else;
  * nothing outside reads what it computes) and fails otherwise.  The plan supports h2w_plan_num_cells / _proof_words / _num_records /
- * _workspace_bytes / _status, h2w_fri_witness_batch and h2w_plan_free. */
+ * _workspace_bytes / _status (4: a proof word outside its field, as a compiled plan reports it), h2w_fri_witness_batch, h2w_fri_witness_batch_columns
+ * and h2w_plan_free, and:
+ *   - (proof, query) sharding: the shard units are the instances of the parallel scopes at depth 1 ("verify_query_round": unit q = the q-th
+ *     instance in tape order, where the compiled plan's query block q starts), the prologue block is the root's.  h2w_plan_strand_layout /
+ *     _shard_cells / _shard_block / _shard_workspace_bytes, h2w_fri_witness_batch_shard and h2w_fri_witness_batch_shard_compact (world >= 2) work
+ *     as on the compiled plan of the shape, with its layout.  A plan whose depth-1 instances do not tile the stream behind the root's block (none,
+ *     or only "verify_proof_to_cap_with_cap_index" parallel) refuses every shard call, saying why; so does the packed call with world 1.
+ *   - keygen metadata, when the tracing context was created with witness_gen_only = 0 (the lists it recorded): h2w_plan_num_gates / _num_lookups /
+ *     _selectors / _lookup_cells / _num_equalities / _equalities / _num_const_equalities / _const_equalities (the proof-word constants of
+ *     Goldilocks-Poseidon caps taken from the proof passed in), and so h2w_check_constraints and h2w_layout_lookup_columns.  A plan traced with
+ *     witness_gen_only != 0 refuses them. */
 int h2w_ctx_trace_begin(h2w_ctx *);                                   /* on a fresh context */
 int h2w_trace_input(h2w_ctx *, uint64_t word, uint32_t n_words);      /* no-op on a context that is not tracing */
 h2w_plan *h2w_plan_from_trace(h2w_ctx *, uint64_t proof_words, const char *const *parallel_scopes, size_t n_scopes, int device_id);

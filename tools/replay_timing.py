@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Trace h2w_chip_verify_stark once, lower it, replay it on --batch proofs: wall time per launch (and, under rocprofv3 --kernel-trace, the duration of
-every k_replay dispatch: one per template, depth by depth).  usage: replay_timing.py [--config cfg3] [--hash bn254|gl] [--batch 64] [--reps 2]"""
+every k_replay dispatch: one per template, depth by depth).  usage: replay_timing.py [--config cfg3] [--hash bn254|gl] [--batch 64] [--reps 2]
+--world W --rank R: after the unsharded launches of --batch proofs, what rank R of W runs: a launch of W x batch proofs into its packed buffer
+(h2w_fri_witness_batch_shard_compact) - its own-cell rate beside the unsharded rate, and whether the buffer equals the compiled plan's packed buffer."""
 import argparse, importlib, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -10,6 +12,7 @@ CONFIGS = {"cfg1": (10, 4, 1), "cfg2": (16, 28, 2), "cfg3": (20, 28, 1), "cfg5":
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="cfg3"); ap.add_argument("--hash", default="bn254"); ap.add_argument("--batch", type=int, default=64); ap.add_argument("--reps", type=int, default=2); ap.add_argument("--streams", type=int, default=1)
+    ap.add_argument("--world", type=int, default=1); ap.add_argument("--rank", type=int, default=0)
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -20,12 +23,12 @@ def main():
     ref = api.Plan(sh, k, 0)
     words = ref.proof_words
     prng = np.random.default_rng(7)
-    host = prng.integers(0, 1 << 60, a.batch * words, dtype=np.int64)
+    host = prng.integers(0, 1 << 60, a.batch * max(a.world, 1) * words, dtype=np.int64)
     ctx = api.Context(21, True, 0); ctx.trace_begin()
     t0 = time.perf_counter(); api.verify_stark(ctx, sh, k, host[:words].astype(np.uint64)); t1 = time.perf_counter()
     plan = api.Plan.from_trace(ctx, words); t2 = time.perf_counter()
     ctx.close()
-    proofs = torch.from_numpy(host).cuda()
+    proofs = torch.from_numpy(host).cuda()      # (the unsharded launches take the first --batch)
     adv = torch.empty(a.batch * plan.num_cells * 32, dtype=torch.uint8, device="cuda"); ws = torch.zeros(plan.workspace_bytes(a.batch), dtype=torch.uint8, device="cuda")
     st = torch.cuda.current_stream().cuda_stream
     if a.streams > 1:      # launches in flight: the root kernel of one (two wavefronts) runs beside the other's Merkle lanes
@@ -48,8 +51,27 @@ def main():
     # tie to the compiled plan's stream of proof 0
     chk = torch.empty(ref.num_cells * 32, dtype=torch.uint8, device="cuda"); cws = torch.zeros(ref.workspace_bytes(1), dtype=torch.uint8, device="cuda")
     ref.run(proofs.data_ptr(), 1, chk.data_ptr(), cws.data_ptr(), st); torch.cuda.synchronize()
+    unsharded_rate = plan.num_cells * a.batch / (min(ms[1:]) * 1e-3) / 1e9
     print(json.dumps({"config": a.config, "hash": a.hash, "batch": a.batch, "trace_s": round(t1 - t0, 3), "lower_s": round(t2 - t1, 3), "records": plan.num_records, "ws_GB": round(plan.workspace_bytes(a.batch) / 1e9, 2),
-                      "ms_per_launch": [round(x, 2) for x in ms[1:]], "G_cells_per_s": round(plan.num_cells * a.batch / (min(ms[1:]) * 1e-3) / 1e9, 2), "proof0_equals_compiled_plan": bool(torch.equal(chk, adv[:ref.num_cells * 32]))}))
+                      "ms_per_launch": [round(x, 2) for x in ms[1:]], "G_cells_per_s": round(unsharded_rate, 2), "proof0_equals_compiled_plan": bool(torch.equal(chk, adv[:ref.num_cells * 32]))}))
+    if a.world > 1:
+        del adv, ws, chk, cws
+        n, W, R = a.batch * a.world, a.world, a.rank
+        cells = plan.shard_cells(n, R, W)
+        buf = torch.zeros((cells, 4), dtype=torch.int64, device="cuda"); ws = torch.zeros(plan.shard_workspace_bytes(n, R, W), dtype=torch.uint8, device="cuda")
+        ms = []
+        for i in range(a.reps + 1):
+            torch.cuda.synchronize(); t = time.perf_counter()
+            plan.run_shard_compact(proofs.data_ptr(), n, buf.data_ptr(), ws.data_ptr(), R, W, st)
+            torch.cuda.synchronize(); ms.append((time.perf_counter() - t) * 1e3)
+        ok = plan.status(ws.data_ptr(), n, st) == [0] * n
+        del ws
+        want = torch.zeros_like(buf); cws = torch.zeros(ref.shard_workspace_bytes(n, R, W), dtype=torch.uint8, device="cuda")
+        ref.run_shard_compact(proofs.data_ptr(), n, want.data_ptr(), cws.data_ptr(), R, W, st); torch.cuda.synchronize()      # (both zeroed: the slack of a query slot is written by neither)
+        own_rate = cells / (min(ms[1:]) * 1e-3) / 1e9
+        print(json.dumps({"config": a.config, "hash": a.hash, "world": W, "rank": R, "proofs_per_launch": n, "own_cells": cells, "ms_per_launch": [round(x, 2) for x in ms[1:]],
+                          "own_G_cells_per_s": round(own_rate, 2), "unsharded_G_cells_per_s": round(unsharded_rate, 2), "ratio": round(own_rate / unsharded_rate, 3), "status_ok": ok,
+                          "packed_equals_compiled_plan": bool(torch.equal(buf, want))}))
 
 
 if __name__ == "__main__":
