@@ -189,6 +189,8 @@ SYMBOLS = {
     "h2w_plan_shard_block": (C.c_int, [_vp, C.c_int, C.c_int, C.c_uint64, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "h2w_fri_witness_batch_shard_compact": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, _vp, C.c_int, C.c_int]),
     "h2w_plan_num_record_cells": (C.c_uint64, [_vp]),
+    "h2w_plan_direct_cells": (C.c_int, [_vp, _vp]),
+    "h2w_plan_record_ranges": (C.c_int, [_vp, _vp]),
     "h2w_prover_new": (_vp, [C.POINTER(Shape), C.POINTER(PoseidonConsts), C.c_int]),
     "h2w_prover_free": (None, [_vp]),
     "h2w_prover_num_polys": (C.c_uint64, [_vp]),

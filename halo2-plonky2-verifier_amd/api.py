@@ -11,6 +11,9 @@ from . import (Assigned, Fr, H2WError, PoseidonConsts, Shape, _ck, last_error, l
 
 GL_P = 0xFFFFFFFF00000001
 FR_MODULUS = 21888242871839275222246405745257275088548364400416034343698204186575808495617
+# Plan.configure options (include/h2w.h)
+OPT_FORK_CHAINS, OPT_SERIAL_EXPAND, OPT_CHAIN_PASSES, OPT_VALUES_FORM, OPT_OUTPUT_FORM = 1, 2, 3, 4, 5
+FORM_CANONICAL, FORM_MONTGOMERY = 0, 1      # OPT_OUTPUT_FORM: canonical little-endian Fr / v * 2^256 mod r (halo2curves' in-memory form)
 
 
 class Context:
@@ -307,6 +310,26 @@ class Plan:
 
     def configure(self, option, value):
         _ck(self.L.h2w_plan_configure(self.p, option, value), "h2w_plan_configure")
+
+    def set_output_form(self, form):
+        """FORM_CANONICAL (default) or FORM_MONTGOMERY: every cell the plan's batch calls write holds v * 2^256 mod r, halo2curves' bn256::Fr as it
+        lies in memory (H2W_OPT_OUTPUT_FORM; not for traced plans)."""
+        self.configure(OPT_OUTPUT_FORM, form)
+
+    def direct_cells(self):
+        """One bit per cell (numpy uint8 bitmap, bit i of byte i // 8): the cell is written by a value kernel itself, not by the expansion kernel."""
+        import numpy as np
+        bm = np.zeros((self.num_cells + 7) // 8, dtype=np.uint8)
+        _ck(self.L.h2w_plan_direct_cells(self.p, bm.ctypes.data), "h2w_plan_direct_cells")
+        return bm
+
+    def record_ranges(self):
+        """numpy uint64 [num_records][2]: first cell and number of cells of every block record (what the expansion kernel writes)."""
+        import numpy as np
+        n = int(self.L.h2w_plan_num_records(self.p))
+        out = np.zeros((n, 2), dtype=np.uint64)
+        _ck(self.L.h2w_plan_record_ranges(self.p, out.ctypes.data), "h2w_plan_record_ranges")
+        return out
 
     def expand_records(self, n, advice_ptr, workspace_ptr, stream=0):
         """The expansion kernel alone over the records a previous run() left in the workspace (measurement)."""

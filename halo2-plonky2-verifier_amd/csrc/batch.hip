@@ -39,6 +39,7 @@ struct PlanSink : SinkBase {
     void glp_note() { nglp++; }
     // keygen metadata pass (h2w_plan_metadata): one bit per cell, set from the template slot flags / the backend's G()/LK() markers
     std::vector<uint8_t> *sel_bits = nullptr, *lk_bits = nullptr; uint8_t pend = 0;
+    std::vector<uint64_t> *direct = nullptr;      // one bit per cell: written by a value kernel itself, not by the expansion kernel (H2W_OPT_OUTPUT_FORM)
     void mark(uint64_t cell, uint8_t f) {
         if (f & CF_GATE) { if (sel_bits->size() <= cell / 8) sel_bits->resize(cell / 8 + 4096, 0); (*sel_bits)[cell / 8] |= (uint8_t)(1u << (cell & 7)); }
         if (f & CF_LOOKUP) { if (lk_bits->size() <= cell / 8) lk_bits->resize(cell / 8 + 4096, 0); (*lk_bits)[cell / 8] |= (uint8_t)(1u << (cell & 7)); }
@@ -50,7 +51,11 @@ struct PlanSink : SinkBase {
         if (sel_bits) { const tmpl_info_t &ti = tt->info[t]; for (int i = 0; i < ti.ncells; i++) { const uint8_t f = tt->slot_flags[ti.slot_base + i]; if (f) mark(cell_off + i, f); } }
         nrec++; cell_off += (uint64_t)tt->ncells(t);
     }
-    void cell(const fr_t &) { if (sel_bits && pend) mark(cell_off, pend); pend = 0; cell_off++; }
+    void cell(const fr_t &) {
+        if (sel_bits && pend) mark(cell_off, pend);
+        if (direct) { if (direct->size() <= cell_off / 64) direct->resize(cell_off / 64 + 65536, 0); (*direct)[cell_off / 64] |= 1ull << (cell_off & 63); }
+        pend = 0; cell_off++;
+    }
     void skip(uint64_t, uint64_t) {}
     void merkle_begin(int, int, bool zc, uint64_t) { mk_rec0 = nrec; mk_cell0 = cell_off; mk_zc = zc; mk_unit0 = nunit; mk_glp0 = nglp; }
     void merkle_end(int q, int kind, bool zc) {
@@ -169,6 +174,50 @@ template <bool COLS> __global__ __launch_bounds__(QUAD_BLOCK) H2W_QUAD_ATTR void
     Sink sink;
     quad_strand<QuadB>(A, sink, idx, p, q, kind);
 }
+// H2W_OPT_OUTPUT_FORM = Montgomery, the direct cells: the cells of a proof's stream that the value kernels wrote themselves (canonical; the plan's bitmap)
+// get the full product, in place, at the address their writer used - column shift, and with (proof, query) sharding only the blocks of this rank, at their
+// packed addresses in the compact form.  A wavefront takes 64 words of the bitmap (4,096 cells) and walks the words that have a bit set, lane = cell.
+struct DirectArgs {
+    const uint64_t *bits; uint64_t ncells; fr_t *out; uint64_t cell_stride; ColMap cm;
+    int rank, world, compact; uint32_t nq; uint64_t pro_ncell, q_cell0_first, q_cell0_rest, q_ncell_rest, q_slot;
+    fr_t kconst; uint64_t ninv;
+};
+template <bool COLS> __global__ __launch_bounds__(256) void k_direct_to_montgomery(DirectArgs D) {
+    const uint64_t p = blockIdx.y; const int lane = threadIdx.x & 63;
+    const uint64_t nwords = (D.ncells + 63) / 64, w0 = ((uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 64;
+    if (w0 >= nwords) return;
+    const unsigned long long mine = w0 + (uint64_t)lane < nwords ? g_load_u64(D.bits + w0 + lane) : 0ull;
+    ColPolicy<COLS> cc; cc.init(D.cm);
+    unsigned long long nz = __ballot(mine != 0);
+    while (nz) {
+        const int k = __ffsll((long long)nz) - 1; nz &= nz - 1;
+        const unsigned long long word = __shfl(mine, k, 64);      // (before any lane leaves the iteration: nz and k are wavefront-uniform, every lane reaches this)
+        if (!((word >> lane) & 1)) continue;
+        const uint64_t cell = (w0 + (uint64_t)k) * 64 + (uint64_t)lane;
+        fr_t *base = D.out + p * D.cell_stride;
+        if (D.world > 1) {      // the block of the cell: prologue (q < 0) or query q; batchargs.h block_out
+            const uint64_t W = (uint64_t)D.world, r = (uint64_t)D.rank, u0 = p * D.nq;
+            long long q = -1;
+            if (cell >= D.pro_ncell) {
+                q = (D.nq == 1 || cell < D.q_cell0_rest) ? 0 : 1 + (long long)((cell - D.q_cell0_rest) / (D.q_ncell_rest ? D.q_ncell_rest : 1));
+                if (q >= (long long)D.nq) q = (long long)D.nq - 1;
+            }
+            if ((q < 0 ? p : u0 + (uint64_t)q) % W != r) continue;
+            if (D.compact) {
+                const uint64_t pro_before = (p + W - 1 - r) / W, units_before = (u0 + W - 1 - r) / W;
+                uint64_t local = pro_before * D.pro_ncell + units_before * D.q_slot, global = 0;
+                if (q >= 0) {
+                    if (p % W == r) local += D.pro_ncell;
+                    local += ((u0 + (uint64_t)q + W - 1 - r) / W - units_before) * D.q_slot;
+                    global = q == 0 ? D.q_cell0_first : D.q_cell0_rest + (uint64_t)(q - 1) * D.q_ncell_rest;
+                }
+                base = D.out + local - global;
+            }
+        }
+        fr_t *at = base + cc.map(cell);
+        g_store_fr(at, fr_mont_mul(g_load_fr(at), D.kconst, D.ninv));
+    }
+}
 __global__ void k_digest(const ulonglong4 *cells, uint64_t n, unsigned long long *out4) {
     unsigned long long a0 = 0, a1 = 0, a2 = 0, a3 = 0;
     for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
@@ -218,6 +267,7 @@ h2w_plan *h2w_plan_compile(const h2w_shape_t *shape, const h2w_poseidon_consts_t
     std::vector<uint64_t> meta; std::vector<uint64_t> zero_proof(pl->pl.total, 0);
     {
         PlanSink sink; sink.meta = &meta; sink.tt = &pl->tt; sink.st = &pl->st; sink.unit_cell = &unit_cell; sink.items = &items; sink.cap_items = &cap_items;
+        sink.direct = &pl->direct_bits;
         ValCfg cfg; cfg.proof = zero_proof.data(); cfg.mode = s.hash_mode; cfg.L = s.lookup_bits; cfg.P = pl->P;
         cfg.inv_pos = inv.data(); cfg.inv_neg = inv.data() + INV_TAB; cfg.st = nullptr; cfg.split = false; cfg.split_bn = false; cfg.load_items = nullptr; cfg.n_load_items = 0; cfg.load_nrec = cfg.load_ncell = 0;
         ValBackend<PlanSink> be(sink, cfg, false);
@@ -233,6 +283,8 @@ h2w_plan *h2w_plan_compile(const h2w_shape_t *shape, const h2w_poseidon_consts_t
             pl->load_nrec = last.rec + last_nrec - items.front().rec; pl->load_ncell = last.cell + last_ncell - items.front().cell;
         }
         pl->nrec = sink.nrec; pl->ncells = sink.cell_off; pl->nunit = sink.nunit; pl->st.total_unit = sink.nunit;
+        pl->direct_bits.resize((size_t)(((pl->ncells + 63) / 64 + 63) / 64 * 64), 0);
+        for (uint64_t w : pl->direct_bits) pl->n_direct += (uint64_t)__builtin_popcountll(w);
         for (uint64_t m : meta) pl->rec_cells += (uint64_t)pl->tt.ncells((int)meta_tmpl(m));
         pl->st.pro_nrec = pl->st.q_rec0[0]; pl->st.pro_ncell = pl->st.q_cell0[0]; pl->st.total_rec = sink.nrec; pl->st.total_cell = sink.cell_off;
         if (s.num_queries == 1) {
@@ -257,7 +309,7 @@ h2w_plan *h2w_plan_compile(const h2w_shape_t *shape, const h2w_poseidon_consts_t
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
         // no GPU: the plan is still usable for layout queries (cells, records, proof words); batch calls fail.
-        pl->device = -1; return pl;
+        pl->device = -1; pl->h_meta.swap(meta); return pl;      // (h2w_plan_record_ranges: with a device it reads d_meta back)
     }
     if (device_id < 0 || device_id >= ndev) { set_error("h2w_plan_compile: device_id out of range"); delete pl; return nullptr; }
     DeviceGuard dg(device_id);
@@ -323,6 +375,8 @@ void h2w_plan_free(h2w_plan *p) {
     if (p->d_lookup_cells) (void)hipFree(p->d_lookup_cells);
     if (p->d_sel_bits) (void)hipFree(p->d_sel_bits);
     if (p->d_col_tab) (void)hipFree(p->d_col_tab);
+    if (p->d_direct_bits) (void)hipFree(p->d_direct_bits);
+    if (p->d_mont) (void)hipFree(p->d_mont);
     if (p->ev_ready) for (int r = 0; r < h2w_plan::EV_RING; r++) for (int i = 0; i < h2w_plan::N_EV; i++) (void)hipEventDestroy(p->evr[r][i]);
     for (int i = 0; i < p->n_side; i++) (void)hipStreamDestroy(p->side[i]);
     p->dt.free();
@@ -332,6 +386,24 @@ uint64_t h2w_plan_num_cells(const h2w_plan *p) { return p ? p->ncells : 0; }
 uint64_t h2w_plan_proof_words(const h2w_plan *p) { return p ? p->pl.total : 0; }
 uint64_t h2w_plan_num_records(const h2w_plan *p) { return p ? p->nrec : 0; }
 uint64_t h2w_plan_num_record_cells(const h2w_plan *p) { return p ? p->rec_cells : 0; }
+int h2w_plan_direct_cells(const h2w_plan *p, uint8_t *bitmap) {
+    if (!p || !bitmap) { set_error("h2w_plan_direct_cells: null argument"); return -1; }
+    if (p->traced) { set_error("h2w_plan_direct_cells: not for traced plans"); return -1; }
+    for (uint64_t i = 0; i < (p->ncells + 7) / 8; i++) bitmap[i] = (uint8_t)(p->direct_bits[i / 8] >> (8 * (i & 7)));
+    return 0;
+}
+int h2w_plan_record_ranges(const h2w_plan *p, uint64_t *ranges) {
+    if (!p || !ranges) { set_error("h2w_plan_record_ranges: null argument"); return -1; }
+    if (p->traced) { set_error("h2w_plan_record_ranges: not for traced plans"); return -1; }
+    std::vector<uint64_t> back; const uint64_t *m = p->h_meta.data();
+    if (p->device >= 0) {
+        DeviceGuard dg(p->device); back.resize((size_t)p->nrec);
+        H2W_HIP(hipMemcpy(back.data(), p->d_meta, back.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        m = back.data();
+    }
+    for (uint64_t i = 0; i < p->nrec; i++) { ranges[2 * i] = meta_off(m[i]); ranges[2 * i + 1] = (uint64_t)p->tt.ncells((int)meta_tmpl(m[i])); }
+    return 0;
+}
 int h2w_plan_strand_layout(const h2w_plan *p, uint64_t out[4]) {
     if (!p || !out) { set_error("h2w_plan_strand_layout: null argument"); return -1; }
     out[0] = p->st.pro_ncell; out[1] = p->st.q_ncell[0]; out[2] = p->shape.num_queries > 1 ? p->st.q_ncell[1] : p->st.q_ncell[0]; out[3] = p->ncells;
@@ -372,6 +444,8 @@ uint64_t h2w_plan_shard_workspace_bytes(const h2w_plan *p, uint64_t n_proofs, in
     return ws_layout(p, n_proofs, sh).total;
 }
 static int run_batch(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void *advice_dev, void *workspace_dev, void *stream_, void *emit_stream_, ColMap cm, uint64_t cell_stride, ShardSpec sh = ShardSpec());
+// 2^(256 + 261) mod r: the device product divides by 2^261, so a product with this constant is the Montgomery form with R = 2^256
+static const fr_t &mont_k() { static const fr_t K = [] { fr_t x = fr_from_u64(1); for (int i = 0; i < 256 + FR_MONT_BITS; i++) x = fr_add(x, x); return x; }(); return K; }
 int h2w_fri_witness_batch(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void *advice_dev, void *workspace_dev, void *stream_) {
     ColMap flat; flat.starts = nullptr; flat.ncols = 0; flat.k = 0;
     return run_batch(p, proofs_dev, n_proofs, advice_dev, workspace_dev, stream_, stream_, flat, p ? p->ncells : 0);
@@ -470,7 +544,7 @@ int h2w::launch_plan_expand(const h2w_plan *p, uint64_t n_proofs, const rec_t *r
     E.meta = p->d_meta; E.recs = recs; E.nrec = p->nrec; E.rec_stride = p->nrec; E.out = out; E.cell_stride = cell_stride; E.pool = nullptr; E.cm = cm;
     if (sh) fill_expand_shard(p, E, *sh); else expand_unsharded(E);
     p->dt.fill(E);
-    E.tile_ctr = tile_ctr; E.roam_per_cu = roam_per_cu;
+    E.tile_ctr = tile_ctr; E.roam_per_cu = roam_per_cu; E.mont = p->output_form == H2W_FORM_MONTGOMERY ? p->d_mont : nullptr;
     H2W_HIP(hipMemsetAsync(tile_ctr, 0, n_proofs * sizeof(uint32_t), stream));
     int gx = (int)(2048 / (n_proofs < 2048 ? n_proofs : 2048)); if (gx < 8) gx = 8;
     return launch_expand(E, n_proofs, gx, stream);
@@ -601,10 +675,26 @@ static int run_batch(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs,
         if (p->serial_expand != 0 && prev_ev) H2W_HIP(hipStreamWaitEvent(estream, prev_ev[H2W_EV_EXPAND_END], 0));
         H2W_HIP(hipEventRecord(ev[H2W_EV_EXPAND_START], estream));
         if (launch_plan_expand(p, n_proofs, A.recs, (uint32_t *)(ws + wl.ctr), A.out, cell_stride, cm, &sh,
-                               p->shape.hash_mode == 0 ? 2 : 1, estream) != 0) return -1;      // roam_per_cu: profiles/r02_expand_grid.txt
+                               (p->shape.hash_mode == 0 || p->output_form == H2W_FORM_MONTGOMERY) ? 2 : 1, estream) != 0) return -1;      // roam_per_cu: profiles/r02_expand_grid.txt;
+                               // the Montgomery form's kernel is bound by instruction issue, not by stores: it needs every wavefront a CU holds (profiles/montgomery_form_cfg3.json)
         H2W_HIP(hipEventRecord(ev[H2W_EV_EXPAND_END], estream));
+        // 6. Montgomery form: the direct cells, behind the chain kernels on the stream they ran on, beside the expansion kernel (which converts its own cells
+        //    as it writes them).  The glue strands' and the prologue's direct cells were written on the caller's stream: the side stream waits for them.
+        const bool mont = p->output_form == H2W_FORM_MONTGOMERY;
+        if (mont) {
+            if (cstream != stream) { H2W_HIP(hipStreamWaitEvent(cstream, ev[H2W_EV_GLUE_END], 0)); forked = true; }
+            DirectArgs D;
+            D.bits = p->d_direct_bits; D.ncells = p->ncells; D.out = A.out; D.cell_stride = cell_stride; D.cm = cm;
+            D.rank = sh.rank; D.world = sh.world; D.compact = sh.compact; D.nq = (uint32_t)p->shape.num_queries;
+            D.pro_ncell = p->st.pro_ncell; D.q_cell0_first = p->st.q_cell0[0]; D.q_cell0_rest = p->st.q_cell0[1]; D.q_ncell_rest = p->st.q_ncell[1]; D.q_slot = shard_q_slot(p);
+            D.kconst = mont_k(); D.ninv = p->P.ninv;
+            const uint64_t nwaves = ((p->ncells + 63) / 64 + 63) / 64;
+            const dim3 dgrid((unsigned)((nwaves + 3) / 4), (unsigned)n_proofs);
+            if (cm.starts) hipLaunchKernelGGL(k_direct_to_montgomery<true>, dgrid, dim3(256), 0, cstream, D); else hipLaunchKernelGGL(k_direct_to_montgomery<false>, dgrid, dim3(256), 0, cstream, D);
+            if (cstream != stream) H2W_HIP(hipEventRecord(ev[h2w_plan::EV_DIRECT_END], cstream));
+        }
         if (estream != stream) H2W_HIP(hipStreamWaitEvent(stream, ev[H2W_EV_EXPAND_END], 0));    // the caller's stream completes when the advice is complete
-        if (forked) { H2W_HIP(hipStreamWaitEvent(stream, ev[H2W_EV_CHAINS_END], 0)); forked = false; }
+        if (forked) { H2W_HIP(hipStreamWaitEvent(stream, ev[mont ? (int)h2w_plan::EV_DIRECT_END : (int)H2W_EV_CHAINS_END], 0)); forked = false; }
         H2W_HIP(hipEventRecord(ev[H2W_EV_CALL_END], stream));
         H2W_HIP(hipGetLastError());
         return 0;
@@ -631,7 +721,7 @@ int h2w_fri_expand_records(h2w_plan *p, uint64_t n_proofs, void *advice_dev, voi
     char *ws = (char *)workspace_dev;
     const ShardSpec one_rank{};
     if (launch_plan_expand(p, n_proofs, (rec_t *)(ws + wl.recs), (uint32_t *)(ws + wl.ctr), (fr_t *)advice_dev, p->ncells, ColMap{nullptr, 0, 0}, &one_rank,
-                           p->shape.hash_mode == 0 ? 2 : 1, stream) != 0) return -1;      // (as run_batch)
+                           (p->shape.hash_mode == 0 || p->output_form == H2W_FORM_MONTGOMERY) ? 2 : 1, stream) != 0) return -1;      // (as run_batch)
     H2W_HIP(hipGetLastError());
     return 0;
 }
@@ -887,8 +977,7 @@ int h2w_advice_to_montgomery(void *cells_dev, uint64_t n_cells, void *stream_) {
     if (n_cells == 0) return 0;
     DeviceGuard dg(device_of(cells_dev));
     static const FrParams P = fr_params_init();
-    static const fr_t K = [] { fr_t x = fr_from_u64(1); for (int i = 0; i < 256 + FR_MONT_BITS; i++) x = fr_add(x, x); return x; }();
-    hipLaunchKernelGGL(k_to_montgomery, dim3(4096), dim3(256), 0, (hipStream_t)stream_, (fr_t *)cells_dev, n_cells, K, P.ninv);
+    hipLaunchKernelGGL(k_to_montgomery, dim3(4096), dim3(256), 0, (hipStream_t)stream_, (fr_t *)cells_dev, n_cells, mont_k(), P.ninv);
     H2W_HIP(hipGetLastError());
     return 0;
 }
@@ -936,6 +1025,25 @@ int h2w_plan_configure(h2w_plan *p, int option, int value) {
     if (option == H2W_OPT_SERIAL_EXPAND) { p->serial_expand = value != 0; return 0; }      // (negative: the default, on)
     if (option == H2W_OPT_VALUES_FORM) { if (value < 0 || value > 2) { set_error("h2w_plan_configure: H2W_OPT_VALUES_FORM is 0 (by launch size), 1 (four lanes per path) or 2 (one wavefront per path)"); return -1; } p->values_form = value; return 0; }
     if (option == H2W_OPT_CHAIN_PASSES) { if (value < 0 || value > 2) { set_error("h2w_plan_configure: H2W_OPT_CHAIN_PASSES is 0 (by launch size), 1 or 2"); return -1; } p->chain_passes = value; return 0; }
+    if (option == H2W_OPT_OUTPUT_FORM) {
+        if (value != H2W_FORM_CANONICAL && value != H2W_FORM_MONTGOMERY) { set_error("h2w_plan_configure: H2W_OPT_OUTPUT_FORM is 0 (canonical cells) or 1 (Montgomery form, R = 2^256)"); return -1; }
+        if (value == H2W_FORM_MONTGOMERY && p->traced) { set_error("h2w_plan_configure: a traced plan (h2w_plan_from_trace) writes canonical cells only; convert its stream with h2w_advice_to_montgomery"); return -1; }
+        if (value == H2W_FORM_MONTGOMERY && p->device >= 0 && !p->d_mont) {      // first use: the form's constants (derived from r) and the direct-cell bitmap
+            DeviceGuard dg(p->device);
+            MontForm K; montform_init(K, p->tt.rb);
+            uint64_t *bits = nullptr; MontForm *d = nullptr;
+            auto up = [&]() -> int {
+                H2W_HIP(hipMalloc((void **)&bits, p->direct_bits.size() * sizeof(uint64_t)));
+                H2W_HIP(hipMemcpy(bits, p->direct_bits.data(), p->direct_bits.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+                H2W_HIP(hipMalloc((void **)&d, sizeof(MontForm)));
+                H2W_HIP(hipMemcpy(d, &K, sizeof(MontForm), hipMemcpyHostToDevice));
+                return 0;
+            };
+            if (up() != 0) { if (bits) (void)hipFree(bits); if (d) (void)hipFree(d); return -1; }      // (nothing kept: the next call starts over)
+            p->d_direct_bits = bits; p->d_mont = d;
+        }
+        p->output_form = value; return 0;
+    }
     set_error("h2w_plan_configure: unknown option"); return -1;
 }
 

@@ -43,6 +43,7 @@ uint64_t plan_cells(const h2w_plan *);
 bool plan_traced(const h2w_plan *);
 
 // arguments of the expansion kernel (expand.hip)
+struct MontForm;      // montform.h
 struct ExpandArgs {
     const uint64_t *meta;      // [nrec] template id << 56 | first cell offset (per proof, shared by the batch)
     const rec_t *recs;         // [nproofs][rec_stride]
@@ -66,6 +67,7 @@ struct ExpandArgs {
     // (p * nq + q) % world == rank; shard_compact: the blocks go to the rank's packed buffer (batchargs.h ShardMap)
     uint32_t nq, shard_rank, shard_world, shard_compact;
     uint64_t pro_nrec, q_rec0_first, q_rec0_rest, q_nrec_first, q_nrec_rest, pro_ncell, q_cell0_first, q_cell0_rest, q_ncell_rest, q_slot;
+    const MontForm *mont = nullptr;      // set: the cells leave in Montgomery form (H2W_OPT_OUTPUT_FORM); the plan's constants, device memory
 };
 int launch_expand(const ExpandArgs &A, uint64_t nproofs, int grid_x, hipStream_t stream);
 inline void expand_unsharded(ExpandArgs &A) {      // one block per proof: all of its records

@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include "records.h"
 #include "common.h"
+#include "montform.h"
 #include <cstdlib>
 
 namespace h2w {
@@ -21,7 +22,8 @@ struct __attribute__((aligned(16))) u128s { ull lo, hi; };
 // static MAX_* worst case would be 9 KB) — the expansion kernel shares its CUs with the strand kernels of other batches, whose
 // staging regions hold most of the LDS, and every 16 KB block that does not fit is four fewer wavefronts streaming.
 extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn_tables[];
-template <int TILE_RECS, int NSTEP, bool COLS = false> __global__ __launch_bounds__(EXPAND_THREADS) void expand_kernel_t(ExpandArgs A) {
+// MONT: the cells leave in Montgomery form (montform.h), each by the route its width allows (a constant or literal cell: the full one)
+template <int TILE_RECS, int NSTEP, bool COLS, bool MONT> __device__ __forceinline__ void expand_generic_body(const ExpandArgs &A) {
     u128s *s_consts = reinterpret_cast<u128s *>(s_dyn_tables);
     uint32_t *s_slots = reinterpret_cast<uint32_t *>(s_consts + A.nconsts * 2);
     __shared__ tmpl_info_t s_info[T_MAX];
@@ -146,6 +148,11 @@ template <int TILE_RECS, int NSTEP, bool COLS = false> __global__ __launch_bound
             ull cellidx = s_coff[i] + s;
             if constexpr (COLS) { if (s >= s_split[i]) cellidx += s_dd[i]; }
             u128s *dst = (u128s *)(out + cellidx);
+            if constexpr (MONT) {
+                fr_t cv; cv.l[0] = vlo.lo; cv.l[1] = vlo.hi; cv.l[2] = vhi.lo; cv.l[3] = vhi.hi;
+                cv = mont_from_cell(cv, *A.mont);
+                vlo = u128s{cv.l[0], cv.l[1]}; vhi = u128s{cv.l[2], cv.l[3]};
+            }
             dst[0] = vlo; dst[1] = vhi;
         }
         __syncthreads();
@@ -154,7 +161,8 @@ template <int TILE_RECS, int NSTEP, bool COLS = false> __global__ __launch_bound
     }
 }
 
-
+template <int TILE_RECS, int NSTEP, bool COLS = false> __global__ __launch_bounds__(EXPAND_THREADS) void expand_kernel_t(ExpandArgs A) { expand_generic_body<TILE_RECS, NSTEP, COLS, false>(A); }
+template <int TILE_RECS, int NSTEP, bool COLS> __global__ __launch_bounds__(EXPAND_THREADS) void expand_kernel_mont(ExpandArgs A) { expand_generic_body<TILE_RECS, NSTEP, COLS, true>(A); }
 
 // ---------------------------------------------------------------------------------------------------------------
 // expand_fast: the batched hot path's expansion kernel.  Same records, same cells as expand_kernel_t, ~8x fewer
@@ -270,7 +278,26 @@ __device__ __forceinline__ bool fast_tile_range(const ExpandArgs &A, uint64_t pr
     return true;
 }
 constexpr int FAST_MAX_COLS = 64;                           // column-major emission through the fast kernel: the column table lives in LDS
-template <int L, bool ROAM, bool COLS> __global__ __launch_bounds__(EXPAND_THREADS, 2) void expand_fast(ExpandArgs A) {
+// MONT (H2W_OPT_OUTPUT_FORM): the cells leave in Montgomery form.  The LDS tile still holds the canonical low halves; the conversion happens in the
+// flush, in registers, one lane per CELL: a flush step covers 16 virtual cells of four records, the two lanes of a pair k take cells 16 c + k and
+// 16 c + 8 + k, convert them (montform.h), and swap halves with their neighbour (one DPP move per dword), so that each of the step's two store
+// instructions still writes 256 contiguous bytes per record (cells 16 c .. 16 c + 7, then 16 c + 8 .. 16 c + 15): the canonical kernel's store pattern,
+// every conversion done once, on all 64 lanes.  The step loop is unrolled, so the number of 32-bit words a step's cells can have (fast_step_words: two for
+// Goldilocks words, limbs and their sums, three from x + 2^RB - p on, four for V and q p + r) is a constant of each step.  The one full-width cell,
+// -2^RB, is a constant of the plan.  The canonical instantiations carry none of this.
+template <int L> constexpr int fast_cell_words(int v) {
+    typedef FastMap<L> M;
+    if (v == 4 || v == M::VT - 1) return 4;
+    if (v >= 5 && v < 5 + 2 * M::LW) return (v - 5) % M::LW > M::RC ? 3 : 2;      // load_witness(x): x and range_check(x) | x + 2^RB - p, x + 2^RB and their range check
+    return 2;
+}
+template <int L> constexpr int fast_step_words(int c) {
+    int w = 2;
+    for (int v = 16 * c; v < 16 * c + 16 && v < FastMap<L>::VT; v++) if (fast_cell_words<L>(v) > w) w = fast_cell_words<L>(v);
+    return w;
+}
+typedef __attribute__((address_space(4))) const uint32_t cu32_t;
+template <int L, bool ROAM, bool COLS, bool MONT> __device__ __forceinline__ void expand_fast_body(const ExpandArgs &A) {
     typedef FastMap<L> M;
     constexpr int NCH = (M::VT + FAST_CH - 1) / FAST_CH;
     constexpr int ROW = M::VT * 16 + 16;                      // bytes per record row of the LDS tile: the low halves of its virtual cells (+ padding); the last step's lanes past VT never read
@@ -285,6 +312,17 @@ template <int L, bool ROAM, bool COLS> __global__ __launch_bounds__(EXPAND_THREA
     __shared__ ull s_cd0[EXPAND_THREADS / 64][COLS ? FAST_T : 1], s_cdd[EXPAND_THREADS / 64][COLS ? FAST_T : 1]; __shared__ uint32_t s_csplit[EXPAND_THREADS / 64][COLS ? FAST_T : 1];
     if constexpr (COLS) { for (uint32_t i = threadIdx.x; i < A.cm.ncols; i += EXPAND_THREADS) s_cstart[i] = A.cm.starts[i]; __syncthreads(); }
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    MontForm KM;      // (wavefront-uniform: scalar loads, once)
+    if constexpr (MONT) {
+        const cu32_t *km = (const cu32_t *)A.mont;
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+#pragma unroll
+            for (int j = 0; j < 8; j++) KM.c[i][j] = km[i * 8 + j];
+        KM.mu[0] = km[64]; KM.mu[1] = km[65];
+#pragma unroll
+        for (int j = 0; j < 8; j++) KM.neg_rb[j] = km[66 + j];
+    }
     // which proof: one column of the grid per proof (static), or - roam - a grid of as many blocks as the chip holds at once, whose wavefronts
     // start spread over the proofs and move on to the next proof that has tiles left.  With more blocks than fit, the late ones start when
     // the first proofs are done and ramp up again: 5.5-5.8 TB/s for a launch alone against 6.3 with every block resident from the start
@@ -403,6 +441,35 @@ template <int L, bool ROAM, bool COLS> __global__ __launch_bounds__(EXPAND_THREA
                 uint32_t split = 0xffffffffu; ull dd = 0;
                 if constexpr (COLS) { const int ri = g * 4 + (lane >> 4); first += (long long)s_cd0[wv][ri]; split = s_csplit[wv][ri]; dd = s_cdd[wv][ri]; }
                 unsigned char *const dst = out_half + first * 32;       // + 256 c per step: an immediate offset
+                if constexpr (MONT) {
+                    static_assert(M::RB + 1 <= 96, "x + 2^RB must fit three words");
+                    constexpr int NCHM = (M::VT + 15) / 16;
+                    const unsigned char *const rdm = rd_base + g * 4 * ROW + (hi ? 8 * 16 : 0);      // this lane's cell of step 0: kc (even lane) or 8 + kc (odd lane)
+                    const long long flat0 = (long long)(uint32_t)(br.x + (uint32_t)kc + 16u) - 16;
+#pragma clang loop unroll(full)
+                    for (int c = 0; c < NCHM; c++) {
+                        const int va = 16 * c + kc, vb = va + 8, v = hi ? vb : va, vr = v < M::VT ? v : M::VT - 1;      // (past the list: a cell nobody stores)
+                        const u128s x = *reinterpret_cast<const u128s *>(rdm + (vr - (hi ? 8 : 0) - kc) * 16);
+                        const uint32_t w[4] = {(uint32_t)x.lo, (uint32_t)(x.lo >> 32), (uint32_t)x.hi, (uint32_t)(x.hi >> 32)}; uint32_t o[8];
+                        mf_convert_upto<4>(w, fast_step_words<L>(c), KM, o);
+                        if (v == 5 + 1 + M::RC + 4 || v == 5 + M::LW + 1 + M::RC + 4) {      // fast_is_neg: -2^RB, the plan's constant
+#pragma unroll
+                            for (int j = 0; j < 8; j++) o[j] = KM.neg_rb[j];
+                        }
+                        // the even lane keeps its low half and gets the odd lane's, the odd lane keeps its high half and gets the even lane's (every lane of the
+                        // wavefront is here: the exchange stands outside the stores' conditions)
+                        // (the halves are picked dword by dword with a lane mask: written as hi ? o[4 + j] : o[j] the compiler indexes o[] in scratch memory)
+                        const uint32_t hm = hi ? 0xffffffffu : 0u; uint32_t sa[4], sb[4];      // what this lane stores for cell va / for cell vb
+#pragma unroll
+                        for (int j = 0; j < 4; j++) {
+                            const uint32_t got = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)((o[j] & hm) | (o[4 + j] & ~hm)), 0xB1 /* quad_perm [1, 0, 3, 2] */, 0xf, 0xf, false);
+                            sa[j] = (got & hm) | (o[j] & ~hm); sb[j] = (o[4 + j] & hm) | (got & ~hm);
+                        }
+                        const bool over_a = COLS && split != 0xffffffffu && flat0 + 16 * c >= (long long)split, over_b = COLS && split != 0xffffffffu && flat0 + 16 * c + 8 >= (long long)split;
+                        if (va >= vs_ && va < ve_) *reinterpret_cast<u128s *>(dst + c * 512 + (over_a ? (long long)dd * 32 : 0)) = u128s{((ull)sa[1] << 32) | sa[0], ((ull)sa[3] << 32) | sa[2]};            // cells 16 c .. 16 c + 7
+                        if (vb >= vs_ && vb < ve_) *reinterpret_cast<u128s *>(dst + c * 512 + 256 + (over_b ? (long long)dd * 32 : 0)) = u128s{((ull)sb[1] << 32) | sb[0], ((ull)sb[3] << 32) | sb[2]};      // cells 16 c + 8 .. 16 c + 15
+                    }
+                } else
                 if (COLS && __any(split != 0xffffffffu)) {          // a record of the group runs into the next column (once per column and proof): per-cell shifts
                     const long long flat0 = (long long)(uint32_t)(br.x + (uint32_t)kc + 16u) - 16;
 #pragma unroll 1
@@ -427,6 +494,10 @@ template <int L, bool ROAM, bool COLS> __global__ __launch_bounds__(EXPAND_THREA
                     const u128s z{0, 0}; ull d0 = 0, dd = 0; uint32_t split = 0xffffffffu;
                     if constexpr (COLS) { d0 = s_cd0[wv][lane]; dd = s_cdd[wv][lane]; split = s_csplit[wv][lane]; }
                     auto at = [&](int i) { return reinterpret_cast<u128s *>(outb + (coff + (ull)i + d0 + ((COLS && coff + (ull)i >= split) ? dd : 0)) * 32); };
+                    if constexpr (MONT) {      // 64-bit values: the two-word route
+                        if (t == T_CONST4) { const ull w4[4] = {rc.a, rc.b, rc.c, rc.d}; for (int i = 0; i < 4; i++) { const fr_t m = mont_from_u64(w4[i], KM); u128s *d = at(i); d[0] = u128s{m.l[0], m.l[1]}; d[1] = u128s{m.l[2], m.l[3]}; } }
+                        else { const fr_t m = mont_from_u64(rc.a, KM); for (int i = 0; i < 12; i++) { u128s *d = at(i); d[0] = u128s{m.l[0], m.l[1]}; d[1] = u128s{m.l[2], m.l[3]}; } }
+                    } else
                     if (t == T_CONST4) { const ull w4[4] = {rc.a, rc.b, rc.c, rc.d}; for (int i = 0; i < 4; i++) { u128s *d = at(i); d[0] = u128s{w4[i], 0}; d[1] = z; } }
                     else { for (int i = 0; i < 12; i++) { u128s *d = at(i); d[0] = u128s{rc.a, 0}; d[1] = z; } }
                 }
@@ -447,6 +518,9 @@ template <int L, bool ROAM, bool COLS> __global__ __launch_bounds__(EXPAND_THREA
     proof = (uint64_t)__builtin_amdgcn_readfirstlane(nx);
   }
 }
+
+template <int L, bool ROAM, bool COLS> __global__ __launch_bounds__(EXPAND_THREADS, 2) void expand_fast(ExpandArgs A) { expand_fast_body<L, ROAM, COLS, false>(A); }
+template <int L, bool ROAM, bool COLS> __global__ __launch_bounds__(EXPAND_THREADS, 2) void expand_fast_mont(ExpandArgs A) { expand_fast_body<L, ROAM, COLS, true>(A); }
 
 // every template id a batched plan emits is fixed (< T_DYNAMIC; dynamic range-check templates and literal runs are eager-context
 // features), so the fast kernel serves the batched path whenever it is instantiated for the plan's lookup_bits
@@ -480,7 +554,8 @@ int launch_expand(const ExpandArgs &A, uint64_t nproofs, int grid_x, hipStream_t
             B.roam = 1; grid = dim3((unsigned)nb, 1);
         }
         const bool cols = A.cm.starts != nullptr;
-#define H2W_LAUNCH_FAST(LB, RM, CL) hipLaunchKernelGGL((expand_fast<LB, RM, CL>), grid, dim3(EXPAND_THREADS), 0, stream, B)
+#define H2W_LAUNCH_FAST(LB, RM, CL) do { if (B.mont) hipLaunchKernelGGL((expand_fast_mont<LB, RM, CL>), grid, dim3(EXPAND_THREADS), 0, stream, B); \
+                                         else hipLaunchKernelGGL((expand_fast<LB, RM, CL>), grid, dim3(EXPAND_THREADS), 0, stream, B); } while (0)
 #define H2W_LAUNCH_FAST_L(LB) do { if (B.roam) { if (cols) H2W_LAUNCH_FAST(LB, true, true); else H2W_LAUNCH_FAST(LB, true, false); } \
                                    else { if (cols) H2W_LAUNCH_FAST(LB, false, true); else H2W_LAUNCH_FAST(LB, false, false); } } while (0)
         if (A.lookup_bits == 21) H2W_LAUNCH_FAST_L(21); else if (A.lookup_bits == 13) H2W_LAUNCH_FAST_L(13); else H2W_LAUNCH_FAST_L(8);
@@ -494,7 +569,10 @@ int launch_expand(const ExpandArgs &A, uint64_t nproofs, int grid_x, hipStream_t
     uint64_t gx = (uint64_t)grid_x; if (gx > ntiles) gx = ntiles; if (gx < 1) gx = 1;
     const dim3 grid((unsigned)gx, (unsigned)nproofs);
     const size_t dyn = ((size_t)A.nconsts * 32 + (size_t)A.nslots * 4 + 15) & ~(size_t)15;      // expand_kernel_t's tables
-    if (A.cm.starts) hipLaunchKernelGGL((expand_kernel_t<32, 5, true>), grid, dim3(EXPAND_THREADS), dyn, stream, A);
+    if (A.mont) {
+        if (A.cm.starts) hipLaunchKernelGGL((expand_kernel_mont<32, 5, true>), grid, dim3(EXPAND_THREADS), dyn, stream, A);
+        else hipLaunchKernelGGL((expand_kernel_mont<32, 5, false>), grid, dim3(EXPAND_THREADS), dyn, stream, A);
+    } else if (A.cm.starts) hipLaunchKernelGGL((expand_kernel_t<32, 5, true>), grid, dim3(EXPAND_THREADS), dyn, stream, A);
     else hipLaunchKernelGGL((expand_kernel_t<32, 5, false>), grid, dim3(EXPAND_THREADS), dyn, stream, A);
     return 0;
 }

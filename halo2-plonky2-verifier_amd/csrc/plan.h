@@ -2,6 +2,7 @@
 #pragma once
 #include "common.h"
 #include "batchargs.h"
+#include "montform.h"
 
 namespace h2w {
 struct TracedPlan;
@@ -25,12 +26,15 @@ struct h2w_plan {
     static constexpr int EV_RING = 64, N_SIDE = 16;
     // event slots of a call: slot i < H2W_EV_COUNT is the public H2W_EV_* i (include/h2w.h: call start / end, prologue block complete, glue (+ Goldilocks
     // Merkle strands) start / end, chain kernels start / end, expansion start / end), then the internal ones
-    enum { EV_PROLOGUE_VALUES_END = H2W_EV_COUNT, EV_CHAIN_VALUES_END, EV_GLP_START, EV_GLP_END, N_EV };
+    enum { EV_PROLOGUE_VALUES_END = H2W_EV_COUNT, EV_CHAIN_VALUES_END, EV_GLP_START, EV_GLP_END, EV_DIRECT_END, N_EV };
     hipEvent_t evr[EV_RING][N_EV]; int passes_of[EV_RING] = {0};
     hipStream_t side[N_SIDE]; hipStream_t side_of[N_SIDE]; int n_side = 0;   // PoseidonBN254 chain kernels run beside the glue + expansion kernels
     int chain_passes = 0;            // H2W_OPT_CHAIN_PASSES (0: by the size of the launch)
     int values_form = 0;             // H2W_OPT_VALUES_FORM (0: by the size of the launch)
     int serial_expand = 1;           // H2W_OPT_SERIAL_EXPAND: the expansion kernel of a call waits for the previous call's
+    // H2W_OPT_OUTPUT_FORM.  The shape compiler marks the cells of a proof's stream that value kernels write themselves (one bit per cell, padded to whole
+    // 64-word rows for k_direct_to_montgomery); the Montgomery form's constants and the bitmap go to the device when the form is first selected.
+    int output_form = 0; std::vector<uint64_t> direct_bits, h_meta; uint64_t n_direct = 0; uint64_t *d_direct_bits = nullptr; MontForm *d_mont = nullptr;
     bool fork_chains = true;         // of their own batch (they share only the prologue): one side stream per caller stream seen (created on demand)
     hipEvent_t *ev = evr[0]; uint64_t n_batches = 0; bool ev_ready = false, ev_recorded = false;
     h2w::TracedPlan *traced = nullptr;      // set: the plan replays a recorded tape (replay.hip); the strand tables above are unused

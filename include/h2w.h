@@ -334,6 +334,25 @@ int h2w_comm_allgather_digests(h2w_comm *, const uint64_t *digest4_dev, uint64_t
 /* Output format: the stream is canonical little-endian Fr (what Fr::from_repr / to_repr use).  For a consumer that copies cells into
  * halo2curves' in-memory representation (Montgomery form, R = 2^256) this converts n_cells cells in place on the device. */
 int h2w_advice_to_montgomery(void *cells_dev, uint64_t n_cells, void *stream);
+/* H2W_OPT_OUTPUT_FORM (default H2W_FORM_CANONICAL): the form of every cell that h2w_fri_witness_batch, _batch2, _columns, _shard and _shard_compact
+ * (and h2w_fri_expand_records) write for this plan.  H2W_FORM_MONTGOMERY: every cell holds v * 2^256 mod r, four little-endian u64 limbs - halo2curves'
+ * bn256::Fr as it lies in memory, so a consumer fills Context::advice with a plain copy - without a second pass over the stream: the expansion kernel
+ * converts its cells in registers as it writes them (by their width: they are values below 2^128), and one ranged kernel converts the cells the value
+ * kernels wrote themselves (h2w_plan_direct_cells) in place before the call completes.  Column layouts (boundary cells repeated, unused rows zero) and
+ * sharded calls (only this rank's blocks are touched) hold as in the canonical form.  Status words, workspace sizes, cell counts, layouts and the
+ * keygen metadata do not depend on the form.  h2w_advice_digest, h2w_check_constraints, h2w_check_equalities, h2w_layout_columns and
+ * h2w_layout_lookup_columns read cells as canonical values: they are meant for canonical streams (the layouts only move cells and work on either).
+ * A plan made by h2w_plan_from_trace refuses H2W_FORM_MONTGOMERY (-1): its stream is canonical; convert it with h2w_advice_to_montgomery.
+ * Any other value: -1.  The form may be changed between calls. */
+#define H2W_OPT_OUTPUT_FORM 5
+#define H2W_FORM_CANONICAL 0
+#define H2W_FORM_MONTGOMERY 1
+/* The cells of a proof's stream that value kernels write themselves (PoseidonBN254 permutation units, selects, inverses, ...): bit i of the bitmap
+ * ((num_cells + 7) / 8 bytes) = cell i; the others - h2w_plan_num_record_cells of them - are written by the expansion kernel, record by record:
+ * ranges[2 i] = first cell of record i, ranges[2 i + 1] = its cells (h2w_plan_num_records records).  Static per shape, no device needed; not for
+ * traced plans. */
+int h2w_plan_direct_cells(const h2w_plan *, uint8_t *bitmap);
+int h2w_plan_record_ranges(const h2w_plan *, uint64_t *ranges);
 /* Scheduling options of a plan.  H2W_OPT_FORK_CHAINS (default 1): with PoseidonBN254 Merkle caps the chain kernel of a batch call
  * runs on a library-owned side stream beside the query-glue and expansion kernels of the same call (they depend on the prologue
  * only); the caller's stream still completes when the whole advice is written.  0: every kernel on the caller's stream. */
