@@ -74,6 +74,8 @@ def fibonacci_shape(degree_bits, num_queries, rate_bits=1, cap_height=4, hash_mo
 _vp = C.c_void_p
 _av = C.POINTER(Assigned)
 _fr = C.POINTER(Fr)
+H2W_TRACE_FUSE_GL_PERMUTE = 1      # flags of h2w_plan_from_trace_ex (include/h2w.h)
+
 SYMBOLS = {
     "h2w_abi_version": (C.c_int, []),
     "h2w_poseidon_published": (C.c_int, [C.POINTER(PoseidonConsts)]),
@@ -124,6 +126,9 @@ SYMBOLS = {
     "h2w_ctx_reserve": (C.c_int, [_vp, C.c_uint64, C.c_uint64]),
     "h2w_trace_input": (C.c_int, [_vp, C.c_uint64, C.c_uint32]),
     "h2w_plan_from_trace": (_vp, [_vp, C.c_uint64, C.POINTER(C.c_char_p), C.c_size_t, C.c_int]),
+    "h2w_plan_from_trace_ex": (_vp, [_vp, C.c_uint64, C.POINTER(C.c_char_p), C.c_size_t, C.c_int, C.POINTER(PoseidonConsts), C.c_uint32]),
+    "h2w_plan_trace_info": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
+    "h2w_plan_trace_timing": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_uint32]),
     "h2w_chip_ext_op": (C.c_int, [_vp, C.c_int, _av, _av, _av, _av]),
     "h2w_chip_gl_exp_from_bits_const_base": (C.c_int, [_vp, C.c_uint64, _av, C.c_size_t, _av]),
     "h2w_chip_gl_poseidon_permute": (C.c_int, [_vp, C.POINTER(PoseidonConsts), _av, _av]),

@@ -30,6 +30,7 @@
 #include "plan.h"
 #include "trace.h"
 #include "keygen.h"
+#include "glpval.h"
 
 struct h2w_ctx;
 namespace h2w {
@@ -55,7 +56,9 @@ constexpr int SLOTS_OF[3] = {1, 2, 4};
 enum { DOP_END = 0, DOP_SKIP, DOP_CONST1, DOP_FRCELL, DOP_LOADW, DOP_LOADW_DIV, DOP_LOADW_EXTINV, DOP_GLOP, DOP_GATE, DOP_REDUCE, DOP_CLT,
        DOP_FR_ADD, DOP_FR_MUL, DOP_FR_MULADD, DOP_SELECT, DOP_FR_SELECT, DOP_IDX2IND, DOP_SELIND, DOP_FR_SELIND, DOP_NUM2BITS, DOP_BITS2NUM,
        DOP_DECOMP565, DOP_LIMBS2NUM, DOP_RANGE, DOP_FETCH,
-       DOP_GLOPRUN };      // n consecutive DOP_GLOP ops as one: [hdr][cells of the run][A, B, C, out slot | template << 24] x n (2 + 4 n words: its length is NOT in the header)
+       DOP_GLOPRUN,        // n consecutive DOP_GLOP ops as one: [hdr][cells of the run][A, B, C, out slot | template << 24] x n (2 + 4 n words: its length is NOT in the header)
+       DOP_GLPERM };       // a verified Goldilocks-Poseidon permutation as one op (H2W_TRACE_FUSE_GL_PERMUTE): [hdr][12 operands][first output slot][list slot][cells of its record block]
+constexpr uint32_t GLPERM_WORDS = 16;
 // operand words of an op: [first, first + count)
 HD void operand_span(uint32_t op, uint32_t n, uint32_t &first, uint32_t &count) {
     first = 1; count = 0;
@@ -65,6 +68,7 @@ HD void operand_span(uint32_t op, uint32_t n, uint32_t &first, uint32_t &count) 
         case DOP_GLOP: case DOP_GATE: case DOP_FR_MULADD: case DOP_SELECT: case DOP_FR_SELECT: count = 3; break;
         case DOP_SELIND: case DOP_FR_SELIND: count = 2 * n; break;
         case DOP_BITS2NUM: case DOP_LIMBS2NUM: count = n; break;
+        case DOP_GLPERM: count = SPONGE_WIDTH; break;
         default: break;
     }
 }
@@ -72,7 +76,8 @@ constexpr int MAX_TMPL = 48;
 constexpr uint32_t NO_SLOT = 0xffffffffu;
 
 // unit: the depth-1 parallel instance (shard unit) the instance is or lies in, NO_SLOT for the root; ucell0: that unit's first cell (root: 0)
-struct InstD { uint64_t cell0, rec0, ucell0; uint32_t imp0, in0, unit, pad; };
+// glp0: the instance's first entry in the proof's list of fused permutations
+struct InstD { uint64_t cell0, rec0, ucell0; uint32_t imp0, in0, unit, glp0; };
 struct ImpD { uint32_t tmpl, inst, slot; };
 struct TmplD { uint32_t tape0, nslots, ninst, inst0, depth; };
 
@@ -87,6 +92,8 @@ struct ReplayArgs {
     // (proof, query) sharding (ShardSpec): lanes != null lists the lanes of this rank, template t's at [lane0[t], lane0[t + 1]) (lane_table)
     const uint32_t *lanes; uint32_t lane0[MAX_TMPL + 1];
     uint32_t sh_world, sh_rank, sh_compact, nq; uint64_t pro_ncell, q_slot;      // the packed layout (batchargs.h block_out)
+    // fused permutations (DOP_GLPERM): the Goldilocks block of the tables the lowering verified them on; the list [nproofs][nglp][GLP_LIST_WORDS]
+    const uint64_t *glk; uint64_t *glist; uint32_t nglp;
 };
 
 struct TracedPlan {
@@ -94,6 +101,9 @@ struct TracedPlan {
     TmplD *d_tm = nullptr; uint64_t *d_prefix = nullptr; uint32_t npool64 = 0, npoolfr = 0;
     uint32_t *d_tape = nullptr; InstD *d_insts = nullptr; ImpD *d_imps = nullptr; uint32_t *d_inputs = nullptr; uint64_t *d_pool64 = nullptr; fr_t *d_poolfr = nullptr;
     uint64_t n_ops = 0, n_segments = 0;
+    // fused Goldilocks-Poseidon permutations: per proof nglp list entries (entry e belongs to shard unit h_glp_unit[e], NO_SLOT: the root's block)
+    uint32_t nglp = 0; uint64_t n_candidates = 0; std::vector<uint32_t> h_glp_unit; uint32_t *d_glp_unit = nullptr;
+    hipEvent_t tev[16]; int n_tev = 0, tev_used = 0; bool timing = false;      // h2w_plan_trace_timing: around every kernel of the last call
     // sharding: the depth-1 instances are the units (query q = the q-th in tape order); why_unshardable empty: they tile the stream behind the root's block
     std::string why_unshardable; std::vector<uint32_t> h_unit;      // h_unit: the unit of every instance (InstD order)
     std::vector<uint32_t> h_lanes, lane0; uint32_t *d_lanes = nullptr; uint64_t lanes_n = 0; int lanes_rank = -1, lanes_world = 0;      // the lane table of the last (n, rank, world)
@@ -154,7 +164,7 @@ __global__ __launch_bounds__(64) __attribute__((flatten)) void k_replay(ReplayAr
     } else { g = gl; if (g >= R.nproofs * ninst) return; }
     const uint32_t p = g / ninst, inst = g % ninst;
     const InstD *const I = R.insts + inst0 + inst;
-    const uint32_t imp0 = I->imp0, in0 = I->in0;
+    const uint32_t imp0 = I->imp0, in0 = I->in0, glp0 = I->glp0;
     fr_t *outb = R.out + (uint64_t)p * R.cell_stride;
     if (R.sh_compact) {         // the packed buffer: the lane's block (the root's: the prologue block) at its local start, its cells at their global offsets
         const uint64_t W = R.sh_world, r = R.sh_rank, u0 = (uint64_t)p * R.nq, unit = I->unit;
@@ -254,6 +264,24 @@ __global__ __launch_bounds__(64) __attribute__((flatten)) void k_replay(ReplayAr
                 sink.nrec += n; sink.cell_off += w1;
                 break;
             }
+            case DOP_GLPERM: {     // the lane keeps the VALUES of the permutation; its records are k_glp_emit_traced's, from the listed input state
+                uint64_t st[SPONGE_WIDTH];
+#pragma unroll
+                for (uint32_t i = 0; i < (uint32_t)SPONGE_WIDTH; i++) st[i] = get64(tw(tape, pc + 1 + i), 0);
+                const uint32_t o = tw(tape, pc + 13), ls = tw(tape, pc + 14), nc = tw(tape, pc + 15);
+                if (sink.emit) {
+                    uint64_t *e = R.glist + ((uint64_t)p * R.nglp + glp0 + ls) * GLP_LIST_WORDS;
+                    H2W_GSTORE64(e, sink.nrec);
+#pragma unroll
+                    for (int i = 0; i < SPONGE_WIDTH; i++) H2W_GSTORE64(e + 1 + i, st[i]);
+                }
+                const uint64_t *const glk = R.glk;
+                glp_permute_values(st, [&](int i) -> uint64_t { return H2W_CLOAD64(glk + i); });
+#pragma unroll
+                for (uint32_t i = 0; i < (uint32_t)SPONGE_WIDTH; i++) st1(o + i, st[i]);
+                sink.skip(GLP_RECS, nc);
+                break;
+            }
             case DOP_FETCH: {      // a far operand into the ring (no write-through: a copy)
                 bool ge = true;        // a proof word (every one enters here): at least the modulus of its field (one word: Goldilocks, four: BN254)?
                 for (uint32_t j = 0; j < n; j++) {
@@ -271,6 +299,27 @@ __global__ __launch_bounds__(64) __attribute__((flatten)) void k_replay(ReplayAr
     if (bad_word) atomicOr(&R.lflag[p], 4u);
 }
 
+// One wavefront per listed permutation of the launch: its GLP_RECS records from the entry {first record, input state}, as k_glp_emit (batch.hip)
+// writes a compiled plan's - the traced plan's list is flat, [proof][entry].  Sharded: the entries of this rank's blocks only.
+struct GlpEmitArgs { const h2w_poseidon_consts_t *consts; const uint64_t *list; rec_t *recs; uint64_t rec_stride; const uint16_t *ncells; const uint32_t *unit; uint32_t nglp, world, rank, nq; };
+__global__ __launch_bounds__(64) void k_glp_emit_traced(GlpEmitArgs A) {
+    typedef CoopSinkT<false, false> Sink;
+    const uint32_t p = blockIdx.x / A.nglp, e = blockIdx.x % A.nglp;
+    if (A.world > 1) {
+        const uint32_t u = A.unit[e];
+        if ((u == NO_SLOT ? (uint64_t)p : (uint64_t)p * A.nq + u) % A.world != A.rank) return;
+    }
+    stage_glp_consts(A.consts, threadIdx.x, 64);
+    Sink sink; sink.recs = A.recs + (uint64_t)p * A.rec_stride; sink.out = nullptr; sink.ncells = A.ncells; sink.lane = threadIdx.x; sink.bind_lds(); sink.cell_off = 0; sink.emit = true;
+    const uint64_t *ent = A.list + ((uint64_t)p * A.nglp + e) * GLP_LIST_WORDS;
+    const uint64_t w = threadIdx.x < GLP_LIST_WORDS ? g_load_u64(ent + threadIdx.x) : 0;
+    uint64_t st[SPONGE_WIDTH];
+#pragma unroll
+    for (int i = 0; i < SPONGE_WIDTH; i++) st[i] = readlane64(w, i + 1);
+    sink.nrec = readlane64(w, 0);
+    sink.coop_poseidon_permute(st, A.consts);
+}
+
 // ------------------------------------------------------------------------------------------------------------------- host: lowering
 struct ValInfo { uint32_t seg, slot; uint8_t width, is_static; uint32_t lit; };
 struct SegInfo {
@@ -280,7 +329,59 @@ struct SegInfo {
     uint64_t cell0 = 0, rec0 = 0, ncells = 0, nrecs = 0, all_recs = 0; bool started = false;      // all_recs: with the nested segments' (ncells includes them)
     uint32_t unit = NO_SLOT;      // the depth-1 instance (shard unit) this segment is or lies in
     int tmpl = -1; uint32_t inst = 0;
-    long last_const_at = -1; uint64_t last_const_cell = 0;      // the op emitted last is a static CONST1 (its tape position, its cell): a GLOP right behind it that takes it as operand A fuses with it
+    long last_const_at = -1; uint64_t last_const_cell = 0; size_t last_const_tr = 0;      // the op emitted last is a static CONST1 (its tape position, its cell): a GLOP right behind it that takes it as operand A fuses with it
+    uint32_t nglp = 0, glp0 = 0;      // fused permutations (DOP_GLPERM) of this segment; its first entry in the proof's list
+    struct Matcher *mt = nullptr;     // the search for permutation-shaped stretches (first lowering of a fused plan)
+};
+// ---- stretches of a tape that ARE a Goldilocks-Poseidon permutation (H2W_TRACE_FUSE_GL_PERMUTE).  A lowered op, before its operands become fast refs:
+struct NormOp {
+    uint32_t hdr = 0, nin = 0, ref[3] = {0, 0, 0}, out = NO_SLOT, slots_before = 0; uint64_t lit[3] = {0, 0, 0};      // hdr: op | n << 8 | aux << 16; ref: mkref words; lit: the value of a literal operand
+    size_t tr0 = 0, tr1 = 0; uint64_t cell0 = 0, cell1 = 0, out_cell = 0; const TraceIn *tin = nullptr;               // the trace ops / cells it covers; its result handle; its operands on the trace
+};
+// an operand of the canonical tape: a literal (its value), a value computed inside the stretch (the op that produced it, relative to the start), one of the 12 inputs
+enum { CK_LIT = 0, CK_INTERIOR = 1, CK_INPUT = 2 };
+struct CanonOp { uint32_t hdr, nin; uint8_t kind[3]; uint64_t arg[3]; bool has_out; };
+struct Canon { std::vector<CanonOp> ops; uint32_t out_prod[SPONGE_WIDTH]; uint64_t ncells = 0; };
+// a stretch that matched the canonical tape in op codes, record templates and dataflow; const_bad: on other constants; escaped: an interior value is read outside
+struct Stretch { size_t tr0, tr1; int seg; TraceIn in[SPONGE_WIDTH]; uint64_t out[SPONGE_WIDTH]; uint64_t cell0, cell1; bool const_bad, escaped; };
+// One per segment: the ops arrive in tape order, one behind the lowering (a static CONST1 may still fuse with the GLOP behind it).  A partial match that
+// fails restarts AT the failing op, not inside the failed part: a permutation may then stay interpreted (canonical tapes whose first ops repeat
+// themselves), it is never fused wrongly.
+struct Matcher {
+    const Canon *cn; std::vector<Stretch> *found; int seg;
+    NormOp pend; bool has_pend = false;
+    size_t pos = 0; uint32_t slot0 = 0; std::vector<int32_t> prod;      // matched ops so far; the first slot of the stretch; slot - slot0 -> the op that wrote it
+    bool bound[SPONGE_WIDTH]; uint32_t bref[SPONGE_WIDTH]; Stretch cur;
+    void reset() { pos = 0; prod.clear(); }
+    bool step(const NormOp &o) {
+        const CanonOp &c = cn->ops[pos];
+        if (o.hdr != c.hdr || o.nin != c.nin || (o.out != NO_SLOT) != c.has_out) return false;
+        if (pos == 0) { slot0 = o.slots_before; for (int i = 0; i < SPONGE_WIDTH; i++) bound[i] = false; cur.tr0 = o.tr0; cur.cell0 = o.cell0; cur.seg = seg; cur.const_bad = cur.escaped = false; }
+        for (uint32_t k = 0; k < c.nin; k++) {
+            const uint32_t r = o.ref[k]; const int rk = ref_kind(r);
+            if (ref_width(r) != W64) return false;
+            const bool interior = rk == RK_LOCAL && ref_idx(r) >= slot0;
+            if (c.kind[k] == CK_LIT) { if (rk != RK_LIT64) return false; if (o.lit[k] != c.arg[k]) cur.const_bad = true; }
+            else if (c.kind[k] == CK_INTERIOR) { if (!interior || ref_idx(r) - slot0 >= prod.size() || prod[ref_idx(r) - slot0] != (int32_t)c.arg[k]) return false; }
+            else {
+                if (interior) return false;
+                const uint64_t n = c.arg[k];
+                if (!bound[n]) { bound[n] = true; bref[n] = r; cur.in[n] = o.tin[k]; } else if (bref[n] != r) return false;
+            }
+        }
+        if (o.out != NO_SLOT) { const uint32_t rel = o.out - slot0; if (prod.size() <= rel) prod.resize(rel + 1, -1); prod[rel] = (int32_t)pos; }
+        for (int i = 0; i < SPONGE_WIDTH; i++) if (cn->out_prod[i] == pos) cur.out[i] = o.out_cell;
+        if (++pos == cn->ops.size()) {
+            cur.tr1 = o.tr1; cur.cell1 = o.cell1; bool all = true; for (int i = 0; i < SPONGE_WIDTH; i++) all = all && bound[i];
+            if (all) found->push_back(cur);
+            reset();
+        }
+        return true;
+    }
+    void commit() { if (!has_pend) return; has_pend = false; if (!step(pend)) { const bool retry = pos != 0; reset(); if (retry) { if (!step(pend)) reset(); } } }
+    void feed(const NormOp &o) { commit(); pend = o; has_pend = true; }
+    void drop_pending() { has_pend = false; }                   // the pending CONST1 became part of the op that follows
+    void boundary() { commit(); reset(); }                      // a stretch never crosses a segment boundary
 };
 static uint64_t rc_cells(int L, uint64_t bits) { if (bits == 0) return 0; const uint64_t n = (bits + L - 1) / L, rem = bits % L; return (n > 1 ? 1 + 3 * (n - 1) : 0) + (rem ? 4 : 0); }
 
@@ -293,13 +394,14 @@ uint64_t traced_workspace_bytes(const h2w_plan *p, uint64_t n);
 int traced_run(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void *advice_dev, void *workspace_dev, void *stream_, ColMap cm, uint64_t cell_stride, const ShardSpec &sh);
 void traced_free(h2w_plan *p);
 const char *traced_shard_refusal(const h2w_plan *p) { return p->traced && !p->traced->why_unshardable.empty() ? p->traced->why_unshardable.c_str() : nullptr; }
-struct TracedWs { size_t recs, status, lflag, ctr, vals, total; };
+struct TracedWs { size_t recs, status, lflag, ctr, vals, glist, total; };
 static size_t al(size_t x) { return (x + 255) / 256 * 256; }
 static TracedWs traced_ws(const h2w_plan *p, uint64_t n) {
     TracedWs w; size_t o = 0;
     w.recs = o; o += al((size_t)n * p->nrec * sizeof(rec_t));
     w.status = o; o += al((size_t)n * 4); w.lflag = o; o += al((size_t)n * 4); w.ctr = o; o += al((size_t)n * 4);
     w.vals = o; o += al((size_t)n * p->traced->total_slot_lanes * 8);
+    w.glist = o; o += al((size_t)n * p->traced->nglp * GLP_LIST_WORDS * 8);      // the fused permutations' list (none: the layout of an unfused plan)
     w.total = o; return w;
 }
 uint64_t traced_workspace_bytes(const h2w_plan *p, uint64_t n) { return traced_ws(p, n).total; }
@@ -309,7 +411,8 @@ void traced_free(h2w_plan *p) {
     if (t->d_tm) (void)hipFree(t->d_tm); if (t->d_prefix) (void)hipFree(t->d_prefix);
     if (t->d_tape) (void)hipFree(t->d_tape); if (t->d_insts) (void)hipFree(t->d_insts); if (t->d_imps) (void)hipFree(t->d_imps);
     if (t->d_inputs) (void)hipFree(t->d_inputs); if (t->d_pool64) (void)hipFree(t->d_pool64); if (t->d_poolfr) (void)hipFree(t->d_poolfr);
-    if (t->d_lanes) (void)hipFree(t->d_lanes);
+    if (t->d_lanes) (void)hipFree(t->d_lanes); if (t->d_glp_unit) (void)hipFree(t->d_glp_unit);
+    for (int i = 0; i < t->n_tev; i++) (void)hipEventDestroy(t->tev[i]);
     delete t; p->traced = nullptr;
 }
 // The lanes a rank launches (sharded calls), template by template: the root lane of every proof - those of the proofs the rank owns first, then, from
@@ -354,6 +457,7 @@ int traced_run(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void 
     R.proofs = proofs_dev; R.proof_words = p->pl.total; R.recs = (rec_t *)(ws + wl.recs); R.rec_stride = p->nrec; R.out = (fr_t *)advice_dev; R.cell_stride = cell_stride; R.cm = cm;      // (cm.starts: the FlexGate columns of every proof, cell_stride = ncols << k; else the flat stream)
     R.vals = (uint64_t *)(ws + wl.vals); R.status = (uint32_t *)(ws + wl.status); R.ncells = p->d_ncells; R.inv_pos = p->d_inv; R.inv_neg = p->d_inv + INV_TAB; R.P = p->P; R.L = p->shape.lookup_bits;
     R.nproofs = (uint32_t)n_proofs; R.lflag = (uint32_t *)(ws + wl.lflag);
+    R.glk = reinterpret_cast<const uint64_t *>(p->d_consts); R.glist = (uint64_t *)(ws + wl.glist); R.nglp = t->nglp;
     R.ntmpl = (uint32_t)t->tmpls.size(); R.tm = t->d_tm; R.prefix = t->d_prefix; R.npool64 = t->npool64; R.npoolfr = t->npoolfr;
     if (sharded) {
         R.lanes = t->d_lanes; for (size_t i = 0; i < t->lane0.size(); i++) R.lane0[i] = t->lane0[i];
@@ -363,6 +467,7 @@ int traced_run(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void 
     H2W_HIP(hipMemsetAsync(ws + wl.status, 0, n_proofs * 4, stream));
     H2W_HIP(hipMemsetAsync(ws + wl.lflag, 0, n_proofs * 4, stream));
     uint32_t maxd = 0; for (const TmplD &T : t->tmpls) if (T.depth > maxd) maxd = T.depth;
+    t->tev_used = 0;
     for (uint32_t d = 0; d <= maxd; d++) {      // a segment reads its ancestors' values: depth by depth; the templates of one depth in one launch
         uint32_t nb = 0;
         for (size_t i = 0; i < t->tmpls.size(); i++) {
@@ -370,26 +475,55 @@ int traced_run(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void 
             if (t->tmpls[i].depth == d) nb += (uint32_t)(((sharded ? t->lane0[i + 1] - t->lane0[i] : n_proofs * t->tmpls[i].ninst) + 63) / 64);
         }
         R.blk0[t->tmpls.size()] = nb; R.depth = d;
+        if (t->timing && t->tev_used < 12) H2W_HIP(hipEventRecord(t->tev[t->tev_used++], stream));
         if (nb) hipLaunchKernelGGL(k_replay, dim3(nb), dim3(64), 0, stream, R);
     }
+    if (t->timing) H2W_HIP(hipEventRecord(t->tev[t->tev_used++], stream));
+    if (t->nglp) {      // the records of the listed permutations, side by side
+        GlpEmitArgs E; E.consts = p->d_consts; E.list = R.glist; E.recs = R.recs; E.rec_stride = R.rec_stride; E.ncells = p->d_ncells; E.unit = t->d_glp_unit;
+        E.nglp = t->nglp; E.world = sharded ? (uint32_t)sh.world : 1u; E.rank = (uint32_t)sh.rank; E.nq = (uint32_t)p->shape.num_queries;
+        if ((uint64_t)n_proofs * t->nglp >= 0x7fffffffull) { set_error("h2w_fri_witness_batch: too many fused permutations in one call"); return -1; }
+        hipLaunchKernelGGL(k_glp_emit_traced, dim3((uint32_t)(n_proofs * t->nglp)), dim3(64), 0, stream, E);
+    }
+    if (t->timing) H2W_HIP(hipEventRecord(t->tev[t->tev_used++], stream));
     // expansion of the block records
     if (launch_plan_expand(p, n_proofs, R.recs, (uint32_t *)(ws + wl.ctr), R.out, cell_stride, cm, sharded ? &sh : nullptr, 2, stream) != 0) return -1;
+    if (t->timing) H2W_HIP(hipEventRecord(t->tev[t->tev_used++], stream));
     H2W_HIP(hipGetLastError());
     return 0;
 }
 }  // namespace h2w
 
-extern "C" h2w_plan *h2w_plan_from_trace(h2w_ctx *ctx, uint64_t proof_words, const char *const *parallel_scopes, size_t n_scopes, int device_id) {
-    Trace *tr = ctx_trace(ctx);
-    if (!tr) { set_error("h2w_plan_from_trace: the context is not in trace mode (h2w_ctx_trace_begin)"); return nullptr; }
-    if (!tr->err.empty()) { set_error("h2w_plan_from_trace: " + tr->err); return nullptr; }
-    if (tr->pending.kind) { set_error("h2w_plan_from_trace: a h2w_trace_input tag was never consumed"); return nullptr; }
-    const int L = ctx_lookup_bits(ctx);
-    std::string err;
+// The tape lowered segment by segment (passes 1 and 2 of h2w_plan_from_trace): what a plan is assembled from.
+struct Lowered {
+    std::vector<SegInfo> segs; std::vector<ValInfo> vals; std::unordered_map<uint64_t, uint32_t> val_of;      // val_of: cell offset of a handle -> value
+    std::vector<uint64_t> pool64; std::map<uint64_t, uint32_t> pool64_of; std::vector<fr_t> poolfr;
+    std::vector<uint64_t> meta; uint64_t nrec = 0; std::string err;
+};
+// The record block of one permutation as CoopSinkT::coop_poseidon_permute writes it (what k_glp_emit_traced runs): the sequential gadget on the
+// value backend, which is how h2w_plan_compile lays a compiled plan's out.  meta: (template, cell relative to the block).
+struct LayoutSink : SinkBase {
+    std::vector<uint64_t> *meta; const TemplateTable *tt; uint64_t nrec = 0, cell_off = 0, ndirect = 0;
+    void rec(int t, uint64_t, uint64_t, uint64_t, uint64_t) { meta->push_back(meta_pack((uint32_t)t, cell_off)); nrec++; cell_off += (uint64_t)tt->ncells(t); }
+    void cell(const fr_t &) { ndirect++; cell_off++; }
+    void skip(uint64_t, uint64_t) {}
+};
+static uint64_t glp_block_layout(const TemplateTable &tt, int L, const h2w_poseidon_consts_t *consts, std::vector<uint64_t> &meta) {
+    LayoutSink sink; sink.meta = &meta; sink.tt = &tt;
+    ValCfg cfg; memset(&cfg, 0, sizeof(cfg)); cfg.L = L; cfg.P = fr_params_init();
+    ValBackend<LayoutSink> be(sink, cfg, true);
+    PoseidonPermutationChip<ValBackend<LayoutSink>> pg(be, consts);
+    uint64_t st[SPONGE_WIDTH] = {0}; pg.permute(st);
+    return sink.ndirect == 0 && sink.nrec == (uint64_t)GLP_RECS ? sink.cell_off : 0;
+}
+// fuse: the stretches to lower as ONE op (by their first trace op), glp_meta their record block; cn: look for stretches instead (-> found);
+// capture: the lowered ops of the root segment as they are (the canonical tape is made from them)
+static void lower_trace(const Trace *tr, int L, TemplateTable &tt, const char *const *parallel_scopes, size_t n_scopes, Lowered &LW,
+                        const std::map<size_t, Stretch> *fuse, const std::vector<uint64_t> *glp_meta, const Canon *cn, std::vector<Stretch> *found, std::vector<NormOp> *capture) {
+    std::string &err = LW.err;
     auto bad = [&](const std::string &m) { if (err.empty()) err = m; };
-    TemplateTable tt(L);
     // ---- pass 1: segments
-    std::vector<SegInfo> segs(1);
+    std::vector<SegInfo> &segs = LW.segs; segs.assign(1, SegInfo());
     std::vector<int> op_seg(tr->ops.size(), 0);
     {
         std::vector<int> stack;      // per open scope: the segment it opened, or -1 (an ordinary scope)
@@ -412,12 +546,13 @@ extern "C" h2w_plan *h2w_plan_from_trace(h2w_ctx *ctx, uint64_t proof_words, con
     // scope names compare by string: give every parallel name one id
     { std::map<std::string, uint32_t> ids; for (SegInfo &s : segs) { if (s.parent < 0) continue; auto it = ids.find(tr->names[s.name]); if (it == ids.end()) it = ids.emplace(tr->names[s.name], (uint32_t)ids.size() + 1).first; s.name = it->second; } }
     // ---- pass 2: lowering, in tape order
-    std::unordered_map<uint64_t, uint32_t> val_of;      // cell offset of a handle -> value
-    std::vector<ValInfo> vals;
-    std::vector<uint64_t> pool64; std::map<uint64_t, uint32_t> pool64_of; std::vector<fr_t> poolfr;
+    std::unordered_map<uint64_t, uint32_t> &val_of = LW.val_of; std::vector<ValInfo> &vals = LW.vals;
+    std::vector<uint64_t> &pool64 = LW.pool64; std::map<uint64_t, uint32_t> &pool64_of = LW.pool64_of; std::vector<fr_t> &poolfr = LW.poolfr;
+    std::vector<Matcher> matchers;
+    if (cn) { matchers.resize(segs.size()); for (size_t si = 0; si < segs.size(); si++) { matchers[si].cn = cn; matchers[si].found = found; matchers[si].seg = (int)si; segs[si].mt = &matchers[si]; } }
     auto lit64 = [&](uint64_t v) { auto it = pool64_of.find(v); if (it != pool64_of.end()) return it->second; pool64.push_back(v); pool64_of[v] = (uint32_t)pool64.size() - 1; return (uint32_t)pool64.size() - 1; };
     auto litfr = [&](const fr_t &v) { for (size_t i = 0; i < poolfr.size(); i++) if (fr_eq(poolfr[i], v)) return (uint32_t)i; poolfr.push_back(v); return (uint32_t)poolfr.size() - 1; };
-    std::vector<uint64_t> meta; uint64_t nrec = 0;
+    std::vector<uint64_t> &meta = LW.meta; uint64_t &nrec = LW.nrec;
     auto is_ancestor = [&](int a, int s) { for (int x = s; x >= 0; x = segs[(size_t)x].parent) if (x == a) return true; return false; };
     // operand of op in segment s: the handle's cell, or a literal
     auto ref_of = [&](int s, const TraceIn &in, int *width_out) -> uint32_t {
@@ -446,7 +581,7 @@ extern "C" h2w_plan *h2w_plan_from_trace(h2w_ctx *ctx, uint64_t proof_words, con
         if (o.code == TR_SCOPE_PUSH || o.code == TR_SCOPE_POP) {
             // entering a parallel child: the parent steps over its records and cells (filled in when the child ends)
             if (o.code == TR_SCOPE_PUSH && s != prev_seg && segs[(size_t)s].parent == prev_seg) {
-                SegInfo &Pn = segs[(size_t)prev_seg]; Pn.tape.push_back(DOP_SKIP | (5u << 24)); Pn.last_const_at = -1; open_child[(size_t)s] = (int)Pn.tape.size(); for (int k = 0; k < 4; k++) Pn.tape.push_back(0);
+                SegInfo &Pn = segs[(size_t)prev_seg]; Pn.tape.push_back(DOP_SKIP | (5u << 24)); Pn.last_const_at = -1; if (Pn.mt) Pn.mt->boundary(); open_child[(size_t)s] = (int)Pn.tape.size(); for (int k = 0; k < 4; k++) Pn.tape.push_back(0);
                 S.cell0 = o.cell0; S.rec0 = nrec; S.started = true;
             }
             if (o.code == TR_SCOPE_POP && s != prev_seg && segs[(size_t)prev_seg].parent == s) {
@@ -462,6 +597,19 @@ extern "C" h2w_plan *h2w_plan_from_trace(h2w_ctx *ctx, uint64_t proof_words, con
         std::vector<uint32_t> &T = S.tape; uint64_t want_cells = 0; int w0 = 0, w1 = 0, w2 = 0;
         size_t op_at = T.size();
         auto head = [&](uint32_t op, uint32_t n = 0, uint32_t aux = 0) { if (aux > 255) bad("internal: op parameter too wide"); T.push_back(op | (n << 8) | (aux << 16)); };
+        const uint32_t slots_before = S.nslots; bool ka_fused = false;
+        const Stretch *fz = nullptr;
+        if (fuse) { auto f = fuse->find(i); if (f != fuse->end()) fz = &f->second; }
+        if (fz) {      // a verified permutation: one op, its 12 results in fresh slots, its record block laid out as the emission kernel writes it
+            head(DOP_GLPERM);
+            for (int k = 0; k < SPONGE_WIDTH; k++) { int w; T.push_back(ref_of(s, fz->in[k], &w)); if (w != W64) bad("internal: a wide input of a fused permutation"); }
+            const uint32_t base = S.nslots;
+            for (int k = 0; k < SPONGE_WIDTH; k++) new_val(s, fz->out[k], W64, false, 0);
+            T.push_back(base); T.push_back(S.nglp++); T.push_back((uint32_t)(fz->cell1 - fz->cell0));
+            for (uint64_t m : *glp_meta) meta.push_back(meta_pack(meta_tmpl(m), fz->cell0 + meta_off(m)));
+            nrec += glp_meta->size(); S.nrecs += glp_meta->size(); S.last_const_at = -1;
+            want_cells = o.ncells; i = fz->tr1 - 1;      // (the loop goes on behind the stretch)
+        } else
         switch (o.code) {
             case TR_LOAD_CONSTANT: {
                 const fr_t c = tr->consts[(size_t)o.imm]; const bool small = (c.l[1] | c.l[2] | c.l[3]) == 0;
@@ -471,7 +619,7 @@ extern "C" h2w_plan *h2w_plan_from_trace(h2w_ctx *ctx, uint64_t proof_words, con
                     add_rec(s, T_CONST1, o.cell0); want_cells = 1;
                 } else if (o.tag.kind != 0) bad("a hint tag on a constant");
                 else if (small) { const uint32_t li = lit64(c.l[0]); head(DOP_CONST1); T.push_back(mkref(RK_LIT64, W64, li)); T.push_back(NO_SLOT); new_val(s, out[0], W64, true, li); add_rec(s, T_CONST1, o.cell0); want_cells = 1;
-                                  S.last_const_at = (long)op_at; S.last_const_cell = o.cell0; }
+                                  S.last_const_at = (long)op_at; S.last_const_cell = o.cell0; S.last_const_tr = i; }
                 else { const uint32_t li = litfr(c); head(DOP_FRCELL); T.push_back(mkref(RK_LITFR, WFR, li)); T.push_back(NO_SLOT); new_val(s, out[0], WFR, true, li); want_cells = 1; }
                 break;
             }
@@ -565,7 +713,7 @@ extern "C" h2w_plan *h2w_plan_from_trace(h2w_ctx *ctx, uint64_t proof_words, con
                 if (w0 != W64 || w1 != W64 || w2 != W64) { bad("a Goldilocks op on a wide value"); break; }
                 if (o.sub == T_GLOP && !in[0].lit && S.last_const_at >= 0 && (size_t)S.last_const_at + 3 == T.size() && in[0].v == S.last_const_cell && S.last_const_cell + 1 == o.cell0 && ref_kind(a) == RK_LIT64) {
                     // load_constant(K) immediately followed by the op that takes it (GoldilocksChip's constant operands, e.g. hash/poseidon/permutation.rs:55-68): ONE record [K][C, A, B, V]...
-                    op_at = (size_t)S.last_const_at; T.resize(op_at); meta.pop_back(); nrec--; S.nrecs--;
+                    op_at = (size_t)S.last_const_at; T.resize(op_at); meta.pop_back(); nrec--; S.nrecs--; ka_fused = true;
                     T.push_back(DOP_GLOP | ((uint32_t)T_KA_GLOP << 16)); T.push_back(a); T.push_back(b); T.push_back(c3); T.push_back(new_val(s, out[0], W64, false, 0)); add_rec(s, T_KA_GLOP, o.cell0 - 1);
                     S.last_const_at = -1; want_cells = (uint64_t)tt.ncells(T_GLOP); break;
                 }
@@ -573,8 +721,16 @@ extern "C" h2w_plan *h2w_plan_from_trace(h2w_ctx *ctx, uint64_t proof_words, con
             }
             default: bad("unknown op in the trace");
         }
-        if (!(o.code == TR_LOAD_CONSTANT && S.last_const_at == (long)op_at)) S.last_const_at = -1;
+        if (fz || !(o.code == TR_LOAD_CONSTANT && S.last_const_at == (long)op_at)) S.last_const_at = -1;
         if (T.size() > op_at) {
+            if ((S.mt || (capture && s == 0)) && err.empty()) {      // the op as lowered, its operands still as mkref words
+                uint32_t first, count; operand_span(T[op_at] & 0xff, (T[op_at] >> 8) & 0xff, first, count);
+                NormOp no; no.hdr = T[op_at] & 0xffffffu; no.nin = count <= 3 ? count : 0xffu; no.slots_before = slots_before;
+                for (uint32_t k2 = 0; k2 < count && k2 < 3; k2++) { no.ref[k2] = T[op_at + first + k2]; if (ref_kind(no.ref[k2]) == RK_LIT64) no.lit[k2] = pool64[ref_idx(no.ref[k2])]; }
+                no.out = count <= 3 && op_at + first + count < T.size() ? T[op_at + first + count] : NO_SLOT;
+                no.tr0 = ka_fused ? S.last_const_tr : i; no.tr1 = i + 1; no.cell0 = ka_fused ? o.cell0 - 1 : o.cell0; no.cell1 = o.cell0 + o.ncells; no.out_cell = o.n_out ? out[0] : 0; no.tin = in;
+                if (S.mt) { if (ka_fused) S.mt->drop_pending(); S.mt->feed(no); } else { if (ka_fused) capture->pop_back(); capture->push_back(no); }
+            }
             const size_t len = T.size() - op_at; if (len > 255) bad("internal: op too long"); T[op_at] |= (uint32_t)len << 24;
             // operands: those in the lane's ring or in the LDS part of the pools become fast refs; the others are fetched into fresh ring slots by DOP_FETCH
             // ops in front of this one.  The ring holds the last RING_K slots WRITTEN, the temporaries included: decided against the slot count after them.
@@ -605,8 +761,98 @@ extern "C" h2w_plan *h2w_plan_from_trace(h2w_ctx *ctx, uint64_t proof_words, con
         }
         if (err.empty() && want_cells != o.ncells) bad("internal: op " + std::to_string(o.code) + " appended " + std::to_string(o.ncells) + " cells on the host, the device template has " + std::to_string(want_cells));
     }
-    if (!err.empty()) { set_error("h2w_plan_from_trace: " + err); return nullptr; }
+    for (Matcher &m : matchers) m.commit();
+    for (SegInfo &S : segs) S.mt = nullptr;
+    if (!err.empty()) return;
     segs[0].tape.push_back(DOP_END | (1u << 24)); segs[0].cell0 = 0; segs[0].rec0 = 0;
+}
+
+// The canonical tape of ONE permutation on `consts`: the library's own PoseidonChip::permute (what h2w_chip_gl_poseidon_permute runs) recorded on 12
+// abstract inputs and lowered by lower_trace like any tape; its operands classified (a literal, a value of the stretch, an input).
+static bool canonical_tape(int L, TemplateTable &tt, const h2w_poseidon_consts_t *consts, Canon &cn, std::string &err) {
+    h2w_ctx *c = h2w_ctx_new(L, 1, -1);
+    if (!c) { err = "cannot create the recording context"; return false; }
+    h2w_assigned_t in[SPONGE_WIDTH], out[SPONGE_WIDTH]; int rc = h2w_ctx_trace_begin(c);
+    for (int i = 0; i < SPONGE_WIDTH && rc == 0; i++) { rc = h2w_trace_input(c, (uint64_t)i, 1); if (rc == 0) rc = h2w_gl_load_witness(c, (uint64_t)i, &in[i]); }
+    if (rc == 0) rc = h2w_chip_gl_poseidon_permute(c, consts, in, out);
+    const Trace *tr = ctx_trace(c);
+    if (rc != 0 || !tr || !tr->err.empty()) { err = "cannot record the canonical permutation"; h2w_ctx_free(c); return false; }
+    Lowered LW; std::vector<NormOp> ops;
+    lower_trace(tr, L, tt, nullptr, 0, LW, nullptr, nullptr, nullptr, nullptr, &ops);
+    bool ok = LW.err.empty() && ops.size() > (size_t)SPONGE_WIDTH;
+    if (!ok) err = "the canonical permutation does not lower: " + LW.err;
+    // the 12 loads come first
+    std::unordered_map<uint32_t, uint32_t> prod, inslot;      // slot -> op of the stretch; slot -> input
+    for (int i = 0; ok && i < SPONGE_WIDTH; i++) {
+        if ((ops[(size_t)i].hdr & 0xff) != DOP_LOADW || ops[(size_t)i].out == NO_SLOT) { ok = false; err = "internal: inputs of the canonical tape"; } else inslot[ops[(size_t)i].out] = (uint32_t)i;
+    }
+    for (size_t j = SPONGE_WIDTH; ok && j < ops.size(); j++) {
+        const NormOp &o = ops[j]; CanonOp c2; c2.hdr = o.hdr; c2.nin = o.nin; c2.has_out = o.out != NO_SLOT;
+        if (o.nin > 3) { ok = false; err = "internal: an op of the canonical tape with more than three operands"; break; }
+        for (uint32_t k = 0; k < o.nin; k++) {
+            const int rk = ref_kind(o.ref[k]); const uint32_t ix = ref_idx(o.ref[k]);
+            if (rk == RK_LIT64) { c2.kind[k] = CK_LIT; c2.arg[k] = o.lit[k]; }
+            else if (rk == RK_LOCAL && inslot.count(ix)) { c2.kind[k] = CK_INPUT; c2.arg[k] = inslot[ix]; }
+            else if (rk == RK_LOCAL && prod.count(ix)) { c2.kind[k] = CK_INTERIOR; c2.arg[k] = prod[ix]; }
+            else { ok = false; err = "internal: an operand of the canonical tape"; }
+        }
+        if (c2.has_out) prod[o.out] = (uint32_t)cn.ops.size();
+        cn.ops.push_back(c2);
+    }
+    for (int i = 0; ok && i < SPONGE_WIDTH; i++) {
+        auto it = LW.val_of.find(out[i].offset);
+        if (!out[i].has_cell || it == LW.val_of.end() || LW.vals[it->second].is_static || !prod.count(LW.vals[it->second].slot)) { ok = false; err = "internal: outputs of the canonical tape"; break; }
+        cn.out_prod[i] = prod[LW.vals[it->second].slot];
+    }
+    if (ok) cn.ncells = ops.back().cell1 - ops[SPONGE_WIDTH].cell0;
+    h2w_ctx_free(c);
+    return ok;
+}
+
+static h2w_plan *plan_from_trace(h2w_ctx *ctx, uint64_t proof_words, const char *const *parallel_scopes, size_t n_scopes, int device_id, const h2w_poseidon_consts_t *consts, uint32_t flags) {
+    Trace *tr = ctx_trace(ctx);
+    if (!tr) { set_error("h2w_plan_from_trace: the context is not in trace mode (h2w_ctx_trace_begin)"); return nullptr; }
+    if (!tr->err.empty()) { set_error("h2w_plan_from_trace: " + tr->err); return nullptr; }
+    if (tr->pending.kind) { set_error("h2w_plan_from_trace: a h2w_trace_input tag was never consumed"); return nullptr; }
+    const bool fusing = (flags & H2W_TRACE_FUSE_GL_PERMUTE) != 0;
+    if (flags & ~(uint32_t)H2W_TRACE_FUSE_GL_PERMUTE) { set_error("h2w_plan_from_trace_ex: unknown flag"); return nullptr; }
+    if (fusing && !consts) { set_error("h2w_plan_from_trace_ex: H2W_TRACE_FUSE_GL_PERMUTE needs the Poseidon tables the permutations are claimed to use"); return nullptr; }
+    const int L = ctx_lookup_bits(ctx);
+    TemplateTable tt(L);
+    Lowered LW; std::map<size_t, Stretch> fuse; std::vector<uint64_t> glp_meta; uint64_t n_candidates = 0, glp_block_cells = 0;
+    if (fusing) {
+        // the stretches that equal the canonical tape word for word, found on a first lowering; those nothing outside reads into are lowered as one op
+        Canon cn; std::string cerr; std::vector<Stretch> found;
+        if (!canonical_tape(L, tt, consts, cn, cerr)) { set_error("h2w_plan_from_trace_ex: " + cerr); return nullptr; }
+        const uint64_t block_cells = glp_block_cells = glp_block_layout(tt, L, consts, glp_meta);
+        if (block_cells == 0 || block_cells != cn.ncells) { set_error("h2w_plan_from_trace_ex: the record block of a permutation (" + std::to_string(block_cells) + " cells) is not the traced one (" + std::to_string(cn.ncells) + " cells)"); return nullptr; }
+        { Lowered first; lower_trace(tr, L, tt, parallel_scopes, n_scopes, first, nullptr, nullptr, &cn, &found, nullptr); if (!first.err.empty()) { set_error("h2w_plan_from_trace: " + first.err); return nullptr; } }
+        std::sort(found.begin(), found.end(), [](const Stretch &a, const Stretch &b) { return a.cell0 < b.cell0; });
+        // an interior value read outside its stretch: every operand handle of the trace (the hints' operands too) against the stretches' cell ranges
+        auto reads = [&](size_t op, uint64_t cell) {
+            auto it = std::upper_bound(found.begin(), found.end(), cell, [](uint64_t c, const Stretch &x) { return c < x.cell0; });
+            if (it == found.begin()) return;
+            Stretch &x = *(it - 1);
+            if (cell >= x.cell1 || (op >= x.tr0 && op < x.tr1)) return;
+            for (int k = 0; k < SPONGE_WIDTH; k++) if (x.out[k] == cell) return;
+            x.escaped = true;
+        };
+        for (size_t i = 0; i < tr->ops.size(); i++) {
+            const TraceOp &o = tr->ops[i];
+            for (uint32_t k = 0; k < o.n_in; k++) if (!tr->ins[o.first_in + k].lit) reads(i, tr->ins[o.first_in + k].v);
+            if (o.tag.kind >= 2) { reads(i, o.tag.a); reads(i, o.tag.b); }
+        }
+        for (const Stretch &x : found) {
+            if (x.cell1 - x.cell0 != block_cells) { set_error("h2w_plan_from_trace_ex: a permutation's stretch has " + std::to_string(x.cell1 - x.cell0) + " traced cells, its record block " + std::to_string(block_cells)); return nullptr; }
+            if (x.const_bad || x.escaped) n_candidates++; else fuse.emplace(x.tr0, x);
+        }
+    }
+    lower_trace(tr, L, tt, parallel_scopes, n_scopes, LW, fuse.empty() ? nullptr : &fuse, &glp_meta, nullptr, nullptr, nullptr);
+    std::string &err = LW.err;
+    auto bad = [&](const std::string &m) { if (err.empty()) err = m; };
+    if (!err.empty()) { set_error("h2w_plan_from_trace: " + err); return nullptr; }
+    std::vector<SegInfo> &segs = LW.segs; std::vector<uint64_t> &meta = LW.meta; const uint64_t nrec = LW.nrec;
+    std::vector<uint64_t> &pool64 = LW.pool64; std::vector<fr_t> &poolfr = LW.poolfr;
     // ---- shard units: the depth-1 instances in tape order (unit q: the q-th; "verify_query_round" instance q of the standard trace, where the
     // compiled plan's query block q starts: AbiBackend::query_begin).  Shardable: the root's block [0, unit 0) and the units back to back to the end
     // of the stream and of the records, units 1.. all of one size (the compiled plan's StrandTable: query 0, a later query).
@@ -658,7 +904,7 @@ extern "C" h2w_plan *h2w_plan_from_trace(h2w_ctx *ctx, uint64_t proof_words, con
                 int found = -1;
                 for (size_t t = 0; t < members.size() && found < 0; t++) {
                     const SegInfo &M = segs[(size_t)members[t][0]];
-                    if (M.depth == S.depth && M.name == S.name && M.nslots == S.nslots && M.imps.size() == S.imps.size() && M.inputs.size() == S.inputs.size() && M.tape == S.tape) found = (int)t;
+                    if (M.depth == S.depth && M.name == S.name && M.nslots == S.nslots && M.nglp == S.nglp && M.imps.size() == S.imps.size() && M.inputs.size() == S.inputs.size() && M.tape == S.tape) found = (int)t;
                 }
                 if (found < 0) { members.push_back({}); found = (int)members.size() - 1; }
                 S.tmpl = found; S.inst = (uint32_t)members[(size_t)found].size(); members[(size_t)found].push_back((int)si);
@@ -671,7 +917,8 @@ extern "C" h2w_plan *h2w_plan_from_trace(h2w_ctx *ctx, uint64_t proof_words, con
             for (int si : members[t]) {
                 const SegInfo &S = segs[(size_t)si];
                 InstD I; I.cell0 = S.cell0; I.rec0 = S.rec0; I.imp0 = (uint32_t)imps.size(); I.in0 = (uint32_t)inputs.size();
-                I.unit = S.unit; I.ucell0 = S.unit == NO_SLOT ? 0 : segs[(size_t)units[S.unit]].cell0; I.pad = 0; tp->h_unit.push_back(S.unit);
+                I.unit = S.unit; I.ucell0 = S.unit == NO_SLOT ? 0 : segs[(size_t)units[S.unit]].cell0; tp->h_unit.push_back(S.unit);
+                I.glp0 = tp->nglp; tp->nglp += S.nglp; tp->h_glp_unit.insert(tp->h_glp_unit.end(), S.nglp, S.unit);
                 for (const ImpD &m : S.imps) { const SegInfo &Pn = segs[(size_t)m.tmpl]; imps.push_back(ImpD{(uint32_t)Pn.tmpl, Pn.inst, m.slot}); }
                 inputs.insert(inputs.end(), S.inputs.begin(), S.inputs.end());
                 insts.push_back(I);
@@ -710,6 +957,8 @@ extern "C" h2w_plan *h2w_plan_from_trace(h2w_ctx *ctx, uint64_t proof_words, con
             if (ok) switch (op) {
                 case DOP_SKIP: ok = len == 5; break;
                 case DOP_GLOPRUN: ok = n >= 2; for (uint32_t k2 = 0; ok && k2 < n; k2++) ok = okref(R_(2 + 4 * k2), 1) && okref(R_(3 + 4 * k2), 1) && okref(R_(4 + 4 * k2), 1) && (uint64_t)(R_(5 + 4 * k2) & 0xffffffu) + 1 <= M.nslots && (R_(5 + 4 * k2) >> 24) < T_DYNAMIC; break;
+                case DOP_GLPERM: ok = len == GLPERM_WORDS && fusing && glp_meta.size() == (size_t)GLP_RECS && okout(R_(13), SPONGE_WIDTH) && R_(13) != NO_SLOT && R_(14) < M.nglp && R_(15) == (uint32_t)glp_block_cells;
+                                 for (uint32_t k2 = 0; ok && k2 < (uint32_t)SPONGE_WIDTH; k2++) ok = okref(R_(1 + k2), 1) && ((R_(1 + k2) >> 27) & 3u) == W64; break;
                 case DOP_FETCH: ok = len == 3 && n >= 1 && n <= 4 && okslow(R_(1)) && (uint64_t)R_(2) + n <= M.nslots; break;
                 case DOP_CONST1: case DOP_LOADW: ok = len == 3 && okref(R_(1), 1) && okout(R_(2), 1); break;
                 case DOP_FRCELL: ok = len == 3 && okref(R_(1), 4) && okout(R_(2), 4); break;
@@ -735,13 +984,14 @@ extern "C" h2w_plan *h2w_plan_from_trace(h2w_ctx *ctx, uint64_t proof_words, con
     }
     if (!err.empty()) { set_error("h2w_plan_from_trace: " + err); delete tp; return nullptr; }
     for (uint32_t w : inputs) if (w >= proof_words) { set_error("h2w_plan_from_trace: an input tag beyond proof_words"); delete tp; return nullptr; }
-    tp->n_ops = tr->ops.size(); tp->n_segments = segs.size(); tp->why_unshardable = why_unshardable;
+    tp->n_ops = tr->ops.size(); tp->n_segments = segs.size(); tp->why_unshardable = why_unshardable; tp->n_candidates = n_candidates;
 
     // ---- the plan handle
     h2w_plan *pl = new h2w_plan(L);
     memset(&pl->shape, 0, sizeof(pl->shape)); pl->shape.lookup_bits = L; pl->shape.num_queries = 1; pl->shape.hash_mode = 1;
     pl->device = device_id; pl->P = fr_params_init(); memset(&pl->st, 0, sizeof(pl->st)); memset(&pl->pl, 0, sizeof(pl->pl)); memset(&pl->d, 0, sizeof(pl->d));
     pl->pl.total = proof_words; pl->nrec = nrec; pl->ncells = ctx_num_cells(ctx); pl->traced = tp;
+    if (consts) pl->h_consts = *consts;
     for (uint64_t m : meta) pl->rec_cells += (uint64_t)pl->tt.ncells((int)meta_tmpl(m));
     // the block structure (StrandTable: what h2w_plan_strand_layout / _shard_cells / _shard_block and the sharded expansion read): unshardable, one block
     StrandTable &st = pl->st; st.first_zero_kind = -1; st.first_zero_unit = -1; st.total_rec = nrec; st.total_cell = pl->ncells;
@@ -795,8 +1045,42 @@ extern "C" h2w_plan *h2w_plan_from_trace(h2w_ctx *ctx, uint64_t proof_words, con
         std::vector<fr_t> inv(2 * INV_TAB, fr_zero());
         for (int k2 = 1; k2 < INV_TAB; k2++) { inv[k2] = fr_inv(fr_from_u64((uint64_t)k2), pl->P); inv[INV_TAB + k2] = fr_neg(inv[k2]); }
         if (put((void **)&pl->d_inv, inv.data(), inv.size() * sizeof(fr_t)) != 0) return -1;
+        if (tp->nglp) {      // the tables the fused permutations were verified on, the derived tables behind them (as h2w_plan_compile builds a compiled plan's)
+            std::vector<uint64_t> aux(GLP_AUX_WORDS); glp_aux_tables(*consts, aux.data());
+            H2W_HIP(hipMalloc((void **)&pl->d_consts, sizeof(h2w_poseidon_consts_t) + aux.size() * sizeof(uint64_t)));
+            H2W_HIP(hipMemcpy(pl->d_consts, consts, sizeof(h2w_poseidon_consts_t), hipMemcpyHostToDevice));
+            H2W_HIP(hipMemcpy(pl->d_consts + 1, aux.data(), aux.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+            if (put((void **)&tp->d_glp_unit, tp->h_glp_unit.data(), tp->h_glp_unit.size() * 4) != 0) return -1;
+        }
         return 0;
     };
     if (up() != 0) { h2w_plan_free(pl); return nullptr; }
     return pl;
+}
+
+extern "C" h2w_plan *h2w_plan_from_trace(h2w_ctx *ctx, uint64_t proof_words, const char *const *parallel_scopes, size_t n_scopes, int device_id) {
+    return plan_from_trace(ctx, proof_words, parallel_scopes, n_scopes, device_id, nullptr, 0);
+}
+extern "C" h2w_plan *h2w_plan_from_trace_ex(h2w_ctx *ctx, uint64_t proof_words, const char *const *parallel_scopes, size_t n_scopes, int device_id, const h2w_poseidon_consts_t *consts, uint32_t flags) {
+    return plan_from_trace(ctx, proof_words, parallel_scopes, n_scopes, device_id, consts, flags);
+}
+extern "C" int h2w_plan_trace_info(const h2w_plan *p, uint64_t out[6]) {
+    if (!p || !out) { set_error("h2w_plan_trace_info: null argument"); return -1; }
+    if (!p->traced) { set_error("h2w_plan_trace_info: not a traced plan (h2w_plan_from_trace)"); return -1; }
+    const TracedPlan *t = p->traced;
+    out[0] = t->n_ops; out[1] = t->n_segments; out[2] = t->tmpls.size(); out[3] = t->nglp; out[4] = t->n_candidates; out[5] = t->nglp;
+    return 0;
+}
+// ms of the kernels of the last call: the k_replay launch of every depth, k_glp_emit_traced, the expansion.  The first call switches the events on
+// (0 entries); later ones wait for the last call and report it.
+extern "C" int h2w_plan_trace_timing(h2w_plan *p, float *ms, uint32_t cap) {
+    if (!p || !ms) { set_error("h2w_plan_trace_timing: null argument"); return -1; }
+    if (!p->traced || p->device < 0) { set_error("h2w_plan_trace_timing: not a traced plan on a device"); return -1; }
+    TracedPlan *t = p->traced; DeviceGuard dg(p->device);
+    if (!t->timing) { for (; t->n_tev < 16; t->n_tev++) H2W_HIP(hipEventCreate(&t->tev[t->n_tev])); t->timing = true; return 0; }
+    if (t->tev_used < 2) return 0;
+    H2W_HIP(hipEventSynchronize(t->tev[t->tev_used - 1]));
+    int n = 0;
+    for (int i = 0; i + 1 < t->tev_used && (uint32_t)n < cap; i++, n++) H2W_HIP(hipEventElapsedTime(&ms[n], t->tev[i], t->tev[i + 1]));
+    return n;
 }

@@ -190,6 +190,25 @@ int h2w_chip_verify_stark(h2w_ctx *, const h2w_shape_t *, const h2w_poseidon_con
 int h2w_ctx_trace_begin(h2w_ctx *);                                   /* on a fresh context */
 int h2w_trace_input(h2w_ctx *, uint64_t word, uint32_t n_words);      /* no-op on a context that is not tracing */
 h2w_plan *h2w_plan_from_trace(h2w_ctx *, uint64_t proof_words, const char *const *parallel_scopes, size_t n_scopes, int device_id);
+/* h2w_plan_from_trace with options (flags == 0: exactly h2w_plan_from_trace; consts may then be null).
+ * H2W_TRACE_FUSE_GL_PERMUTE: stretches of the tape that ARE a Goldilocks-Poseidon permutation on `consts` run as one device op each instead of
+ * ~2,600 interpreted ones.  The library records its own PoseidonChip::permute (h2w_chip_gl_poseidon_permute) on `consts` once, lowers it like the
+ * caller's tape, and fuses a stretch only if it equals that canonical tape word for word - op codes, record templates, constant values, dataflow -
+ * with its 12 inputs abstracted, lies in one segment, and nothing outside it reads a value it computes other than its 12 outputs.  Scope names play
+ * no part, traced values neither.  Everything else - a permutation on other tables, a hand-driven variant, a stretch with a value that escapes - stays
+ * interpreted: the stream is the same either way.  The lane computes the permutation's values (plonky2's fast form) and lists {first record,
+ * input state}; one wavefront per listed permutation writes its records before the expansion.  The plan needs 104 more bytes of workspace per
+ * fused permutation and proof; every call that works on a traced plan works on it.
+ * h2w_plan_trace_info: out = {ops of the trace, segments, templates, fused permutations, permutation-shaped stretches left interpreted (other
+ * constants, or an interior value read outside), list entries per proof}.
+ * h2w_plan_trace_timing (a traced plan on a device): the first call switches event timing on and returns 0; later calls wait for the plan's last
+ * witness call and fill ms[] with the time of each of its kernels in launch order - k_replay depth by depth, the permutation records' kernel (0
+ * without fused permutations), the expansion - and return how many (at most cap). */
+#define H2W_TRACE_FUSE_GL_PERMUTE 1
+h2w_plan *h2w_plan_from_trace_ex(h2w_ctx *, uint64_t proof_words, const char *const *parallel_scopes, size_t n_scopes, int device_id,
+                                 const h2w_poseidon_consts_t *consts, uint32_t flags);
+int h2w_plan_trace_info(const h2w_plan *, uint64_t out[6]);
+int h2w_plan_trace_timing(h2w_plan *, float *ms, uint32_t cap);
 
 /* ------------------------------------------------------------------ advice hand-off (eager contexts) */
 /* Expands all pending records on the GPU; *dev_ptr receives a device pointer to num_cells*32 bytes

@@ -2,7 +2,10 @@
 """Trace h2w_chip_verify_stark once, lower it, replay it on --batch proofs: wall time per launch (and, under rocprofv3 --kernel-trace, the duration of
 every k_replay dispatch: one per template, depth by depth).  usage: replay_timing.py [--config cfg3] [--hash bn254|gl] [--batch 64] [--reps 2]
 --world W --rank R: after the unsharded launches of --batch proofs, what rank R of W runs: a launch of W x batch proofs into its packed buffer
-(h2w_fri_witness_batch_shard_compact) - its own-cell rate beside the unsharded rate, and whether the buffer equals the compiled plan's packed buffer."""
+(h2w_fri_witness_batch_shard_compact) - its own-cell rate beside the unsharded rate, and whether the buffer equals the compiled plan's packed buffer.
+--fuse: BOTH plans from the one trace - h2w_plan_from_trace and h2w_plan_from_trace_ex with H2W_TRACE_FUSE_GL_PERMUTE - in one process: for each, ms per
+launch, cells/s, the time of every kernel of a launch (h2w_plan_trace_timing: k_replay depth by depth, the permutation records' kernel, the expansion),
+one proof enqueue to completion, and whether the two streams are equal.  --out FILE: the JSON lines appended to FILE as well."""
 import argparse, importlib, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -13,6 +16,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="cfg3"); ap.add_argument("--hash", default="bn254"); ap.add_argument("--batch", type=int, default=64); ap.add_argument("--reps", type=int, default=2); ap.add_argument("--streams", type=int, default=1)
     ap.add_argument("--world", type=int, default=1); ap.add_argument("--rank", type=int, default=0)
+    ap.add_argument("--fuse", action="store_true"); ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -27,8 +31,12 @@ def main():
     ctx = api.Context(21, True, 0); ctx.trace_begin()
     t0 = time.perf_counter(); api.verify_stark(ctx, sh, k, host[:words].astype(np.uint64)); t1 = time.perf_counter()
     plan = api.Plan.from_trace(ctx, words); t2 = time.perf_counter()
+    fused = api.Plan.from_trace(ctx, words, fuse_consts=k) if a.fuse else None; t3 = time.perf_counter()
     ctx.close()
     proofs = torch.from_numpy(host).cuda()      # (the unsharded launches take the first --batch)
+    if a.fuse:
+        fuse_report(a, torch, plan, fused, proofs, {"trace_s": round(t1 - t0, 3), "lower_s": round(t2 - t1, 3), "lower_fused_s": round(t3 - t2, 3)})
+        return
     adv = torch.empty(a.batch * plan.num_cells * 32, dtype=torch.uint8, device="cuda"); ws = torch.zeros(plan.workspace_bytes(a.batch), dtype=torch.uint8, device="cuda")
     st = torch.cuda.current_stream().cuda_stream
     if a.streams > 1:      # launches in flight: the root kernel of one (two wavefronts) runs beside the other's Merkle lanes
@@ -72,6 +80,41 @@ def main():
         print(json.dumps({"config": a.config, "hash": a.hash, "world": W, "rank": R, "proofs_per_launch": n, "own_cells": cells, "ms_per_launch": [round(x, 2) for x in ms[1:]],
                           "own_G_cells_per_s": round(own_rate, 2), "unsharded_G_cells_per_s": round(unsharded_rate, 2), "ratio": round(own_rate / unsharded_rate, 3), "status_ok": ok,
                           "packed_equals_compiled_plan": bool(torch.equal(buf, want))}))
+
+
+def fuse_report(a, torch, plan, fused, proofs, times):
+    st = torch.cuda.current_stream().cuda_stream
+    lines = [dict(config=a.config, hash=a.hash, batch=a.batch, reps=a.reps, cells_per_proof=plan.num_cells, trace_info=fused.trace_info(), **times)]
+    streams = []
+    for name, pl in (("unfused", plan), ("fused", fused)):
+        adv = torch.empty(a.batch * pl.num_cells * 32, dtype=torch.uint8, device="cuda"); ws = torch.zeros(pl.workspace_bytes(a.batch), dtype=torch.uint8, device="cuda")
+        pl.trace_timing()                                  # events on
+        ms, kern = [], []
+        for i in range(a.reps + 1):                        # (the first launch is the warm-up)
+            torch.cuda.synchronize(); t = time.perf_counter()
+            pl.run(proofs.data_ptr(), a.batch, adv.data_ptr(), ws.data_ptr(), st)
+            torch.cuda.synchronize(); ms.append((time.perf_counter() - t) * 1e3); kern.append(pl.trace_timing())
+        assert pl.status(ws.data_ptr(), a.batch, st) == [0] * a.batch
+        one = []
+        for i in range(a.reps + 1):                        # one proof, enqueue to completion
+            torch.cuda.synchronize(); t = time.perf_counter()
+            pl.run(proofs.data_ptr(), 1, adv.data_ptr(), ws.data_ptr(), st)
+            torch.cuda.synchronize(); one.append((time.perf_counter() - t) * 1e3)
+        pl.run(proofs.data_ptr(), a.batch, adv.data_ptr(), ws.data_ptr(), st); torch.cuda.synchronize()
+        streams.append(adv)
+        nd = len(kern[0]) - 2                              # k_replay launches (one per depth), then the records' kernel, then the expansion
+        lines.append({"plan": name, "records": pl.num_records, "ws_GB": round(pl.workspace_bytes(a.batch) / 1e9, 3), "ms_per_launch": [round(x, 3) for x in ms[1:]],
+                      "G_cells_per_s": [round(pl.num_cells * a.batch / (x * 1e-3) / 1e9, 3) for x in ms[1:]],
+                      "k_replay_ms_by_depth": [[round(x, 3) for x in kk[:nd]] for kk in kern[1:]], "glp_emit_ms": [round(kk[nd], 3) for kk in kern[1:]],
+                      "expand_ms": [round(kk[nd + 1], 3) for kk in kern[1:]], "one_proof_ms": [round(x, 3) for x in one[1:]]})
+    lines.append({"streams_equal": bool(torch.equal(streams[0], streams[1]))})
+    for ln in lines:
+        print(json.dumps(ln))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "a") as f:
+            for ln in lines:
+                f.write(json.dumps(ln) + "\n")
 
 
 if __name__ == "__main__":
