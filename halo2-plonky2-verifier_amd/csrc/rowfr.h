@@ -20,7 +20,8 @@
 // v_permlane16_swap / v_permlane32_swap (gfx950), a dynamic operand is replicated with nine v_readlane.
 //
 // The same source runs on the host with the lanes simulated (tests/cpp/rowfr_check.cpp pins the arithmetic, the bounds and the whole
-// permutation against field.h and chips.h before any GPU sees it).
+// permutation against field.h and chips.h before any GPU sees it).  What the host form only models - the DPP row shifts with bound_ctrl, the bank masks, the
+// quad_perm broadcasts and the lane swaps - is checked on the device with the same operands: tests/test_gpu_devcheck.py (tests/hip/devcheck.hip).
 #pragma once
 #include "field.h"
 

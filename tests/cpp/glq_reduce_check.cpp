@@ -1,6 +1,8 @@
 // Host restatement of the two reductions csrc/glperm.h writes in assembly (glq_reduce, glq_reduce96), instruction by instruction in 32 / 64-bit integer
 // arithmetic, against x mod p computed with 128-bit integers: the ALGORITHM (one multiply-add folds the 2^64 word; its carry and the borrow of the 2^96
-// word become one 64-bit correction; no second wrap) on edge values and random ones.  The device parity tests check the instructions themselves.
+// word become one 64-bit correction; no second wrap) on edge values and random ones.  The instructions themselves - the carry-out into a scalar pair, the vcc
+// chain, the wait states - are checked on the device, on the same edge values and with the four correction classes mixed in one wavefront:
+// tests/test_gpu_devcheck.py (tests/hip/devcheck.hip).
 // g++ -O2 -std=c++17 tests/cpp/glq_reduce_check.cpp
 #include <cstdint>
 #include <cstdio>
