@@ -79,7 +79,7 @@ def test_goldilocks_ops(h2w_api, oracle, lookup_bits):
     pr.check()
 
 
-@pytest.mark.parametrize("lookup_bits", [21, 13])
+@pytest.mark.parametrize("lookup_bits", [21, 13, 8])
 def test_reduce_at_the_edges_of_its_range(h2w_api, oracle, lookup_bits):
     """GoldilocksChip::reduce (base.rs:346-368) on 128-bit values around the points where its hint changes shape: the largest
     mul_add value p(p-1)+(p-1), p^2 (quotient = p wraps to 0), 2^128-1 (quotient >= 2^64), multiples of p, tiny values.  The cells
