@@ -7,7 +7,7 @@ argument meaning and error behaviour (a non-zero status raises H2WError where th
 """
 import ctypes as C
 
-from . import (Assigned, Fr, H2W_TRACE_FUSE_GL_PERMUTE, H2WError, PoseidonConsts, Shape, _ck, last_error, lib)
+from . import (Assigned, Fr, H2W_TRACE_FUSE_BN_PERMUTE, H2W_TRACE_FUSE_GL_PERMUTE, H2WError, PoseidonConsts, Shape, _ck, last_error, lib)
 
 GL_P = 0xFFFFFFFF00000001
 FR_MODULUS = 21888242871839275222246405745257275088548364400416034343698204186575808495617
@@ -251,18 +251,23 @@ class Plan:
         self.num_chain_cells = int(self.L.h2w_plan_num_chain_cells(self.p))
 
     @classmethod
-    def from_trace(cls, ctx, proof_words, parallel_scopes=("verify_query_round", "verify_proof_to_cap_with_cap_index"), device_id=0, fuse_consts=None):
+    def from_trace(cls, ctx, proof_words, parallel_scopes=("verify_query_round", "verify_proof_to_cap_with_cap_index"), device_id=0, fuse_consts=None, fuse_bn=False, fuse_gl=True):
         """h2w_plan_from_trace: the tape `ctx` recorded (Context.trace_begin, then ONE run through the level-1 / level-2 calls) as a plan that
         h2w_fri_witness_batch replays on other proofs of the shape.  parallel_scopes: the #[count] scopes whose instances are independent
         (fri/mod.rs:488-501, merkle/mod.rs:57-78); the library checks the claim on the tape.  The depth-1 instances (the query rounds) are the
         units of the sharded calls; a context created with witness_gen_only=False also gives the plan its keygen metadata (selectors(),
         lookup_cells(), equalities(), const_equalities(), break_points(), check_constraints()).
         fuse_consts: Poseidon tables (h2w_plan_from_trace_ex, H2W_TRACE_FUSE_GL_PERMUTE): every stretch of the tape that the library verifies to be
-        a Goldilocks-Poseidon permutation on these tables runs as one device op; trace_info() says how many did.  The stream is the same."""
+        a Goldilocks-Poseidon permutation on these tables runs as one device op; trace_info() says how many did.  The stream is the same.
+        fuse_bn (with fuse_consts): H2W_TRACE_FUSE_BN_PERMUTE as well - the PoseidonBN254 permutations on these tables run as one op each, their cells
+        written by a kernel of their own; trace_info_bn() says how many did.  fuse_gl=False with fuse_bn: the PoseidonBN254 flag alone."""
         L = lib()
         names = (C.c_char_p * len(parallel_scopes))(*[s.encode() for s in parallel_scopes])
+        if fuse_bn and fuse_consts is None:
+            raise H2WError("Plan.from_trace: fuse_bn needs fuse_consts")
         if fuse_consts is not None:
-            h = L.h2w_plan_from_trace_ex(ctx.p, proof_words, names, len(parallel_scopes), device_id, C.byref(fuse_consts), H2W_TRACE_FUSE_GL_PERMUTE)
+            flags = (H2W_TRACE_FUSE_GL_PERMUTE if fuse_gl else 0) | (H2W_TRACE_FUSE_BN_PERMUTE if fuse_bn else 0)
+            h = L.h2w_plan_from_trace_ex(ctx.p, proof_words, names, len(parallel_scopes), device_id, C.byref(fuse_consts), flags)
         else:
             h = L.h2w_plan_from_trace(ctx.p, proof_words, names, len(parallel_scopes), device_id)
         if not h:
@@ -274,6 +279,12 @@ class Plan:
         out = (C.c_uint64 * 6)()
         _ck(self.L.h2w_plan_trace_info(self.p, out), "h2w_plan_trace_info")
         return dict(zip(("ops", "segments", "templates", "fused", "candidates_left", "list_entries"), (int(x) for x in out)))
+
+    def trace_info_bn(self):
+        """h2w_plan_trace_info_bn of a traced plan: what H2W_TRACE_FUSE_BN_PERMUTE fused and what it left interpreted."""
+        out = (C.c_uint64 * 3)()
+        _ck(self.L.h2w_plan_trace_info_bn(self.p, out), "h2w_plan_trace_info_bn")
+        return dict(zip(("fused", "left", "list_entries"), (int(x) for x in out)))
 
     def trace_timing(self):
         """h2w_plan_trace_timing: ms of every kernel of the last call of a traced plan, in launch order (the first call switches the timing on: [])."""

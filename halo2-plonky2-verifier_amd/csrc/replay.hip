@@ -31,6 +31,7 @@
 #include "trace.h"
 #include "keygen.h"
 #include "glpval.h"
+#include "bnpval.h"
 
 struct h2w_ctx;
 namespace h2w {
@@ -57,8 +58,12 @@ enum { DOP_END = 0, DOP_SKIP, DOP_CONST1, DOP_FRCELL, DOP_LOADW, DOP_LOADW_DIV, 
        DOP_FR_ADD, DOP_FR_MUL, DOP_FR_MULADD, DOP_SELECT, DOP_FR_SELECT, DOP_IDX2IND, DOP_SELIND, DOP_FR_SELIND, DOP_NUM2BITS, DOP_BITS2NUM,
        DOP_DECOMP565, DOP_LIMBS2NUM, DOP_RANGE, DOP_FETCH,
        DOP_GLOPRUN,        // n consecutive DOP_GLOP ops as one: [hdr][cells of the run][A, B, C, out slot | template << 24] x n (2 + 4 n words: its length is NOT in the header)
-       DOP_GLPERM };       // a verified Goldilocks-Poseidon permutation as one op (H2W_TRACE_FUSE_GL_PERMUTE): [hdr][12 operands][first output slot][list slot][cells of its record block]
-constexpr uint32_t GLPERM_WORDS = 16;
+       DOP_GLPERM,         // a verified Goldilocks-Poseidon permutation as one op (H2W_TRACE_FUSE_GL_PERMUTE): [hdr][12 operands][first output slot][list slot][cells of its record block]
+       DOP_BNPERM };       // a verified PoseidonBN254 permutation as one op (H2W_TRACE_FUSE_BN_PERMUTE): [hdr][4 operands][first output slot (4 x 4 slots)][list slot][its cells]
+constexpr uint32_t GLPERM_WORDS = 16, BNPERM_WORDS = 8;
+// a list entry of a fused PoseidonBN254 permutation: {first cell of its block in the proof's stream, zero-cell flag (1: the Context's load_zero cell is
+// cached, the block is the 4,032 cells), the 4 x 32-byte input state}
+constexpr uint32_t BNP_LIST_WORDS = 18;
 // operand words of an op: [first, first + count)
 HD void operand_span(uint32_t op, uint32_t n, uint32_t &first, uint32_t &count) {
     first = 1; count = 0;
@@ -69,6 +74,7 @@ HD void operand_span(uint32_t op, uint32_t n, uint32_t &first, uint32_t &count) 
         case DOP_SELIND: case DOP_FR_SELIND: count = 2 * n; break;
         case DOP_BITS2NUM: case DOP_LIMBS2NUM: count = n; break;
         case DOP_GLPERM: count = SPONGE_WIDTH; break;
+        case DOP_BNPERM: count = BN_WIDTH; break;
         default: break;
     }
 }
@@ -95,6 +101,15 @@ struct ReplayArgs {
     // fused permutations (DOP_GLPERM): the Goldilocks block of the tables the lowering verified them on; the list [nproofs][nglp][GLP_LIST_WORDS]
     const uint64_t *glk; uint64_t *glist; uint32_t nglp;
 };
+// the arguments of k_replay<BN>: plans without fused PoseidonBN254 permutations pass exactly ReplayArgs
+template <bool BN> struct ReplayArgsSel { typedef ReplayArgs type; };
+// fused PoseidonBN254 permutations (DOP_BNPERM): the times-R half of the plan's table (bntab.h); the list [nproofs][nbnp][BNP_LIST_WORDS]; bnp0: per
+// instance (InstD order) its first entry in the proof's list
+struct ReplayArgsBN : ReplayArgs { const fr_t *bnk; uint64_t *blist; const uint32_t *bnp0; uint32_t nbnp; };
+template <> struct ReplayArgsSel<true> { typedef ReplayArgsBN type; };
+template <bool BN> using ReplayArgsT = typename ReplayArgsSel<BN>::type;
+// a listed PoseidonBN254 permutation, static per plan: its first cell in the proof's stream, its shard unit (NO_SLOT: the root's block), that unit's first cell
+struct BnpD { uint64_t cell0, ucell0; uint32_t unit, pad; };
 
 struct TracedPlan {
     std::vector<TmplD> tmpls; uint64_t total_slot_lanes = 0;      // sum over templates of nslots * ninst: u64 elements of the value store per proof
@@ -103,6 +118,8 @@ struct TracedPlan {
     uint64_t n_ops = 0, n_segments = 0;
     // fused Goldilocks-Poseidon permutations: per proof nglp list entries (entry e belongs to shard unit h_glp_unit[e], NO_SLOT: the root's block)
     uint32_t nglp = 0; uint64_t n_candidates = 0; std::vector<uint32_t> h_glp_unit; uint32_t *d_glp_unit = nullptr;
+    // fused PoseidonBN254 permutations: per proof nbnp list entries; items: the (proof, entry) pairs of this rank's blocks (sharded calls, beside the lane table)
+    bool bn_flag = false; uint32_t nbnp = 0; uint64_t n_bn_left = 0; std::vector<BnpD> h_bnp; BnpD *d_bnp = nullptr; std::vector<uint32_t> h_bnp0; uint32_t *d_bnp0 = nullptr, *d_bn_items = nullptr; uint64_t n_bn_items = 0;
     hipEvent_t tev[16]; int n_tev = 0, tev_used = 0; bool timing = false;      // h2w_plan_trace_timing: around every kernel of the last call
     // sharding: the depth-1 instances are the units (query q = the q-th in tape order); why_unshardable empty: they tile the stream behind the root's block
     std::string why_unshardable; std::vector<uint32_t> h_unit;      // h_unit: the unit of every instance (InstD order)
@@ -137,7 +154,9 @@ __device__ __noinline__ uint64_t slow_get64(uint32_t r, uint32_t j, const uint64
     return H2W_GLOAD64(s_cx.gvals + (uint64_t)s_cx.nproofs * s_cx.prefix[d.tmpl] + (uint64_t)(d.slot + j) * ((uint64_t)s_cx.nproofs * ni) + (uint64_t)p * ni + d.inst);
 }
 
-__global__ __launch_bounds__(64) __attribute__((flatten)) void k_replay(ReplayArgs R) {
+// BN: the instantiation with the DOP_BNPERM case (plans built with H2W_TRACE_FUSE_BN_PERMUTE); every other plan launches k_replay<false>, whose code is
+// what it was without that op
+template <bool BN> __global__ __launch_bounds__(64) __attribute__((flatten)) void k_replay(ReplayArgsT<BN> R) {
     const uint32_t lane = threadIdx.x;
     if (lane < T_MAX) s_nc[lane] = R.ncells[lane];
     if (lane == 0) { s_cx.gvals = R.vals; s_cx.tm = R.tm; s_cx.prefix = R.prefix; s_cx.imps = R.imps; s_cx.inputs = R.inputs; s_cx.pool64 = R.pool64; s_cx.poolfr = R.poolfr; s_cx.nproofs = R.nproofs; }
@@ -165,6 +184,7 @@ __global__ __launch_bounds__(64) __attribute__((flatten)) void k_replay(ReplayAr
     const uint32_t p = g / ninst, inst = g % ninst;
     const InstD *const I = R.insts + inst0 + inst;
     const uint32_t imp0 = I->imp0, in0 = I->in0, glp0 = I->glp0;
+    [[maybe_unused]] uint32_t bnp0 = 0; if constexpr (BN) bnp0 = R.bnp0[inst0 + inst];
     fr_t *outb = R.out + (uint64_t)p * R.cell_stride;
     if (R.sh_compact) {         // the packed buffer: the lane's block (the root's: the prologue block) at its local start, its cells at their global offsets
         const uint64_t W = R.sh_world, r = R.sh_rank, u0 = (uint64_t)p * R.nq, unit = I->unit;
@@ -211,6 +231,25 @@ __global__ __launch_bounds__(64) __attribute__((flatten)) void k_replay(ReplayAr
         if (op == DOP_END) break;
         const uint32_t pcn = pc + (op == DOP_GLOPRUN ? 2u + 4u * n : (h >> 24));
         const uint32_t n0 = tw(tape, pcn), n1 = tw(tape, pcn + 1), n2 = tw(tape, pcn + 2), n3 = tw(tape, pcn + 3), n4 = tw(tape, pcn + 4);
+        if constexpr (BN) {
+            if (op == DOP_BNPERM) {     // (in front of the switch: the instantiation without it keeps its code)  The lane keeps the VALUES of the permutation (bnpval.h); its cells are k_bn_emit_traced's, from the listed input state
+                fr_t st[BN_WIDTH];
+                st[0] = getfr(w1); st[1] = getfr(w2); st[2] = getfr(w3); st[3] = getfr(w4);
+                const uint32_t o = tw(tape, pc + 5), ls = tw(tape, pc + 6), nc = tw(tape, pc + 7);
+                if (sink.emit) {
+                    uint64_t *e = R.blist + ((uint64_t)p * R.nbnp + bnp0 + ls) * BNP_LIST_WORDS;
+                    H2W_GSTORE64(e, sink.cell_off); H2W_GSTORE64(e + 1, 1ull);
+#pragma unroll
+                    for (int i = 0; i < BN_WIDTH; i++) { H2W_GSTORE64(e + 2 + 4 * i, st[i].l[0]); H2W_GSTORE64(e + 3 + 4 * i, st[i].l[1]); H2W_GSTORE64(e + 4 + 4 * i, st[i].l[2]); H2W_GSTORE64(e + 5 + 4 * i, st[i].l[3]); }
+                }
+                const unsigned long long *const bk = reinterpret_cast<const unsigned long long *>(R.bnk);
+                bn_permute_values(st, R.P, [&](int i) -> fr_t { fr_t v; v.l[0] = H2W_CLOAD64(bk + 4 * i); v.l[1] = H2W_CLOAD64(bk + 4 * i + 1); v.l[2] = H2W_CLOAD64(bk + 4 * i + 2); v.l[3] = H2W_CLOAD64(bk + 4 * i + 3); return v; });
+                putfr(o, st[0]); putfr(o + 4, st[1]); putfr(o + 8, st[2]); putfr(o + 12, st[3]);
+                sink.skip(0, nc);
+                pc = pcn; w0 = n0; w1 = n1; w2 = n2; w3 = n3; w4 = n4;
+                continue;
+            }
+        }
         switch (op) {
             case DOP_SKIP: { const uint64_t nr = ((uint64_t)w2 << 32) | w1, nc = ((uint64_t)w4 << 32) | w3; sink.skip(nr, nc); break; }
             case DOP_CONST1: { const uint64_t v = get64(w1, 0); sink.rec(T_CONST1, v, 0, 0, 0); put64(w2, v); break; }
@@ -320,6 +359,47 @@ __global__ __launch_bounds__(64) void k_glp_emit_traced(GlpEmitArgs A) {
     sink.coop_poseidon_permute(st, A.consts);
 }
 
+// One QUAD per listed PoseidonBN254 permutation of the launch: its 4,032 cells from the entry's input state, by the one-pass emitter the compiled plan's
+// k_merkle_bn_fused runs (coop.h QuadSinkT::bn_emit_cells<false>: it walks the S-box chain itself; 64 contiguous bytes per quad and store).  The launch
+// works from a dense list of items: every (proof, entry) pair, or - sharded - `items`, the pairs of this rank's blocks (the others' entries were never
+// written).  The quads of a wavefront cooperate (cross-lane moves over the whole wavefront): none leaves early, tail quads redo the last item and write
+// identical bytes.  WHERE a permutation's cells go is static (BnpD, checked against the entry: status 97 if the interpreter listed another cell); only
+// the state comes from the list.  LDS: the tables (34.7 KB) + 10 KB of value slots per wavefront, as k_merkle_bn_fused: two blocks per CU.
+struct BnEmitArgs {
+    const fr_t *bn_tab; const uint64_t *list; const BnpD *bnp; const uint32_t *items; uint64_t nitems; uint32_t nbnp;
+    fr_t *out; uint64_t cell_stride; ColMap cm; FrParams P; uint32_t *status;
+    uint32_t sh_world, sh_rank, sh_compact, nq; uint64_t pro_ncell, q_slot;
+};
+template <bool COLS> __global__ __launch_bounds__(QUAD_BLOCK) H2W_QUAD_ATTR void k_bn_emit_traced(BnEmitArgs A) {
+    typedef QuadSinkT<COLS, QUAD_FUSED> Sink;
+    stage_bn_consts(A.bn_tab, threadIdx.x, QUAD_BLOCK);      // (block-wide barrier inside: before any wavefront leaves)
+    if ((((uint64_t)blockIdx.x * QUAD_BLOCK + (threadIdx.x & ~63u)) >> 2) >= A.nitems) return;      // a whole wavefront past the last item
+    uint64_t g = ((uint64_t)blockIdx.x * QUAD_BLOCK + threadIdx.x) >> 2;
+    if (g >= A.nitems) g = A.nitems - 1;
+    const uint64_t it = A.items ? (uint64_t)A.items[g] : g;      // proof * nbnp + entry
+    const uint64_t p = it / A.nbnp; const uint32_t e = (uint32_t)(it % A.nbnp);
+    const BnpD D = A.bnp[e];
+    const uint64_t *ent = A.list + it * BNP_LIST_WORDS;
+    fr_t *outb = A.out + p * A.cell_stride;
+    if (A.sh_compact) {         // the packed buffer: as k_replay places the lane's block
+        const uint64_t W = A.sh_world, r = A.sh_rank, u0 = p * A.nq, unit = D.unit;
+        const uint64_t units_before = (u0 + W - 1 - r) / W;
+        uint64_t local = ((p + W - 1 - r) / W) * A.pro_ncell + units_before * A.q_slot;
+        if (D.unit != NO_SLOT) local += (p % W == r ? A.pro_ncell : 0) + ((u0 + unit + W - 1 - r) / W - units_before) * A.q_slot;
+        outb = A.out + local - D.ucell0;
+    }
+    if (g_load_u64(ent) != D.cell0 && (threadIdx.x & 3) == 0) atomicCAS(&A.status[p], 0u, 97u);
+    fr_t st[BN_WIDTH];
+#pragma unroll
+    for (int i = 0; i < BN_WIDTH; i++) st[i] = g_load_fr(reinterpret_cast<const fr_t *>(ent + 2) + i);
+    Sink sink; sink.recs = nullptr; sink.nrec = 0; sink.out = outb; sink.cell_off = D.cell0; sink.ncells = nullptr; sink.l4 = threadIdx.x & 3; sink.cc.init(A.cm);
+    sink.ustate = nullptr; sink.sbx = nullptr;
+    ValCfg cfg; cfg.proof = nullptr; cfg.mode = 1; cfg.L = 0; cfg.P = A.P; cfg.inv_pos = cfg.inv_neg = nullptr; cfg.st = nullptr; cfg.split = false; cfg.split_bn = true;
+    cfg.load_items = nullptr; cfg.n_load_items = 0; cfg.load_nrec = cfg.load_ncell = 0; cfg.n_cap_items = 0; cfg.fri = nullptr;
+    bool zc = true;             // (a stretch with the Context's load_zero cell in it is never fused)
+    sink.template bn_emit_cells<false>(st, cfg, zc);
+}
+
 // ------------------------------------------------------------------------------------------------------------------- host: lowering
 struct ValInfo { uint32_t seg, slot; uint8_t width, is_static; uint32_t lit; };
 struct SegInfo {
@@ -331,48 +411,53 @@ struct SegInfo {
     int tmpl = -1; uint32_t inst = 0;
     long last_const_at = -1; uint64_t last_const_cell = 0; size_t last_const_tr = 0;      // the op emitted last is a static CONST1 (its tape position, its cell): a GLOP right behind it that takes it as operand A fuses with it
     uint32_t nglp = 0, glp0 = 0;      // fused permutations (DOP_GLPERM) of this segment; its first entry in the proof's list
-    struct Matcher *mt = nullptr;     // the search for permutation-shaped stretches (first lowering of a fused plan)
+    std::vector<struct Matcher *> mt; // the searches for permutation-shaped stretches (first lowering of a fused plan): one per canonical tape
+    uint32_t nbnp = 0, bnp0 = 0; std::vector<uint64_t> bnp_cells;      // fused PoseidonBN254 permutations (DOP_BNPERM) of this segment: their first cells; its first entry in the proof's list
 };
-// ---- stretches of a tape that ARE a Goldilocks-Poseidon permutation (H2W_TRACE_FUSE_GL_PERMUTE).  A lowered op, before its operands become fast refs:
+// ---- stretches of a tape that ARE a permutation (H2W_TRACE_FUSE_GL_PERMUTE, H2W_TRACE_FUSE_BN_PERMUTE).  A lowered op, before its operands become fast refs:
 struct NormOp {
-    uint32_t hdr = 0, nin = 0, ref[3] = {0, 0, 0}, out = NO_SLOT, slots_before = 0; uint64_t lit[3] = {0, 0, 0};      // hdr: op | n << 8 | aux << 16; ref: mkref words; lit: the value of a literal operand
+    uint32_t hdr = 0, nin = 0, ref[3] = {0, 0, 0}, out = NO_SLOT, slots_before = 0; fr_t lit[3] = {fr_zero(), fr_zero(), fr_zero()};      // hdr: op | n << 8 | aux << 16; ref: mkref words; lit: the value of a literal operand
     size_t tr0 = 0, tr1 = 0; uint64_t cell0 = 0, cell1 = 0, out_cell = 0; const TraceIn *tin = nullptr;               // the trace ops / cells it covers; its result handle; its operands on the trace
 };
-// an operand of the canonical tape: a literal (its value), a value computed inside the stretch (the op that produced it, relative to the start), one of the 12 inputs
+// an operand of the canonical tape: a literal (its value, kind and width), a value computed inside the stretch (the op that produced it, relative to the
+// start; its width), one of the inputs
 enum { CK_LIT = 0, CK_INTERIOR = 1, CK_INPUT = 2 };
-struct CanonOp { uint32_t hdr, nin; uint8_t kind[3]; uint64_t arg[3]; bool has_out; };
-struct Canon { std::vector<CanonOp> ops; uint32_t out_prod[SPONGE_WIDTH]; uint64_t ncells = 0; };
-// a stretch that matched the canonical tape in op codes, record templates and dataflow; const_bad: on other constants; escaped: an interior value is read outside
-struct Stretch { size_t tr0, tr1; int seg; TraceIn in[SPONGE_WIDTH]; uint64_t out[SPONGE_WIDTH]; uint64_t cell0, cell1; bool const_bad, escaped; };
-// One per segment: the ops arrive in tape order, one behind the lowering (a static CONST1 may still fuse with the GLOP behind it).  A partial match that
-// fails restarts AT the failing op, not inside the failed part: a permutation may then stay interpreted (canonical tapes whose first ops repeat
-// themselves), it is never fused wrongly.
+enum { CANON_GL = 0, CANON_BN = 1, CANON_BN_ZERO = 2 };      // CANON_BN_ZERO: the PoseidonBN254 tape recorded on a fresh context (the load_zero cell inside its first mix)
+constexpr int MAX_PERM_IO = SPONGE_WIDTH;
+struct CanonOp { uint32_t hdr, nin; uint8_t kind[3], rk[3], width[3]; uint64_t arg[3]; fr_t lit[3]; bool has_out; };
+// nio: inputs = outputs (12 one-word values; 4 of width WFR).  in_any_width: an input may be of any width (nothing of the lowering depends on it: the
+// PoseidonBN254 tape adds a wide constant to every input first); else an input is one word, as the canonical one.
+struct Canon { int id = CANON_GL, nio = SPONGE_WIDTH; bool in_any_width = false; std::vector<CanonOp> ops; uint32_t out_prod[MAX_PERM_IO]; uint64_t ncells = 0; };
+// a stretch that matched a canonical tape in op codes, record templates, widths and dataflow; const_bad: on other constants; escaped: an interior value is read outside
+struct Stretch { size_t tr0, tr1; int seg, canon, nio; TraceIn in[MAX_PERM_IO]; uint64_t out[MAX_PERM_IO]; uint64_t cell0, cell1; bool const_bad, escaped; };
+// One per segment and canonical tape: the ops arrive in tape order, one behind the lowering (a static CONST1 may still fuse with the GLOP behind it).  A
+// partial match that fails restarts AT the failing op, not inside the failed part: a permutation may then stay interpreted (canonical tapes whose first
+// ops repeat themselves), it is never fused wrongly.
 struct Matcher {
     const Canon *cn; std::vector<Stretch> *found; int seg;
     NormOp pend; bool has_pend = false;
     size_t pos = 0; uint32_t slot0 = 0; std::vector<int32_t> prod;      // matched ops so far; the first slot of the stretch; slot - slot0 -> the op that wrote it
-    bool bound[SPONGE_WIDTH]; uint32_t bref[SPONGE_WIDTH]; Stretch cur;
+    bool bound[MAX_PERM_IO]; uint32_t bref[MAX_PERM_IO]; Stretch cur;
     void reset() { pos = 0; prod.clear(); }
     bool step(const NormOp &o) {
         const CanonOp &c = cn->ops[pos];
         if (o.hdr != c.hdr || o.nin != c.nin || (o.out != NO_SLOT) != c.has_out) return false;
-        if (pos == 0) { slot0 = o.slots_before; for (int i = 0; i < SPONGE_WIDTH; i++) bound[i] = false; cur.tr0 = o.tr0; cur.cell0 = o.cell0; cur.seg = seg; cur.const_bad = cur.escaped = false; }
+        if (pos == 0) { slot0 = o.slots_before; for (int i = 0; i < cn->nio; i++) bound[i] = false; cur.tr0 = o.tr0; cur.cell0 = o.cell0; cur.seg = seg; cur.canon = cn->id; cur.nio = cn->nio; cur.const_bad = cur.escaped = false; }
         for (uint32_t k = 0; k < c.nin; k++) {
             const uint32_t r = o.ref[k]; const int rk = ref_kind(r);
-            if (ref_width(r) != W64) return false;
             const bool interior = rk == RK_LOCAL && ref_idx(r) >= slot0;
-            if (c.kind[k] == CK_LIT) { if (rk != RK_LIT64) return false; if (o.lit[k] != c.arg[k]) cur.const_bad = true; }
-            else if (c.kind[k] == CK_INTERIOR) { if (!interior || ref_idx(r) - slot0 >= prod.size() || prod[ref_idx(r) - slot0] != (int32_t)c.arg[k]) return false; }
+            if (c.kind[k] == CK_LIT) { if (rk != (int)c.rk[k] || ref_width(r) != (int)c.width[k]) return false; if (!fr_eq(o.lit[k], c.lit[k])) cur.const_bad = true; }
+            else if (c.kind[k] == CK_INTERIOR) { if (!interior || ref_width(r) != (int)c.width[k] || ref_idx(r) - slot0 >= prod.size() || prod[ref_idx(r) - slot0] != (int32_t)c.arg[k]) return false; }
             else {
-                if (interior) return false;
+                if (interior || (!cn->in_any_width && ref_width(r) != (int)c.width[k])) return false;
                 const uint64_t n = c.arg[k];
                 if (!bound[n]) { bound[n] = true; bref[n] = r; cur.in[n] = o.tin[k]; } else if (bref[n] != r) return false;
             }
         }
         if (o.out != NO_SLOT) { const uint32_t rel = o.out - slot0; if (prod.size() <= rel) prod.resize(rel + 1, -1); prod[rel] = (int32_t)pos; }
-        for (int i = 0; i < SPONGE_WIDTH; i++) if (cn->out_prod[i] == pos) cur.out[i] = o.out_cell;
+        for (int i = 0; i < cn->nio; i++) if (cn->out_prod[i] == pos) cur.out[i] = o.out_cell;
         if (++pos == cn->ops.size()) {
-            cur.tr1 = o.tr1; cur.cell1 = o.cell1; bool all = true; for (int i = 0; i < SPONGE_WIDTH; i++) all = all && bound[i];
+            cur.tr1 = o.tr1; cur.cell1 = o.cell1; bool all = true; for (int i = 0; i < cn->nio; i++) all = all && bound[i];
             if (all) found->push_back(cur);
             reset();
         }
@@ -394,7 +479,7 @@ uint64_t traced_workspace_bytes(const h2w_plan *p, uint64_t n);
 int traced_run(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void *advice_dev, void *workspace_dev, void *stream_, ColMap cm, uint64_t cell_stride, const ShardSpec &sh);
 void traced_free(h2w_plan *p);
 const char *traced_shard_refusal(const h2w_plan *p) { return p->traced && !p->traced->why_unshardable.empty() ? p->traced->why_unshardable.c_str() : nullptr; }
-struct TracedWs { size_t recs, status, lflag, ctr, vals, glist, total; };
+struct TracedWs { size_t recs, status, lflag, ctr, vals, glist, blist, total; };
 static size_t al(size_t x) { return (x + 255) / 256 * 256; }
 static TracedWs traced_ws(const h2w_plan *p, uint64_t n) {
     TracedWs w; size_t o = 0;
@@ -402,6 +487,7 @@ static TracedWs traced_ws(const h2w_plan *p, uint64_t n) {
     w.status = o; o += al((size_t)n * 4); w.lflag = o; o += al((size_t)n * 4); w.ctr = o; o += al((size_t)n * 4);
     w.vals = o; o += al((size_t)n * p->traced->total_slot_lanes * 8);
     w.glist = o; o += al((size_t)n * p->traced->nglp * GLP_LIST_WORDS * 8);      // the fused permutations' list (none: the layout of an unfused plan)
+    w.blist = o; o += al((size_t)n * p->traced->nbnp * BNP_LIST_WORDS * 8);      // the fused PoseidonBN254 permutations' list (none: nothing)
     w.total = o; return w;
 }
 uint64_t traced_workspace_bytes(const h2w_plan *p, uint64_t n) { return traced_ws(p, n).total; }
@@ -412,6 +498,7 @@ void traced_free(h2w_plan *p) {
     if (t->d_tape) (void)hipFree(t->d_tape); if (t->d_insts) (void)hipFree(t->d_insts); if (t->d_imps) (void)hipFree(t->d_imps);
     if (t->d_inputs) (void)hipFree(t->d_inputs); if (t->d_pool64) (void)hipFree(t->d_pool64); if (t->d_poolfr) (void)hipFree(t->d_poolfr);
     if (t->d_lanes) (void)hipFree(t->d_lanes); if (t->d_glp_unit) (void)hipFree(t->d_glp_unit);
+    if (t->d_bnp) (void)hipFree(t->d_bnp); if (t->d_bnp0) (void)hipFree(t->d_bnp0); if (t->d_bn_items) (void)hipFree(t->d_bn_items);
     for (int i = 0; i < t->n_tev; i++) (void)hipEventDestroy(t->tev[i]);
     delete t; p->traced = nullptr;
 }
@@ -435,7 +522,21 @@ static int lane_table(h2w_plan *p, uint64_t n, const ShardSpec &sh) {
                 for (uint32_t k = 0; k < T.ninst; k++) if ((pr * nq + t->h_unit[T.inst0 + k]) % W == r) L.push_back((uint32_t)(pr * T.ninst + k));
     }
     t->lane0[t->tmpls.size()] = (uint32_t)L.size();
+    // the listed PoseidonBN254 permutations of this rank's blocks, dense: (proof, entry) as proof * nbnp + entry - the root's of the proofs it owns, a
+    // unit's where it owns the unit (the lanes above that run with emit set: the entries that get written)
+    std::vector<uint32_t> items;
+    if (t->nbnp) {
+        if (n * t->nbnp >= 0xffffffffull) { set_error("h2w_fri_witness_batch_shard: too many fused permutations in one call"); return -1; }
+        for (uint64_t pr = 0; pr < n; pr++)
+            for (uint32_t e = 0; e < t->nbnp; e++) {
+                const uint32_t u = t->h_bnp[e].unit;
+                if ((u == NO_SLOT ? pr : pr * nq + u) % W == r) items.push_back((uint32_t)(pr * t->nbnp + e));
+            }
+    }
     H2W_HIP(hipDeviceSynchronize());      // a previous call may still read the old table (plans are single-threaded handles, include/h2w.h)
+    if (t->d_bn_items) { (void)hipFree(t->d_bn_items); t->d_bn_items = nullptr; }
+    t->n_bn_items = items.size();
+    if (t->nbnp) { H2W_HIP(hipMalloc((void **)&t->d_bn_items, (items.empty() ? 1 : items.size()) * 4)); if (!items.empty()) H2W_HIP(hipMemcpy(t->d_bn_items, items.data(), items.size() * 4, hipMemcpyHostToDevice)); }
     if (t->d_lanes) { (void)hipFree(t->d_lanes); t->d_lanes = nullptr; }
     H2W_HIP(hipMalloc((void **)&t->d_lanes, (L.empty() ? 1 : L.size()) * 4));
     if (!L.empty()) H2W_HIP(hipMemcpy(t->d_lanes, L.data(), L.size() * 4, hipMemcpyHostToDevice));
@@ -467,6 +568,7 @@ int traced_run(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void 
     H2W_HIP(hipMemsetAsync(ws + wl.status, 0, n_proofs * 4, stream));
     H2W_HIP(hipMemsetAsync(ws + wl.lflag, 0, n_proofs * 4, stream));
     uint32_t maxd = 0; for (const TmplD &T : t->tmpls) if (T.depth > maxd) maxd = T.depth;
+    uint64_t *const blist = (uint64_t *)(ws + wl.blist);
     t->tev_used = 0;
     for (uint32_t d = 0; d <= maxd; d++) {      // a segment reads its ancestors' values: depth by depth; the templates of one depth in one launch
         uint32_t nb = 0;
@@ -476,7 +578,10 @@ int traced_run(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void 
         }
         R.blk0[t->tmpls.size()] = nb; R.depth = d;
         if (t->timing && t->tev_used < 12) H2W_HIP(hipEventRecord(t->tev[t->tev_used++], stream));
-        if (nb) hipLaunchKernelGGL(k_replay, dim3(nb), dim3(64), 0, stream, R);
+        if (nb && t->nbnp) {
+            ReplayArgsT<true> RB; static_cast<ReplayArgs &>(RB) = R; RB.bnk = p->d_bn_tab + BK_T; RB.blist = blist; RB.bnp0 = t->d_bnp0; RB.nbnp = t->nbnp;
+            hipLaunchKernelGGL(k_replay<true>, dim3(nb), dim3(64), 0, stream, RB);
+        } else if (nb) hipLaunchKernelGGL(k_replay<false>, dim3(nb), dim3(64), 0, stream, R);
     }
     if (t->timing) H2W_HIP(hipEventRecord(t->tev[t->tev_used++], stream));
     if (t->nglp) {      // the records of the listed permutations, side by side
@@ -484,6 +589,18 @@ int traced_run(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void 
         E.nglp = t->nglp; E.world = sharded ? (uint32_t)sh.world : 1u; E.rank = (uint32_t)sh.rank; E.nq = (uint32_t)p->shape.num_queries;
         if ((uint64_t)n_proofs * t->nglp >= 0x7fffffffull) { set_error("h2w_fri_witness_batch: too many fused permutations in one call"); return -1; }
         hipLaunchKernelGGL(k_glp_emit_traced, dim3((uint32_t)(n_proofs * t->nglp)), dim3(64), 0, stream, E);
+    }
+    if (t->timing && t->bn_flag) H2W_HIP(hipEventRecord(t->tev[t->tev_used++], stream));
+    if (t->nbnp) {      // the cells of the listed PoseidonBN254 permutations, a quad each (direct cells: nothing of the expansion depends on them, nor they on it)
+        BnEmitArgs E; memset(&E, 0, sizeof(E));
+        E.bn_tab = p->d_bn_tab; E.list = blist; E.bnp = t->d_bnp; E.nbnp = t->nbnp; E.out = R.out; E.cell_stride = cell_stride; E.cm = cm; E.P = p->P; E.status = R.status;
+        if (sharded) {
+            E.items = t->d_bn_items; E.nitems = t->n_bn_items;
+            E.sh_world = R.sh_world; E.sh_rank = R.sh_rank; E.sh_compact = R.sh_compact; E.nq = R.nq; E.pro_ncell = R.pro_ncell; E.q_slot = R.q_slot;
+        } else { E.items = nullptr; E.nitems = (uint64_t)n_proofs * t->nbnp; }
+        const uint64_t nblk = (E.nitems * 4 + QUAD_BLOCK - 1) / QUAD_BLOCK;
+        if (nblk >= 0x7fffffffull) { set_error("h2w_fri_witness_batch: too many fused permutations in one call"); return -1; }
+        if (nblk) { if (cm.starts) hipLaunchKernelGGL(k_bn_emit_traced<true>, dim3((uint32_t)nblk), dim3(QUAD_BLOCK), 0, stream, E); else hipLaunchKernelGGL(k_bn_emit_traced<false>, dim3((uint32_t)nblk), dim3(QUAD_BLOCK), 0, stream, E); }
     }
     if (t->timing) H2W_HIP(hipEventRecord(t->tev[t->tev_used++], stream));
     // expansion of the block records
@@ -519,7 +636,7 @@ static uint64_t glp_block_layout(const TemplateTable &tt, int L, const h2w_posei
 // fuse: the stretches to lower as ONE op (by their first trace op), glp_meta their record block; cn: look for stretches instead (-> found);
 // capture: the lowered ops of the root segment as they are (the canonical tape is made from them)
 static void lower_trace(const Trace *tr, int L, TemplateTable &tt, const char *const *parallel_scopes, size_t n_scopes, Lowered &LW,
-                        const std::map<size_t, Stretch> *fuse, const std::vector<uint64_t> *glp_meta, const Canon *cn, std::vector<Stretch> *found, std::vector<NormOp> *capture) {
+                        const std::map<size_t, Stretch> *fuse, const std::vector<uint64_t> *glp_meta, const std::vector<const Canon *> *cns, std::vector<Stretch> *found, std::vector<NormOp> *capture) {
     std::string &err = LW.err;
     auto bad = [&](const std::string &m) { if (err.empty()) err = m; };
     // ---- pass 1: segments
@@ -549,7 +666,10 @@ static void lower_trace(const Trace *tr, int L, TemplateTable &tt, const char *c
     std::unordered_map<uint64_t, uint32_t> &val_of = LW.val_of; std::vector<ValInfo> &vals = LW.vals;
     std::vector<uint64_t> &pool64 = LW.pool64; std::map<uint64_t, uint32_t> &pool64_of = LW.pool64_of; std::vector<fr_t> &poolfr = LW.poolfr;
     std::vector<Matcher> matchers;
-    if (cn) { matchers.resize(segs.size()); for (size_t si = 0; si < segs.size(); si++) { matchers[si].cn = cn; matchers[si].found = found; matchers[si].seg = (int)si; segs[si].mt = &matchers[si]; } }
+    if (cns) {
+        matchers.resize(segs.size() * cns->size());
+        for (size_t si = 0; si < segs.size(); si++) for (size_t ci = 0; ci < cns->size(); ci++) { Matcher &m = matchers[si * cns->size() + ci]; m.cn = (*cns)[ci]; m.found = found; m.seg = (int)si; segs[si].mt.push_back(&m); }
+    }
     auto lit64 = [&](uint64_t v) { auto it = pool64_of.find(v); if (it != pool64_of.end()) return it->second; pool64.push_back(v); pool64_of[v] = (uint32_t)pool64.size() - 1; return (uint32_t)pool64.size() - 1; };
     auto litfr = [&](const fr_t &v) { for (size_t i = 0; i < poolfr.size(); i++) if (fr_eq(poolfr[i], v)) return (uint32_t)i; poolfr.push_back(v); return (uint32_t)poolfr.size() - 1; };
     std::vector<uint64_t> &meta = LW.meta; uint64_t &nrec = LW.nrec;
@@ -581,7 +701,7 @@ static void lower_trace(const Trace *tr, int L, TemplateTable &tt, const char *c
         if (o.code == TR_SCOPE_PUSH || o.code == TR_SCOPE_POP) {
             // entering a parallel child: the parent steps over its records and cells (filled in when the child ends)
             if (o.code == TR_SCOPE_PUSH && s != prev_seg && segs[(size_t)s].parent == prev_seg) {
-                SegInfo &Pn = segs[(size_t)prev_seg]; Pn.tape.push_back(DOP_SKIP | (5u << 24)); Pn.last_const_at = -1; if (Pn.mt) Pn.mt->boundary(); open_child[(size_t)s] = (int)Pn.tape.size(); for (int k = 0; k < 4; k++) Pn.tape.push_back(0);
+                SegInfo &Pn = segs[(size_t)prev_seg]; Pn.tape.push_back(DOP_SKIP | (5u << 24)); Pn.last_const_at = -1; for (Matcher *m : Pn.mt) m->boundary(); open_child[(size_t)s] = (int)Pn.tape.size(); for (int k = 0; k < 4; k++) Pn.tape.push_back(0);
                 S.cell0 = o.cell0; S.rec0 = nrec; S.started = true;
             }
             if (o.code == TR_SCOPE_POP && s != prev_seg && segs[(size_t)prev_seg].parent == s) {
@@ -600,7 +720,15 @@ static void lower_trace(const Trace *tr, int L, TemplateTable &tt, const char *c
         const uint32_t slots_before = S.nslots; bool ka_fused = false;
         const Stretch *fz = nullptr;
         if (fuse) { auto f = fuse->find(i); if (f != fuse->end()) fz = &f->second; }
-        if (fz) {      // a verified permutation: one op, its 12 results in fresh slots, its record block laid out as the emission kernel writes it
+        if (fz && fz->canon == CANON_BN) {      // a verified PoseidonBN254 permutation: one op, its 4 results in fresh slots; no records - its cells are direct cells
+            head(DOP_BNPERM);
+            for (int k = 0; k < BN_WIDTH; k++) { int w; T.push_back(ref_of(s, fz->in[k], &w)); }
+            const uint32_t base = S.nslots;
+            for (int k = 0; k < BN_WIDTH; k++) new_val(s, fz->out[k], WFR, false, 0);
+            T.push_back(base); T.push_back(S.nbnp++); T.push_back((uint32_t)(fz->cell1 - fz->cell0)); S.bnp_cells.push_back(fz->cell0);
+            S.last_const_at = -1;
+            want_cells = o.ncells; i = fz->tr1 - 1;
+        } else if (fz) {      // a verified permutation: one op, its 12 results in fresh slots, its record block laid out as the emission kernel writes it
             head(DOP_GLPERM);
             for (int k = 0; k < SPONGE_WIDTH; k++) { int w; T.push_back(ref_of(s, fz->in[k], &w)); if (w != W64) bad("internal: a wide input of a fused permutation"); }
             const uint32_t base = S.nslots;
@@ -723,13 +851,13 @@ static void lower_trace(const Trace *tr, int L, TemplateTable &tt, const char *c
         }
         if (fz || !(o.code == TR_LOAD_CONSTANT && S.last_const_at == (long)op_at)) S.last_const_at = -1;
         if (T.size() > op_at) {
-            if ((S.mt || (capture && s == 0)) && err.empty()) {      // the op as lowered, its operands still as mkref words
+            if ((!S.mt.empty() || (capture && s == 0)) && err.empty()) {      // the op as lowered, its operands still as mkref words
                 uint32_t first, count; operand_span(T[op_at] & 0xff, (T[op_at] >> 8) & 0xff, first, count);
                 NormOp no; no.hdr = T[op_at] & 0xffffffu; no.nin = count <= 3 ? count : 0xffu; no.slots_before = slots_before;
-                for (uint32_t k2 = 0; k2 < count && k2 < 3; k2++) { no.ref[k2] = T[op_at + first + k2]; if (ref_kind(no.ref[k2]) == RK_LIT64) no.lit[k2] = pool64[ref_idx(no.ref[k2])]; }
+                for (uint32_t k2 = 0; k2 < count && k2 < 3; k2++) { no.ref[k2] = T[op_at + first + k2]; if (ref_kind(no.ref[k2]) == RK_LIT64) no.lit[k2] = fr_from_u64(pool64[ref_idx(no.ref[k2])]); else if (ref_kind(no.ref[k2]) == RK_LITFR) no.lit[k2] = poolfr[ref_idx(no.ref[k2])]; }
                 no.out = count <= 3 && op_at + first + count < T.size() ? T[op_at + first + count] : NO_SLOT;
                 no.tr0 = ka_fused ? S.last_const_tr : i; no.tr1 = i + 1; no.cell0 = ka_fused ? o.cell0 - 1 : o.cell0; no.cell1 = o.cell0 + o.ncells; no.out_cell = o.n_out ? out[0] : 0; no.tin = in;
-                if (S.mt) { if (ka_fused) S.mt->drop_pending(); S.mt->feed(no); } else { if (ka_fused) capture->pop_back(); capture->push_back(no); }
+                if (!S.mt.empty()) { for (Matcher *m : S.mt) { if (ka_fused) m->drop_pending(); m->feed(no); } } else { if (ka_fused) capture->pop_back(); capture->push_back(no); }
             }
             const size_t len = T.size() - op_at; if (len > 255) bad("internal: op too long"); T[op_at] |= (uint32_t)len << 24;
             // operands: those in the lane's ring or in the LDS part of the pools become fast refs; the others are fetched into fresh ring slots by DOP_FETCH
@@ -762,36 +890,48 @@ static void lower_trace(const Trace *tr, int L, TemplateTable &tt, const char *c
         if (err.empty() && want_cells != o.ncells) bad("internal: op " + std::to_string(o.code) + " appended " + std::to_string(o.ncells) + " cells on the host, the device template has " + std::to_string(want_cells));
     }
     for (Matcher &m : matchers) m.commit();
-    for (SegInfo &S : segs) S.mt = nullptr;
+    for (SegInfo &S : segs) S.mt.clear();
     if (!err.empty()) return;
     segs[0].tape.push_back(DOP_END | (1u << 24)); segs[0].cell0 = 0; segs[0].rec0 = 0;
 }
 
-// The canonical tape of ONE permutation on `consts`: the library's own PoseidonChip::permute (what h2w_chip_gl_poseidon_permute runs) recorded on 12
-// abstract inputs and lowered by lower_trace like any tape; its operands classified (a literal, a value of the stretch, an input).
-static bool canonical_tape(int L, TemplateTable &tt, const h2w_poseidon_consts_t *consts, Canon &cn, std::string &err) {
+// The canonical tape of ONE permutation on `consts`: the library's own PoseidonChip::permute / PoseidonBN254PermutationChip::permute (what
+// h2w_chip_gl_poseidon_permute / h2w_chip_bn_poseidon_permute run) recorded on abstract inputs and lowered by lower_trace like any tape; its operands
+// classified (a literal, a value of the stretch, an input).  CANON_BN: recorded behind a load_zero (the cell cached, as every PoseidonBN254 permutation
+// of a run but the first to use it finds it); CANON_BN_ZERO: on a fresh context (the load_zero cell inside the first mix).
+static bool canonical_tape(int id, int L, TemplateTable &tt, const h2w_poseidon_consts_t *consts, Canon &cn, std::string &err) {
+    const bool bn = id != CANON_GL; const int nio = bn ? BN_WIDTH : SPONGE_WIDTH;
+    cn.id = id; cn.nio = nio; cn.in_any_width = bn;
     h2w_ctx *c = h2w_ctx_new(L, 1, -1);
     if (!c) { err = "cannot create the recording context"; return false; }
-    h2w_assigned_t in[SPONGE_WIDTH], out[SPONGE_WIDTH]; int rc = h2w_ctx_trace_begin(c);
-    for (int i = 0; i < SPONGE_WIDTH && rc == 0; i++) { rc = h2w_trace_input(c, (uint64_t)i, 1); if (rc == 0) rc = h2w_gl_load_witness(c, (uint64_t)i, &in[i]); }
-    if (rc == 0) rc = h2w_chip_gl_poseidon_permute(c, consts, in, out);
+    h2w_assigned_t in[MAX_PERM_IO], out[MAX_PERM_IO], z; int rc = h2w_ctx_trace_begin(c);
+    const size_t lead = id == CANON_BN ? 1 : 0;      // ops in front of the input loads
+    if (rc == 0 && id == CANON_BN) rc = h2w_load_zero(c, &z);
+    for (int i = 0; i < nio && rc == 0; i++) {
+        if (bn) { const fr_t v = fr_from_u64((uint64_t)i); rc = h2w_trace_input(c, 4 * (uint64_t)i, 4); if (rc == 0) rc = h2w_load_witness(c, &v, &in[i]); }
+        else { rc = h2w_trace_input(c, (uint64_t)i, 1); if (rc == 0) rc = h2w_gl_load_witness(c, (uint64_t)i, &in[i]); }
+    }
+    if (rc == 0) rc = bn ? h2w_chip_bn_poseidon_permute(c, consts, in, out) : h2w_chip_gl_poseidon_permute(c, consts, in, out);
     const Trace *tr = ctx_trace(c);
     if (rc != 0 || !tr || !tr->err.empty()) { err = "cannot record the canonical permutation"; h2w_ctx_free(c); return false; }
     Lowered LW; std::vector<NormOp> ops;
     lower_trace(tr, L, tt, nullptr, 0, LW, nullptr, nullptr, nullptr, nullptr, &ops);
-    bool ok = LW.err.empty() && ops.size() > (size_t)SPONGE_WIDTH;
+    const size_t first = lead + (size_t)nio;
+    bool ok = LW.err.empty() && ops.size() > first;
     if (!ok) err = "the canonical permutation does not lower: " + LW.err;
-    // the 12 loads come first
+    // the loads come first
     std::unordered_map<uint32_t, uint32_t> prod, inslot;      // slot -> op of the stretch; slot -> input
-    for (int i = 0; ok && i < SPONGE_WIDTH; i++) {
-        if ((ops[(size_t)i].hdr & 0xff) != DOP_LOADW || ops[(size_t)i].out == NO_SLOT) { ok = false; err = "internal: inputs of the canonical tape"; } else inslot[ops[(size_t)i].out] = (uint32_t)i;
+    for (int i = 0; ok && i < nio; i++) {
+        const NormOp &o = ops[lead + (size_t)i];
+        if ((o.hdr & 0xff) != (uint32_t)(bn ? DOP_FRCELL : DOP_LOADW) || o.out == NO_SLOT) { ok = false; err = "internal: inputs of the canonical tape"; } else inslot[o.out] = (uint32_t)i;
     }
-    for (size_t j = SPONGE_WIDTH; ok && j < ops.size(); j++) {
-        const NormOp &o = ops[j]; CanonOp c2; c2.hdr = o.hdr; c2.nin = o.nin; c2.has_out = o.out != NO_SLOT;
+    for (size_t j = first; ok && j < ops.size(); j++) {
+        const NormOp &o = ops[j]; CanonOp c2; memset(&c2, 0, sizeof(c2)); c2.hdr = o.hdr; c2.nin = o.nin; c2.has_out = o.out != NO_SLOT;
         if (o.nin > 3) { ok = false; err = "internal: an op of the canonical tape with more than three operands"; break; }
         for (uint32_t k = 0; k < o.nin; k++) {
             const int rk = ref_kind(o.ref[k]); const uint32_t ix = ref_idx(o.ref[k]);
-            if (rk == RK_LIT64) { c2.kind[k] = CK_LIT; c2.arg[k] = o.lit[k]; }
+            c2.rk[k] = (uint8_t)rk; c2.width[k] = (uint8_t)ref_width(o.ref[k]);
+            if (rk == RK_LIT64 || rk == RK_LITFR) { c2.kind[k] = CK_LIT; c2.lit[k] = o.lit[k]; }
             else if (rk == RK_LOCAL && inslot.count(ix)) { c2.kind[k] = CK_INPUT; c2.arg[k] = inslot[ix]; }
             else if (rk == RK_LOCAL && prod.count(ix)) { c2.kind[k] = CK_INTERIOR; c2.arg[k] = prod[ix]; }
             else { ok = false; err = "internal: an operand of the canonical tape"; }
@@ -799,12 +939,13 @@ static bool canonical_tape(int L, TemplateTable &tt, const h2w_poseidon_consts_t
         if (c2.has_out) prod[o.out] = (uint32_t)cn.ops.size();
         cn.ops.push_back(c2);
     }
-    for (int i = 0; ok && i < SPONGE_WIDTH; i++) {
+    for (int i = 0; ok && i < nio; i++) {
         auto it = LW.val_of.find(out[i].offset);
         if (!out[i].has_cell || it == LW.val_of.end() || LW.vals[it->second].is_static || !prod.count(LW.vals[it->second].slot)) { ok = false; err = "internal: outputs of the canonical tape"; break; }
         cn.out_prod[i] = prod[LW.vals[it->second].slot];
     }
-    if (ok) cn.ncells = ops.back().cell1 - ops[SPONGE_WIDTH].cell0;
+    if (ok) cn.ncells = ops.back().cell1 - ops[first].cell0;
+    if (ok && id == CANON_BN && LW.nrec != 1) { ok = false; err = "a PoseidonBN254 permutation on these tables has block records (a table entry below 2^64): it cannot be fused"; }
     h2w_ctx_free(c);
     return ok;
 }
@@ -814,19 +955,29 @@ static h2w_plan *plan_from_trace(h2w_ctx *ctx, uint64_t proof_words, const char 
     if (!tr) { set_error("h2w_plan_from_trace: the context is not in trace mode (h2w_ctx_trace_begin)"); return nullptr; }
     if (!tr->err.empty()) { set_error("h2w_plan_from_trace: " + tr->err); return nullptr; }
     if (tr->pending.kind) { set_error("h2w_plan_from_trace: a h2w_trace_input tag was never consumed"); return nullptr; }
-    const bool fusing = (flags & H2W_TRACE_FUSE_GL_PERMUTE) != 0;
-    if (flags & ~(uint32_t)H2W_TRACE_FUSE_GL_PERMUTE) { set_error("h2w_plan_from_trace_ex: unknown flag"); return nullptr; }
+    const bool fusing = (flags & H2W_TRACE_FUSE_GL_PERMUTE) != 0, fusing_bn = (flags & H2W_TRACE_FUSE_BN_PERMUTE) != 0;
+    if (flags & ~(uint32_t)(H2W_TRACE_FUSE_GL_PERMUTE | H2W_TRACE_FUSE_BN_PERMUTE)) { set_error("h2w_plan_from_trace_ex: unknown flag"); return nullptr; }
     if (fusing && !consts) { set_error("h2w_plan_from_trace_ex: H2W_TRACE_FUSE_GL_PERMUTE needs the Poseidon tables the permutations are claimed to use"); return nullptr; }
+    if (fusing_bn && !consts) { set_error("h2w_plan_from_trace_ex: H2W_TRACE_FUSE_BN_PERMUTE needs the Poseidon tables the permutations are claimed to use"); return nullptr; }
     const int L = ctx_lookup_bits(ctx);
     TemplateTable tt(L);
-    Lowered LW; std::map<size_t, Stretch> fuse; std::vector<uint64_t> glp_meta; uint64_t n_candidates = 0, glp_block_cells = 0;
-    if (fusing) {
-        // the stretches that equal the canonical tape word for word, found on a first lowering; those nothing outside reads into are lowered as one op
-        Canon cn; std::string cerr; std::vector<Stretch> found;
-        if (!canonical_tape(L, tt, consts, cn, cerr)) { set_error("h2w_plan_from_trace_ex: " + cerr); return nullptr; }
-        const uint64_t block_cells = glp_block_cells = glp_block_layout(tt, L, consts, glp_meta);
-        if (block_cells == 0 || block_cells != cn.ncells) { set_error("h2w_plan_from_trace_ex: the record block of a permutation (" + std::to_string(block_cells) + " cells) is not the traced one (" + std::to_string(cn.ncells) + " cells)"); return nullptr; }
-        { Lowered first; lower_trace(tr, L, tt, parallel_scopes, n_scopes, first, nullptr, nullptr, &cn, &found, nullptr); if (!first.err.empty()) { set_error("h2w_plan_from_trace: " + first.err); return nullptr; } }
+    Lowered LW; std::map<size_t, Stretch> fuse; std::vector<uint64_t> glp_meta; uint64_t n_candidates = 0, glp_block_cells = 0, n_bn_left = 0;
+    if (fusing || fusing_bn) {
+        // the stretches that equal a canonical tape word for word, found on a first lowering; those nothing outside reads into are lowered as one op
+        Canon cn, cnb, cnz; std::string cerr; std::vector<Stretch> found; std::vector<const Canon *> cns;
+        uint64_t block_cells = 0;
+        if (fusing) {
+            if (!canonical_tape(CANON_GL, L, tt, consts, cn, cerr)) { set_error("h2w_plan_from_trace_ex: " + cerr); return nullptr; }
+            block_cells = glp_block_cells = glp_block_layout(tt, L, consts, glp_meta);
+            if (block_cells == 0 || block_cells != cn.ncells) { set_error("h2w_plan_from_trace_ex: the record block of a permutation (" + std::to_string(block_cells) + " cells) is not the traced one (" + std::to_string(cn.ncells) + " cells)"); return nullptr; }
+            cns.push_back(&cn);
+        }
+        if (fusing_bn) {
+            if (!canonical_tape(CANON_BN, L, tt, consts, cnb, cerr) || !canonical_tape(CANON_BN_ZERO, L, tt, consts, cnz, cerr)) { set_error("h2w_plan_from_trace_ex: " + cerr); return nullptr; }
+            if (cnb.ncells != (uint64_t)BN_PERM_CELLS || cnz.ncells != (uint64_t)BN_PERM_CELLS + 1) { set_error("h2w_plan_from_trace_ex: a PoseidonBN254 permutation has " + std::to_string(cnb.ncells) + " traced cells, the emission kernel writes " + std::to_string(BN_PERM_CELLS)); return nullptr; }
+            cns.push_back(&cnb); cns.push_back(&cnz);
+        }
+        { Lowered first; lower_trace(tr, L, tt, parallel_scopes, n_scopes, first, nullptr, nullptr, &cns, &found, nullptr); if (!first.err.empty()) { set_error("h2w_plan_from_trace: " + first.err); return nullptr; } }
         std::sort(found.begin(), found.end(), [](const Stretch &a, const Stretch &b) { return a.cell0 < b.cell0; });
         // an interior value read outside its stretch: every operand handle of the trace (the hints' operands too) against the stretches' cell ranges
         auto reads = [&](size_t op, uint64_t cell) {
@@ -834,7 +985,7 @@ static h2w_plan *plan_from_trace(h2w_ctx *ctx, uint64_t proof_words, const char 
             if (it == found.begin()) return;
             Stretch &x = *(it - 1);
             if (cell >= x.cell1 || (op >= x.tr0 && op < x.tr1)) return;
-            for (int k = 0; k < SPONGE_WIDTH; k++) if (x.out[k] == cell) return;
+            for (int k = 0; k < x.nio; k++) if (x.out[k] == cell) return;
             x.escaped = true;
         };
         for (size_t i = 0; i < tr->ops.size(); i++) {
@@ -842,10 +993,19 @@ static h2w_plan *plan_from_trace(h2w_ctx *ctx, uint64_t proof_words, const char 
             for (uint32_t k = 0; k < o.n_in; k++) if (!tr->ins[o.first_in + k].lit) reads(i, tr->ins[o.first_in + k].v);
             if (o.tag.kind >= 2) { reads(i, o.tag.a); reads(i, o.tag.b); }
         }
+        uint64_t n_zero = 0;
         for (const Stretch &x : found) {
-            if (x.cell1 - x.cell0 != block_cells) { set_error("h2w_plan_from_trace_ex: a permutation's stretch has " + std::to_string(x.cell1 - x.cell0) + " traced cells, its record block " + std::to_string(block_cells)); return nullptr; }
-            if (x.const_bad || x.escaped) n_candidates++; else fuse.emplace(x.tr0, x);
+            if (x.canon == CANON_GL) {
+                if (x.cell1 - x.cell0 != block_cells) { set_error("h2w_plan_from_trace_ex: a permutation's stretch has " + std::to_string(x.cell1 - x.cell0) + " traced cells, its record block " + std::to_string(block_cells)); return nullptr; }
+                if (x.const_bad || x.escaped) n_candidates++; else fuse.emplace(x.tr0, x);
+            } else if (x.canon == CANON_BN) {
+                if (x.cell1 - x.cell0 != (uint64_t)BN_PERM_CELLS) { set_error("h2w_plan_from_trace_ex: a PoseidonBN254 permutation's stretch has " + std::to_string(x.cell1 - x.cell0) + " traced cells, the emission kernel writes " + std::to_string(BN_PERM_CELLS)); return nullptr; }
+                if (x.const_bad || x.escaped) n_bn_left++; else fuse.emplace(x.tr0, x);
+            } else {      // the permutation that holds the Context's load_zero cell (every later mix of the run reads it): recognised, left interpreted
+                n_bn_left++; if (!x.const_bad) n_zero++;
+            }
         }
+        if (n_zero > 1) { set_error("h2w_plan_from_trace_ex: internal: more than one PoseidonBN254 permutation with the load_zero cell"); return nullptr; }
     }
     lower_trace(tr, L, tt, parallel_scopes, n_scopes, LW, fuse.empty() ? nullptr : &fuse, &glp_meta, nullptr, nullptr, nullptr);
     std::string &err = LW.err;
@@ -904,7 +1064,7 @@ static h2w_plan *plan_from_trace(h2w_ctx *ctx, uint64_t proof_words, const char 
                 int found = -1;
                 for (size_t t = 0; t < members.size() && found < 0; t++) {
                     const SegInfo &M = segs[(size_t)members[t][0]];
-                    if (M.depth == S.depth && M.name == S.name && M.nslots == S.nslots && M.nglp == S.nglp && M.imps.size() == S.imps.size() && M.inputs.size() == S.inputs.size() && M.tape == S.tape) found = (int)t;
+                    if (M.depth == S.depth && M.name == S.name && M.nslots == S.nslots && M.nglp == S.nglp && M.nbnp == S.nbnp && M.imps.size() == S.imps.size() && M.inputs.size() == S.inputs.size() && M.tape == S.tape) found = (int)t;
                 }
                 if (found < 0) { members.push_back({}); found = (int)members.size() - 1; }
                 S.tmpl = found; S.inst = (uint32_t)members[(size_t)found].size(); members[(size_t)found].push_back((int)si);
@@ -919,6 +1079,7 @@ static h2w_plan *plan_from_trace(h2w_ctx *ctx, uint64_t proof_words, const char 
                 InstD I; I.cell0 = S.cell0; I.rec0 = S.rec0; I.imp0 = (uint32_t)imps.size(); I.in0 = (uint32_t)inputs.size();
                 I.unit = S.unit; I.ucell0 = S.unit == NO_SLOT ? 0 : segs[(size_t)units[S.unit]].cell0; tp->h_unit.push_back(S.unit);
                 I.glp0 = tp->nglp; tp->nglp += S.nglp; tp->h_glp_unit.insert(tp->h_glp_unit.end(), S.nglp, S.unit);
+                tp->h_bnp0.push_back(tp->nbnp); tp->nbnp += S.nbnp; for (uint64_t c0 : S.bnp_cells) tp->h_bnp.push_back(BnpD{c0, I.ucell0, S.unit, 0});
                 for (const ImpD &m : S.imps) { const SegInfo &Pn = segs[(size_t)m.tmpl]; imps.push_back(ImpD{(uint32_t)Pn.tmpl, Pn.inst, m.slot}); }
                 inputs.insert(inputs.end(), S.inputs.begin(), S.inputs.end());
                 insts.push_back(I);
@@ -959,6 +1120,8 @@ static h2w_plan *plan_from_trace(h2w_ctx *ctx, uint64_t proof_words, const char 
                 case DOP_GLOPRUN: ok = n >= 2; for (uint32_t k2 = 0; ok && k2 < n; k2++) ok = okref(R_(2 + 4 * k2), 1) && okref(R_(3 + 4 * k2), 1) && okref(R_(4 + 4 * k2), 1) && (uint64_t)(R_(5 + 4 * k2) & 0xffffffu) + 1 <= M.nslots && (R_(5 + 4 * k2) >> 24) < T_DYNAMIC; break;
                 case DOP_GLPERM: ok = len == GLPERM_WORDS && fusing && glp_meta.size() == (size_t)GLP_RECS && okout(R_(13), SPONGE_WIDTH) && R_(13) != NO_SLOT && R_(14) < M.nglp && R_(15) == (uint32_t)glp_block_cells;
                                  for (uint32_t k2 = 0; ok && k2 < (uint32_t)SPONGE_WIDTH; k2++) ok = okref(R_(1 + k2), 1) && ((R_(1 + k2) >> 27) & 3u) == W64; break;
+                case DOP_BNPERM: ok = len == BNPERM_WORDS && fusing_bn && okout(R_(5), 4 * BN_WIDTH) && R_(5) != NO_SLOT && R_(6) < M.nbnp && R_(7) == (uint32_t)BN_PERM_CELLS;
+                                 for (uint32_t k2 = 0; ok && k2 < (uint32_t)BN_WIDTH; k2++) ok = okref(R_(1 + k2), 4); break;
                 case DOP_FETCH: ok = len == 3 && n >= 1 && n <= 4 && okslow(R_(1)) && (uint64_t)R_(2) + n <= M.nslots; break;
                 case DOP_CONST1: case DOP_LOADW: ok = len == 3 && okref(R_(1), 1) && okout(R_(2), 1); break;
                 case DOP_FRCELL: ok = len == 3 && okref(R_(1), 4) && okout(R_(2), 4); break;
@@ -985,6 +1148,8 @@ static h2w_plan *plan_from_trace(h2w_ctx *ctx, uint64_t proof_words, const char 
     if (!err.empty()) { set_error("h2w_plan_from_trace: " + err); delete tp; return nullptr; }
     for (uint32_t w : inputs) if (w >= proof_words) { set_error("h2w_plan_from_trace: an input tag beyond proof_words"); delete tp; return nullptr; }
     tp->n_ops = tr->ops.size(); tp->n_segments = segs.size(); tp->why_unshardable = why_unshardable; tp->n_candidates = n_candidates;
+    tp->bn_flag = fusing_bn; tp->n_bn_left = n_bn_left;
+    for (const BnpD &b : tp->h_bnp) if (b.cell0 + (uint64_t)BN_PERM_CELLS > ctx_num_cells(ctx)) { set_error("h2w_plan_from_trace_ex: internal: a fused permutation's cells lie beyond the stream"); delete tp; return nullptr; }
 
     // ---- the plan handle
     h2w_plan *pl = new h2w_plan(L);
@@ -1052,6 +1217,12 @@ static h2w_plan *plan_from_trace(h2w_ctx *ctx, uint64_t proof_words, const char 
             H2W_HIP(hipMemcpy(pl->d_consts + 1, aux.data(), aux.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
             if (put((void **)&tp->d_glp_unit, tp->h_glp_unit.data(), tp->h_glp_unit.size() * 4) != 0) return -1;
         }
+        if (tp->nbnp) {      // the PoseidonBN254 tables, canonical and times R (as h2w_plan_compile builds a compiled plan's); where every listed permutation lies
+            std::vector<fr_t> tab(BK_ALL); bn_table_build(*consts, pl->P, tab.data());
+            if (put((void **)&pl->d_bn_tab, tab.data(), tab.size() * sizeof(fr_t)) != 0) return -1;
+            if (put((void **)&tp->d_bnp, tp->h_bnp.data(), tp->h_bnp.size() * sizeof(BnpD)) != 0) return -1;
+            if (put((void **)&tp->d_bnp0, tp->h_bnp0.data(), tp->h_bnp0.size() * 4) != 0) return -1;
+        }
         return 0;
     };
     if (up() != 0) { h2w_plan_free(pl); return nullptr; }
@@ -1071,7 +1242,14 @@ extern "C" int h2w_plan_trace_info(const h2w_plan *p, uint64_t out[6]) {
     out[0] = t->n_ops; out[1] = t->n_segments; out[2] = t->tmpls.size(); out[3] = t->nglp; out[4] = t->n_candidates; out[5] = t->nglp;
     return 0;
 }
-// ms of the kernels of the last call: the k_replay launch of every depth, k_glp_emit_traced, the expansion.  The first call switches the events on
+extern "C" int h2w_plan_trace_info_bn(const h2w_plan *p, uint64_t out[3]) {
+    if (!p || !out) { set_error("h2w_plan_trace_info_bn: null argument"); return -1; }
+    if (!p->traced) { set_error("h2w_plan_trace_info_bn: not a traced plan (h2w_plan_from_trace)"); return -1; }
+    const TracedPlan *t = p->traced;
+    out[0] = t->nbnp; out[1] = t->n_bn_left; out[2] = t->nbnp;
+    return 0;
+}
+// ms of the kernels of the last call: the k_replay launch of every depth, k_glp_emit_traced, (plans built with H2W_TRACE_FUSE_BN_PERMUTE) k_bn_emit_traced, the expansion.  The first call switches the events on
 // (0 entries); later ones wait for the last call and report it.
 extern "C" int h2w_plan_trace_timing(h2w_plan *p, float *ms, uint32_t cap) {
     if (!p || !ms) { set_error("h2w_plan_trace_timing: null argument"); return -1; }

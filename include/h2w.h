@@ -203,11 +203,29 @@ h2w_plan *h2w_plan_from_trace(h2w_ctx *, uint64_t proof_words, const char *const
  * constants, or an interior value read outside), list entries per proof}.
  * h2w_plan_trace_timing (a traced plan on a device): the first call switches event timing on and returns 0; later calls wait for the plan's last
  * witness call and fill ms[] with the time of each of its kernels in launch order - k_replay depth by depth, the permutation records' kernel (0
- * without fused permutations), the expansion - and return how many (at most cap). */
+ * without fused permutations), the expansion - and return how many (at most cap).
+ * H2W_TRACE_FUSE_BN_PERMUTE (may be combined with H2W_TRACE_FUSE_GL_PERMUTE; `consts` is required when either is set): the same for PoseidonBN254.
+ * The canonical tape is the library's own PoseidonBN254PermutationChip::permute (h2w_chip_bn_poseidon_permute) on `consts`' bn_c / bn_s / bn_m / bn_p
+ * with its 4 inputs abstracted - an input may be whatever the caller's tape has there: a computed value of any width, a value of an enclosing scope, a
+ * proof hash, a literal such as the sponge's zero capacity element.  A fused stretch is ONE device op instead of ~700: the lane computes the four
+ * outputs (state times R, one Montgomery product per multiplication, x^5 in three) and lists {first cell of the permutation in the proof's stream,
+ * zero-cell flag, the 4 x 32-byte input state}; a second kernel, one quad of lanes per listed permutation, writes its 4,032 cells from that state
+ * (64 contiguous bytes per quad and store) after the interpreter and beside nothing it depends on.  halo2-base caches the first load_zero cell of a
+ * context, so the first PoseidonBN254 permutation to run may hold that one extra cell inside its first mix: such a stretch is recognised (the
+ * canonical tape is recorded in both variants) and left interpreted - at most one per trace.  The plan needs 144 more bytes of workspace per fused
+ * PoseidonBN254 permutation and proof (the list entry: 18 u64 words, behind the value store and the Goldilocks list); h2w_plan_workspace_bytes changes
+ * for plans built with this flag only (the value store loses the fused stretches' interior values: the total is usually smaller).  Every call that works on a traced plan works on it (flat, _columns, _shard, _shard_compact, _status, the
+ * keygen metadata); flags 0 and 1 are exactly as before.
+ * h2w_plan_trace_info_bn: out = {fused PoseidonBN254 permutations, PoseidonBN254-shaped stretches left interpreted (other constants, an interior
+ * value read outside, the zero-cell variant), list entries per proof}; h2w_plan_trace_info's counts stay the Goldilocks ones.
+ * h2w_plan_trace_timing of a plan built with H2W_TRACE_FUSE_BN_PERMUTE reports one more kernel: the PoseidonBN254 emission, behind the Goldilocks
+ * record kernel's slot and in front of the expansion (0 when nothing was fused). */
 #define H2W_TRACE_FUSE_GL_PERMUTE 1
+#define H2W_TRACE_FUSE_BN_PERMUTE 2
 h2w_plan *h2w_plan_from_trace_ex(h2w_ctx *, uint64_t proof_words, const char *const *parallel_scopes, size_t n_scopes, int device_id,
                                  const h2w_poseidon_consts_t *consts, uint32_t flags);
 int h2w_plan_trace_info(const h2w_plan *, uint64_t out[6]);
+int h2w_plan_trace_info_bn(const h2w_plan *, uint64_t out[3]);
 int h2w_plan_trace_timing(h2w_plan *, float *ms, uint32_t cap);
 
 /* ------------------------------------------------------------------ advice hand-off (eager contexts) */

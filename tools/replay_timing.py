@@ -5,7 +5,9 @@ every k_replay dispatch: one per template, depth by depth).  usage: replay_timin
 (h2w_fri_witness_batch_shard_compact) - its own-cell rate beside the unsharded rate, and whether the buffer equals the compiled plan's packed buffer.
 --fuse: BOTH plans from the one trace - h2w_plan_from_trace and h2w_plan_from_trace_ex with H2W_TRACE_FUSE_GL_PERMUTE - in one process: for each, ms per
 launch, cells/s, the time of every kernel of a launch (h2w_plan_trace_timing: k_replay depth by depth, the permutation records' kernel, the expansion),
-one proof enqueue to completion, and whether the two streams are equal.  --out FILE: the JSON lines appended to FILE as well."""
+one proof enqueue to completion, and whether the two streams are equal.  --out FILE: the JSON lines appended to FILE as well.
+--fuse-bn: THREE plans from the one trace - unfused, H2W_TRACE_FUSE_GL_PERMUTE, and both flags (H2W_TRACE_FUSE_BN_PERMUTE as well) - in one process: the
+same figures for each (the third reports the PoseidonBN254 emission kernel too), and whether proof 0's h2w_advice_digest is equal across the three."""
 import argparse, importlib, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -16,7 +18,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="cfg3"); ap.add_argument("--hash", default="bn254"); ap.add_argument("--batch", type=int, default=64); ap.add_argument("--reps", type=int, default=2); ap.add_argument("--streams", type=int, default=1)
     ap.add_argument("--world", type=int, default=1); ap.add_argument("--rank", type=int, default=0)
-    ap.add_argument("--fuse", action="store_true"); ap.add_argument("--out", default=None)
+    ap.add_argument("--fuse", action="store_true"); ap.add_argument("--fuse-bn", action="store_true"); ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -31,9 +33,14 @@ def main():
     ctx = api.Context(21, True, 0); ctx.trace_begin()
     t0 = time.perf_counter(); api.verify_stark(ctx, sh, k, host[:words].astype(np.uint64)); t1 = time.perf_counter()
     plan = api.Plan.from_trace(ctx, words); t2 = time.perf_counter()
-    fused = api.Plan.from_trace(ctx, words, fuse_consts=k) if a.fuse else None; t3 = time.perf_counter()
+    fused = api.Plan.from_trace(ctx, words, fuse_consts=k) if a.fuse or a.fuse_bn else None; t3 = time.perf_counter()
+    fused_bn = api.Plan.from_trace(ctx, words, fuse_consts=k, fuse_bn=True) if a.fuse_bn else None; t4 = time.perf_counter()
     ctx.close()
     proofs = torch.from_numpy(host).cuda()      # (the unsharded launches take the first --batch)
+    if a.fuse_bn:
+        fuse_bn_report(a, torch, [("unfused", plan), ("fused_gl", fused), ("fused_gl_bn", fused_bn)], proofs,
+                       {"trace_s": round(t1 - t0, 3), "lower_s": round(t2 - t1, 3), "lower_fused_gl_s": round(t3 - t2, 3), "lower_fused_gl_bn_s": round(t4 - t3, 3)})
+        return
     if a.fuse:
         fuse_report(a, torch, plan, fused, proofs, {"trace_s": round(t1 - t0, 3), "lower_s": round(t2 - t1, 3), "lower_fused_s": round(t3 - t2, 3)})
         return
@@ -115,6 +122,49 @@ def fuse_report(a, torch, plan, fused, proofs, times):
         with open(a.out, "a") as f:
             for ln in lines:
                 f.write(json.dumps(ln) + "\n")
+
+
+def fuse_bn_report(a, torch, plans, proofs, times):
+    st = torch.cuda.current_stream().cuda_stream
+    last = plans[-1][1]
+    lines = [dict(config=a.config, hash=a.hash, batch=a.batch, reps=a.reps, cells_per_proof=last.num_cells, trace_info=last.trace_info(), trace_info_bn=last.trace_info_bn(), **times)]
+    digests = []
+    for name, pl in plans:
+        adv = torch.empty(a.batch * pl.num_cells * 32, dtype=torch.uint8, device="cuda"); ws = torch.zeros(pl.workspace_bytes(a.batch), dtype=torch.uint8, device="cuda")
+        pl.trace_timing()                                  # events on
+        ms, kern = [], []
+        for i in range(a.reps + 1):                        # (the first launch is the warm-up)
+            torch.cuda.synchronize(); t = time.perf_counter()
+            pl.run(proofs.data_ptr(), a.batch, adv.data_ptr(), ws.data_ptr(), st)
+            torch.cuda.synchronize(); ms.append((time.perf_counter() - t) * 1e3); kern.append(pl.trace_timing())
+        assert pl.status(ws.data_ptr(), a.batch, st) == [0] * a.batch
+        one = []
+        for i in range(a.reps + 1):                        # one proof, enqueue to completion
+            torch.cuda.synchronize(); t = time.perf_counter()
+            pl.run(proofs.data_ptr(), 1, adv.data_ptr(), ws.data_ptr(), st)
+            torch.cuda.synchronize(); one.append((time.perf_counter() - t) * 1e3)
+        dg = torch.zeros(4, dtype=torch.int64, device="cuda")
+        pl.advice_digest(adv.data_ptr(), pl.num_cells, dg.data_ptr(), st); torch.cuda.synchronize()
+        digests.append([int(x) & 0xFFFFFFFFFFFFFFFF for x in dg.cpu().tolist()])
+        bn = name == "fused_gl_bn"                         # k_replay launches (one per depth), the records' kernel, (the PoseidonBN254 emission,) the expansion
+        nd = len(kern[0]) - (3 if bn else 2)
+        ln = {"plan": name, "records": pl.num_records, "ws_GB": round(pl.workspace_bytes(a.batch) / 1e9, 3), "ms_per_launch": [round(x, 3) for x in ms[1:]],
+              "G_cells_per_s": [round(pl.num_cells * a.batch / (x * 1e-3) / 1e9, 3) for x in ms[1:]],
+              "k_replay_ms_by_depth": [[round(x, 3) for x in kk[:nd]] for kk in kern[1:]], "glp_emit_ms": [round(kk[nd], 3) for kk in kern[1:]]}
+        if bn:
+            ln["bn_emit_ms"] = [round(kk[nd + 1], 3) for kk in kern[1:]]
+        ln["expand_ms"] = [round(kk[-1], 3) for kk in kern[1:]]; ln["one_proof_ms"] = [round(x, 3) for x in one[1:]]; ln["proof0_digest"] = ["%016x" % x for x in digests[-1]]
+        lines.append(ln)
+        del adv, ws
+    lines.append({"proof0_digests_equal": digests[0] == digests[1] == digests[2]})
+    for ln in lines:
+        print(json.dumps(ln))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "a") as f:
+            for ln in lines:
+                f.write(json.dumps(ln) + "\n")
+    assert lines[-1]["proof0_digests_equal"], "the three plans' streams of proof 0 differ"
 
 
 if __name__ == "__main__":
