@@ -203,7 +203,7 @@ template <bool COLS> __global__ __launch_bounds__(256) void k_direct_to_montgome
                 if (q >= (long long)D.nq) q = (long long)D.nq - 1;
             }
             if ((q < 0 ? p : u0 + (uint64_t)q) % W != r) continue;
-            if (D.compact) {
+            if (D.compact) {      // (shardmap.h packed_block_start, written out: the call costs the kernel a scalar register and three instructions)
                 const uint64_t pro_before = (p + W - 1 - r) / W, units_before = (u0 + W - 1 - r) / W;
                 uint64_t local = pro_before * D.pro_ncell + units_before * D.q_slot, global = 0;
                 if (q >= 0) {
@@ -513,13 +513,9 @@ int h2w_plan_shard_block(const h2w_plan *p, int rank, int world, uint64_t proof,
     const uint64_t W = (uint64_t)world, r = (uint64_t)rank, nq = (uint64_t)p->shape.num_queries, u0 = proof * nq;
     const bool owned = query < 0 ? proof % W == r : (u0 + (uint64_t)query) % W == r;
     if (!owned) return 1;
-    const uint64_t pro_before = (proof + W - 1 - r) / W, units_before = (u0 + W - 1 - r) / W;
-    uint64_t local = pro_before * p->st.pro_ncell + units_before * shard_q_slot(p), n = p->st.pro_ncell, g = 0;
-    if (query >= 0) {
-        if (proof % W == r) local += p->st.pro_ncell;
-        local += ((u0 + (uint64_t)query + W - 1 - r) / W - units_before) * shard_q_slot(p);
-        n = p->st.q_ncell[query == 0 ? 0 : 1]; g = strand_q_cell(p->st, query);
-    }
+    const uint64_t local = packed_block_start(W, r, nq, p->st.pro_ncell, shard_q_slot(p), proof, query);
+    uint64_t n = p->st.pro_ncell, g = 0;
+    if (query >= 0) { n = p->st.q_ncell[query == 0 ? 0 : 1]; g = strand_q_cell(p->st, query); }
     if (local_cell) *local_cell = local; if (n_cells) *n_cells = n; if (global_cell) *global_cell = g;
     return 0;
 }

@@ -3,6 +3,7 @@
 #include "valbackend.h"
 #include "coop.h"
 #include "rowfr.h"
+#include "shardmap.h"
 
 namespace h2w {
 
@@ -52,6 +53,7 @@ __device__ __forceinline__ bool own_unit_at(const BatchArgs &A, unsigned i, int 
 }
 // Where the cells of proof p's block (q < 0: prologue, else query q) go: the pointer that the block's GLOBAL in-proof cell offsets are
 // added to.  Flat layout: out + p * cell_stride.  Compact layout: shifted so that the block lands in the rank's packed buffer.
+// (The placement is shardmap.h packed_block_start, written out: calling it here moves a few instructions in every batched kernel.)
 __device__ __forceinline__ fr_t *block_out(const BatchArgs &A, int p, int q) {
     if (!A.sh.compact) return A.out + (uint64_t)p * A.cell_stride;
     const uint64_t W = (uint64_t)A.sh.world, r = (uint64_t)A.sh.rank;

@@ -259,6 +259,7 @@ __device__ __forceinline__ bool fast_tile_range(const ExpandArgs &A, uint64_t pr
     const bool own_pro = proof % W == r;
     const uint32_t tp = own_pro ? (uint32_t)((A.pro_nrec + FAST_TR - 1) / FAST_TR) : 0u;
     const uint64_t units_before = (u0 + W - 1 - r) / W;
+    // (shardmap.h packed_block_start states this placement; here it is written out: the rank's j-th query needs no division, and the call costs every expand_fast 350+ instructions)
     uint64_t local = ((proof + W - 1 - r) / W) * A.pro_ncell + units_before * A.q_slot;      // the rank's packed buffer: owned blocks before this proof
     if (tile < tp) {
         rbeg = (uint64_t)tile * FAST_TR; rend = rbeg + FAST_TR < A.pro_nrec ? rbeg + FAST_TR : A.pro_nrec;
