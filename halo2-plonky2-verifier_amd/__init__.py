@@ -76,6 +76,10 @@ _av = C.POINTER(Assigned)
 _fr = C.POINTER(Fr)
 H2W_TRACE_FUSE_GL_PERMUTE = 1      # flags of h2w_plan_from_trace_ex (include/h2w.h)
 H2W_TRACE_FUSE_BN_PERMUTE = 2
+# batched chip ops (include/h2w.h 2c): the hash and Merkle ops of h2w_chipbatch_new_hash, and the option of h2w_chipbatch_configure
+H2W_OP_GL_PERMUTE, H2W_OP_BN_PERMUTE, H2W_OP_HASH_NO_PAD, H2W_OP_TWO_TO_ONE, H2W_OP_MERKLE_VERIFY = 9, 10, 11, 12, 13
+H2W_CHIPBATCH_MAX_N_IN = 4096
+H2W_CHIPBATCH_OPT_CHUNK = 1
 
 SYMBOLS = {
     "h2w_abi_version": (C.c_int, []),
@@ -182,6 +186,8 @@ SYMBOLS = {
     "h2w_chipbatch_num_operands": (C.c_uint64, [_vp]),
     "h2w_chipbatch_num_cells": (C.c_uint64, [_vp]),
     "h2w_chipbatch_run": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, _vp]),
+    "h2w_chipbatch_new_hash": (_vp, [C.c_int, C.POINTER(PoseidonConsts), C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int]),
+    "h2w_chipbatch_configure": (C.c_int, [_vp, C.c_int, C.c_uint64]),
     "h2w_comm_unique_id": (C.c_int, [_vp]),
     "h2w_comm_init": (_vp, [_vp, C.c_int, C.c_int, C.c_int]),
     "h2w_comm_free": (None, [_vp]),

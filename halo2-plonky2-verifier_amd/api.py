@@ -7,7 +7,7 @@ argument meaning and error behaviour (a non-zero status raises H2WError where th
 """
 import ctypes as C
 
-from . import (Assigned, Fr, H2W_TRACE_FUSE_BN_PERMUTE, H2W_TRACE_FUSE_GL_PERMUTE, H2WError, PoseidonConsts, Shape, _ck, last_error, lib)
+from . import (Assigned, Fr, H2W_CHIPBATCH_OPT_CHUNK, H2W_TRACE_FUSE_BN_PERMUTE, H2W_TRACE_FUSE_GL_PERMUTE, H2WError, PoseidonConsts, Shape, _ck, last_error, lib)
 
 GL_P = 0xFFFFFFFF00000001
 FR_MODULUS = 21888242871839275222246405745257275088548364400416034343698204186575808495617
@@ -540,3 +540,58 @@ def advice_digest_reference(cells_bytes, chunk_cells=1 << 22):
             for j in range(4):
                 acc[j] = (acc[j] + int((part[:, j] * (m + np.uint64(2 * j))).sum(dtype=np.uint64))) & 0xFFFFFFFFFFFFFFFF
     return acc
+
+
+class ChipBatch:
+    """Batched chip operations on the device (h2w_chipbatch_*): n independent instances of one chip op, each in a fresh Context."""
+
+    def __init__(self, op, lookup_bits=21, device_id=0, _handle=None):
+        """h2w_chipbatch_new: one of the nine GoldilocksChip / GoldilocksQuadExtChip ops (H2W_OP_GL_ADD .. H2W_OP_EXT_DIV)."""
+        self.L = lib()
+        self.p = _handle if _handle is not None else self.L.h2w_chipbatch_new(op, lookup_bits, device_id)
+        if not self.p:
+            raise H2WError("h2w_chipbatch_new: " + last_error())
+        self.consts = None
+
+    @classmethod
+    def new_hash(cls, op, consts, hash_mode=0, n_in=0, depth=0, cap_height=0, lookup_bits=21, device_id=0):
+        """h2w_chipbatch_new_hash: a hash or Merkle chip op (H2W_OP_GL_PERMUTE .. H2W_OP_MERKLE_VERIFY) on the Poseidon tables `consts`.
+        hash_mode: 0 Goldilocks-Poseidon, 1 PoseidonBN254 (HASH_NO_PAD, TWO_TO_ONE, MERKLE_VERIFY); n_in: words hashed (HASH_NO_PAD) / the
+        leaf's length (MERKLE_VERIFY); depth, cap_height: the Merkle path (MERKLE_VERIFY).  A parameter the op does not use stays 0.
+        Operand order per instance: include/h2w.h 2c."""
+        h = lib().h2w_chipbatch_new_hash(op, C.byref(consts), hash_mode, n_in, depth, cap_height, lookup_bits, device_id)
+        if not h:
+            raise H2WError("h2w_chipbatch_new_hash: " + last_error())
+        b = cls(op, lookup_bits, device_id, _handle=h)
+        b.consts = consts
+        return b
+
+    def close(self):
+        if getattr(self, "p", None):
+            self.L.h2w_chipbatch_free(self.p)
+            self.p = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def num_operands(self):
+        """u64 words per instance of operands_dev[n][num_operands]."""
+        return int(self.L.h2w_chipbatch_num_operands(self.p))
+
+    def num_cells(self):
+        """Advice cells per instance of advice_dev[n][num_cells]."""
+        return int(self.L.h2w_chipbatch_num_cells(self.p))
+
+    def configure(self, option, value):
+        """h2w_chipbatch_configure (H2W_CHIPBATCH_OPT_CHUNK: instances per internal launch of a hash / Merkle handle)."""
+        _ck(self.L.h2w_chipbatch_configure(self.p, option, value), "h2w_chipbatch_configure")
+
+    def set_chunk(self, instances):
+        self.configure(H2W_CHIPBATCH_OPT_CHUNK, instances)
+
+    def run(self, operands_ptr, n, advice_ptr, status_ptr, stream=0):
+        """h2w_chipbatch_run: device pointers; status_ptr: n u32 words (0, 1 / 2 where the reference panics, 4: an operand outside its field)."""
+        _ck(self.L.h2w_chipbatch_run(self.p, operands_ptr, n, advice_ptr, status_ptr, stream), "h2w_chipbatch_run")

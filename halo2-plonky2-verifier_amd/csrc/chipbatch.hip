@@ -9,6 +9,7 @@
 #include <vector>
 #include "common.h"
 #include "valbackend.h"
+#include "chipbatch.h"
 
 namespace h2w {
 
@@ -68,16 +69,11 @@ __global__ __launch_bounds__(64) void k_chip_batch(ChipArgs A) {
 
 using namespace h2w;
 
-struct h2w_chipbatch {
-    int op, L, device, nw; TemplateTable tt; DeviceTables dt; FrParams P;
-    uint64_t nrec = 0, ncells = 0; uint64_t *d_meta = nullptr; uint16_t *d_tmpl_cells = nullptr;
-    explicit h2w_chipbatch(int L_) : tt(L_) {}
-};
-
 extern "C" {
 
 h2w_chipbatch *h2w_chipbatch_new(int op, int lookup_bits, int device_id) {
     const int nw = chip_op_operands(op);
+    if (op >= H2W_OP_GL_PERMUTE && op <= H2W_OP_MERKLE_VERIFY) { set_error("h2w_chipbatch_new: the hash and Merkle ops (9-13) take parameters: use h2w_chipbatch_new_hash"); return nullptr; }
     if (nw < 0 || lookup_bits < 2 || lookup_bits > 28) { set_error("h2w_chipbatch_new: unknown op / lookup_bits outside [2, 28]"); return nullptr; }
     h2w_chipbatch *h = new h2w_chipbatch(lookup_bits);
     h->op = op; h->L = lookup_bits; h->device = device_id; h->nw = nw; h->P = fr_params_init();
@@ -111,6 +107,7 @@ void h2w_chipbatch_free(h2w_chipbatch *h) {
     DeviceGuard dg(h->device);
     if (h->d_meta) (void)hipFree(h->d_meta);
     if (h->d_tmpl_cells) (void)hipFree(h->d_tmpl_cells);
+    if (h->hash) chiphash_free(h);
     h->dt.free();
     delete h;
 }
@@ -120,6 +117,7 @@ int h2w_chipbatch_run(h2w_chipbatch *h, const uint64_t *operands_dev, uint64_t n
     if (!h || !operands_dev || !advice_dev || !status_dev) { set_error("h2w_chipbatch_run: null argument"); return -1; }
     if (h->device < 0) { set_error("h2w_chipbatch_run: no HIP device - cells are only produced on the GPU (no CPU fallback)"); return -1; }
     if (n == 0) return 0;
+    if (h->hash) return chiphash_run(h, operands_dev, n, advice_dev, status_dev, stream_);
     DeviceGuard dg(h->device);
     hipStream_t stream = (hipStream_t)stream_;
     const uint64_t CH = 32768;                                // instances per launch (grid.y of the expansion kernel)

@@ -466,6 +466,37 @@ void           h2w_chipbatch_free(h2w_chipbatch *);
 uint64_t       h2w_chipbatch_num_operands(const h2w_chipbatch *);   /* u64 words per instance */
 uint64_t       h2w_chipbatch_num_cells(const h2w_chipbatch *);      /* advice cells per instance */
 int            h2w_chipbatch_run(h2w_chipbatch *, const uint64_t *operands_dev, uint64_t n, void *advice_dev, uint32_t *status_dev, void *stream);
+/* The hash and Merkle chips, batched the same way (csrc/chiphash.hip): every instance a fresh Context, its operands loaded the way the
+ * verifier's WitnessChip loads them, then the op.  Created by h2w_chipbatch_new_hash (h2w_chipbatch_new refuses these ops, and
+ * h2w_chipbatch_new_hash refuses ops 0-8); num_operands / num_cells / run / free are the calls above.  Operand words per instance, in
+ * this order:
+ *   GL_PERMUTE     12 Goldilocks words                          GoldilocksChip::load_witness each, then permute (hash_mode ignored)
+ *   BN_PERMUTE     4 x 4 words (little-endian Fr)               NativeChip::load_witness each, then permute
+ *   HASH_NO_PAD    n_in Goldilocks words                        load_witness each, then hash_no_pad
+ *   TWO_TO_ONE     2 hashes x 4 words                           HasherChip::load_witness each, then two_to_one
+ *   MERKLE_VERIFY  leaf[n_in], leaf_index, cap[2^cap_height][4], siblings[depth - cap_height][4]:
+ *                  the leaf by load_witness; the index by load_witness, then num_to_bits(index, depth); the cap, then the siblings, by
+ *                  HasherChip::load_witness; cap_index = bits_to_num(bits[depth - cap_height ..]); verify_proof_to_cap_with_cap_index
+ * A hash is four words in both modes: four Goldilocks words loaded as CONSTANTS (hash_mode 0, poseidon/hash.rs:86-96) or one Fr loaded as
+ * a native witness (hash_mode 1).  Parameters an op does not use must be 0.  n_in >= 1 (ops 11, 13), at most H2W_CHIPBATCH_MAX_N_IN;
+ * 1 <= depth <= 32; cap_height <= min(depth, 6).
+ * status_dev[i]: 0, or 4 where an operand word is outside its field (a Goldilocks word >= p, an Fr >= r: the cells are still produced,
+ * from the raw value, as h2w_plan_status defines 4) or the leaf index is >= 2^depth (the cells of that instance are unspecified).
+ * The chips' assert_equal emits no cells: a Merkle verdict is not part of this (h2w_check_equalities is the check).
+ * hash_mode 0 and GL_PERMUTE: one wavefront per instance, its permutations' records written by one wavefront per permutation;
+ * hash_mode 1 and BN_PERMUTE: four lanes per instance, which emit every permutation's 4,032 cells themselves. */
+#define H2W_OP_GL_PERMUTE     9   /* PoseidonPermutationChip::permute           hash/poseidon/permutation.rs:270-284 */
+#define H2W_OP_BN_PERMUTE    10   /* PoseidonBN254PermutationChip::permute      hash/poseidon_bn254/permutation.rs:190-203 */
+#define H2W_OP_HASH_NO_PAD   11   /* HasherChip::hash_no_pad                    poseidon/hash.rs:161-184, poseidon_bn254/hash.rs:156-179 */
+#define H2W_OP_TWO_TO_ONE    12   /* HasherChip::two_to_one                     poseidon/hash.rs:187-214, poseidon_bn254/hash.rs:182-209 */
+#define H2W_OP_MERKLE_VERIFY 13   /* MerkleTreeChip::verify_proof_to_cap        merkle/mod.rs:80-102 */
+#define H2W_CHIPBATCH_MAX_N_IN 4096   /* largest n_in of HASH_NO_PAD / MERKLE_VERIFY */
+h2w_chipbatch *h2w_chipbatch_new_hash(int op, const h2w_poseidon_consts_t *, int hash_mode, uint32_t n_in, uint32_t depth, uint32_t cap_height,
+                                      int lookup_bits, int device_id);
+/* H2W_CHIPBATCH_OPT_CHUNK: instances per internal launch of a handle made by h2w_chipbatch_new_hash (1 .. 32768; the default keeps the
+ * call's internal workspace - records, permutation lists - under a fixed number of bytes). */
+#define H2W_CHIPBATCH_OPT_CHUNK 1
+int            h2w_chipbatch_configure(h2w_chipbatch *, int option, uint64_t value);
 
 /* ------------------------------------------------------------------ the step BEFORE the path
  * Synthetic VALID FRI instances generated on the GPU (SURVEY 8(d) variant (A)): low-degree extension (Goldilocks NTT on the coset
