@@ -1,4 +1,4 @@
-// batchargs.h - kernel arguments of the batched hot path, shared by its translation units (batch.hip, glue.hip).
+// batchargs.h - kernel arguments of the batched hot path, shared by its translation units (batch.hip, glue.hip; the plan handle, plan.h, rests on it).
 #pragma once
 #include "valbackend.h"
 #include "coop.h"

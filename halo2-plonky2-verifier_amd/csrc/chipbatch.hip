@@ -7,8 +7,6 @@
 // operand, exactly like the batched verifier path (include/h2w.h "device status words").
 #include <hip/hip_runtime.h>
 #include <vector>
-#include "common.h"
-#include "valbackend.h"
 #include "chipbatch.h"
 
 namespace h2w {
@@ -55,7 +53,7 @@ struct ChipArgs { int op, nw, L; FrParams P; const uint64_t *operands; rec_t *re
 __global__ __launch_bounds__(64) void k_chip_batch(ChipArgs A) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= A.n) return;
-    DevSink sink; sink.recs = A.recs + i * A.nrec; sink.nrec = 0; sink.out = A.out + i * A.ncells; sink.cell_off = 0; sink.ncells = A.tmpl_cells; sink.cc.init(ColMap{nullptr, 0, 0});
+    DevSink sink; sink.recs = A.recs + i * A.nrec; sink.nrec = 0; sink.out = A.out + i * A.ncells; sink.cell_off = 0; sink.ncells = A.tmpl_cells; sink.cc.init(flat_cols());
     ValCfg cfg; cfg.proof = nullptr; cfg.mode = 0; cfg.L = A.L; cfg.P = A.P; cfg.inv_pos = cfg.inv_neg = nullptr; cfg.st = nullptr; cfg.split = false; cfg.split_bn = false;
     cfg.load_items = nullptr; cfg.n_load_items = 0; cfg.load_nrec = cfg.load_ncell = 0;
     ValBackend<DevSink> be(sink, cfg, true);
@@ -79,8 +77,7 @@ h2w_chipbatch *h2w_chipbatch_new(int op, int lookup_bits, int device_id) {
     h->op = op; h->L = lookup_bits; h->device = device_id; h->nw = nw; h->P = fr_params_init();
     CountSink cs; cs.tt = &h->tt;
     {   // layout of one instance: replay on harmless operands (1: no division by zero)
-        ValCfg cfg; cfg.proof = nullptr; cfg.mode = 0; cfg.L = lookup_bits; cfg.P = h->P; cfg.inv_pos = cfg.inv_neg = nullptr; cfg.st = nullptr; cfg.split = false; cfg.split_bn = false;
-        cfg.load_items = nullptr; cfg.n_load_items = 0; cfg.load_nrec = cfg.load_ncell = 0;
+        ValCfg cfg{}; cfg.L = lookup_bits; cfg.P = h->P;      // (host: every other field null / 0 / false)
         ValBackend<CountSink> be(cs, cfg, true);
         const uint64_t ones[4] = {1, 1, 1, 1};
         chip_program(be, op, ones);
@@ -90,25 +87,13 @@ h2w_chipbatch *h2w_chipbatch_new(int op, int lookup_bits, int device_id) {
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { h->device = -1; return h; }      // layout queries still work; h2w_chipbatch_run fails
     if (device_id < 0 || device_id >= ndev) { set_error("h2w_chipbatch_new: device_id out of range"); delete h; return nullptr; }
     DeviceGuard dg(device_id);
-    auto up = [&]() -> int {
-        if (h->dt.upload(h->tt) != 0) return -1;
-        H2W_HIP(hipMalloc((void **)&h->d_meta, h->nrec * sizeof(uint64_t)));
-        H2W_HIP(hipMemcpy(h->d_meta, cs.meta.data(), h->nrec * sizeof(uint64_t), hipMemcpyHostToDevice));
-        std::vector<uint16_t> nc(T_MAX, 0); for (size_t i = 0; i < h->tt.info.size(); i++) nc[i] = h->tt.info[i].ncells;
-        H2W_HIP(hipMalloc((void **)&h->d_tmpl_cells, nc.size() * sizeof(uint16_t)));
-        H2W_HIP(hipMemcpy(h->d_tmpl_cells, nc.data(), nc.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-        return 0;
-    };
-    if (up() != 0) { h2w_chipbatch_free(h); return nullptr; }
+    if (h->dt.upload(h->tt) != 0 || h->d_meta.upload(cs.meta) != 0 || upload_tmpl_cells(h->d_tmpl_cells, h->tt) != 0) { h2w_chipbatch_free(h); return nullptr; }
     return h;
 }
 void h2w_chipbatch_free(h2w_chipbatch *h) {
     if (!h) return;
     DeviceGuard dg(h->device);
-    if (h->d_meta) (void)hipFree(h->d_meta);
-    if (h->d_tmpl_cells) (void)hipFree(h->d_tmpl_cells);
-    if (h->hash) chiphash_free(h);
-    h->dt.free();
+    chiphash_free(h);
     delete h;
 }
 uint64_t h2w_chipbatch_num_operands(const h2w_chipbatch *h) { return h ? (uint64_t)h->nw : 0; }
@@ -127,11 +112,11 @@ int h2w_chipbatch_run(h2w_chipbatch *h, const uint64_t *operands_dev, uint64_t n
         for (uint64_t first = 0; first < n; first += CH) {
             const uint64_t m = n - first < CH ? n - first : CH;
             ChipArgs A; A.op = h->op; A.nw = h->nw; A.L = h->L; A.P = h->P; A.operands = operands_dev + first * (uint64_t)h->nw; A.recs = (rec_t *)ws; A.nrec = h->nrec; A.ncells = h->ncells; A.n = m;
-            A.out = (fr_t *)advice_dev + first * h->ncells; A.tmpl_cells = h->d_tmpl_cells; A.status = status_dev + first;
+            A.out = (fr_t *)advice_dev + first * h->ncells; A.tmpl_cells = h->d_tmpl_cells.get(); A.status = status_dev + first;
             hipLaunchKernelGGL(k_chip_batch, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, stream, A);
             ExpandArgs E;
-            E.meta = h->d_meta; E.recs = A.recs; E.nrec = h->nrec; E.rec_stride = h->nrec; E.out = A.out; E.cell_stride = h->ncells; E.pool = nullptr;
-            E.cm = ColMap{nullptr, 0, 0}; expand_unsharded(E);
+            E.meta = h->d_meta.get(); E.recs = A.recs; E.nrec = h->nrec; E.rec_stride = h->nrec; E.out = A.out; E.cell_stride = h->ncells; E.pool = nullptr;
+            E.cm = flat_cols(); expand_unsharded(E);
             h->dt.fill(E);
             E.tile_ctr = (uint32_t *)(ws + b_recs);
             H2W_HIP(hipMemsetAsync(E.tile_ctr, 0, m * sizeof(uint32_t), stream));

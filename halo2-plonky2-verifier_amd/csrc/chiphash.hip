@@ -17,7 +17,6 @@
 #define H2W_FLATTEN_CHIPS 1      // the gadget stack inlined into the two value kernels (field.h HNI): the sinks below exist in this unit alone
 #include <hip/hip_runtime.h>
 #include <vector>
-#include "common.h"
 #include "batchargs.h"
 #include "chipbatch.h"
 
@@ -125,7 +124,7 @@ __global__ __launch_bounds__(64) __attribute__((flatten)) void k_chiphash_gl(Has
     typedef ValBackend<HashCoopSink> CoopB;
     stage_glp_consts<true>(A.consts, threadIdx.x, 64);
     const uint64_t i = blockIdx.x;      // (the grid is the instances of the launch)
-    HashCoopSink sink; sink.recs = A.recs + i * A.nrec; sink.out = A.out + i * A.ncells; sink.ncells = A.tmpl_cells; sink.lane = threadIdx.x; sink.cc.init(ColMap{nullptr, 0, 0});
+    HashCoopSink sink; sink.recs = A.recs + i * A.nrec; sink.out = A.out + i * A.ncells; sink.ncells = A.tmpl_cells; sink.lane = threadIdx.x; sink.cc.init(flat_cols());
     sink.glp = A.glist + i * (uint64_t)A.nglp * GLP_LIST_WORDS; sink.small_mds = A.small_mds != 0; sink.bind_lds();
     sink.nrec = 0; sink.cell_off = 0; sink.glp_slot = 0; sink.emit = true;
     CoopB be(sink, chiphash_cfg(0, A.L, A.P, A.inv, false), false);
@@ -158,7 +157,7 @@ __global__ __launch_bounds__(QUAD_BLOCK) H2W_QUAD_ATTR __attribute__((flatten)) 
     uint64_t i = ((uint64_t)blockIdx.x * QUAD_BLOCK + threadIdx.x) >> 2;
     if (i >= A.n) i = A.n - 1;
     HashQuadSink sink; sink.recs = A.recs + i * A.nrec; sink.nrec = 0; sink.out = A.out + i * A.ncells; sink.cell_off = 0; sink.ncells = A.tmpl_cells; sink.l4 = threadIdx.x & 3;
-    sink.cc.init(ColMap{nullptr, 0, 0}); sink.ustate = nullptr; sink.sbx = nullptr;
+    sink.cc.init(flat_cols()); sink.ustate = nullptr; sink.sbx = nullptr;
     QuadB be(sink, chiphash_cfg(1, A.L, A.P, A.inv, true), false);      // a fresh Context: its first permutation holds the cached load_zero cell
     const HashParams hp = A.hp;
     hash_program<1>(be, hp, nullptr, A.operands + i * (uint64_t)A.nw);
@@ -184,14 +183,11 @@ __global__ __launch_bounds__(256) void k_chiphash_check(CheckArgs C) {
 
 struct ChipHash {
     HashParams hp; OperandLayout o; bool bn; uint32_t nglp = 0; int small_mds = 0; uint64_t chunk = 0;      // chunk 0: by CHIPHASH_WS_BYTES
-    h2w_poseidon_consts_t *d_consts = nullptr; fr_t *d_bn_tab = nullptr, *d_inv = nullptr;
+    DevBuf<GlpConsts> d_consts; DevBuf<fr_t> d_bn_tab, d_inv;
 };
 
-void chiphash_free(h2w_chipbatch *h) {
-    ChipHash *c = h->hash; if (!c) return;
-    if (c->d_consts) (void)hipFree(c->d_consts); if (c->d_bn_tab) (void)hipFree(c->d_bn_tab); if (c->d_inv) (void)hipFree(c->d_inv);
-    delete c; h->hash = nullptr;
-}
+
+void chiphash_free(h2w_chipbatch *h) { delete h->hash; h->hash = nullptr; }
 
 int chiphash_run(h2w_chipbatch *h, const uint64_t *operands_dev, uint64_t n, void *advice_dev, uint32_t *status_dev, void *stream_) {
     ChipHash *c = h->hash;
@@ -206,8 +202,8 @@ int chiphash_run(h2w_chipbatch *h, const uint64_t *operands_dev, uint64_t n, voi
         for (uint64_t first = 0; first < n; first += CH) {
             const uint64_t m = n - first < CH ? n - first : CH;
             HashArgs A; A.hp = c->hp; A.L = h->L; A.P = h->P; A.operands = operands_dev + first * (uint64_t)h->nw; A.nw = (uint32_t)h->nw; A.recs = (rec_t *)ws; A.nrec = h->nrec; A.ncells = h->ncells; A.n = m;
-            A.out = (fr_t *)advice_dev + first * h->ncells; A.tmpl_cells = h->d_tmpl_cells; A.inv = c->d_inv;
-            A.consts = c->d_consts; A.glist = (uint64_t *)(ws + b_recs); A.nglp = c->nglp; A.small_mds = c->small_mds; A.bn_tab = c->d_bn_tab;
+            A.out = (fr_t *)advice_dev + first * h->ncells; A.tmpl_cells = h->d_tmpl_cells.get(); A.inv = c->d_inv.get();
+            A.consts = c->d_consts.get(); A.glist = (uint64_t *)(ws + b_recs); A.nglp = c->nglp; A.small_mds = c->small_mds; A.bn_tab = c->d_bn_tab.get();
             uint32_t *const status = status_dev + first;
             H2W_HIP(hipMemsetAsync(status, 0, m * sizeof(uint32_t), stream));
             CheckArgs K; K.operands = A.operands; K.o = c->o; K.depth = c->hp.depth; K.n = m; K.status = status;
@@ -216,13 +212,13 @@ int chiphash_run(h2w_chipbatch *h, const uint64_t *operands_dev, uint64_t n, voi
             if (c->bn) hipLaunchKernelGGL(k_chiphash_bn, dim3((unsigned)((m * 4 + QUAD_BLOCK - 1) / QUAD_BLOCK)), dim3(QUAD_BLOCK), 0, stream, A);
             else {
                 hipLaunchKernelGGL(k_chiphash_gl, dim3((unsigned)m), dim3(64), 0, stream, A);
-                HashEmitArgs G; G.consts = c->d_consts; G.list = A.glist; G.recs = A.recs; G.nrec = h->nrec; G.tmpl_cells = h->d_tmpl_cells; G.nglp = c->nglp;
+                HashEmitArgs G; G.consts = c->d_consts.get(); G.list = A.glist; G.recs = A.recs; G.nrec = h->nrec; G.tmpl_cells = h->d_tmpl_cells.get(); G.nglp = c->nglp;
                 if (c->nglp) hipLaunchKernelGGL(k_chiphash_glp_emit, dim3((unsigned)(m * c->nglp)), dim3(64), 0, stream, G);
             }
             if (h->nrec) {      // expansion of the block records
                 ExpandArgs E;
-                E.meta = h->d_meta; E.recs = A.recs; E.nrec = h->nrec; E.rec_stride = h->nrec; E.out = A.out; E.cell_stride = h->ncells; E.pool = nullptr;
-                E.cm = ColMap{nullptr, 0, 0}; expand_unsharded(E);
+                E.meta = h->d_meta.get(); E.recs = A.recs; E.nrec = h->nrec; E.rec_stride = h->nrec; E.out = A.out; E.cell_stride = h->ncells; E.pool = nullptr;
+                E.cm = flat_cols(); expand_unsharded(E);
                 h->dt.fill(E);
                 E.tile_ctr = (uint32_t *)(ws + b_recs + b_list);
                 H2W_HIP(hipMemsetAsync(E.tile_ctr, 0, m * sizeof(uint32_t), stream));
@@ -262,8 +258,7 @@ h2w_chipbatch *h2w_chipbatch_new_hash(int op, const h2w_poseidon_consts_t *const
     c->hp = HashParams{op, op == H2W_OP_GL_PERMUTE ? 0 : op == H2W_OP_BN_PERMUTE ? 1 : hash_mode, n_in, depth, cap_height};
     c->o = operand_layout(c->hp); c->bn = c->hp.mode == 1; c->small_mds = glp_small_mds(*consts) ? 1 : 0;
     h->op = op; h->L = lookup_bits; h->device = device_id; h->nw = (int)c->o.nw; h->P = fr_params_init();
-    std::vector<fr_t> inv(2 * INV_TAB, fr_zero());      // Assigned::Rational(1, x) of is_zero (the cap lookup's indicator)
-    for (int k2 = 1; k2 < INV_TAB; k2++) { inv[k2] = fr_inv(fr_from_u64((uint64_t)k2), h->P); inv[INV_TAB + k2] = fr_neg(inv[k2]); }
+    const std::vector<fr_t> inv = inverse_table(h->P);      // Assigned::Rational(1, x) of is_zero (the cap lookup's indicator)
     HashLayoutSink ls; ls.tt = &h->tt;
     {   // layout of one instance: replay on harmless operands (all zero: in every field, index 0)
         ValBackend<HashLayoutSink> be(ls, chiphash_cfg(c->hp.mode, lookup_bits, h->P, inv.data(), false), false);
@@ -275,28 +270,9 @@ h2w_chipbatch *h2w_chipbatch_new_hash(int op, const h2w_poseidon_consts_t *const
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { h->device = -1; return h; }      // layout queries still work; h2w_chipbatch_run fails
     if (device_id < 0 || device_id >= ndev) { set_error("h2w_chipbatch_new_hash: device_id out of range"); h->device = -1; h2w_chipbatch_free(h); return nullptr; }
     DeviceGuard dg(device_id);
-    auto up = [&]() -> int {
-        if (h->dt.upload(h->tt) != 0) return -1;
-        H2W_HIP(hipMalloc((void **)&h->d_meta, (h->nrec ? h->nrec : 1) * sizeof(uint64_t)));
-        if (h->nrec) H2W_HIP(hipMemcpy(h->d_meta, ls.meta.data(), h->nrec * sizeof(uint64_t), hipMemcpyHostToDevice));
-        std::vector<uint16_t> nc(T_MAX, 0); for (size_t i = 0; i < h->tt.info.size(); i++) nc[i] = h->tt.info[i].ncells;
-        H2W_HIP(hipMalloc((void **)&h->d_tmpl_cells, nc.size() * sizeof(uint16_t)));
-        H2W_HIP(hipMemcpy(h->d_tmpl_cells, nc.data(), nc.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-        H2W_HIP(hipMalloc((void **)&c->d_inv, inv.size() * sizeof(fr_t)));
-        H2W_HIP(hipMemcpy(c->d_inv, inv.data(), inv.size() * sizeof(fr_t), hipMemcpyHostToDevice));
-        if (c->bn) {    // PoseidonBN254 tables: canonical and R-premultiplied (bntab.h), as h2w_plan_compile builds them
-            std::vector<fr_t> tab(BK_ALL); bn_table_build(*consts, h->P, tab.data());
-            H2W_HIP(hipMalloc((void **)&c->d_bn_tab, tab.size() * sizeof(fr_t)));
-            H2W_HIP(hipMemcpy(c->d_bn_tab, tab.data(), tab.size() * sizeof(fr_t), hipMemcpyHostToDevice));
-        } else {        // the constants, and behind them the derived tables of the values phase (glptab.h glp_aux_tables)
-            std::vector<uint64_t> aux(GLP_AUX_WORDS); glp_aux_tables(*consts, aux.data());
-            H2W_HIP(hipMalloc((void **)&c->d_consts, sizeof(h2w_poseidon_consts_t) + aux.size() * sizeof(uint64_t)));
-            H2W_HIP(hipMemcpy(c->d_consts, consts, sizeof(h2w_poseidon_consts_t), hipMemcpyHostToDevice));
-            H2W_HIP(hipMemcpy(c->d_consts + 1, aux.data(), aux.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
-        }
-        return 0;
-    };
-    if (up() != 0) { h2w_chipbatch_free(h); return nullptr; }
+    // the tables of the op's hash: PoseidonBN254's, or the Goldilocks-Poseidon constants (handletabs.h)
+    if (h->dt.upload(h->tt) != 0 || h->d_meta.upload(ls.meta) != 0 || upload_tmpl_cells(h->d_tmpl_cells, h->tt) != 0 || c->d_inv.upload(inv) != 0 ||
+        (c->bn ? upload_bn_tab(c->d_bn_tab, *consts, h->P) : upload_glp_consts(c->d_consts, *consts)) != 0) { h2w_chipbatch_free(h); return nullptr; }
     return h;
 }
 

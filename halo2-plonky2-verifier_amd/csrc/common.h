@@ -4,14 +4,11 @@
 #include <string>
 #include <vector>
 #include "records.h"
+#include "devbuf.h"      // set_error, H2W_HIP, DevBuf
 
 namespace h2w {
 
-void set_error(const std::string &s);
 extern thread_local std::string g_last_error;
-
-#define H2W_HIP(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { \
-    h2w::set_error(std::string(#expr) + ": " + hipGetErrorString(_e)); return -1; } } while (0)
 
 // Makes `device` the calling thread's current HIP device for the lifetime of the guard (a caller that drives several GPUs from
 // one thread must not have to bracket every call with hipSetDevice); -1 = leave as is.  device_of: the device a pointer lives on.
@@ -80,7 +77,7 @@ constexpr int MAX_CONSTS = 96;
 
 // device copies of a TemplateTable
 struct DeviceTables {
-    uint32_t *slots = nullptr; tmpl_info_t *info = nullptr; fr_t *consts = nullptr;
+    DevBuf<uint32_t> slots; DevBuf<tmpl_info_t> info; DevBuf<fr_t> consts;
     uint32_t nslots = 0, ntmpl = 0, nconsts = 0, max_cells = 0; int rb = 0, L = 0;
     int upload(const TemplateTable &tt) {
         free();
@@ -88,19 +85,10 @@ struct DeviceTables {
         max_cells = 0; for (const tmpl_info_t &ti : tt.info) if (ti.ncells > max_cells) max_cells = ti.ncells;
         if (tt.slots.size() > MAX_SLOTS || tt.consts.size() > MAX_CONSTS || tt.info.size() > T_MAX) { set_error("template table too large"); return -1; }
         nslots = (uint32_t)tt.slots.size(); ntmpl = (uint32_t)tt.info.size(); nconsts = (uint32_t)tt.consts.size();
-        H2W_HIP(hipMalloc((void **)&slots, nslots * sizeof(uint32_t)));
-        H2W_HIP(hipMalloc((void **)&info, ntmpl * sizeof(tmpl_info_t)));
-        H2W_HIP(hipMalloc((void **)&consts, (nconsts ? nconsts : 1) * sizeof(fr_t)));
-        H2W_HIP(hipMemcpy(slots, tt.slots.data(), nslots * sizeof(uint32_t), hipMemcpyHostToDevice));
-        H2W_HIP(hipMemcpy(info, tt.info.data(), ntmpl * sizeof(tmpl_info_t), hipMemcpyHostToDevice));
-        if (nconsts) H2W_HIP(hipMemcpy(consts, tt.consts.data(), nconsts * sizeof(fr_t), hipMemcpyHostToDevice));
-        return 0;
+        return slots.upload(tt.slots) != 0 || info.upload(tt.info) != 0 || consts.upload(tt.consts) != 0 ? -1 : 0;
     }
-    void fill(ExpandArgs &A) const { A.slots = slots; A.nslots = nslots; A.info = info; A.ntmpl = ntmpl; A.consts = consts; A.nconsts = nconsts; A.max_cells = max_cells; A.rb = rb; A.lookup_bits = L; }
-    void free() {
-        if (slots) hipFree(slots); if (info) hipFree(info); if (consts) hipFree(consts);
-        slots = nullptr; info = nullptr; consts = nullptr;
-    }
+    void fill(ExpandArgs &A) const { A.slots = slots.get(); A.nslots = nslots; A.info = info.get(); A.ntmpl = ntmpl; A.consts = consts.get(); A.nconsts = nconsts; A.max_cells = max_cells; A.rb = rb; A.lookup_bits = L; }
+    void free() { slots.reset(); info.reset(); consts.reset(); }
 };
 
 }  // namespace h2w

@@ -42,7 +42,7 @@ struct h2w_ctx {
     struct Node { int parent; std::string name; uint64_t cells; std::vector<int> children; };
     std::vector<Node> nodes{Node{-1, "all", 0, {}}}; int cur = 0; std::vector<uint64_t> enter;
     // device side
-    void *d_out = nullptr, *d_meta = nullptr, *d_recs = nullptr, *d_pool = nullptr;
+    DevBuf<fr_t> d_out, d_pool; DevBuf<uint64_t> d_meta; DevBuf<rec_t> d_recs;
     DeviceTables dt;
     bool dt_ready = false; size_t dt_nslots = 0, dt_nconsts = 0, dt_ntmpl = 0;
     Trace *trace = nullptr;      // trace mode (h2w_ctx_trace_begin): the op tape of this run (trace.h)
@@ -217,12 +217,7 @@ h2w_ctx *h2w_ctx_new(int lookup_bits, int witness_gen_only, int device_id) {
 }
 void h2w_ctx_free(h2w_ctx *c) {
     if (!c) return;
-    DeviceGuard dg(c->d_out || c->d_meta || c->dt.slots ? c->device : -1);
-    if (c->d_out) hipFree(c->d_out);
-    if (c->d_meta) hipFree(c->d_meta);
-    if (c->d_recs) hipFree(c->d_recs);
-    if (c->d_pool) hipFree(c->d_pool);
-    c->dt.free();
+    DeviceGuard dg(c->d_out.get() || c->d_meta.get() || c->dt.slots.get() ? c->device : -1);
     delete c;
 }
 // The context as new, its host memory kept: the next proof's run appends into vectors that are already sized and mapped (a PoseidonBN254 proof streams 350 MB of
@@ -553,30 +548,19 @@ static int ensure_expanded(h2w_ctx *c) {
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(c, "h2w: no HIP device visible — the advice stream is only produced on the GPU (no CPU fallback)");
     if (c->device >= ndev) return fail(c, "h2w: device_id out of range");
     DeviceGuard dg(c->device);
-    if (c->d_out) { hipFree(c->d_out); c->d_out = nullptr; }
-    if (c->d_meta) { hipFree(c->d_meta); c->d_meta = nullptr; }
-    if (c->d_recs) { hipFree(c->d_recs); c->d_recs = nullptr; }
-    if (c->d_pool) { hipFree(c->d_pool); c->d_pool = nullptr; }
+    c->d_out.reset(); c->d_meta.reset(); c->d_recs.reset(); c->d_pool.reset();
     if (c->ncells == 0) return 0;
     if (!c->dt_ready || c->dt_nslots != c->tt.slots.size() || c->dt_nconsts != c->tt.consts.size() || c->dt_ntmpl != c->tt.info.size()) {
         if (c->dt.upload(c->tt) != 0) return fail(c, "h2w: template upload failed: " + g_last_error);
         c->dt_ready = true; c->dt_nslots = c->tt.slots.size(); c->dt_nconsts = c->tt.consts.size(); c->dt_ntmpl = c->tt.info.size();
     }
     size_t nrec = c->recs.size();
-    H2W_HIP(hipMalloc(&c->d_out, c->ncells * sizeof(fr_t)));
-    H2W_HIP(hipMalloc(&c->d_meta, nrec * sizeof(uint64_t)));
-    H2W_HIP(hipMalloc(&c->d_recs, nrec * sizeof(rec_t)));
-    H2W_HIP(hipMemcpy(c->d_meta, c->meta.data(), nrec * sizeof(uint64_t), hipMemcpyHostToDevice));
-    H2W_HIP(hipMemcpy(c->d_recs, c->recs.data(), nrec * sizeof(rec_t), hipMemcpyHostToDevice));
-    if (!c->pool.empty()) {
-        H2W_HIP(hipMalloc(&c->d_pool, c->pool.size() * sizeof(fr_t)));
-        H2W_HIP(hipMemcpy(c->d_pool, c->pool.data(), c->pool.size() * sizeof(fr_t), hipMemcpyHostToDevice));
-    }
+    if (c->d_out.alloc(c->ncells) != 0 || c->d_meta.upload(c->meta) != 0 || c->d_recs.upload(c->recs) != 0 || (!c->pool.empty() && c->d_pool.upload(c->pool) != 0)) return -1;
     ExpandArgs A;
-    A.meta = (const uint64_t *)c->d_meta; A.recs = (const rec_t *)c->d_recs; A.nrec = nrec; A.rec_stride = nrec;
-    A.out = (fr_t *)c->d_out; A.cell_stride = c->ncells; A.pool = (const fr_t *)c->d_pool;
+    A.meta = c->d_meta.get(); A.recs = c->d_recs.get(); A.nrec = nrec; A.rec_stride = nrec;
+    A.out = c->d_out.get(); A.cell_stride = c->ncells; A.pool = c->d_pool.get();
     c->dt.fill(A); A.rb = c->tt.rb;
-    A.tile_ctr = nullptr; A.cm.starts = nullptr; A.cm.ncols = 0; A.cm.k = 0; expand_unsharded(A);
+    A.tile_ctr = nullptr; A.cm = flat_cols(); expand_unsharded(A);
     if (launch_expand(A, 1, 2048, nullptr) != 0) return -1;
     H2W_HIP(hipGetLastError());
     H2W_HIP(hipDeviceSynchronize());
@@ -585,7 +569,7 @@ static int ensure_expanded(h2w_ctx *c) {
 int h2w_ctx_advice_device(h2w_ctx *c, void **dev_ptr) {
     if (!check(c, "h2w_ctx_advice_device")) return -1;
     if (ensure_expanded(c) != 0) return -1;
-    *dev_ptr = c->d_out; return 0;
+    *dev_ptr = c->d_out.get(); return 0;
 }
 int h2w_ctx_download(h2w_ctx *c, uint64_t first, uint64_t count, h2w_fr_t *host_dst) {
     if (!check(c, "h2w_ctx_download")) return -1;
@@ -593,7 +577,7 @@ int h2w_ctx_download(h2w_ctx *c, uint64_t first, uint64_t count, h2w_fr_t *host_
     if (ensure_expanded(c) != 0) return -1;
     if (count == 0) return 0;
     DeviceGuard dg(c->device);
-    H2W_HIP(hipMemcpy(host_dst, (const fr_t *)c->d_out + first, count * sizeof(fr_t), hipMemcpyDeviceToHost));
+    H2W_HIP(hipMemcpy(host_dst, c->d_out.get() + first, count * sizeof(fr_t), hipMemcpyDeviceToHost));
     return 0;
 }
 

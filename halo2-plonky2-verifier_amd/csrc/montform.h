@@ -1,7 +1,7 @@
 // montform.h — canonical cell -> Montgomery form of BN254 Fr (halo2curves bn256::Fr in memory: v * 2^256 mod r), by the WIDTH of v.
 //
 // The expansion kernel's cells are bit-fields of values below 2^128 (expand.hip); a full 254 x 254-bit Montgomery product per cell is
-// what a second pass pays (batch.hip k_to_montgomery), not what they need.  Route for a value of N 32-bit words w_0 .. w_{N-1}:
+// what a second pass pays (advicetools.hip k_to_montgomery), not what they need.  Route for a value of N 32-bit words w_0 .. w_{N-1}:
 //     S = sum_i w_i * C_i,   C_i = 2^(256 + 32 i) mod r            N rows of eight 32 x 32-bit multiply-adds; S <= (2^32 - 1) sum_i C_i, nine words: up to
 //                                                                  N = 4 because S < 4 2^32 r < 2^288, for N = 8 because C_0 + .. + C_7 < 2^256 for this r
 //                                                                  (montform_init checks it; montform_check.cpp runs the all-ones input)
@@ -121,5 +121,8 @@ inline void montform_init(MontForm &K, int rb) {
     uint32_t x[8]; mf_host_pow2(256 + rb, x); uint64_t bw = 0;
     for (int j = 0; j < 8; j++) { const uint64_t d = (uint64_t)mf_r(j) - x[j] - bw; K.neg_rb[j] = (uint32_t)d; bw = (d >> 32) & 1; }
 }
+// 2^(256 + 261) mod r: the device product divides by 2^261, so a product with this constant is the Montgomery form with R = 2^256 (the full-product
+// passes: batch.hip k_direct_to_montgomery, advicetools.hip k_to_montgomery)
+inline const fr_t &mont_k() { static const fr_t K = [] { fr_t x = fr_from_u64(1); for (int i = 0; i < 256 + FR_MONT_BITS; i++) x = fr_add(x, x); return x; }(); return K; }
 
 }  // namespace h2w

@@ -1,28 +1,30 @@
-// plan.h — the plan handle of API level 3 (include/h2w.h): a compiled shape (batch.hip h2w_plan_compile) or a traced run (replay.hip h2w_plan_from_trace).
+// plan.h — the plan handle of API level 3 (include/h2w.h): a compiled shape (plancompile.cpp h2w_plan_compile) or a traced run (replay.hip h2w_plan_from_trace).
+// Every device table of the handle is a DevBuf (devbuf.h): h2w_plan_free sets the device and deletes the handle.
 #pragma once
 #include "common.h"
 #include "batchargs.h"
 #include "montform.h"
+#include "handletabs.h"
 
 namespace h2w {
 struct TracedPlan;
 struct ShardSpec { int rank = 0, world = 1, compact = 0; };
 }
-using namespace h2w;      // (included by batch.hip and replay.hip only, which live in that namespace's vocabulary)
+using namespace h2w;      // (included by the plan's units only - plancompile.cpp, batch.hip, advicetools.hip, replay.hip -, which live in that namespace's vocabulary)
 struct h2w_plan {
     h2w_shape_t shape; int device;
     TemplateTable tt; DeviceTables dt; StrandTable st; FrParams P;
     Derived d; ProofLayout pl;
     uint64_t nrec = 0, ncells = 0, rec_cells = 0;
-    LoadItem *d_items = nullptr; uint32_t n_items = 0, n_cap_items = 0; uint64_t load_nrec = 0, load_ncell = 0;      // d_items: the load phase's items, then the cap hashes'
+    DevBuf<LoadItem> d_items; uint32_t n_items = 0, n_cap_items = 0; uint64_t load_nrec = 0, load_ncell = 0;      // d_items: the load phase's items, then the cap hashes'
     h2w_poseidon_consts_t h_consts;                       // host copy (keygen-metadata replay)
-    bool meta_ready = false; std::vector<uint8_t> sel_bits, lk_bits; uint64_t n_gates = 0, n_lookups = 0; uint32_t *d_lookup_cells = nullptr; uint8_t *d_sel_bits = nullptr;
-    uint64_t *d_col_tab = nullptr; std::vector<uint64_t> h_col_tab; int col_k = -1;     // column-major emission: [starts | lens] of the last break-point set
+    bool meta_ready = false; std::vector<uint8_t> sel_bits, lk_bits; uint64_t n_gates = 0, n_lookups = 0; DevBuf<uint32_t> d_lookup_cells; DevBuf<uint8_t> d_sel_bits;
+    DevBuf<uint64_t> d_col_tab; std::vector<uint64_t> h_col_tab; int col_k = -1;     // column-major emission: [starts | lens] of the last break-point set
     PlanEqualities eqs;
-    fr_t *d_bn_tab = nullptr; uint32_t *d_bn_tab9 = nullptr; FriTab *d_fri = nullptr; uint64_t nunit = 0; rf::RowConst *d_rowk = nullptr;     // PoseidonBN254 tables of this plan (coop.h bn_table_build)
-    StrandTable *d_st = nullptr;                      // device copy of st
+    DevBuf<fr_t> d_bn_tab; DevBuf<uint32_t> d_bn_tab9; DevBuf<FriTab> d_fri; uint64_t nunit = 0; DevBuf<rf::RowConst> d_rowk;     // PoseidonBN254 tables of this plan (handletabs.h upload_bn_tab)
+    DevBuf<StrandTable> d_st;                         // device copy of st
     bool small_mds = false;                           // Goldilocks-Poseidon MDS entries are tiny (coop.h glp_small_mds)
-    uint64_t *d_meta = nullptr; h2w_poseidon_consts_t *d_consts = nullptr; uint16_t *d_ncells = nullptr; fr_t *d_inv = nullptr;
+    DevBuf<uint64_t> d_meta; DevBuf<GlpConsts> d_consts; DevBuf<uint16_t> d_ncells; DevBuf<fr_t> d_inv;
     static constexpr int EV_RING = 64, N_SIDE = 16;
     // event slots of a call: slot i < H2W_EV_COUNT is the public H2W_EV_* i (include/h2w.h: call start / end, prologue block complete, glue (+ Goldilocks
     // Merkle strands) start / end, chain kernels start / end, expansion start / end), then the internal ones
@@ -34,14 +36,15 @@ struct h2w_plan {
     int serial_expand = 1;           // H2W_OPT_SERIAL_EXPAND: the expansion kernel of a call waits for the previous call's
     // H2W_OPT_OUTPUT_FORM.  The shape compiler marks the cells of a proof's stream that value kernels write themselves (one bit per cell, padded to whole
     // 64-word rows for k_direct_to_montgomery); the Montgomery form's constants and the bitmap go to the device when the form is first selected.
-    int output_form = 0; std::vector<uint64_t> direct_bits, h_meta; uint64_t n_direct = 0; uint64_t *d_direct_bits = nullptr; MontForm *d_mont = nullptr;
+    int output_form = 0; std::vector<uint64_t> direct_bits, h_meta; uint64_t n_direct = 0; DevBuf<uint64_t> d_direct_bits; DevBuf<MontForm> d_mont;
     bool fork_chains = true;         // of their own batch (they share only the prologue): one side stream per caller stream seen (created on demand)
     hipEvent_t *ev = evr[0]; uint64_t n_batches = 0; bool ev_ready = false, ev_recorded = false;
     h2w::TracedPlan *traced = nullptr;      // set: the plan replays a recorded tape (replay.hip); the strand tables above are unused
     explicit h2w_plan(int L) : tt(L) {}
 };
+extern "C" int h2w_plan_metadata(h2w_plan *pl);      // plancompile.cpp: the keygen-metadata replay, once per plan (the selector / lookup queries and advicetools.hip call it)
 namespace h2w {
-// The expansion launch of a plan's call (batch.hip run_batch, h2w_fri_expand_records; replay.hip traced_run): records[n_proofs][p->nrec] -> cells
+// The expansion launch of a plan's call (batch.hip: run_batch, h2w_fri_expand_records; replay.hip traced_run): records[n_proofs][p->nrec] -> cells
 // out[n_proofs][cell_stride] through cm.  sh: the (proof, query) sharding of the record ranges; null: every proof is one block (a traced plan has
 // no strand table).  tile_ctr: n_proofs words of workspace, zeroed here.  roam_per_cu: ExpandArgs.
 int launch_plan_expand(const h2w_plan *p, uint64_t n_proofs, const rec_t *recs, uint32_t *tile_ctr, fr_t *out, uint64_t cell_stride, ColMap cm,

@@ -27,6 +27,7 @@ HD void g_store_rec(rec_t *p, uint64_t a, uint64_t b, uint64_t c, uint64_t d) {
 // a cell i lives at (c << k) + (i - starts[c]) for the LAST column c with starts[c] <= i; a fix-up kernel repeats the boundary cells
 // in the previous column and zero-fills the unused rows.  starts == nullptr: flat layout.
 struct ColMap { const uint64_t *starts; uint32_t ncols, k; };
+HD ColMap flat_cols() { return ColMap{nullptr, 0, 0}; }
 struct ColRange { uint64_t lo, hi, delta; };
 // rare (once per column a strand enters): kept out of line - and OUT OF THE CURSOR: as a member function it took the cursor's address, which put
 // the cursor of every column-layout kernel on the stack (each of its reads a flat load behind the record stores)

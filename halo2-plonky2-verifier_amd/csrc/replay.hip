@@ -62,17 +62,17 @@ template <bool BN> using ReplayArgsT = typename ReplayArgsSel<BN>::type;
 
 struct TracedPlan {
     std::vector<TmplD> tmpls; uint64_t total_slot_lanes = 0;      // sum over templates of nslots * ninst: u64 elements of the value store per proof
-    TmplD *d_tm = nullptr; uint64_t *d_prefix = nullptr; uint32_t npool64 = 0, npoolfr = 0;
-    uint32_t *d_tape = nullptr; InstD *d_insts = nullptr; ImpD *d_imps = nullptr; uint32_t *d_inputs = nullptr; uint64_t *d_pool64 = nullptr; fr_t *d_poolfr = nullptr;
+    DevBuf<TmplD> d_tm; DevBuf<uint64_t> d_prefix; uint32_t npool64 = 0, npoolfr = 0;
+    DevBuf<uint32_t> d_tape; DevBuf<InstD> d_insts; DevBuf<ImpD> d_imps; DevBuf<uint32_t> d_inputs; DevBuf<uint64_t> d_pool64; DevBuf<fr_t> d_poolfr;
     uint64_t n_ops = 0, n_segments = 0;
     // fused Goldilocks-Poseidon permutations: per proof nglp list entries (entry e belongs to shard unit h_glp_unit[e], NO_SLOT: the root's block)
-    uint32_t nglp = 0; uint64_t n_candidates = 0; std::vector<uint32_t> h_glp_unit; uint32_t *d_glp_unit = nullptr;
+    uint32_t nglp = 0; uint64_t n_candidates = 0; std::vector<uint32_t> h_glp_unit; DevBuf<uint32_t> d_glp_unit;
     // fused PoseidonBN254 permutations: per proof nbnp list entries; items: the (proof, entry) pairs of this rank's blocks (sharded calls, beside the lane table)
-    bool bn_flag = false; uint32_t nbnp = 0; uint64_t n_bn_left = 0; std::vector<BnpD> h_bnp; BnpD *d_bnp = nullptr; std::vector<uint32_t> h_bnp0; uint32_t *d_bnp0 = nullptr, *d_bn_items = nullptr; uint64_t n_bn_items = 0;
+    bool bn_flag = false; uint32_t nbnp = 0; uint64_t n_bn_left = 0; std::vector<BnpD> h_bnp; DevBuf<BnpD> d_bnp; std::vector<uint32_t> h_bnp0; DevBuf<uint32_t> d_bnp0, d_bn_items; uint64_t n_bn_items = 0;
     hipEvent_t tev[16]; int n_tev = 0, tev_used = 0; bool timing = false;      // h2w_plan_trace_timing: around every kernel of the last call
     // sharding: the depth-1 instances are the units (query q = the q-th in tape order); why_unshardable empty: they tile the stream behind the root's block
     std::string why_unshardable; std::vector<uint32_t> h_unit;      // h_unit: the unit of every instance (InstD order)
-    std::vector<uint32_t> h_lanes, lane0; uint32_t *d_lanes = nullptr; uint64_t lanes_n = 0; int lanes_rank = -1, lanes_world = 0;      // the lane table of the last (n, rank, world)
+    std::vector<uint32_t> h_lanes, lane0; DevBuf<uint32_t> d_lanes; uint64_t lanes_n = 0; int lanes_rank = -1, lanes_world = 0;      // the lane table of the last (n, rank, world)
 };
 
 // ------------------------------------------------------------------------------------------------------------------- device
@@ -369,11 +369,6 @@ uint64_t traced_workspace_bytes(const h2w_plan *p, uint64_t n) { return traced_w
 uint64_t traced_status_offset(const h2w_plan *p, uint64_t n, bool flags) { const TracedWs w = traced_ws(p, n); return flags ? w.lflag : w.status; }
 void traced_free(h2w_plan *p) {
     TracedPlan *t = p->traced; if (!t) return;
-    if (t->d_tm) (void)hipFree(t->d_tm); if (t->d_prefix) (void)hipFree(t->d_prefix);
-    if (t->d_tape) (void)hipFree(t->d_tape); if (t->d_insts) (void)hipFree(t->d_insts); if (t->d_imps) (void)hipFree(t->d_imps);
-    if (t->d_inputs) (void)hipFree(t->d_inputs); if (t->d_pool64) (void)hipFree(t->d_pool64); if (t->d_poolfr) (void)hipFree(t->d_poolfr);
-    if (t->d_lanes) (void)hipFree(t->d_lanes); if (t->d_glp_unit) (void)hipFree(t->d_glp_unit);
-    if (t->d_bnp) (void)hipFree(t->d_bnp); if (t->d_bnp0) (void)hipFree(t->d_bnp0); if (t->d_bn_items) (void)hipFree(t->d_bn_items);
     for (int i = 0; i < t->n_tev; i++) (void)hipEventDestroy(t->tev[i]);
     delete t; p->traced = nullptr;
 }
@@ -382,7 +377,7 @@ void traced_free(h2w_plan *p) {
 // template only the (proof, instance) pairs whose unit (proof * nq + q) % world == rank (h2w_plan_shard_block, distributed.py unit_owner).
 static int lane_table(h2w_plan *p, uint64_t n, const ShardSpec &sh) {
     TracedPlan *t = p->traced;
-    if (t->d_lanes && t->lanes_n == n && t->lanes_rank == sh.rank && t->lanes_world == sh.world) return 0;
+    if (t->d_lanes.get() && t->lanes_n == n && t->lanes_rank == sh.rank && t->lanes_world == sh.world) return 0;
     const uint64_t W = (uint64_t)sh.world, r = (uint64_t)sh.rank, nq = (uint64_t)p->shape.num_queries;
     std::vector<uint32_t> &L = t->h_lanes; L.clear(); t->lane0.assign(t->tmpls.size() + 1, 0);
     for (size_t i = 0; i < t->tmpls.size(); i++) {
@@ -409,12 +404,8 @@ static int lane_table(h2w_plan *p, uint64_t n, const ShardSpec &sh) {
             }
     }
     H2W_HIP(hipDeviceSynchronize());      // a previous call may still read the old table (plans are single-threaded handles, include/h2w.h)
-    if (t->d_bn_items) { (void)hipFree(t->d_bn_items); t->d_bn_items = nullptr; }
-    t->n_bn_items = items.size();
-    if (t->nbnp) { H2W_HIP(hipMalloc((void **)&t->d_bn_items, (items.empty() ? 1 : items.size()) * 4)); if (!items.empty()) H2W_HIP(hipMemcpy(t->d_bn_items, items.data(), items.size() * 4, hipMemcpyHostToDevice)); }
-    if (t->d_lanes) { (void)hipFree(t->d_lanes); t->d_lanes = nullptr; }
-    H2W_HIP(hipMalloc((void **)&t->d_lanes, (L.empty() ? 1 : L.size()) * 4));
-    if (!L.empty()) H2W_HIP(hipMemcpy(t->d_lanes, L.data(), L.size() * 4, hipMemcpyHostToDevice));
+    t->d_lanes.reset(); t->d_bn_items.reset(); t->n_bn_items = items.size();      // (a failed upload leaves no lane table: the next call builds it again)
+    if ((t->nbnp && t->d_bn_items.upload(items) != 0) || t->d_lanes.upload(L) != 0) return -1;
     t->lanes_n = n; t->lanes_rank = sh.rank; t->lanes_world = sh.world;
     return 0;
 }
@@ -429,14 +420,14 @@ int traced_run(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void 
     hipStream_t stream = (hipStream_t)stream_;
     const TracedWs wl = traced_ws(p, n_proofs); char *ws = (char *)workspace_dev;
     ReplayArgs R; memset(&R, 0, sizeof(R));
-    R.tape = t->d_tape; R.insts = t->d_insts; R.imps = t->d_imps; R.inputs = t->d_inputs; R.pool64 = t->d_pool64; R.poolfr = t->d_poolfr;
+    R.tape = t->d_tape.get(); R.insts = t->d_insts.get(); R.imps = t->d_imps.get(); R.inputs = t->d_inputs.get(); R.pool64 = t->d_pool64.get(); R.poolfr = t->d_poolfr.get();
     R.proofs = proofs_dev; R.proof_words = p->pl.total; R.recs = (rec_t *)(ws + wl.recs); R.rec_stride = p->nrec; R.out = (fr_t *)advice_dev; R.cell_stride = cell_stride; R.cm = cm;      // (cm.starts: the FlexGate columns of every proof, cell_stride = ncols << k; else the flat stream)
-    R.vals = (uint64_t *)(ws + wl.vals); R.status = (uint32_t *)(ws + wl.status); R.ncells = p->d_ncells; R.inv_pos = p->d_inv; R.inv_neg = p->d_inv + INV_TAB; R.P = p->P; R.L = p->shape.lookup_bits;
+    R.vals = (uint64_t *)(ws + wl.vals); R.status = (uint32_t *)(ws + wl.status); R.ncells = p->d_ncells.get(); R.inv_pos = p->d_inv.get(); R.inv_neg = p->d_inv.get() + INV_TAB; R.P = p->P; R.L = p->shape.lookup_bits;
     R.nproofs = (uint32_t)n_proofs; R.lflag = (uint32_t *)(ws + wl.lflag);
-    R.glk = reinterpret_cast<const uint64_t *>(p->d_consts); R.glist = (uint64_t *)(ws + wl.glist); R.nglp = t->nglp;
-    R.ntmpl = (uint32_t)t->tmpls.size(); R.tm = t->d_tm; R.prefix = t->d_prefix; R.npool64 = t->npool64; R.npoolfr = t->npoolfr;
+    R.glk = reinterpret_cast<const uint64_t *>(p->d_consts.get()); R.glist = (uint64_t *)(ws + wl.glist); R.nglp = t->nglp;
+    R.ntmpl = (uint32_t)t->tmpls.size(); R.tm = t->d_tm.get(); R.prefix = t->d_prefix.get(); R.npool64 = t->npool64; R.npoolfr = t->npoolfr;
     if (sharded) {
-        R.lanes = t->d_lanes; for (size_t i = 0; i < t->lane0.size(); i++) R.lane0[i] = t->lane0[i];
+        R.lanes = t->d_lanes.get(); for (size_t i = 0; i < t->lane0.size(); i++) R.lane0[i] = t->lane0[i];
         R.sh_world = (uint32_t)sh.world; R.sh_rank = (uint32_t)sh.rank; R.sh_compact = (uint32_t)sh.compact; R.nq = (uint32_t)p->shape.num_queries;
         R.pro_ncell = p->st.pro_ncell; R.q_slot = std::max(p->st.q_ncell[0], p->st.q_ncell[1]);
     }
@@ -454,13 +445,13 @@ int traced_run(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void 
         R.blk0[t->tmpls.size()] = nb; R.depth = d;
         if (t->timing && t->tev_used < 12) H2W_HIP(hipEventRecord(t->tev[t->tev_used++], stream));
         if (nb && t->nbnp) {
-            ReplayArgsT<true> RB; static_cast<ReplayArgs &>(RB) = R; RB.bnk = p->d_bn_tab + BK_T; RB.blist = blist; RB.bnp0 = t->d_bnp0; RB.nbnp = t->nbnp;
+            ReplayArgsT<true> RB; static_cast<ReplayArgs &>(RB) = R; RB.bnk = p->d_bn_tab.get() + BK_T; RB.blist = blist; RB.bnp0 = t->d_bnp0.get(); RB.nbnp = t->nbnp;
             hipLaunchKernelGGL(k_replay<true>, dim3(nb), dim3(64), 0, stream, RB);
         } else if (nb) hipLaunchKernelGGL(k_replay<false>, dim3(nb), dim3(64), 0, stream, R);
     }
     if (t->timing) H2W_HIP(hipEventRecord(t->tev[t->tev_used++], stream));
     if (t->nglp) {      // the records of the listed permutations, side by side
-        GlpEmitArgs E; E.consts = p->d_consts; E.list = R.glist; E.recs = R.recs; E.rec_stride = R.rec_stride; E.ncells = p->d_ncells; E.unit = t->d_glp_unit;
+        GlpEmitArgs E; E.consts = p->d_consts.get(); E.list = R.glist; E.recs = R.recs; E.rec_stride = R.rec_stride; E.ncells = p->d_ncells.get(); E.unit = t->d_glp_unit.get();
         E.nglp = t->nglp; E.world = sharded ? (uint32_t)sh.world : 1u; E.rank = (uint32_t)sh.rank; E.nq = (uint32_t)p->shape.num_queries;
         if ((uint64_t)n_proofs * t->nglp >= 0x7fffffffull) { set_error("h2w_fri_witness_batch: too many fused permutations in one call"); return -1; }
         hipLaunchKernelGGL(k_glp_emit_traced, dim3((uint32_t)(n_proofs * t->nglp)), dim3(64), 0, stream, E);
@@ -468,9 +459,9 @@ int traced_run(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void 
     if (t->timing && t->bn_flag) H2W_HIP(hipEventRecord(t->tev[t->tev_used++], stream));
     if (t->nbnp) {      // the cells of the listed PoseidonBN254 permutations, a quad each (direct cells: nothing of the expansion depends on them, nor they on it)
         BnEmitArgs E; memset(&E, 0, sizeof(E));
-        E.bn_tab = p->d_bn_tab; E.list = blist; E.bnp = t->d_bnp; E.nbnp = t->nbnp; E.out = R.out; E.cell_stride = cell_stride; E.cm = cm; E.P = p->P; E.status = R.status;
+        E.bn_tab = p->d_bn_tab.get(); E.list = blist; E.bnp = t->d_bnp.get(); E.nbnp = t->nbnp; E.out = R.out; E.cell_stride = cell_stride; E.cm = cm; E.P = p->P; E.status = R.status;
         if (sharded) {
-            E.items = t->d_bn_items; E.nitems = t->n_bn_items;
+            E.items = t->d_bn_items.get(); E.nitems = t->n_bn_items;
             E.sh_world = R.sh_world; E.sh_rank = R.sh_rank; E.sh_compact = R.sh_compact; E.nq = R.nq; E.pro_ncell = R.pro_ncell; E.q_slot = R.q_slot;
         } else { E.items = nullptr; E.nitems = (uint64_t)n_proofs * t->nbnp; }
         const uint64_t nblk = (E.nitems * 4 + QUAD_BLOCK - 1) / QUAD_BLOCK;
@@ -521,9 +512,11 @@ static h2w_plan *plan_from_trace(h2w_ctx *ctx, uint64_t proof_words, const char 
     tp->bn_flag = fusing_bn; tp->n_bn_left = F.n_bn_left;
 
     // ---- the plan handle
+    int ndev = 0; const bool on_device = hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0;      // (none: layout queries only)
+    if (on_device && (device_id < 0 || device_id >= ndev)) { set_error("h2w_plan_from_trace: device_id out of range"); delete tp; return nullptr; }
     h2w_plan *pl = new h2w_plan(L);
     memset(&pl->shape, 0, sizeof(pl->shape)); pl->shape.lookup_bits = L; pl->shape.num_queries = U.num_queries; pl->shape.hash_mode = 1;
-    pl->device = device_id; pl->P = fr_params_init(); memset(&pl->st, 0, sizeof(pl->st)); memset(&pl->pl, 0, sizeof(pl->pl)); memset(&pl->d, 0, sizeof(pl->d));
+    pl->device = on_device ? device_id : -1; pl->P = fr_params_init(); memset(&pl->st, 0, sizeof(pl->st)); memset(&pl->pl, 0, sizeof(pl->pl)); memset(&pl->d, 0, sizeof(pl->d));
     pl->pl.total = proof_words; pl->nrec = LP.nrec; pl->ncells = ncells; pl->traced = tp;
     if (consts) pl->h_consts = *consts;
     for (uint64_t m : LP.meta) pl->rec_cells += (uint64_t)pl->tt.ncells((int)meta_tmpl(m));
@@ -549,47 +542,20 @@ static h2w_plan *plan_from_trace(h2w_ctx *ctx, uint64_t proof_words, const char 
         }
         E.ready = true;
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { pl->device = -1; return pl; }      // layout queries only
-    if (device_id < 0 || device_id >= ndev) { set_error("h2w_plan_from_trace: device_id out of range"); h2w_plan_free(pl); return nullptr; }
+    if (!on_device) return pl;
     DeviceGuard dg(device_id);
-    auto up = [&]() -> int {
-        if (pl->dt.upload(pl->tt) != 0) return -1;
-        auto put = [&](void **d, const void *h, size_t bytes) -> int { H2W_HIP(hipMalloc(d, bytes ? bytes : 8)); if (bytes) H2W_HIP(hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice)); return 0; };
-        if (put((void **)&pl->d_meta, LP.meta.data(), LP.meta.size() * 8) != 0) return -1;
-        for (int k2 = 0; k2 < 16; k2++) LP.tape.push_back(DOP_END | (1u << 24));      // the interpreter reads a window ahead
-        if (put((void **)&tp->d_tape, LP.tape.data(), LP.tape.size() * 4) != 0) return -1;
-        std::vector<uint64_t> prefix(tp->tmpls.size()); uint64_t acc = 0;
-        for (size_t i = 0; i < tp->tmpls.size(); i++) { prefix[i] = acc; acc += (uint64_t)tp->tmpls[i].nslots * tp->tmpls[i].ninst; }
-        if (put((void **)&tp->d_tm, tp->tmpls.data(), tp->tmpls.size() * sizeof(TmplD)) != 0) return -1;
-        if (put((void **)&tp->d_prefix, prefix.data(), prefix.size() * 8) != 0) return -1;
-        if (put((void **)&tp->d_insts, LP.insts.data(), LP.insts.size() * sizeof(InstD)) != 0) return -1;
-        if (put((void **)&tp->d_imps, LP.imps.data(), LP.imps.size() * sizeof(ImpD)) != 0) return -1;
-        if (put((void **)&tp->d_inputs, LP.inputs.data(), LP.inputs.size() * 4) != 0) return -1;
-        tp->npool64 = (uint32_t)LP.pool64.size(); tp->npoolfr = (uint32_t)LP.poolfr.size();
-        if (put((void **)&tp->d_pool64, LP.pool64.data(), LP.pool64.size() * 8) != 0) return -1;
-        if (put((void **)&tp->d_poolfr, LP.poolfr.data(), LP.poolfr.size() * sizeof(fr_t)) != 0) return -1;
-        std::vector<uint16_t> nc(T_MAX, 0); for (size_t i = 0; i < pl->tt.info.size(); i++) nc[i] = pl->tt.info[i].ncells;
-        if (put((void **)&pl->d_ncells, nc.data(), nc.size() * 2) != 0) return -1;
-        std::vector<fr_t> inv(2 * INV_TAB, fr_zero());
-        for (int k2 = 1; k2 < INV_TAB; k2++) { inv[k2] = fr_inv(fr_from_u64((uint64_t)k2), pl->P); inv[INV_TAB + k2] = fr_neg(inv[k2]); }
-        if (put((void **)&pl->d_inv, inv.data(), inv.size() * sizeof(fr_t)) != 0) return -1;
-        if (tp->nglp) {      // the tables the fused permutations were verified on, the derived tables behind them (as h2w_plan_compile builds a compiled plan's)
-            std::vector<uint64_t> aux(GLP_AUX_WORDS); glp_aux_tables(*consts, aux.data());
-            H2W_HIP(hipMalloc((void **)&pl->d_consts, sizeof(h2w_poseidon_consts_t) + aux.size() * sizeof(uint64_t)));
-            H2W_HIP(hipMemcpy(pl->d_consts, consts, sizeof(h2w_poseidon_consts_t), hipMemcpyHostToDevice));
-            H2W_HIP(hipMemcpy(pl->d_consts + 1, aux.data(), aux.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
-            if (put((void **)&tp->d_glp_unit, tp->h_glp_unit.data(), tp->h_glp_unit.size() * 4) != 0) return -1;
-        }
-        if (tp->nbnp) {      // the PoseidonBN254 tables, canonical and times R (as h2w_plan_compile builds a compiled plan's); where every listed permutation lies
-            std::vector<fr_t> tab(BK_ALL); bn_table_build(*consts, pl->P, tab.data());
-            if (put((void **)&pl->d_bn_tab, tab.data(), tab.size() * sizeof(fr_t)) != 0) return -1;
-            if (put((void **)&tp->d_bnp, tp->h_bnp.data(), tp->h_bnp.size() * sizeof(BnpD)) != 0) return -1;
-            if (put((void **)&tp->d_bnp0, tp->h_bnp0.data(), tp->h_bnp0.size() * 4) != 0) return -1;
-        }
-        return 0;
-    };
-    if (up() != 0) { h2w_plan_free(pl); return nullptr; }
+    for (int k2 = 0; k2 < 16; k2++) LP.tape.push_back(DOP_END | (1u << 24));      // the interpreter reads a window ahead
+    std::vector<uint64_t> prefix(tp->tmpls.size()); uint64_t acc = 0;
+    for (size_t i = 0; i < tp->tmpls.size(); i++) { prefix[i] = acc; acc += (uint64_t)tp->tmpls[i].nslots * tp->tmpls[i].ninst; }
+    tp->npool64 = (uint32_t)LP.pool64.size(); tp->npoolfr = (uint32_t)LP.poolfr.size();
+    bool ok = pl->dt.upload(pl->tt) == 0 && pl->d_meta.upload(LP.meta) == 0 && tp->d_tape.upload(LP.tape) == 0 && tp->d_tm.upload(tp->tmpls) == 0 &&
+              tp->d_prefix.upload(prefix) == 0 && tp->d_insts.upload(LP.insts) == 0 && tp->d_imps.upload(LP.imps) == 0 && tp->d_inputs.upload(LP.inputs) == 0 &&
+              tp->d_pool64.upload(LP.pool64) == 0 && tp->d_poolfr.upload(LP.poolfr) == 0 && upload_tmpl_cells(pl->d_ncells, pl->tt) == 0 &&
+              pl->d_inv.upload(inverse_table(pl->P)) == 0;
+    // the tables the fused permutations were verified on (handletabs.h); which shard unit a listed permutation belongs to / where it lies
+    if (ok && tp->nglp) ok = upload_glp_consts(pl->d_consts, *consts) == 0 && tp->d_glp_unit.upload(tp->h_glp_unit) == 0;
+    if (ok && tp->nbnp) ok = upload_bn_tab(pl->d_bn_tab, *consts, pl->P) == 0 && tp->d_bnp.upload(tp->h_bnp) == 0 && tp->d_bnp0.upload(tp->h_bnp0) == 0;
+    if (!ok) { h2w_plan_free(pl); return nullptr; }
     return pl;
 }
 

@@ -80,7 +80,7 @@ struct LayoutSink : SinkBase {
 };
 static uint64_t glp_block_layout(const TemplateTable &tt, int L, const h2w_poseidon_consts_t *consts, std::vector<uint64_t> &meta) {
     LayoutSink sink; sink.meta = &meta; sink.tt = &tt;
-    ValCfg cfg; memset(&cfg, 0, sizeof(cfg)); cfg.L = L; cfg.P = fr_params_init();
+    ValCfg cfg{}; cfg.L = L; cfg.P = fr_params_init();
     ValBackend<LayoutSink> be(sink, cfg, true);
     PoseidonPermutationChip<ValBackend<LayoutSink>> pg(be, consts);
     uint64_t st[SPONGE_WIDTH] = {0}; pg.permute(st);
