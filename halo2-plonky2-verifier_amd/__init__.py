@@ -134,6 +134,7 @@ SYMBOLS = {
     "h2w_plan_from_trace_ex": (_vp, [_vp, C.c_uint64, C.POINTER(C.c_char_p), C.c_size_t, C.c_int, C.POINTER(PoseidonConsts), C.c_uint32]),
     "h2w_plan_trace_info": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
     "h2w_plan_trace_info_bn": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
+    "h2w_plan_trace_op_counts": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.c_size_t]),
     "h2w_plan_trace_timing": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_uint32]),
     "h2w_chip_ext_op": (C.c_int, [_vp, C.c_int, _av, _av, _av, _av]),
     "h2w_chip_gl_exp_from_bits_const_base": (C.c_int, [_vp, C.c_uint64, _av, C.c_size_t, _av]),

@@ -286,6 +286,16 @@ class Plan:
         _ck(self.L.h2w_plan_trace_info_bn(self.p, out), "h2w_plan_trace_info_bn")
         return dict(zip(("fused", "left", "list_entries"), (int(x) for x in out)))
 
+    def trace_op_counts(self):
+        """h2w_plan_trace_op_counts of a traced plan: [ops of each device op code (csrc/tapefmt.h DOP_*) ..., DOP_FETCH ops of each reference kind
+        (RK_LOCAL .. RK_LITFR) ..., the longest DOP_GLOPRUN], counted over the final tapes of all templates."""
+        n = self.L.h2w_plan_trace_op_counts(self.p, None, 0)
+        if n < 0:
+            raise H2WError("h2w_plan_trace_op_counts: " + last_error())
+        out = (C.c_uint64 * n)()
+        _ck(min(self.L.h2w_plan_trace_op_counts(self.p, out, n), 0), "h2w_plan_trace_op_counts")
+        return [int(x) for x in out]
+
     def trace_timing(self):
         """h2w_plan_trace_timing: ms of every kernel of the last call of a traced plan, in launch order (the first call switches the timing on: [])."""
         ms = (C.c_float * 16)()

@@ -65,6 +65,7 @@ struct TracedPlan {
     DevBuf<TmplD> d_tm; DevBuf<uint64_t> d_prefix; uint32_t npool64 = 0, npoolfr = 0;
     DevBuf<uint32_t> d_tape; DevBuf<InstD> d_insts; DevBuf<ImpD> d_imps; DevBuf<uint32_t> d_inputs; DevBuf<uint64_t> d_pool64; DevBuf<fr_t> d_poolfr;
     uint64_t n_ops = 0, n_segments = 0;
+    std::vector<uint64_t> op_counts;      // tape_op_counts over the templates' tapes (h2w_plan_trace_op_counts)
     // fused Goldilocks-Poseidon permutations: per proof nglp list entries (entry e belongs to shard unit h_glp_unit[e], NO_SLOT: the root's block)
     uint32_t nglp = 0; uint64_t n_candidates = 0; std::vector<uint32_t> h_glp_unit; DevBuf<uint32_t> d_glp_unit;
     // fused PoseidonBN254 permutations: per proof nbnp list entries; items: the (proof, entry) pairs of this rank's blocks (sharded calls, beside the lane table)
@@ -200,6 +201,8 @@ template <bool BN> __global__ __launch_bounds__(64) __attribute__((flatten)) voi
                 continue;
             }
         }
+        // Every case reads ALL its operands (into registers, ta / tb) before its first st1 / putfr: the lowering lets an op's result slots alias the ring
+        // slots of its fetched operands (tracelower.cpp bounds the fetched slots alone by RING_K; tape_check the same).  A case that stores before its last read breaks that.
         switch (op) {
             case DOP_SKIP: { const uint64_t nr = ((uint64_t)w2 << 32) | w1, nc = ((uint64_t)w4 << 32) | w3; sink.skip(nr, nc); break; }
             case DOP_CONST1: { const uint64_t v = get64(w1, 0); sink.rec(T_CONST1, v, 0, 0, 0); put64(w2, v); break; }
@@ -236,7 +239,7 @@ template <bool BN> __global__ __launch_bounds__(64) __attribute__((flatten)) voi
             case DOP_NUM2BITS: { be.num_to_bits(get64(w1, 0), (int)n, ta); const uint32_t o = w2; for (uint32_t i = 0; i < n; i++) st1(o + i, ta[i]); break; }
             case DOP_BITS2NUM: { for (uint32_t i = 0; i < n; i++) ta[i] = get64(tw(tape, pc + 1 + i), 0); put64(tw(tape, pc + 1 + n), be.bits_to_num(ta, (int)n)); break; }
             case DOP_DECOMP565: { be.decompose_le_56_5(getfr(w1), ta); const uint32_t o = w2; for (int i = 0; i < 5; i++) st1(o + i, ta[i]); break; }
-            case DOP_LIMBS2NUM: { for (uint32_t i = 0; i < n; i++) ta[i] = get64(tw(tape, pc + 1 + i), 0); putfr(tw(tape, pc + 1 + n), be.limbs_to_num(ta, (int)n)); break; }
+            case DOP_LIMBS2NUM: { for (uint32_t i = 0; i < n; i++) ta[i] = get64(tw(tape, pc + 1 + i), 0); putfr(tw(tape, pc + 1 + n), n == 4 ? be.limbs_to_num4(ta) : be.limbs_to_num(ta, (int)n)); break; }
             case DOP_RANGE: { be.range_check(get64(w1, 0), (int)aux); break; }
             case DOP_GLOPRUN: {      // the Goldilocks-level ops of a gadget come in runs (a Poseidon round: hash/poseidon/permutation.rs:43-239): no dispatch between them, the next op's words requested before this one is computed
                 uint32_t q = pc + 2; uint32_t a = w2, b = w3, c = w4, o = tw(tape, pc + 5);
@@ -504,12 +507,15 @@ static h2w_plan *plan_from_trace(h2w_ctx *ctx, uint64_t proof_words, const char 
         err = tape_check(LP.tape.data() + t0, t1 - t0, M);
         if (!err.empty()) { set_error("h2w_plan_from_trace: " + err); return nullptr; }
     }
+    std::vector<uint64_t> op_counts(TAPE_COUNTS, 0);      // h2w_plan_trace_op_counts: over every template's final tape
+    for (size_t t = 0; t < LP.tmpls.size(); t++) { const size_t t0 = LP.tmpls[t].tape0, t1 = t + 1 < LP.tmpls.size() ? LP.tmpls[t + 1].tape0 : LP.tape.size(); tape_op_counts(LP.tape.data() + t0, t1 - t0, op_counts.data()); }
     for (uint32_t w : LP.inputs) if (w >= proof_words) { set_error("h2w_plan_from_trace: an input tag beyond proof_words"); return nullptr; }
     for (const BnpD &b : LP.bnp) if (b.cell0 + (uint64_t)BN_PERM_CELLS > ncells) { set_error("h2w_plan_from_trace_ex: internal: a fused permutation's cells lie beyond the stream"); return nullptr; }
     TracedPlan *tp = new TracedPlan();
     tp->tmpls = LP.tmpls; tp->total_slot_lanes = LP.total_slot_lanes; tp->h_unit = LP.unit; tp->nglp = LP.nglp; tp->h_glp_unit = LP.glp_unit; tp->nbnp = LP.nbnp; tp->h_bnp = LP.bnp; tp->h_bnp0 = LP.bnp0;
     tp->n_ops = tr->ops.size(); tp->n_segments = LP.n_segments; tp->why_unshardable = U.why_unshardable; tp->n_candidates = F.n_candidates;
     tp->bn_flag = fusing_bn; tp->n_bn_left = F.n_bn_left;
+    tp->op_counts.swap(op_counts);
 
     // ---- the plan handle
     int ndev = 0; const bool on_device = hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0;      // (none: layout queries only)
@@ -571,6 +577,13 @@ extern "C" int h2w_plan_trace_info(const h2w_plan *p, uint64_t out[6]) {
     const TracedPlan *t = p->traced;
     out[0] = t->n_ops; out[1] = t->n_segments; out[2] = t->tmpls.size(); out[3] = t->nglp; out[4] = t->n_candidates; out[5] = t->nglp;
     return 0;
+}
+extern "C" int h2w_plan_trace_op_counts(const h2w_plan *p, uint64_t *out, size_t n_out) {
+    if (!p || (!out && n_out)) { set_error("h2w_plan_trace_op_counts: null argument"); return -1; }
+    if (!p->traced) { set_error("h2w_plan_trace_op_counts: not a traced plan (h2w_plan_from_trace)"); return -1; }
+    const std::vector<uint64_t> &c = p->traced->op_counts;
+    for (size_t i = 0; i < n_out; i++) out[i] = i < c.size() ? c[i] : 0;
+    return (int)c.size();
 }
 extern "C" int h2w_plan_trace_info_bn(const h2w_plan *p, uint64_t out[3]) {
     if (!p || !out) { set_error("h2w_plan_trace_info_bn: null argument"); return -1; }

@@ -138,11 +138,13 @@ inline std::string tape_check(const uint32_t *T, size_t nwords, const TapeLimits
     };
     auto okout = [&](uint32_t slot, uint32_t nsl, bool no_slot_ok) { return slot == NO_SLOT ? no_slot_ok : (uint64_t)slot + nsl <= M.nslots; };
     size_t pc = 0; bool ended = false;
+    uint32_t fetched = 0;      // slots the DOP_FETCH ops in front of one op have written: beyond RING_K the later ones overwrite the earlier ones (slot mod RING_K) before the op reads them
     while (pc < nwords) {
         const uint32_t h = T[pc], op = h & 0xff, n = (h >> 8) & 0xff, len = op == DOP_GLOPRUN ? 2 + 4 * n : h >> 24; bool ok = len >= 1 && pc + len <= nwords;
         if (op == DOP_END) { ended = ok && pc + 1 == nwords; break; }
         const uint32_t *R = T + pc;
-        if (ok && op == DOP_FETCH) ok = len == 3 && n >= 1 && n <= 4 && okslow(R[1]) && (uint64_t)R[2] + n <= M.nslots;
+        fetched = op == DOP_FETCH ? fetched + n : 0;
+        if (ok && op == DOP_FETCH) ok = len == 3 && n >= 1 && n <= 4 && okslow(R[1]) && (uint64_t)R[2] + n <= M.nslots && fetched <= RING_K;
         else if (ok && op == DOP_GLOPRUN) {      // [hdr][cells][A, B, C, out slot | template << 24] x n
             ok = n >= 2;
             for (uint32_t k = 0; ok && k < n; k++) ok = okref(R[2 + 4 * k]) && okref(R[3 + 4 * k]) && okref(R[4 + 4 * k]) && (uint64_t)(R[5 + 4 * k] & 0xffffffu) + 1 <= M.nslots && (R[5 + 4 * k] >> 24) < T_DYNAMIC;
@@ -161,6 +163,21 @@ inline std::string tape_check(const uint32_t *T, size_t nwords, const TapeLimits
         pc += len;
     }
     return ended ? std::string() : std::string("internal: a device tape does not end");
+}
+
+// ---- what a tape holds (h2w_plan_trace_op_counts), counted on a tape that passed tape_check: out[op] for every op; out[DOP_COUNT + k]: the
+// DOP_FETCH ops whose ref is of kind k (RK_LOCAL .. RK_LITFR); out[DOP_COUNT + RK_RING]: the longest DOP_GLOPRUN (kept as a maximum, not summed)
+constexpr size_t TAPE_COUNTS = DOP_COUNT + RK_RING + 1;
+inline void tape_op_counts(const uint32_t *T, size_t nwords, uint64_t *out) {
+    for (size_t pc = 0; pc < nwords;) {
+        const uint32_t h = T[pc], op = h & 0xff, n = (h >> 8) & 0xff, len = op == DOP_GLOPRUN ? 2 + 4 * n : h >> 24;
+        if (op >= DOP_COUNT || len == 0 || pc + len > nwords) return;
+        out[op]++;
+        if (op == DOP_FETCH && ref_kind(T[pc + 1]) < RK_RING) out[DOP_COUNT + ref_kind(T[pc + 1])]++;
+        if (op == DOP_GLOPRUN && n > out[DOP_COUNT + RK_RING]) out[DOP_COUNT + RK_RING] = n;
+        if (op == DOP_END) return;
+        pc += len;
+    }
 }
 
 }  // namespace h2w

@@ -323,6 +323,13 @@ static void lower_pass(const Trace *tr, int L, TemplateTable &tt, const char *co
             auto words_of = [&](uint32_t r) { const int k = ref_kind(r); return (uint32_t)(k == RK_LITFR ? 4 : k == RK_INPUT ? (ref_width(r) == WFR ? 4 : 1) : SLOTS_OF[ref_width(r)]); };
             uint32_t temps = 0;
             for (;;) { uint32_t need = 0; for (uint32_t k2 = 0; k2 < count; k2++) { const uint32_t r = T[op_at + first + k2]; if (!in_lds(r, S.nslots + temps)) need += words_of(r); } if (need == temps) break; temps = need; }
+            // the ring is RING_K slots (slot mod RING_K): with more temporaries than that the later fetches overwrite the earlier ones before the op reads
+            // them.  (The op's own result slots may alias them: every op reads all its operands before it stores a result.)
+            if (temps > RING_K) {
+                bad((o.code == TR_SELECT_BY_INDICATOR ? std::string("select_by_indicator") : "trace op " + std::to_string((int)o.code) + " (device op " + std::to_string(T[op_at] & 0xff) + ")") + " with " + std::to_string(count) + " operands: " + std::to_string(temps) + " slots of them have to be fetched (values of an enclosing scope, values computed more than " +
+                    std::to_string(RING_K) + " slots earlier, proof words, far constants), more than the " + std::to_string(RING_K) + " value slots a lane keeps at hand");
+                break;
+            }
             std::vector<uint32_t> fetches; const uint32_t nf = S.nslots + temps; uint32_t tslot = S.nslots;
             for (uint32_t k2 = 0; k2 < count; k2++) {
                 const uint32_t r = T[op_at + first + k2]; const int k = ref_kind(r), w = ref_width(r); uint32_t fr2;

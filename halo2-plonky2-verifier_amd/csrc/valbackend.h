@@ -215,6 +215,16 @@ template <class Sink> struct ValBackend {
         for (int i = 1; i < n; i++) { acc.l[i] = in[i]; cell64(in[i]); sink.cell(fr_pow2(64 * i)); if (i + 1 < n) G(); cell(acc); }
         return acc;
     }
+    // four limbs (the interpreter of a traced plan only: the gadgets pass at most three): the 256-bit value may be r or more, and the inner product is
+    // in the field - three limbs are below 2^192 < r, the last partial sum is reduced.  A method of its own: the kernels that never call it keep their code.
+    HF Fr limbs_to_num4(const Gl *in) {
+        Fr acc = fr_zero(); acc.l[0] = in[0]; G(); cell64(in[0]);
+        for (int i = 1; i < 4; i++) {
+            if (i < 3) acc.l[i] = in[i]; else acc = h2w::fr_add(acc, h2w::fr_mul(fr_from_u64(in[3]), fr_pow2(192), cfg.P));
+            cell64(in[i]); sink.cell(fr_pow2(64 * i)); if (i < 3) G(); cell(acc);
+        }
+        return acc;
+    }
     HNI void decompose_le_56_5(const Fr &x, Gl *out) {     // RangeChip::decompose_le(x, 56, 5)
         for (int i = 0; i < 5; i++) out[i] = fr_bits(x, 56 * i, 56);
         G(); cell64(out[0]);

@@ -219,13 +219,24 @@ h2w_plan *h2w_plan_from_trace(h2w_ctx *, uint64_t proof_words, const char *const
  * h2w_plan_trace_info_bn: out = {fused PoseidonBN254 permutations, PoseidonBN254-shaped stretches left interpreted (other constants, an interior
  * value read outside, the zero-cell variant), list entries per proof}; h2w_plan_trace_info's counts stay the Goldilocks ones.
  * h2w_plan_trace_timing of a plan built with H2W_TRACE_FUSE_BN_PERMUTE reports one more kernel: the PoseidonBN254 emission, behind the Goldilocks
- * record kernel's slot and in front of the expansion (0 when nothing was fused). */
+ * record kernel's slot and in front of the expansion (0 when nothing was fused).
+ * h2w_plan_trace_op_counts: what the device program consists of, counted on the host when the plan was lowered, over the final tapes of all its
+ * templates: out[op] = how many ops of device op code `op` (csrc/tapefmt.h DOP_*: op < DOP_COUNT), then out[DOP_COUNT + k] = the DOP_FETCH ops whose
+ * operand is of reference kind k (RK_LOCAL .. RK_LITFR: a value of the lane more than 256 slots back, a value of an enclosing scope, a 64-bit
+ * constant beyond the 2,048 kept at hand, a proof word, a wide constant beyond the 472 kept at hand), then the longest DOP_GLOPRUN.  At most n_out
+ * entries are written (the rest of out is zeroed); returns how many there are, -1 on a plan that was not traced.
+ * One op's operands: an operand that is not at hand (above) is fetched into the lane's 256 value slots in front of the op.  An op whose fetched
+ * operands need more than 256 slots is refused by h2w_plan_from_trace, by name and with the count: in practice h2w_select_array_by_indicator /
+ * h2w_select_from_idx on 52 to 64 wide (four-word) entries, whose 4 n + n operand words cannot all be at hand - a traced PoseidonBN254 verifier
+ * with cap_height 6 (64 cap entries) is such a run; up to 51 wide entries (cap_height 5) replay, and so does any
+ * length up to 64 of one-word entries. */
 #define H2W_TRACE_FUSE_GL_PERMUTE 1
 #define H2W_TRACE_FUSE_BN_PERMUTE 2
 h2w_plan *h2w_plan_from_trace_ex(h2w_ctx *, uint64_t proof_words, const char *const *parallel_scopes, size_t n_scopes, int device_id,
                                  const h2w_poseidon_consts_t *consts, uint32_t flags);
 int h2w_plan_trace_info(const h2w_plan *, uint64_t out[6]);
 int h2w_plan_trace_info_bn(const h2w_plan *, uint64_t out[3]);
+int h2w_plan_trace_op_counts(const h2w_plan *, uint64_t *out, size_t n_out);
 int h2w_plan_trace_timing(h2w_plan *, float *ms, uint32_t cap);
 
 /* ------------------------------------------------------------------ advice hand-off (eager contexts) */

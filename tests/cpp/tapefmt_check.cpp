@@ -116,6 +116,17 @@ int main() {
     const size_t b_clt = B.op(DOP_CLT, 0, 0, {ring(399)});
     B.op(DOP_END, 0, 0, {});
     accept(B, M, "tape B");
+    // ---- tape C: the fetches in front of one op fill the ring exactly (RING_K slots: 64 four-word fetches); the op between two such stretches starts the count anew
+    Tape C;
+    for (uint32_t i = 0; i < 64; i++) C.op(DOP_FETCH, 4, 0, {mkref(RK_IMPORT, WFR, 1), 4 * i});
+    std::vector<uint32_t> wsel; for (uint32_t i = 0; i < 64; i++) wsel.push_back(ring(4 * i, WFR)); for (uint32_t i = 0; i < 64; i++) wsel.push_back(p64(i)); wsel.push_back(256);
+    C.opv(DOP_FR_SELIND, 64, 0, wsel);
+    for (uint32_t i = 0; i < 63; i++) C.op(DOP_FETCH, 4, 0, {mkref(RK_IMPORT, WFR, 0), 260 + 2 * i});
+    const size_t c_last4 = C.op(DOP_FETCH, 3, 0, {mkref(RK_LOCAL, WFR, 0), 390});
+    const size_t c_last = C.op(DOP_FETCH, 1, 0, {mkref(RK_LOCAL, W64, 3), 393});
+    C.op(DOP_CLT, 0, 0, {ring(393)});
+    C.op(DOP_END, 0, 0, {});
+    accept(C, M, "tape C");
     { Tape E; E.op(DOP_END, 0, 0, {}); accept(E, M, "the empty tape"); TapeLimits Z; accept(E, Z, "the empty tape, no limits"); }
 
     typedef std::vector<uint32_t> V;
@@ -174,6 +185,9 @@ int main() {
     refuse(A, M, "FETCH into slots past the segment's", malformed(a_f_in4, DOP_FETCH), [&](V &w, TapeLimits &) { w[a_f_in4 + 2] = 397; });
     refuse(A, M, "FETCH of five words", malformed(a_f_in4, DOP_FETCH), [&](V &w, TapeLimits &) { w[a_f_in4] += 1u << 8; });
     refuse(A, M, "FETCH of no word", malformed(a_f_local, DOP_FETCH), [&](V &w, TapeLimits &) { w[a_f_local] -= 1u << 8; });
+    // ---- more fetched slots in front of one op than the ring holds: the later ones would overwrite the earlier ones (slot mod RING_K)
+    refuse(C, M, "257 slots fetched in front of one op", malformed(c_last, DOP_FETCH), [&](V &w, TapeLimits &) { w[c_last4] += 1u << 8; });
+    refuse(C, M, "258 slots fetched: the first fetch past the ring is named", malformed(c_last, DOP_FETCH), [&](V &w, TapeLimits &) { w[c_last4] += 1u << 8; w[c_last] += 1u << 8; });
     // ---- the fused permutations' trailing words
     refuse(A, M, "GLPERM list slot", malformed(a_glperm, DOP_GLPERM), [&](V &w, TapeLimits &) { w[a_glperm + 14] = 2; });
     refuse(A, M, "BNPERM list slot", malformed(a_bnperm, DOP_BNPERM), [&](V &w, TapeLimits &) { w[a_bnperm + 6] = 2; });
