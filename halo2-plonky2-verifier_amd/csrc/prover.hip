@@ -19,6 +19,7 @@
 #include <vector>
 #include "chips.h"
 #include "common.h"
+#include "verifier.h"
 
 namespace h2w {
 namespace {
@@ -533,13 +534,13 @@ extern "C" {
 
 h2w_prover *h2w_prover_new(const h2w_shape_t *shape, const h2w_poseidon_consts_t *consts, int device_id) {
     if (!shape || !consts) { set_error("h2w_prover_new: null argument"); return nullptr; }
+    // the shape limits of every entry point (verifier.h shape_check), then the prover's own: an LDE of at most 2^24 points, at most 64 public inputs
+    if (const char *why = shape_check(*shape)) { set_error(std::string("h2w_prover_new: unsupported shape: ") + why); return nullptr; }
+    const Derived d = derive_shape(*shape);
+    if (d.lde_bits > 24 || d.lde_bits < 1) { set_error("h2w_prover_new: unsupported shape: degree_bits + rate_bits outside [1, 24]"); return nullptr; }
+    if (shape->n_pis > 64) { set_error("h2w_prover_new: unsupported shape: more than 64 public inputs"); return nullptr; }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_error("no HIP device: libh2w has no CPU fallback"); return nullptr; }
-    const Derived d = derive_shape(*shape);
-    if (d.lde_bits > 24 || d.lde_bits < 1 || shape->cap_height > d.lde_bits || shape->n_pis > 64 || shape->n_pis < 0 || shape->num_queries > 4096 || shape->num_queries < 0 ||
-        shape->n_cols + shape->n_perm_z + shape->n_quotient > MAX_BATCH_POLYS || shape->arity_bits > 4 || shape->arity_bits < 1 || d.final_poly_len > MAX_FINAL_POLY * 16) {
-        set_error("h2w_prover_new: unsupported shape"); return nullptr;
-    }
     h2w_prover *p = new h2w_prover();
     p->shape = *shape; p->d = d; p->pl = proof_layout(*shape, d); p->device = device_id;
     p->N = 1ull << shape->degree_bits; p->L = 1ull << d.lde_bits;

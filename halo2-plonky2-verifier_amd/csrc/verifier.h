@@ -71,8 +71,14 @@ template <class B> struct ChallengerChip {
 // index bits of a query as the device Merkle strands see them: bit i of the strand = bit lo + i of the query index (no per-lane array)
 struct PackedBits { uint64_t x; int lo; HF uint64_t operator[](int i) const { return (x >> (lo + i)) & 1; } };
 
-// Limits of a shape, shared by every entry point that takes one (plan compile, the eager StarkChip driver): the chips size their
-// stack arrays by MAX_*; nullptr = fine.
+// fold steps of ConstantArityBits without derive_shape's cap of MAX_STEPS (host only: derive_shape feeds kernels and stays a fixed-trip loop)
+inline int fold_steps_unbounded(const h2w_shape_t &s) {
+    int db = s.degree_bits, n = 0;
+    while (s.arity_bits >= 1 && db > s.final_poly_bits && db + s.rate_bits - s.arity_bits >= s.cap_height) { db -= s.arity_bits; n++; }
+    return n;
+}
+// Limits of a shape, shared by every entry point that takes one (plan compile, the eager StarkChip driver, the prover): the chips size
+// their stack arrays by MAX_*; nullptr = fine.
 inline const char *shape_check(const h2w_shape_t &s) {
     if (s.lookup_bits < 2 || s.lookup_bits > 28) return "lookup_bits outside [2, 28]";
     if (s.num_queries < 1 || s.num_queries > MAX_QUERIES) return "num_queries outside [1, 128]";
@@ -83,6 +89,8 @@ inline const char *shape_check(const h2w_shape_t &s) {
     if (s.degree_bits < 0 || s.rate_bits < 0 || s.degree_bits + s.rate_bits > 63 || s.degree_bits + s.rate_bits < s.cap_height) return "degree_bits / rate_bits do not fit the cap height or 63 bits";
     if (s.pow_bits < 0 || s.pow_bits > 63 || s.n_pis < 0 || s.num_challenges < 0 || s.final_poly_bits < 0) return "negative or oversized protocol parameter";
     if (s.n_perm_z > 0 && s.perm_batch_size < 1) return "perm_batch_size < 1";
+    static_assert(MAX_STEPS == 8, "the reason below names the limit");
+    if (fold_steps_unbounded(s) > MAX_STEPS) return "more than 8 FRI fold steps (MAX_STEPS): the reference would go on folding, derive_shape stops";
     if (derive_shape(s).final_poly_len > MAX_FINAL_POLY) return "final polynomial too long";
     return nullptr;
 }

@@ -44,7 +44,10 @@ typedef struct {
 } h2w_assigned_t;
 
 /* STARK / FRI shape: starky StarkConfig + the Stark trait facts the verifier needs
- * (stark/mod.rs:145-200, challenger/mod.rs:168-222, fri/mod.rs:447-502). */
+ * (stark/mod.rs:145-200, challenger/mod.rs:168-222, fri/mod.rs:447-502).
+ * Limit: at most 8 FRI fold steps.  ConstantArityBits folds by arity_bits while degree_bits > final_poly_bits and
+ * degree_bits + rate_bits - arity_bits >= cap_height, without a bound; a shape that would fold a ninth time is refused ("unsupported
+ * shape") by every entry point that takes one (h2w_plan_compile, h2w_chip_verify_stark, h2w_prover_new): raise final_poly_bits or arity_bits. */
 typedef struct {
     int32_t degree_bits, rate_bits, cap_height, num_queries, pow_bits, num_challenges;
     int32_t arity_bits, final_poly_bits;          /* FriReductionStrategy::ConstantArityBits */
@@ -517,7 +520,11 @@ int            h2w_chipbatch_configure(h2w_chipbatch *, int option, uint64_t val
  * h2w_fri_witness_batch consumes, so proofs never visit the host.  The reference obtains such proofs from starky's
  * prover (stark/mod.rs:405-426, test_util/fibonacci_stark.rs); as there, the committed polynomials are inputs: the STARK constraint
  * identity is not part of the verifier gadget (stark/mod.rs:243-321 is commented out), any polynomials of degree < 2^degree_bits do.
- * The serial sponge runs on the host between device phases (a few dozen permutations per proof). */
+ * The serial sponge runs on the host between device phases (a few dozen permutations per proof).
+ * h2w_prover_new accepts the shapes h2w_plan_compile accepts, with degree_bits + rate_bits in [1, 24] and n_pis <= 64; it refuses any
+ * other with "unsupported shape: <reason>" before it looks for a device.  That is stricter than its own earlier check: num_queries in
+ * [1, 128] (was up to 4096), a final polynomial of at most 128 coefficients (was 2048), lookup_bits in [2, 28], hash_mode 0 or 1,
+ * cap_height in [0, 6], pow_bits <= 63, at most 8 fold steps - what the witness generator takes, so every proof made can be witnessed. */
 typedef struct h2w_prover h2w_prover;
 h2w_prover *h2w_prover_new(const h2w_shape_t *, const h2w_poseidon_consts_t *, int device_id);
 void        h2w_prover_free(h2w_prover *);

@@ -247,13 +247,23 @@ int orc_prove_fri_coef(const oshape_t *sh, const oconsts_t *k, const uint64_t *c
     const int fl = d.final_poly_len;                 /* = 2^cur_bits >> rate_bits; the dropped coefficients are zero */
     nvc_observe_ext(&ch, F, fl);
     /* proof of work */
-    uint64_t pow_witness = 0;
-    for (;; pow_witness++) {
-        nvchal_t t = ch; t.in = (uint64_t *)malloc((size_t)(ch.cap_in ? ch.cap_in : 64) * 8); t.cap_in = ch.cap_in ? ch.cap_in : 64; memcpy(t.in, ch.in, (size_t)ch.n_in * 8);
-        nvc_observe(&t, pow_witness); uint64_t r = nvc_challenge(&t); free(t.in);
-        if (sh->pow_bits == 0 || (r >> (64 - sh->pow_bits)) == 0) break;
+    /* the challenge squeezed after observing a candidate is nvc_challenge() of the pending inputs + the candidate: the complete rate
+     * blocks of the pending inputs (the final polynomial) are the same for every candidate and are absorbed once; a candidate costs the
+     * one permutation of the last block.  The witness found goes through nvc_observe / nvc_challenge itself below, and must give the same word. */
+    uint64_t pow_witness = 0, pow_response;
+    {
+        const int full = ch.n_in - ch.n_in % SPONGE_RATE, tail = ch.n_in - full;
+        uint64_t base[SPONGE_WIDTH]; memcpy(base, ch.state, sizeof(base));
+        for (int off = 0; off < full; off += SPONGE_RATE) { memcpy(base, ch.in + off, SPONGE_RATE * 8); nv_gl_permute(k, base); }
+        for (;; pow_witness++) {
+            uint64_t st[SPONGE_WIDTH]; memcpy(st, base, sizeof(st));
+            memcpy(st, ch.in + full, (size_t)tail * 8); st[tail] = pow_witness;
+            nv_gl_permute(k, st); pow_response = st[SPONGE_RATE - 1];
+            if (sh->pow_bits == 0 || (pow_response >> (64 - sh->pow_bits)) == 0) break;
+        }
     }
-    nvc_observe(&ch, pow_witness); (void)nvc_challenge(&ch);
+    nvc_observe(&ch, pow_witness);
+    const int pow_ok = nvc_challenge(&ch) == pow_response;      /* (the proof is refused below if the shortcut above is wrong) */
     /* write the proof */
     uint64_t *w = words;
     for (int i = 0; i < cs; i++) put_hash(&w, cap[o_trace][i]);
@@ -286,7 +296,7 @@ int orc_prove_fri_coef(const oshape_t *sh, const oconsts_t *k, const uint64_t *c
         }
     }
     for (int i = 0; i < sh->n_pis; i++) *w++ = pis[i];
-    int rc = (size_t)(w - words) == orc_proof_words(sh) ? 0 : -1;
+    int rc = pow_ok && (size_t)(w - words) == orc_proof_words(sh) ? 0 : -1;
     for (int o = 0; o < no; o++) { for (int p = 0; p < npoly[o]; p++) { free(coef[o][p]); free(lde[o][p]); } free(coef[o]); free(lde[o]); nv_tree_free(&tree[o]); }
     for (int st = 0; st < d.n_steps; st++) { nv_tree_free(&ftree[st]); free(fvals[st]); }
     free(fvals); free(F); free(ch.in);

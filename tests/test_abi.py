@@ -103,6 +103,75 @@ def test_prover_has_no_cpu_path_and_rejects_bad_shapes(h2w_api, h2w):
         h2w_api.Prover(bad, kh)
 
 
+def _prover_refuses(h2w_api, sh, kh, why):
+    with pytest.raises(h2w_api.H2WError, match="unsupported shape: .*" + why):
+        h2w_api.Prover(sh, kh).close()
+
+
+@pytest.mark.parametrize("field,value,why", [
+    ("hash_mode", 2, "hash_mode"), ("cap_height", -1, "cap_height"), ("cap_height", 6, "cap height"),      # (lde_bits is 4 below)
+    ("n_cols", 0, "polynomials"), ("n_quotient", 0, "polynomials"), ("n_cols", 13, "polynomials"),         # 13 + 2 + 2 = 17
+    ("arity_bits", 0, "arity_bits"), ("arity_bits", 5, "arity_bits"), ("pow_bits", 64, "protocol parameter"),
+    ("num_queries", 0, "num_queries"), ("num_queries", 129, "num_queries"), ("perm_batch_size", 0, "perm_batch_size"),
+    ("n_pis", 65, "public inputs"), ("rate_bits", 22, r"\[1, 24\]")])
+def test_prover_refuses_what_the_plan_refuses(h2w_api, h2w, field, value, why):
+    """h2w_prover_new goes through the shape limits of every entry point (verifier.h shape_check) and its own two (an LDE of at most
+    2^24 points, 64 public inputs), before it looks for a device: each refusal names its reason."""
+    kh = h2w.published_consts()
+    sh = h2w.fibonacci_shape(3, 2, rate_bits=1, cap_height=2)
+    setattr(sh, field, value)
+    _prover_refuses(h2w_api, sh, kh, why)
+    if field not in ("n_pis", "rate_bits"):      # (the prover's own limits)
+        with pytest.raises(h2w_api.H2WError, match="unsupported shape: .*" + why):
+            h2w_api.Plan(sh, kh).close()
+
+
+def _fold_shapes(h2w, oracle, final_poly_bits, mode):
+    """2^11 rows folded by 2 down to 2^final_poly_bits coefficients: 11 - final_poly_bits fold steps (plonky2 ConstantArityBits has no bound)."""
+    sh = h2w.fibonacci_shape(11, 2, rate_bits=1, cap_height=1, hash_mode=mode); osh = oracle.fibonacci_shape(11, 2, rate_bits=1, cap_height=1, hash_mode=mode)
+    for s in (sh, osh):
+        s.arity_bits = 1; s.final_poly_bits = final_poly_bits
+    return sh, osh
+
+
+@pytest.mark.parametrize("entry", ["plan", "eager", "prover"])
+def test_more_than_eight_fold_steps_are_refused(h2w_api, h2w, oracle, entry):
+    """derive_shape folds at most MAX_STEPS = 8 times and the reference goes on: 9 and 10 steps would lay out a proof of another
+    protocol (896 words, the oracle's 920 and 940), so every entry point that takes a shape refuses them and names the limit."""
+    import numpy as np
+    kh = h2w.published_consts()
+    for final_poly_bits in (2, 1):
+        sh, osh = _fold_shapes(h2w, oracle, final_poly_bits, 1)
+        assert oracle.lib().orc_proof_words(C.byref(osh)) == {2: 920, 1: 940}[final_poly_bits]
+        with pytest.raises(h2w_api.H2WError, match="unsupported shape: more than 8 FRI fold steps .MAX_STEPS."):
+            if entry == "plan":
+                h2w_api.Plan(sh, kh).close()
+            elif entry == "prover":
+                h2w_api.Prover(sh, kh).close()
+            else:
+                ctx = h2w_api.Context(21)
+                try:
+                    h2w_api.verify_stark(ctx, sh, kh, np.zeros(940, dtype=np.uint64))
+                finally:
+                    ctx.close()
+
+
+@pytest.mark.parametrize("mode", [1, 0])
+def test_eight_fold_steps_are_laid_out_as_the_oracle_does(h2w_api, h2w, oracle, consts, mode):
+    ko, kh = consts
+    sh, osh = _fold_shapes(h2w, oracle, 3, mode)
+    plan = h2w_api.Plan(sh, kh)
+    ctx = oracle.Ctx(21)
+    assert oracle.verify_stark(ctx, osh, ko, oracle.synth_proof(osh, 5)) == 0
+    assert plan.proof_words == oracle.lib().orc_proof_words(C.byref(osh)) == 896
+    assert plan.num_cells == ctx.num_cells()
+    plan.close(); ctx.close()
+    try:                                       # the prover takes the shape too (where there is a device to make it on)
+        h2w_api.Prover(sh, kh).close()
+    except h2w_api.H2WError as e:
+        assert "no HIP device" in str(e)
+
+
 def test_published_tables_are_a_plain_data_call(h2w):
     """h2w_poseidon_published needs no device; a null pointer is an error, not a crash."""
     assert h2w.lib().h2w_poseidon_published(None) != 0

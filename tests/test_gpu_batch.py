@@ -5,6 +5,8 @@ import ctypes as C
 
 import pytest
 
+from prover_util import custom_shape
+
 pytestmark = pytest.mark.gpu
 
 
@@ -143,18 +145,10 @@ def test_config2_bn254_full(h2w, h2w_api, oracle, consts):
     run_batch(h2w, h2w_api, oracle, consts, (16, 28, 2, 1), [0xF1B00002])
 
 
-def _custom(h2w, oracle, **kw):
-    sh = h2w.fibonacci_shape(kw.pop("d"), kw.pop("q"), rate_bits=kw.pop("rb", 1), cap_height=kw.pop("cap", 4), hash_mode=kw.pop("mode", 1))
-    osh = oracle.fibonacci_shape(sh.degree_bits, sh.num_queries, rate_bits=sh.rate_bits, cap_height=sh.cap_height, hash_mode=sh.hash_mode)
-    for k, v in kw.items():
-        setattr(sh, k, v); setattr(osh, k, v)
-    return sh, osh
-
-
 def run_custom(h2w, h2w_api, oracle, consts, seeds, valid=False, **kw):
     import torch
     ko, kh = consts
-    sh, osh = _custom(h2w, oracle, **kw)
+    sh, osh = custom_shape(h2w, oracle, **kw)
     plan = h2w_api.Plan(sh, kh)
     n = len(seeds)
     proofs = [oracle.prove_fri(osh, ko, s) if valid else oracle.synth_proof(osh, s) for s in seeds]   # valid: oracle/prover.inc
@@ -185,7 +179,8 @@ def test_shape_edge_cases(h2w, h2w_api, oracle, consts, mode):
     merkle/mod.rs:104-115), other pow bits / arity / column counts, one query."""
     cases = [dict(d=6, q=2, n_perm_z=0), dict(d=6, q=1, cap=0), dict(d=8, q=2, rb=2, cap=2, arity_bits=2, final_poly_bits=3),
              dict(d=6, q=2, pow_bits=10, n_cols=6, n_quotient=4, n_pis=1, num_challenges=3), dict(d=9, q=2, rb=3, cap=1, arity_bits=3),
-             dict(d=5, q=2, cap=1, arity_bits=1, final_poly_bits=2)]      # (arity 2: every size of the tabulated FRI constants, chips.h FriTab, is walked by some case)
+             dict(d=5, q=2, cap=1, arity_bits=1, final_poly_bits=2),      # (arity 2: every size of the tabulated FRI constants, chips.h FriTab, is walked by some case)
+             dict(d=10, q=2, cap=1, arity_bits=1, final_poly_bits=2)]     # exactly MAX_STEPS = 8 fold steps: every slot of the per-step arrays
     for kw in cases:
         status, outs, nc = run_custom(h2w, h2w_api, oracle, consts, [11, 12], mode=mode, **kw)
         assert status == [0, 0], (kw, status)
@@ -193,6 +188,9 @@ def test_shape_edge_cases(h2w, h2w_api, oracle, consts, mode):
             assert rc == 0 and n == nc and same, (kw, rc, err, n, nc, same)
     # and one of them on a valid instance (two fold steps of arity 4)
     status, outs, nc = run_custom(h2w, h2w_api, oracle, consts, [13], valid=True, mode=mode, **cases[2])
+    assert status == [0] and all(rc == 0 and n == nc and same for rc, err, n, same in outs)
+    # and the eight fold steps on a valid instance
+    status, outs, nc = run_custom(h2w, h2w_api, oracle, consts, [14], valid=True, mode=mode, **cases[6])
     assert status == [0] and all(rc == 0 and n == nc and same for rc, err, n, same in outs)
 
 

@@ -6,6 +6,8 @@ import ctypes as C
 
 import pytest
 
+from prover_util import gpu_prove
+
 pytestmark = pytest.mark.gpu
 
 SHAPES = [
@@ -15,20 +17,6 @@ SHAPES = [
     (7, 2, 2, 4),      # rate_bits 2, cap of 16
     (13, 5, 1, 4),     # two fold steps, NTT larger than one LDS tile
 ]
-
-
-def gpu_prove(h2w, h2w_api, oracle, kh, sh, osh, seed):
-    import numpy as np
-    import torch
-    coefs, pis = oracle.prove_fri_inputs(osh, seed)
-    pr = h2w_api.Prover(sh, kh)
-    d_coefs = torch.from_numpy(np.frombuffer(coefs, dtype=np.int64).copy()).cuda()
-    assert d_coefs.numel() == pr.num_polys << sh.degree_bits
-    d_proof = torch.zeros(pr.proof_words, dtype=torch.int64, device="cuda")
-    pr.prove(d_coefs.data_ptr(), list(pis)[:sh.n_pis], d_proof.data_ptr(), torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    t = pr.timing(); pr.close()
-    return coefs, pis, d_proof, t
 
 
 @pytest.mark.parametrize("mode", [1, 0])
