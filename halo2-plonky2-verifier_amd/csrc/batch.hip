@@ -337,12 +337,13 @@ static int run_batch(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs,
         int k = 0; while (k < p->n_side && p->side_of[k] != stream) k++;
         if (k == p->n_side && p->n_side < h2w_plan::N_SIDE) {
             int lo_pri = 0, hi_pri = 0; (void)hipDeviceGetStreamPriorityRange(&lo_pri, &hi_pri);      // the chain is the longest dependent piece of a launch: let its blocks be placed first
-            H2W_HIP(hipStreamCreateWithPriority(&p->side[k], hipStreamNonBlocking, hi_pri)); p->side_of[k] = stream; p->n_side++;
+            if (p->side[k].create(hipStreamNonBlocking, hi_pri) != 0) return -1;
+            p->side_of[k] = stream; p->n_side++;
         }
         if (k < p->n_side) cstream = p->side[k];      // (more caller streams than side streams: the extra ones do not fork)
     }
-    hipEvent_t *prev_ev = (p->n_batches && p->ev_recorded) ? p->evr[(p->n_batches - 1) % h2w_plan::EV_RING] : nullptr;
-    hipEvent_t *ev = p->evr[p->n_batches % h2w_plan::EV_RING];
+    const DevEvent *prev_ev = (p->n_batches && p->ev_recorded) ? p->evr[(p->n_batches - 1) % h2w_plan::EV_RING] : nullptr;
+    const DevEvent *ev = p->evr[p->n_batches % h2w_plan::EV_RING];
     const unsigned nunits = A.sh.n_own_units;
     const unsigned nkinds = (unsigned)(p->d.n_oracles + p->d.n_steps);
     bool forked = false;
@@ -461,7 +462,7 @@ static int run_batch(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs,
         if (forked) (void)hipStreamSynchronize(cstream);
         return -1;
     }
-    p->ev = ev; p->n_batches++; p->ev_recorded = true;
+    p->n_batches++; p->ev_recorded = true;
     return 0;
 }
 // Re-expands the block records a previous h2w_fri_witness_batch* call left in `workspace_dev` (same n_proofs) into advice_dev: the
@@ -496,7 +497,7 @@ int h2w_plan_status(h2w_plan *p, const void *workspace_dev, uint64_t n_proofs, u
 }
 int h2w_plan_timing(h2w_plan *p, uint64_t back, float ms[5]) {   // `back` batches before the last one (ring of 64)
     if (!p || !p->ev_recorded || back >= p->n_batches || back >= (uint64_t)h2w_plan::EV_RING) { set_error("h2w_plan_timing: no such batch"); return -1; }
-    hipEvent_t *ev = p->evr[(p->n_batches - 1 - back) % h2w_plan::EV_RING];
+    const DevEvent *ev = p->evr[(p->n_batches - 1 - back) % h2w_plan::EV_RING];
     DeviceGuard dg(p->device);
     H2W_HIP(hipEventSynchronize(ev[H2W_EV_CALL_END]));
     H2W_HIP(hipEventElapsedTime(&ms[0], ev[H2W_EV_CALL_START], ev[H2W_EV_PROLOGUE_END]));   // prologue strands: values (+ with PoseidonBN254 caps: their permutations' records)
@@ -508,7 +509,7 @@ int h2w_plan_timing(h2w_plan *p, uint64_t back, float ms[5]) {   // `back` batch
 }
 int h2w_plan_timing_ex(h2w_plan *p, uint64_t back, float ms[8]) {
     if (!p || !p->ev_recorded || back >= p->n_batches || back >= (uint64_t)h2w_plan::EV_RING) { set_error("h2w_plan_timing_ex: no such batch"); return -1; }
-    hipEvent_t *ev = p->evr[(p->n_batches - 1 - back) % h2w_plan::EV_RING];
+    const DevEvent *ev = p->evr[(p->n_batches - 1 - back) % h2w_plan::EV_RING];
     DeviceGuard dg(p->device);
     H2W_HIP(hipEventSynchronize(ev[H2W_EV_CALL_END]));
     H2W_HIP(hipEventElapsedTime(&ms[0], ev[H2W_EV_CALL_START], ev[h2w_plan::EV_PROLOGUE_VALUES_END]));    // k_prologue_values

@@ -1,7 +1,8 @@
-// devbuf.h — DevBuf<T>: the move-only owner of ONE hipMalloc allocation (host code).  Every long-lived device pointer of a handle is one of
-// these: a constructor that fails half-way, a free function and a re-upload all release memory by the same rule - the member's destructor -
-// so no free list has to know every pointer.  hipFree acts on the current device: the handles' free functions keep their DeviceGuard and then
-// delete the handle.  A failed call leaves the buffer empty and the reason in the last error (tests/cpp/devbuf_check.cpp).
+// devbuf.h — the move-only owners of a handle's device resources (host code): DevBuf<T> of ONE hipMalloc allocation, DevEvent of a hipEvent_t, DevStream
+// of a hipStream_t.  Every long-lived device pointer, event and side stream of a handle is one of these: a constructor that fails half-way, a free
+// function and a re-upload all release by the same rule - the member's destructor - so no free list has to know every member.  hipFree and the destroy
+// calls act on the current device: the handles' free functions keep their DeviceGuard and then delete the handle.  A failed call leaves the owner empty
+// and the reason in the last error (tests/cpp/devbuf_check.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <string>
@@ -41,5 +42,44 @@ public:
     }
     int upload(const std::vector<T> &h) { return upload(h.data(), h.size()); }
 };
+
+// An event / a stream converts to its raw handle and is no larger than it, so an array of owners is indexed and handed to the runtime like an array of handles.
+class DevEvent {
+    hipEvent_t e_ = nullptr;
+public:
+    DevEvent() = default;
+    DevEvent(DevEvent &&o) noexcept : e_(o.e_) { o.e_ = nullptr; }
+    DevEvent &operator=(DevEvent &&o) noexcept { if (this != &o) { reset(); e_ = o.e_; o.e_ = nullptr; } return *this; }
+    DevEvent(const DevEvent &) = delete; DevEvent &operator=(const DevEvent &) = delete;
+    ~DevEvent() { reset(); }
+    operator hipEvent_t() const { return e_; }
+    void reset() { if (e_) (void)hipEventDestroy(e_); e_ = nullptr; }
+    int create() {
+        reset();
+        hipEvent_t e = nullptr;
+        H2W_HIP(hipEventCreate(&e));
+        e_ = e;
+        return 0;
+    }
+};
+class DevStream {
+    hipStream_t s_ = nullptr;
+public:
+    DevStream() = default;
+    DevStream(DevStream &&o) noexcept : s_(o.s_) { o.s_ = nullptr; }
+    DevStream &operator=(DevStream &&o) noexcept { if (this != &o) { reset(); s_ = o.s_; o.s_ = nullptr; } return *this; }
+    DevStream(const DevStream &) = delete; DevStream &operator=(const DevStream &) = delete;
+    ~DevStream() { reset(); }
+    operator hipStream_t() const { return s_; }
+    void reset() { if (s_) (void)hipStreamDestroy(s_); s_ = nullptr; }
+    int create(unsigned flags = hipStreamDefault, int priority = 0) {      // (priority 0: the default one)
+        reset();
+        hipStream_t s = nullptr;
+        H2W_HIP(hipStreamCreateWithPriority(&s, flags, priority));
+        s_ = s;
+        return 0;
+    }
+};
+static_assert(sizeof(DevEvent) == sizeof(hipEvent_t) && sizeof(DevStream) == sizeof(hipStream_t), "owners are as large as their handles");
 
 }  // namespace h2w

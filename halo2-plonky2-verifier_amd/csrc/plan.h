@@ -1,5 +1,5 @@
 // plan.h — the plan handle of API level 3 (include/h2w.h): a compiled shape (plancompile.cpp h2w_plan_compile) or a traced run (replay.hip h2w_plan_from_trace).
-// Every device table of the handle is a DevBuf (devbuf.h): h2w_plan_free sets the device and deletes the handle.
+// Every device table, event and side stream of the handle is an owner of devbuf.h: h2w_plan_free sets the device and deletes the handle.
 #pragma once
 #include "common.h"
 #include "batchargs.h"
@@ -29,8 +29,8 @@ struct h2w_plan {
     // event slots of a call: slot i < H2W_EV_COUNT is the public H2W_EV_* i (include/h2w.h: call start / end, prologue block complete, glue (+ Goldilocks
     // Merkle strands) start / end, chain kernels start / end, expansion start / end), then the internal ones
     enum { EV_PROLOGUE_VALUES_END = H2W_EV_COUNT, EV_CHAIN_VALUES_END, EV_GLP_START, EV_GLP_END, EV_DIRECT_END, N_EV };
-    hipEvent_t evr[EV_RING][N_EV]; int passes_of[EV_RING] = {0};
-    hipStream_t side[N_SIDE]; hipStream_t side_of[N_SIDE]; int n_side = 0;   // PoseidonBN254 chain kernels run beside the glue + expansion kernels
+    DevEvent evr[EV_RING][N_EV]; int passes_of[EV_RING] = {0};      // (created by h2w_plan_compile; a traced plan has none)
+    DevStream side[N_SIDE]; hipStream_t side_of[N_SIDE]; int n_side = 0;   // PoseidonBN254 chain kernels run beside the glue + expansion kernels
     int chain_passes = 0;            // H2W_OPT_CHAIN_PASSES (0: by the size of the launch)
     int values_form = 0;             // H2W_OPT_VALUES_FORM (0: by the size of the launch)
     int serial_expand = 1;           // H2W_OPT_SERIAL_EXPAND: the expansion kernel of a call waits for the previous call's
@@ -38,7 +38,7 @@ struct h2w_plan {
     // 64-word rows for k_direct_to_montgomery); the Montgomery form's constants and the bitmap go to the device when the form is first selected.
     int output_form = 0; std::vector<uint64_t> direct_bits, h_meta; uint64_t n_direct = 0; DevBuf<uint64_t> d_direct_bits; DevBuf<MontForm> d_mont;
     bool fork_chains = true;         // of their own batch (they share only the prologue): one side stream per caller stream seen (created on demand)
-    hipEvent_t *ev = evr[0]; uint64_t n_batches = 0; bool ev_ready = false, ev_recorded = false;
+    uint64_t n_batches = 0; bool ev_recorded = false;
     h2w::TracedPlan *traced = nullptr;      // set: the plan replays a recorded tape (replay.hip); the strand tables above are unused
     explicit h2w_plan(int L) : tt(L) {}
 };

@@ -142,20 +142,17 @@ h2w_plan *h2w_plan_compile(const h2w_shape_t *shape, const h2w_poseidon_consts_t
             upload_bn_tab(pl->d_bn_tab, *consts, pl->P, &pl->d_bn_tab9) != 0 || pl->d_rowk.upload(&rk, 1) != 0 || pl->d_fri.upload(&ft, 1) != 0 ||
             pl->d_st.upload(&pl->st, 1) != 0 || upload_glp_consts(pl->d_consts, *consts) != 0 || upload_tmpl_cells(pl->d_ncells, pl->tt) != 0 ||
             pl->d_inv.upload(inv) != 0) return -1;
-        for (int r = 0; r < h2w_plan::EV_RING; r++) for (int i = 0; i < h2w_plan::N_EV; i++) H2W_HIP(hipEventCreate(&pl->evr[r][i]));
-        pl->ev_ready = true;
+        for (auto &ring : pl->evr) for (DevEvent &e : ring) if (e.create() != 0) return -1;
         return 0;
     };
     if (up() != 0) { h2w_plan_free(pl); return nullptr; }
     return pl;
 }
-// The device tables are DevBufs of the handle (and of its TracedPlan): deleting it with its device current frees them; events and side streams by hand.
+// The device tables are DevBufs of the handle (and of its TracedPlan): the events and side streams are owners too; deleting the handle with its device current releases them all.
 void h2w_plan_free(h2w_plan *p) {
     if (!p) return;
     DeviceGuard dg(p->device);
-    if (p->traced) traced_free(p);
-    if (p->ev_ready) for (int r = 0; r < h2w_plan::EV_RING; r++) for (int i = 0; i < h2w_plan::N_EV; i++) (void)hipEventDestroy(p->evr[r][i]);
-    for (int i = 0; i < p->n_side; i++) (void)hipStreamDestroy(p->side[i]);
+    traced_free(p);
     delete p;
 }
 uint64_t h2w_plan_num_cells(const h2w_plan *p) { return p ? p->ncells : 0; }

@@ -472,17 +472,21 @@ struct HostChallenger {
 
 using namespace h2w;
 
+// device buffers of a batch of `cap` proofs: [proof][...] everywhere.  One struct, so that ensure_capacity empties them all by assigning a fresh one
+struct BatchBufs {
+    DevBuf<uint64_t> lde, fv[MAX_STEPS], x_index;
+    DevBuf<H4> tree, ftree[MAX_STEPS];
+    DevBuf<gle_t> Fa, Fb, T, totals, carry, partial, pts;
+    DevBuf<QuotArgs> qargs; DevBuf<PowArgs> pargs;
+    DevBuf<unsigned long long> best;
+};
 struct h2w_prover {
     h2w_shape_t shape; Derived d; ProofLayout pl; int device = 0;
-    ProverConsts hk; ProverConsts *dk = nullptr;
+    ProverConsts hk; DevBuf<ProverConsts> dk;
     int np = 0, poly0[3] = {0, 0, 0};
-    uint64_t N = 0, L = 0, cap = 0;                              // cap: proofs the batch buffers below are sized for
-    uint64_t *tw = nullptr, *lde = nullptr, *fv[MAX_STEPS] = {nullptr}, *x_index = nullptr;
-    H4 *tree = nullptr, *ftree[MAX_STEPS] = {nullptr};
-    gle_t *Fa = nullptr, *Fb = nullptr, *T = nullptr, *totals = nullptr, *carry = nullptr, *partial = nullptr, *pts = nullptr;
-    QuotArgs *qargs = nullptr; PowArgs *pargs = nullptr;
-    unsigned long long *best = nullptr;
-    hipEvent_t ev[8] = {nullptr};
+    uint64_t N = 0, L = 0, cap = 0;                              // cap: proofs the batch buffers are sized for
+    DevBuf<uint64_t> tw; BatchBufs b;
+    DevEvent ev[8];
     float ms[7] = {0, 0, 0, 0, 0, 0, 0};
     int eval_blocks = 0, scan_blocks = 0;
 };
@@ -492,40 +496,42 @@ inline unsigned blocks(uint64_t n, unsigned per) { return (unsigned)((n + per - 
 // in-place DIF NTT of `count` arrays of 2^bits words each: natural order in, bit-reversed order out
 void ntt_dif(const h2w_prover *p, uint64_t *a, int bits, uint64_t count, hipStream_t s) {
     const uint64_t n = 1ull << bits; const int tb = bits < NTT_TILE_BITS ? bits : NTT_TILE_BITS;
-    for (int st = bits; st > tb; st--) hipLaunchKernelGGL(k_dif_stage, dim3(blocks(n / 2, 256), (unsigned)count), dim3(256), 0, s, a, n, st, p->tw, p->d.lde_bits - st);
-    if (tb >= 1) hipLaunchKernelGGL(k_dif_local, dim3((unsigned)(n >> tb), (unsigned)count), dim3(256), 0, s, a, n, tb, p->tw, p->d.lde_bits);
+    for (int st = bits; st > tb; st--) hipLaunchKernelGGL(k_dif_stage, dim3(blocks(n / 2, 256), (unsigned)count), dim3(256), 0, s, a, n, st, p->tw.get(), p->d.lde_bits - st);
+    if (tb >= 1) hipLaunchKernelGGL(k_dif_local, dim3((unsigned)(n >> tb), (unsigned)count), dim3(256), 0, s, a, n, tb, p->tw.get(), p->d.lde_bits);
 }
 // all levels above the leaves up to the cap (level bits - cap_height) of `count` trees tree_stride hashes apart
 void build_trees(const h2w_prover *p, H4 *base, int bits, uint64_t count, uint64_t tree_stride, hipStream_t s) {
     for (int l = 1; l <= bits - p->shape.cap_height; l++) {
         const uint64_t m = 1ull << (bits - l);
-        hipLaunchKernelGGL(k_tree_level, dim3(blocks(m, 64), (unsigned)count), dim3(64), 0, s, p->dk, p->shape.hash_mode, base + level_off(bits, l - 1), base + level_off(bits, l), m, tree_stride);
+        hipLaunchKernelGGL(k_tree_level, dim3(blocks(m, 64), (unsigned)count), dim3(64), 0, s, p->dk.get(), p->shape.hash_mode, base + level_off(bits, l - 1), base + level_off(bits, l), m, tree_stride);
     }
 }
-void free_batch_buffers(h2w_prover *p) {
-    hipFree(p->lde); hipFree(p->tree); hipFree(p->Fa); hipFree(p->Fb); hipFree(p->T); hipFree(p->totals); hipFree(p->carry); hipFree(p->partial);
-    hipFree(p->pts); hipFree(p->qargs); hipFree(p->pargs); hipFree(p->x_index); hipFree(p->best);
-    for (int st = 0; st < MAX_STEPS; st++) { hipFree(p->fv[st]); hipFree(p->ftree[st]); p->fv[st] = nullptr; p->ftree[st] = nullptr; }
-    p->lde = nullptr; p->tree = nullptr; p->Fa = p->Fb = p->T = p->totals = p->carry = p->partial = p->pts = nullptr; p->qargs = nullptr; p->pargs = nullptr;
-    p->x_index = nullptr; p->best = nullptr; p->cap = 0;
-}
-// device buffers of a batch of n proofs: [proof][...] everywhere
+// device buffers of a batch of n proofs.  Only grows; a failed growth leaves every buffer empty and cap == 0, so that the next call starts over
 int ensure_capacity(h2w_prover *p, uint64_t n) {
     if (n <= p->cap) return 0;
-    free_batch_buffers(p);
-    const Derived &d = p->d; const uint64_t L = p->L, N = p->N;
-    bool ok = true;
-    auto dm = [&](void **q, size_t bytes) { if (ok && hipMalloc(q, bytes ? bytes : 8) != hipSuccess) ok = false; };
-    dm((void **)&p->lde, n * p->np * L * 8);
-    dm((void **)&p->tree, n * d.n_oracles * 2 * L * sizeof(H4));
-    dm((void **)&p->Fa, n * L * sizeof(gle_t)); dm((void **)&p->Fb, n * L * sizeof(gle_t)); dm((void **)&p->T, n * N * sizeof(gle_t));
-    dm((void **)&p->totals, n * p->scan_blocks * sizeof(gle_t)); dm((void **)&p->carry, n * p->scan_blocks * sizeof(gle_t));
-    dm((void **)&p->partial, n * 2 * p->np * p->eval_blocks * sizeof(gle_t));
-    dm((void **)&p->pts, n * 3 * sizeof(gle_t)); dm((void **)&p->qargs, n * sizeof(QuotArgs)); dm((void **)&p->pargs, n * sizeof(PowArgs));
-    { uint64_t m = L; for (int st = 0; st < d.n_steps; st++) { dm((void **)&p->fv[st], n * 2 * m * 8); dm((void **)&p->ftree[st], n * 2 * (m >> d.arity[st]) * sizeof(H4)); m >>= d.arity[st]; } }
-    dm((void **)&p->x_index, n * (size_t)(p->shape.num_queries ? p->shape.num_queries : 1) * 8); dm((void **)&p->best, n * 8);
-    if (!ok) { free_batch_buffers(p); set_error("h2w_prove_fri_batch: out of device memory for this batch size"); (void)hipGetLastError(); return -1; }
+    p->cap = 0; p->b = BatchBufs();      // (released first: the old and the new size are never held together)
+    BatchBufs &b = p->b; const Derived &d = p->d; const uint64_t L = p->L, N = p->N;
+    bool ok = b.lde.alloc(n * p->np * L) == 0 && b.tree.alloc(n * d.n_oracles * 2 * L) == 0 && b.Fa.alloc(n * L) == 0 && b.Fb.alloc(n * L) == 0 && b.T.alloc(n * N) == 0 &&
+              b.totals.alloc(n * p->scan_blocks) == 0 && b.carry.alloc(n * p->scan_blocks) == 0 && b.partial.alloc(n * 2 * p->np * p->eval_blocks) == 0 &&
+              b.pts.alloc(n * 3) == 0 && b.qargs.alloc(n) == 0 && b.pargs.alloc(n) == 0 &&
+              b.x_index.alloc(n * (size_t)(p->shape.num_queries ? p->shape.num_queries : 1)) == 0 && b.best.alloc(n) == 0;
+    { uint64_t m = L; for (int st = 0; st < d.n_steps && ok; st++) { ok = b.fv[st].alloc(n * 2 * m) == 0 && b.ftree[st].alloc(n * 2 * (m >> d.arity[st])) == 0; m >>= d.arity[st]; } }
+    if (!ok) {
+        p->b = BatchBufs(); (void)hipGetLastError();
+        set_error("h2w_prove_fri_batch: out of device memory for this batch size (" + std::to_string(n) + " proofs): " + g_last_error);
+        return -1;
+    }
     p->cap = n;
+    return 0;
+}
+// what h2w_prover_new puts on the device: the constants, the twiddles, the timing events
+int prover_upload(h2w_prover *p) {
+    if (p->dk.upload(&p->hk, 1) != 0 || p->tw.alloc(p->L / 2) != 0) return -1;
+    for (DevEvent &e : p->ev) if (e.create() != 0) return -1;
+    if (p->L >= 2) {
+        hipLaunchKernelGGL(k_twiddles, dim3(blocks(p->L / 2, 256)), dim3(256), 0, 0, p->tw.get(), p->L / 2, gl_primitive_root_of_unity(p->d.lde_bits));
+        H2W_HIP(hipDeviceSynchronize());
+    }
     return 0;
 }
 }  // namespace
@@ -541,6 +547,7 @@ h2w_prover *h2w_prover_new(const h2w_shape_t *shape, const h2w_poseidon_consts_t
     if (shape->n_pis > 64) { set_error("h2w_prover_new: unsupported shape: more than 64 public inputs"); return nullptr; }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_error("no HIP device: libh2w has no CPU fallback"); return nullptr; }
+    if (device_id < 0 || device_id >= ndev) { set_error("h2w_prover_new: device_id out of range"); return nullptr; }
     h2w_prover *p = new h2w_prover();
     p->shape = *shape; p->d = d; p->pl = proof_layout(*shape, d); p->device = device_id;
     p->N = 1ull << shape->degree_bits; p->L = 1ull << d.lde_bits;
@@ -552,20 +559,13 @@ h2w_prover *h2w_prover_new(const h2w_shape_t *shape, const h2w_poseidon_consts_t
     for (int i = 0; i < 88; i++) p->hk.bn.c[i] = fr_mont_mul(consts->bn_c[i], P.r2, P.ninv);
     for (int i = 0; i < 392; i++) p->hk.bn.s[i] = fr_mont_mul(consts->bn_s[i], P.r2, P.ninv);
     for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) { p->hk.bn.m[i][j] = fr_mont_mul(consts->bn_m[i][j], P.r2, P.ninv); p->hk.bn.p[i][j] = fr_mont_mul(consts->bn_p[i][j], P.r2, P.ninv); }
-    bool ok = hipSetDevice(device_id) == hipSuccess;
-    if (ok) ok = hipMalloc((void **)&p->dk, sizeof(ProverConsts)) == hipSuccess;
-    if (ok) ok = hipMalloc((void **)&p->tw, (p->L / 2 ? p->L / 2 : 1) * 8) == hipSuccess;
-    for (int i = 0; i < 8 && ok; i++) ok = hipEventCreate(&p->ev[i]) == hipSuccess;
-    if (ok) ok = hipMemcpy(p->dk, &p->hk, sizeof(ProverConsts), hipMemcpyHostToDevice) == hipSuccess;
-    if (ok && p->L >= 2) { hipLaunchKernelGGL(k_twiddles, dim3(blocks(p->L / 2, 256)), dim3(256), 0, 0, p->tw, p->L / 2, gl_primitive_root_of_unity(d.lde_bits)); ok = hipDeviceSynchronize() == hipSuccess; }
-    if (!ok) { set_error(std::string("h2w_prover_new: ") + hipGetErrorString(hipGetLastError())); h2w_prover_free(p); return nullptr; }
+    DeviceGuard dg(device_id);
+    if (prover_upload(p) != 0) { set_error("h2w_prover_new: " + g_last_error); h2w_prover_free(p); return nullptr; }
     return p;
 }
 void h2w_prover_free(h2w_prover *p) {
     if (!p) return;
-    free_batch_buffers(p);
-    hipFree(p->dk); hipFree(p->tw);
-    for (int i = 0; i < 8; i++) if (p->ev[i]) hipEventDestroy(p->ev[i]);
+    DeviceGuard dg(p->device);
     delete p;
 }
 uint64_t h2w_prover_num_polys(const h2w_prover *p) { return p ? (uint64_t)p->np : 0; }
@@ -580,21 +580,22 @@ int h2w_prove_fri_batch(h2w_prover *p, const uint64_t *coeffs_dev, const uint64_
     const h2w_shape_t &sh = p->shape; const Derived &d = p->d; const ProofLayout &pl = p->pl;
     const int mode = sh.hash_mode, lb = d.lde_bits, capb = sh.cap_height, cs = d.cap_size, no = d.n_oracles, np = p->np;
     const uint64_t N = p->N, L = p->L; const unsigned nb = (unsigned)n;
-    H2W_HIP(hipSetDevice(p->device));
+    DeviceGuard dg(p->device);
     if (ensure_capacity(p, n)) return -1;
+    const BatchBufs &B = p->b;
     std::vector<uint64_t> head(n * pl.queries, 0);             // per proof: the words before the per-query blocks
     // ---- LDE: lde[proof][poly][j] = f(7 w^bitrev(j))
     H2W_HIP(hipEventRecord(p->ev[0], s));
-    hipLaunchKernelGGL(k_scale_pad, dim3(blocks(L, 256), (unsigned)(n * np)), dim3(256), 0, s, coeffs_dev, N, (uint64_t)7, L, p->lde);
-    ntt_dif(p, p->lde, lb, n * np, s);
+    hipLaunchKernelGGL(k_scale_pad, dim3(blocks(L, 256), (unsigned)(n * np)), dim3(256), 0, s, coeffs_dev, N, (uint64_t)7, L, B.lde.get());
+    ntt_dif(p, B.lde.get(), lb, n * np, s);
     H2W_HIP(hipEventRecord(p->ev[1], s));
     // ---- Merkle commitments of the oracles: tree[proof][oracle]
     const uint64_t tstride = 2 * L;
     for (int o = 0; o < no; o++)
-        hipLaunchKernelGGL(k_leaves_initial, dim3(blocks(L, 64), nb), dim3(64), 0, s, p->dk, mode, p->lde + (uint64_t)p->poly0[o] * L, d.oracle_polys[o], L, p->tree + o * tstride, (uint64_t)np * L, no * tstride);
-    build_trees(p, p->tree, lb, n * no, tstride, s);
+        hipLaunchKernelGGL(k_leaves_initial, dim3(blocks(L, 64), nb), dim3(64), 0, s, p->dk.get(), mode, B.lde.get() + (uint64_t)p->poly0[o] * L, d.oracle_polys[o], L, B.tree.get() + o * tstride, (uint64_t)np * L, no * tstride);
+    build_trees(p, B.tree.get(), lb, n * no, tstride, s);
     std::vector<H4> caps(n * no * cs);
-    H2W_HIP(hipMemcpy2DAsync(caps.data(), (size_t)cs * sizeof(H4), p->tree + level_off(lb, lb - capb), tstride * sizeof(H4), (size_t)cs * sizeof(H4), n * no, hipMemcpyDeviceToHost, s));
+    H2W_HIP(hipMemcpy2DAsync(caps.data(), (size_t)cs * sizeof(H4), B.tree.get() + level_off(lb, lb - capb), tstride * sizeof(H4), (size_t)cs * sizeof(H4), n * no, hipMemcpyDeviceToHost, s));
     H2W_HIP(hipEventRecord(p->ev[2], s));
     H2W_HIP(hipStreamSynchronize(s));
     const int o_trace = 0, o_perm = sh.n_perm_z > 0 ? 1 : -1, o_quot = no - 1;
@@ -617,11 +618,11 @@ int h2w_prove_fri_batch(h2w_prover *p, const uint64_t *coeffs_dev, const uint64_
     }
     // ---- openings: batch 0 = every polynomial at zeta, batch 1 = trace and permutation Zs at g zeta
     const int nz = np, nzn = np - d.oracle_polys[o_quot], eb = p->eval_blocks; const uint64_t pstride = (uint64_t)(nz + nzn) * eb;
-    H2W_HIP(hipMemcpyAsync(p->pts, pts.data(), 2 * n * sizeof(gle_t), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_eval_partial, dim3((unsigned)eb, (unsigned)nz, nb), dim3(256), 0, s, coeffs_dev, N, p->pts, p->partial, (uint64_t)np * N, pstride);
-    if (nzn > 0) hipLaunchKernelGGL(k_eval_partial, dim3((unsigned)eb, (unsigned)nzn, nb), dim3(256), 0, s, coeffs_dev, N, p->pts + n, p->partial + (size_t)nz * eb, (uint64_t)np * N, pstride);
+    H2W_HIP(hipMemcpyAsync(B.pts.get(), pts.data(), 2 * n * sizeof(gle_t), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_eval_partial, dim3((unsigned)eb, (unsigned)nz, nb), dim3(256), 0, s, coeffs_dev, N, B.pts.get(), B.partial.get(), (uint64_t)np * N, pstride);
+    if (nzn > 0) hipLaunchKernelGGL(k_eval_partial, dim3((unsigned)eb, (unsigned)nzn, nb), dim3(256), 0, s, coeffs_dev, N, B.pts.get() + n, B.partial.get() + (size_t)nz * eb, (uint64_t)np * N, pstride);
     std::vector<gle_t> part(n * pstride);
-    H2W_HIP(hipMemcpyAsync(part.data(), p->partial, part.size() * sizeof(gle_t), hipMemcpyDeviceToHost, s));
+    H2W_HIP(hipMemcpyAsync(part.data(), B.partial.get(), part.size() * sizeof(gle_t), hipMemcpyDeviceToHost, s));
     H2W_HIP(hipStreamSynchronize(s));
     std::vector<gle_t> opens(n * 2 * MAX_BATCH_POLYS), alphas(n);
     for (uint64_t b = 0; b < n; b++) {
@@ -639,7 +640,7 @@ int h2w_prove_fri_batch(h2w_prover *p, const uint64_t *coeffs_dev, const uint64_
         for (int i = 0; i < nq; i++) { *w++ = open0[nc + npz + i].c[0]; *w++ = open0[nc + npz + i].c[1]; }
     }
     // ---- F = (G_0 - G_0(zeta)) / (X - zeta) * alpha^{n_1} + (G_1 - G_1(g zeta)) / (X - g zeta)
-    gle_t *F = p->Fa, *Fo = p->Fb;
+    gle_t *F = B.Fa.get(), *Fo = B.Fb.get();
     H2W_HIP(hipMemsetAsync(F, 0, n * L * sizeof(gle_t), s));
     std::vector<QuotArgs> qa(n);
     for (int bt = 0; bt < 2; bt++) {
@@ -651,10 +652,10 @@ int h2w_prove_fri_batch(h2w_prover *p, const uint64_t *coeffs_dev, const uint64_
             for (int i = 0; i < nbp; i++) { A.ap[i] = ap; A.gz = gle_add(A.gz, gle_mul(ap, open[i])); ap = gle_mul(ap, alphas[b]); }
             A.an = ap;
         }
-        H2W_HIP(hipMemcpyAsync(p->qargs, qa.data(), n * sizeof(QuotArgs), hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_quot_terms, dim3((unsigned)p->scan_blocks, nb), dim3(256), 0, s, p->qargs, p->T, p->totals);
-        hipLaunchKernelGGL(k_suffix_totals, dim3(nb), dim3(64), 0, s, p->totals, p->carry, p->scan_blocks);
-        hipLaunchKernelGGL(k_quot_finish, dim3((unsigned)p->scan_blocks, nb), dim3(256), 0, s, p->qargs, p->T, p->carry, F, L);
+        H2W_HIP(hipMemcpyAsync(B.qargs.get(), qa.data(), n * sizeof(QuotArgs), hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_quot_terms, dim3((unsigned)p->scan_blocks, nb), dim3(256), 0, s, B.qargs.get(), B.T.get(), B.totals.get());
+        hipLaunchKernelGGL(k_suffix_totals, dim3(nb), dim3(64), 0, s, B.totals.get(), B.carry.get(), p->scan_blocks);
+        hipLaunchKernelGGL(k_quot_finish, dim3((unsigned)p->scan_blocks, nb), dim3(256), 0, s, B.qargs.get(), B.T.get(), B.carry.get(), F, L);
         H2W_HIP(hipStreamSynchronize(s));                      // qa is reused by the second batch
     }
     H2W_HIP(hipEventRecord(p->ev[3], s));
@@ -663,19 +664,19 @@ int h2w_prove_fri_batch(h2w_prover *p, const uint64_t *coeffs_dev, const uint64_
     std::vector<H4> fcap(n * cs);
     for (int st = 0; st < d.n_steps; st++) {
         const int ab = d.arity[st]; const uint64_t m = 1ull << cur, nl = m >> ab;
-        hipLaunchKernelGGL(k_split_scale, dim3(blocks(m, 256), nb), dim3(256), 0, s, F, m, shift, p->fv[st], L);
-        ntt_dif(p, p->fv[st], cur, 2 * n, s);
-        hipLaunchKernelGGL(k_leaves_fri, dim3(blocks(nl, 64), nb), dim3(64), 0, s, p->dk, mode, p->fv[st], ab, m, p->ftree[st], 2 * nl);
-        build_trees(p, p->ftree[st], cur - ab, n, 2 * nl, s);
-        H2W_HIP(hipMemcpy2DAsync(fcap.data(), (size_t)cs * sizeof(H4), p->ftree[st] + level_off(cur - ab, cur - ab - capb), 2 * nl * sizeof(H4), (size_t)cs * sizeof(H4), n, hipMemcpyDeviceToHost, s));
+        hipLaunchKernelGGL(k_split_scale, dim3(blocks(m, 256), nb), dim3(256), 0, s, F, m, shift, B.fv[st].get(), L);
+        ntt_dif(p, B.fv[st].get(), cur, 2 * n, s);
+        hipLaunchKernelGGL(k_leaves_fri, dim3(blocks(nl, 64), nb), dim3(64), 0, s, p->dk.get(), mode, B.fv[st].get(), ab, m, B.ftree[st].get(), 2 * nl);
+        build_trees(p, B.ftree[st].get(), cur - ab, n, 2 * nl, s);
+        H2W_HIP(hipMemcpy2DAsync(fcap.data(), (size_t)cs * sizeof(H4), B.ftree[st].get() + level_off(cur - ab, cur - ab - capb), 2 * nl * sizeof(H4), (size_t)cs * sizeof(H4), n, hipMemcpyDeviceToHost, s));
         H2W_HIP(hipStreamSynchronize(s));
         for (uint64_t b = 0; b < n; b++) {
             memcpy(&head[b * pl.queries + pl.commit_caps + (uint64_t)st * cs * 4], &fcap[b * cs], (size_t)cs * 32);
             for (int i = 0; i < cs; i++) chs[b].observe_hash(mode, fcap[b * cs + i]);
             pts[2 * n + b] = chs[b].ext_challenge();
         }
-        H2W_HIP(hipMemcpyAsync(p->pts + 2 * n, &pts[2 * n], n * sizeof(gle_t), hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_fold, dim3(blocks(nl, 256), nb), dim3(256), 0, s, F, Fo, nl, ab, p->pts + 2 * n, L);
+        H2W_HIP(hipMemcpyAsync(B.pts.get() + 2 * n, &pts[2 * n], n * sizeof(gle_t), hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_fold, dim3(blocks(nl, 256), nb), dim3(256), 0, s, F, Fo, nl, ab, B.pts.get() + 2 * n, L);
         H2W_HIP(hipStreamSynchronize(s));                      // the betas are overwritten by the next step
         gle_t *t = F; F = Fo; Fo = t;
         shift = gl_exp(shift, 1ull << ab); cur -= ab;
@@ -697,14 +698,14 @@ int h2w_prove_fri_batch(h2w_prover *p, const uint64_t *coeffs_dev, const uint64_
         memcpy(PA.state, st, sizeof(st));
         for (int i = 0; i < SPONGE_RATE; i++) PA.tail[i] = i < PA.ntail ? ch.in[full + i] : 0;
     }
-    H2W_HIP(hipMemcpyAsync(p->pargs, pa.data(), n * sizeof(PowArgs), hipMemcpyHostToDevice, s));
-    H2W_HIP(hipMemcpyAsync(p->best, wit.data(), n * 8, hipMemcpyHostToDevice, s));
+    H2W_HIP(hipMemcpyAsync(B.pargs.get(), pa.data(), n * sizeof(PowArgs), hipMemcpyHostToDevice, s));
+    H2W_HIP(hipMemcpyAsync(B.best.get(), wit.data(), n * 8, hipMemcpyHostToDevice, s));
     // 2^pow_bits candidates per round (63 % of the proofs finish in each; finished proofs' blocks exit at once)
     const int round_bits = sh.pow_bits < 8 ? 8 : sh.pow_bits > 22 ? 22 : sh.pow_bits;
     for (uint64_t first = 0;; first += 1ull << round_bits) {
         if (first >> 40) { set_error("h2w_prove_fri_batch: no proof-of-work witness found"); return -1; }
-        hipLaunchKernelGGL(k_pow, dim3(1u << (round_bits - 6), nb), dim3(64), 0, s, p->dk, p->pargs, first, p->best);
-        H2W_HIP(hipMemcpyAsync(wit.data(), p->best, n * 8, hipMemcpyDeviceToHost, s));
+        hipLaunchKernelGGL(k_pow, dim3(1u << (round_bits - 6), nb), dim3(64), 0, s, p->dk.get(), B.pargs.get(), first, B.best.get());
+        H2W_HIP(hipMemcpyAsync(wit.data(), B.best.get(), n * 8, hipMemcpyDeviceToHost, s));
         H2W_HIP(hipStreamSynchronize(s));
         bool all = true; for (uint64_t b = 0; b < n; b++) all = all && wit[b] != ~0ull;
         if (all) break;
@@ -719,12 +720,12 @@ int h2w_prove_fri_batch(h2w_prover *p, const uint64_t *coeffs_dev, const uint64_
         ch.observe(wit[b]); (void)ch.challenge();
         for (int q = 0; q < nq; q++) xs[b * nq + q] = ch.challenge() & (L - 1);
     }
-    H2W_HIP(hipMemcpyAsync(p->x_index, xs.data(), xs.size() * 8, hipMemcpyHostToDevice, s));
-    GatherArgs G; G.lde = p->lde; G.L = L; G.lde_stride = (uint64_t)np * L; G.lb = lb; G.capb = capb; G.no = no; G.tree = p->tree; G.tree_stride = tstride;
+    H2W_HIP(hipMemcpyAsync(B.x_index.get(), xs.data(), xs.size() * 8, hipMemcpyHostToDevice, s));
+    GatherArgs G; G.lde = B.lde.get(); G.L = L; G.lde_stride = (uint64_t)np * L; G.lb = lb; G.capb = capb; G.no = no; G.tree = B.tree.get(); G.tree_stride = tstride;
     for (int o = 0; o < 3; o++) { G.npoly[o] = o < no ? d.oracle_polys[o] : 0; G.poly0[o] = p->poly0[o]; G.init_off[o] = pl.init_off[o]; }
     G.n_steps = d.n_steps;
-    { uint64_t m = L; for (int st = 0; st < MAX_STEPS; st++) { G.ab[st] = st < d.n_steps ? d.arity[st] : 0; G.fv[st] = p->fv[st]; G.fn[st] = m; G.ftree[st] = p->ftree[st]; G.step_off[st] = pl.step_off[st]; if (st < d.n_steps) m >>= d.arity[st]; } }
-    G.proof = proofs_dev; G.proof_stride = pl.total; G.q_base = pl.queries; G.q_words = pl.query_words; G.x_index = p->x_index;
+    { uint64_t m = L; for (int st = 0; st < MAX_STEPS; st++) { G.ab[st] = st < d.n_steps ? d.arity[st] : 0; G.fv[st] = B.fv[st].get(); G.fn[st] = m; G.ftree[st] = B.ftree[st].get(); G.step_off[st] = pl.step_off[st]; if (st < d.n_steps) m >>= d.arity[st]; } }
+    G.proof = proofs_dev; G.proof_stride = pl.total; G.q_base = pl.queries; G.q_words = pl.query_words; G.x_index = B.x_index.get();
     if (nq > 0) hipLaunchKernelGGL(k_gather, dim3((unsigned)nq, nb), dim3(64), 0, s, G);
     H2W_HIP(hipMemcpy2DAsync(proofs_dev, pl.total * 8, head.data(), pl.queries * 8, pl.queries * 8, n, hipMemcpyHostToDevice, s));
     if (sh.n_pis > 0) H2W_HIP(hipMemcpy2DAsync(proofs_dev + pl.pis, pl.total * 8, public_inputs, (size_t)sh.n_pis * 8, (size_t)sh.n_pis * 8, n, hipMemcpyHostToDevice, s));

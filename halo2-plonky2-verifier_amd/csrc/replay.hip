@@ -70,7 +70,7 @@ struct TracedPlan {
     uint32_t nglp = 0; uint64_t n_candidates = 0; std::vector<uint32_t> h_glp_unit; DevBuf<uint32_t> d_glp_unit;
     // fused PoseidonBN254 permutations: per proof nbnp list entries; items: the (proof, entry) pairs of this rank's blocks (sharded calls, beside the lane table)
     bool bn_flag = false; uint32_t nbnp = 0; uint64_t n_bn_left = 0; std::vector<BnpD> h_bnp; DevBuf<BnpD> d_bnp; std::vector<uint32_t> h_bnp0; DevBuf<uint32_t> d_bnp0, d_bn_items; uint64_t n_bn_items = 0;
-    hipEvent_t tev[16]; int n_tev = 0, tev_used = 0; bool timing = false;      // h2w_plan_trace_timing: around every kernel of the last call
+    DevEvent tev[16]; int tev_used = 0; bool timing = false;      // h2w_plan_trace_timing: around every kernel of the last call
     // sharding: the depth-1 instances are the units (query q = the q-th in tape order); why_unshardable empty: they tile the stream behind the root's block
     std::string why_unshardable; std::vector<uint32_t> h_unit;      // h_unit: the unit of every instance (InstD order)
     std::vector<uint32_t> h_lanes, lane0; DevBuf<uint32_t> d_lanes; uint64_t lanes_n = 0; int lanes_rank = -1, lanes_world = 0;      // the lane table of the last (n, rank, world)
@@ -370,11 +370,7 @@ static TracedWs traced_ws(const h2w_plan *p, uint64_t n) {
 }
 uint64_t traced_workspace_bytes(const h2w_plan *p, uint64_t n) { return traced_ws(p, n).total; }
 uint64_t traced_status_offset(const h2w_plan *p, uint64_t n, bool flags) { const TracedWs w = traced_ws(p, n); return flags ? w.lflag : w.status; }
-void traced_free(h2w_plan *p) {
-    TracedPlan *t = p->traced; if (!t) return;
-    for (int i = 0; i < t->n_tev; i++) (void)hipEventDestroy(t->tev[i]);
-    delete t; p->traced = nullptr;
-}
+void traced_free(h2w_plan *p) { delete p->traced; p->traced = nullptr; }      // (its tables and events are owners: devbuf.h)
 // The lanes a rank launches (sharded calls), template by template: the root lane of every proof - those of the proofs the rank owns first, then, from
 // the next wavefront on, the others marked with bit 31 (they compute the values the units import, and store nothing else) -, and of every deeper
 // template only the (proof, instance) pairs whose unit (proof * nq + q) % world == rank (h2w_plan_shard_block, distributed.py unit_owner).
@@ -598,7 +594,7 @@ extern "C" int h2w_plan_trace_timing(h2w_plan *p, float *ms, uint32_t cap) {
     if (!p || !ms) { set_error("h2w_plan_trace_timing: null argument"); return -1; }
     if (!p->traced || p->device < 0) { set_error("h2w_plan_trace_timing: not a traced plan on a device"); return -1; }
     TracedPlan *t = p->traced; DeviceGuard dg(p->device);
-    if (!t->timing) { for (; t->n_tev < 16; t->n_tev++) H2W_HIP(hipEventCreate(&t->tev[t->n_tev])); t->timing = true; return 0; }
+    if (!t->timing) { for (DevEvent &e : t->tev) if (e.create() != 0) return -1; t->timing = true; return 0; }
     if (t->tev_used < 2) return 0;
     H2W_HIP(hipEventSynchronize(t->tev[t->tev_used - 1]));
     int n = 0;

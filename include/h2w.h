@@ -524,7 +524,9 @@ int            h2w_chipbatch_configure(h2w_chipbatch *, int option, uint64_t val
  * h2w_prover_new accepts the shapes h2w_plan_compile accepts, with degree_bits + rate_bits in [1, 24] and n_pis <= 64; it refuses any
  * other with "unsupported shape: <reason>" before it looks for a device.  That is stricter than its own earlier check: num_queries in
  * [1, 128] (was up to 4096), a final polynomial of at most 128 coefficients (was 2048), lookup_bits in [2, 28], hash_mode 0 or 1,
- * cap_height in [0, 6], pow_bits <= 63, at most 8 fold steps - what the witness generator takes, so every proof made can be witnessed. */
+ * cap_height in [0, 6], pow_bits <= 63, at most 8 fold steps - what the witness generator takes, so every proof made can be witnessed.
+ * The handle carries its device like every other: device_id must be below h2w_device_count() ("device_id out of range" otherwise), and
+ * h2w_prover_new, h2w_prove_fri(_batch) and h2w_prover_free make it current for their own duration only. */
 typedef struct h2w_prover h2w_prover;
 h2w_prover *h2w_prover_new(const h2w_shape_t *, const h2w_poseidon_consts_t *, int device_id);
 void        h2w_prover_free(h2w_prover *);

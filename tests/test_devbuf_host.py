@@ -2,7 +2,10 @@
 (tests/cpp/devbuf_check.cpp, compiled by hipcc because the header includes the HIP runtime) holds it to its contract: a failed alloc / upload returns
 -1, leaves the buffer empty and sets the error text; moves leave the source empty; reset() of an empty buffer and the destructor of a never-filled one
 do nothing.  Without a device every hipMalloc fails, which is exactly the failure path; with one the program also round-trips a one-element and a
-zero-element upload (non-null pointer, size 0).  It branches on its first hipMalloc, so it runs on either kind of machine."""
+zero-element upload (non-null pointer, size 0).  It branches on its first hipMalloc, so it runs on either kind of machine.  The event and stream
+owners of the same header (DevEvent, DevStream) are held to the same contract by the same program: without a device create() fails (-1, empty,
+error text; moves and resets of empty owners are no-ops), with one an event is created, moved, recorded and waited for on the null stream, and a
+stream is created with flags and priority and destroyed."""
 import os
 import re
 import shutil
@@ -22,7 +25,7 @@ def test_devbuf_contract(tmp_path):
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and "FAIL" not in r.stdout, r.stdout + r.stderr
     m = re.search(r"^OK device=([01]) checks=(\d+)$", r.stdout, flags=re.M)
-    assert m and int(m.group(2)) >= 10, r.stdout
+    assert m and int(m.group(2)) >= 21, r.stdout
 
 
 def test_the_header_is_host_code_on_the_runtime_alone():

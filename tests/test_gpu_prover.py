@@ -312,3 +312,61 @@ def test_config5_valid_proof(h2w, h2w_api, oracle, published):
     assert ctx.num_cells() == plan.num_cells == 59708779 + 328424 + 1                # verify_proof cells + witness-load cells + the flow's load_zero (stark/mod.rs:483-508)
     assert advice.cpu().numpy().tobytes() == ctx.advice_bytes()
     ctx.close(); plan.close()
+
+
+def _hip_current_device():
+    """hipGetDevice of the one HIP runtime this process holds (the one libh2w.so is bound to: the package's _preload_hip_runtime)."""
+    paths = sorted({line.split()[-1] for line in open("/proc/self/maps") if "libamdhip64" in line})
+    assert len(paths) == 1, paths
+    dev = C.c_int(-1)
+    assert C.CDLL(paths[0]).hipGetDevice(C.byref(dev)) == 0
+    return dev.value
+
+
+def test_device_id_out_of_range_is_refused(h2w, h2w_api, published):
+    """A DeviceGuard whose switch fails is silent, so h2w_prover_new checks device_id against the device count itself (h2w_plan_compile's
+    wording): null and an error that names device_id - the buffers must not land on the caller's device; the next handle is unaffected."""
+    _, kh = published
+    ndev = h2w.lib().h2w_device_count()
+    if ndev == 0:
+        pytest.skip("no HIP device")
+    sh = h2w.fibonacci_shape(6, 2)
+    assert not h2w.lib().h2w_prover_new(C.byref(sh), C.byref(kh), ndev)
+    assert "device_id" in h2w.last_error()
+    h2w_api.Prover(sh, kh, 0).close()
+
+
+def test_prover_on_another_device_restores_the_callers(h2w, h2w_api, oracle, published):
+    """The device rule of include/h2w.h for the prover handle: with device 0 current, a prover on device 1 (coefficients and proofs on cuda:1)
+    proves a batch of 2, then one of 3 - which regrows its buffers -, and after the constructor, each call and close() the thread's current
+    device is still 0; the proofs equal, word for word, those of a handle on device 0 from the same coefficients."""
+    import numpy as np
+    import torch
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs two GPUs")
+    _, kh = published
+    sh = h2w.fibonacci_shape(7, 5, rate_bits=2, hash_mode=0); osh = oracle.fibonacci_shape(7, 5, rate_bits=2, hash_mode=0)
+    ins = [oracle.prove_fri_inputs(osh, 700 + i) for i in range(3)]
+    host = np.concatenate([np.frombuffer(c, dtype=np.int64) for c, _ in ins])
+    pis = [int(x) for _, p_ in ins for x in list(p_)[:sh.n_pis]]
+    torch.cuda.set_device(0)
+    assert _hip_current_device() == 0
+
+    def proofs_on(dev):
+        pr = h2w_api.Prover(sh, kh, dev)
+        assert _hip_current_device() == 0
+        coefs = torch.from_numpy(host).to(f"cuda:{dev}")
+        out = []
+        for n in (2, 3):
+            proofs = torch.full((n * pr.proof_words,), 0x5A5A5A5A5A5A5A5A, dtype=torch.int64, device=f"cuda:{dev}")
+            torch.cuda.synchronize(dev)
+            pr.prove_batch(coefs.data_ptr(), pis[:n * sh.n_pis], proofs.data_ptr(), n, 0)      # (the null stream of the handle's device)
+            assert _hip_current_device() == 0
+            out.append(proofs.cpu().numpy().view(np.uint64))
+        pr.close()
+        assert _hip_current_device() == 0
+        return out
+
+    other, own = proofs_on(1), proofs_on(0)
+    for a, b in zip(other, own):
+        assert a.shape == b.shape and (a == b).all()
