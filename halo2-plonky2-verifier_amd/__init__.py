@@ -80,6 +80,9 @@ H2W_TRACE_FUSE_BN_PERMUTE = 2
 H2W_OP_GL_PERMUTE, H2W_OP_BN_PERMUTE, H2W_OP_HASH_NO_PAD, H2W_OP_TWO_TO_ONE, H2W_OP_MERKLE_VERIFY = 9, 10, 11, 12, 13
 H2W_CHIPBATCH_MAX_N_IN = 4096
 H2W_CHIPBATCH_OPT_CHUNK = 1
+# flags of h2w_verdict_t (include/h2w.h 3b)
+(H2W_VERDICT_POW, H2W_VERDICT_MERKLE_TRACE, H2W_VERDICT_MERKLE_PERM_Z, H2W_VERDICT_MERKLE_QUOTIENT, H2W_VERDICT_MERKLE_STEP, H2W_VERDICT_FOLD,
+ H2W_VERDICT_FINAL) = 1, 2, 4, 8, 16, 32, 64
 
 SYMBOLS = {
     "h2w_abi_version": (C.c_int, []),
@@ -205,6 +208,8 @@ SYMBOLS = {
     "h2w_plan_num_record_cells": (C.c_uint64, [_vp]),
     "h2w_plan_direct_cells": (C.c_int, [_vp, _vp]),
     "h2w_plan_record_ranges": (C.c_int, [_vp, _vp]),
+    "h2w_fri_verdict_batch": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp]),
+    "h2w_plan_proof_layout": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.c_size_t]),
     "h2w_prover_new": (_vp, [C.POINTER(Shape), C.POINTER(PoseidonConsts), C.c_int]),
     "h2w_prover_free": (None, [_vp]),
     "h2w_prover_num_polys": (C.c_uint64, [_vp]),

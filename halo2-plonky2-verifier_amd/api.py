@@ -380,6 +380,44 @@ class Plan:
         _ck(self.L.h2w_plan_status(self.p, workspace_ptr, n, st, stream), "h2w_plan_status")
         return list(st)
 
+    # ---- verdicts without a witness (include/h2w.h 3b)
+    def verdict(self, proofs_ptr, n, stream=0, verdict_ptr=None):
+        """h2w_fri_verdict_batch: per proof (flags, n_failed, first_query, status); a proof is accepted iff flags == 0 and status == 0.
+        verdict_ptr: device memory of n x 4 uint32 - the call is then enqueued on `stream` and nothing is returned (no synchronisation).
+        Without it the verdicts go to a torch buffer on the plan's device, the device is synchronised and they come back as a list of tuples."""
+        if verdict_ptr is not None:
+            _ck(self.L.h2w_fri_verdict_batch(self.p, proofs_ptr, n, verdict_ptr, stream), "h2w_fri_verdict_batch")
+            return None
+        if n == 0:
+            _ck(self.L.h2w_fri_verdict_batch(self.p, proofs_ptr, 0, None, stream), "h2w_fri_verdict_batch")
+            return []
+        import torch
+        dev = f"cuda:{self.device_id}"
+        buf = torch.empty(4 * n, dtype=torch.int32, device=dev) if torch.cuda.is_available() else None      # (no device: the library says so)
+        _ck(self.L.h2w_fri_verdict_batch(self.p, proofs_ptr, n, buf.data_ptr() if buf is not None else None, stream), "h2w_fri_verdict_batch")
+        torch.cuda.synchronize(dev)
+        w = [int(x) & 0xFFFFFFFF for x in buf.cpu().tolist()]
+        return [tuple(w[4 * i:4 * i + 4]) for i in range(n)]
+
+    def proof_layout(self):
+        """h2w_plan_proof_layout: the flat proof layout of the shape, in u64 words, as a dict - the scalar fields, and per initial oracle
+        ("oracles") and per fold step ("steps") a dict {off, leaf, sibs}: within a query the leaf starts at off, its siblings (4 words each) at
+        off + leaf.  Sibling j of a tree of query q: queries + q * query_words + off + leaf + 4 j."""
+        n = self.L.h2w_plan_proof_layout(self.p, None, 0)
+        if n < 0:
+            raise H2WError("h2w_plan_proof_layout: " + last_error())
+        out = (C.c_uint64 * n)()
+        _ck(min(self.L.h2w_plan_proof_layout(self.p, out, n), 0), "h2w_plan_proof_layout")
+        w = [int(x) for x in out]
+        names = ("trace_cap", "quotient_cap", "openings", "perm_cap", "pow_witness", "final_poly", "commit_caps", "queries", "query_words", "pis", "total", "cap_size")
+        d = dict(zip(names, w))
+        k = len(names)
+        for key in ("oracles", "steps"):
+            cnt = w[k]; k += 1
+            d[key] = [dict(off=w[k + 3 * i], leaf=w[k + 3 * i + 1], sibs=w[k + 3 * i + 2]) for i in range(cnt)]
+            k += 3 * cnt
+        return d
+
     # ---- keygen-side metadata and column layout (SURVEY §8f rows 1-2)
     def selectors(self):
         """Context::selector of the shape's cell stream as a bytes bitmap (bit i of byte i // 8 = cell i)."""

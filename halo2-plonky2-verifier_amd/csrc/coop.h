@@ -439,6 +439,7 @@ constexpr BnSrc bn_map_partial(int c) {
 }
 
 enum { QUAD_VALUES = 1, QUAD_EMIT = 2, QUAD_FUSED = 3 };      // QUAD_FUSED: one quad walks its strand AND emits every unit of it (one pass, serial in the path's depth)
+constexpr int QUAD_VERDICT = 4;      // the QUAD_VALUES walk with no store at all: no unit states, no S-box values, and the cap lookup's value taken (verdict.hip)
 template <bool COLS, int MODE> struct QuadSinkT : SinkBase {
     static constexpr bool kBnUnits = true; static constexpr int kHashMode = 1;
     rec_t *recs; uint64_t nrec; fr_t *out; uint64_t cell_off; const uint16_t *ncells; int l4; ColPolicy<COLS> cc;
@@ -601,7 +602,7 @@ template <bool COLS, int MODE> struct QuadSinkT : SinkBase {
     __device__ __forceinline__ bool tail_skip() const { return MODE == QUAD_VALUES || (MODE == QUAD_EMIT && !act); }      // the cap lookup: cells only (no value anyone uses)
     // One permutation unit of the strand (PoseidonBN254PermutationChip::permute, hash/poseidon_bn254/permutation.rs:190-203).
     __device__ __forceinline__ bool bn_emit_inline(fr_t *st, const ValCfg &cfg, bool &zc_ref) {
-        if constexpr (MODE == QUAD_VALUES) { bn_values(st, cfg); unit_local++; return true; }
+        if constexpr (MODE == QUAD_VALUES || MODE == QUAD_VERDICT) { bn_values(st, cfg); unit_local++; return true; }
         else if constexpr (MODE == QUAD_FUSED) { bn_emit_cells<false>(st, cfg, zc_ref); return true; }
         else {
             const int k = unit_local++;
@@ -669,14 +670,14 @@ template <bool COLS, int MODE> struct QuadSinkT : SinkBase {
                     fr_t *const sb = sbu + (uint64_t)r * 3;
                     const fr9_t s0b = quad_bcast9<0>(S);
                     const fr9_t A_ = fr9_mont(fr9_sel(l == 0, S, s0p), fr9_sel(l == 0, S, kc_.kp), ninv);
-                    if (l == 0) g_store_fr(sb, fr9_pack(A_));
+                    if constexpr (MODE != QUAD_VERDICT) { if (l == 0) g_store_fr(sb, fr9_pack(A_)); }
                     const fr9_t X2b = quad_bcast9<0>(A_);
                     S = fr9_add_if(l > 0, S, A_);                                       // lanes k: a sum of two until the end of the round
                     const fr9_t B_ = fr9_mont(fr9_sel(l == 0, X2b, fr9_sel(l == 1, s0b, S)), fr9_sel(l == 0, X2b, kc_.k2), ninv);
-                    if (l == 0) g_store_fr(sb + 1, fr9_pack(B_));
+                    if constexpr (MODE != QUAD_VERDICT) { if (l == 0) g_store_fr(sb + 1, fr9_pack(B_)); }
                     const fr9_t X4b = quad_bcast9<0>(B_), XAb = quad_bcast9<1>(B_);
                     const fr9_t C_ = fr9_mont(fr9_sel(l == 1, S, X4b), fr9_sel(l == 0, XAb, fr9_sel(l == 1, kc_.k1, s0b)), ninv);
-                    if (l == 2) g_store_fr(sb + 2, fr9_pack(C_));
+                    if constexpr (MODE != QUAD_VERDICT) { if (l == 2) g_store_fr(sb + 2, fr9_pack(C_)); }
                     s0p = fr9_add(quad_bcast9<2>(C_), kc_.kc);                          // a sum of two: only ever multiplied by a constant
                     fr9_t incl = fr9_add_if(l == 0, fr9_sel(l < 2, C_, B_), kc_.kx);    // T0 + S_0 c, S_1 s_1, S_2 s_2, S_3 s_3
                     incl = fr9_add(incl, quad_dpp9<0xB1>(incl));                         // butterfly over the quad: every lane ends with the sum of the four
@@ -700,7 +701,7 @@ template <bool COLS, int MODE> struct QuadSinkT : SinkBase {
         fr9_t one9; for (int i = 0; i < 9; i++) one9.t[i] = i == 0 ? 1u : 0u;
         fr_t s = fr9_pack(fr9_mont(S, one9, ninv));                                        // back to canonical: S / R < r + 1
         if (fr_geq_mod(s)) s = fr_sub_mod_raw(s);
-        g_store_fr(ustate + (uint64_t)unit_local * 4 + l, s);
+        if constexpr (MODE != QUAD_VERDICT) g_store_fr(ustate + (uint64_t)unit_local * 4 + l, s);
         st[0] = quad_bcast<0>(s); st[1] = quad_bcast<1>(s); st[2] = quad_bcast<2>(s); st[3] = quad_bcast<3>(s);
     }
     // PoseidonBN254 permutation with its 4,032 cells emitted by the quad itself.

@@ -69,6 +69,8 @@ struct ValCfg {
 //   note_load(word, kind), note_cap_hash(w) a witness load / a cap hash's limb decomposition, for the load kernel's items    (verifier.h)
 //   coop_load_proof(cfg) -> bool            true: the sink took WitnessChip::load_proof_with_pis over (cursor stepped past it)
 //   bn_emit_inline(st, cfg, zc) -> bool     true: the sink computed / emitted this PoseidonBN254 permutation (cfg.split_bn)
+//   compare(differ)                         a chip-level assert_equal / assert_equal_fr: whether its two sides differ          (verdict.hip's sinks count them)
+//   site(s)                                 the protocol check the comparisons that follow belong to (verifier.h SITE_*)
 struct SinkBase {
     static constexpr bool kCoop = false, kSplitOnly = false, kBnUnits = false, kDevSponge = false; static constexpr int kHashMode = -1;
     HF void gate() {}
@@ -84,6 +86,8 @@ struct SinkBase {
     HF void note_cap_hash(uint64_t) {}
     HF bool coop_load_proof(const ValCfg &) { return false; }
     HF bool bn_emit_inline(fr_t *, const ValCfg &, bool &) { return false; }
+    HF void compare(bool) {}
+    HF void site(int) {}
 };
 
 template <class Sink> struct ValBackend {
@@ -110,8 +114,9 @@ template <class Sink> struct ValBackend {
     HF void cell64(uint64_t v) { sink.cell(fr_from_u64(v)); }
     // keygen markers for the NEXT direct cell (no-ops on the device sinks; the shape compiler's PlanSink turns them into the
     // selector / lookup bitmaps of SURVEY §8f): G = a vertical gate starts there, LK = the cell is registered for the range lookup
-    HF void assert_equal(Gl, Gl) {}                  // copy constraints are not part of the advice stream
-    HF void assert_equal_fr(const Fr &, const Fr &) {}
+    HF void assert_equal(Gl a, Gl b) { sink.compare(a != b); }      // copy constraints are not part of the advice stream: a sink may look at the verdict (SinkBase: it does not)
+    HF void assert_equal_fr(const Fr &a, const Fr &b) { sink.compare(!fr_eq(a, b)); }
+    HF void site(int s) { sink.site(s); }
     HF void G() { sink.gate(); }
     HF void LK() { sink.lookup(); }
 

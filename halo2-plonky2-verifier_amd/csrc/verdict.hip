@@ -1,0 +1,230 @@
+// verdict.hip - per-proof verdicts without a witness (include/h2w.h 3b): h2w_fri_verdict_batch, h2w_plan_proof_layout.
+//
+// The verifier gadget's protocol checks are assert_equal copy constraints (chips.h MerkleTreeChip, verifier.h query_round): they emit no cells, so a
+// stream made from a rejected proof looks like one made from an accepted proof.  Every value those checks compare is computed by the value kernels
+// of a witness call anyway; this unit runs the same single-source chips on sinks that keep NOTHING but the comparisons (valbackend.h SinkBase
+// compare / site): the only global stores of its kernels are the challenge blocks and the verdict words.
+//   launch_prologue_values  k_prologue_values as it is (glue.hip), with a shard map under which no proof's block is owned: what a non-owner rank of a
+//                           sharded run does - values only -> challenge blocks, the prologue's status word
+//   k_verdict_init          one lane per proof: the verdict's start value, the PoW bit (fri/mod.rs:130-145) from the challenge block
+//   k_verdict_check         one lane per (proof, load item): status 4, as k_prologue_load (batch.hip) decides it
+//   k_verdict_glue          one lane per (proof, query): Verifier::query_round on a sink without cells - the fold steps' consistency checks and the
+//                           final polynomial's evaluation
+//   k_verdict_merkle_gl     Goldilocks caps: one wavefront per (proof, query, tree), permutations on glp_permute_lanes (k_merkle_gl_values without list or records)
+//   k_verdict_merkle_bn     PoseidonBN254 caps: four lanes per (proof, query, tree) on the lazy nine-limb values walk (coop.h QuadSinkT bn_values, QUAD_VERDICT:
+//                           no unit states, no S-box values; the cap lookup's value is taken)
+//   k_verdict_finish        one lane per proof: status 4 where no strand reported a condition of its own (h2w_plan_status's order)
+// Flattened like glue.hip: the sinks below exist in this unit alone (field.h HNI).
+#define H2W_FLATTEN_CHIPS 1
+#include <hip/hip_runtime.h>
+#include <string>
+#include "plan.h"
+
+namespace h2w {
+
+static_assert(sizeof(h2w_verdict_t) == 16, "four words per proof");
+
+// what a sink of this unit does with a comparison: count it, flag its site, note its query - on the one lane of the strand that speaks for it
+struct VerdictAcc {
+    h2w_verdict_t *v; uint32_t q; int n_perm_z, cur; bool on;
+    __device__ __forceinline__ void init(h2w_verdict_t *verdict, int p, int query, int npz, bool speaks) { v = verdict + p; q = (uint32_t)query; n_perm_z = npz; cur = SITE_NONE; on = speaks; }
+    __device__ __forceinline__ uint32_t flag() const {
+        if (cur >= SITE_FINAL) return H2W_VERDICT_FINAL;
+        if (cur >= SITE_FOLD) return H2W_VERDICT_FOLD;
+        if (cur < SITE_MERKLE) return 0;
+        const int kind = cur - SITE_MERKLE;      // verifier.h merkle_kind: without permutation Zs oracle 1 is the quotient tree
+        return kind >= 3 ? H2W_VERDICT_MERKLE_STEP : kind == 0 ? H2W_VERDICT_MERKLE_TRACE : (kind == 1 && n_perm_z > 0) ? H2W_VERDICT_MERKLE_PERM_Z : H2W_VERDICT_MERKLE_QUOTIENT;
+    }
+    __device__ __forceinline__ void compare(bool differ) {
+        if (!differ || !on) return;
+        atomicAdd(&v->n_failed, 1u); atomicOr(&v->flags, flag()); atomicMin(&v->first_query, q);
+    }
+    __device__ __forceinline__ void status(uint32_t s) { if (s && on) atomicCAS(&v->status, 0u, s); }
+};
+
+struct VerdictGlueSink : SinkBase {
+    static constexpr bool kSplitOnly = true;
+    VerdictAcc acc;
+    __device__ __forceinline__ void rec(int, uint64_t, uint64_t, uint64_t, uint64_t) {}
+    __device__ __forceinline__ void cell(const fr_t &) {}
+    __device__ __forceinline__ void skip(uint64_t, uint64_t) {}
+    __device__ __forceinline__ void compare(bool differ) { acc.compare(differ); }
+    __device__ __forceinline__ void site(int s) { acc.cur = s; }
+};
+struct VerdictCoopSink : CoopSinkT<false, true, 0> {      // (emit = false: no list entry; rec / cell hidden: no cursor either)
+    VerdictAcc acc;
+    __device__ __forceinline__ void rec(int, uint64_t, uint64_t, uint64_t, uint64_t) {}
+    __device__ __forceinline__ void cell(const fr_t &) {}
+    __device__ __forceinline__ void skip(uint64_t, uint64_t) {}
+    __device__ __forceinline__ void compare(bool differ) { acc.compare(differ); }
+    __device__ __forceinline__ void site(int s) { acc.cur = s; }
+};
+struct VerdictQuadSink : QuadSinkT<false, QUAD_VERDICT> {
+    VerdictAcc acc;
+    __device__ __forceinline__ void rec(int, uint64_t, uint64_t, uint64_t, uint64_t) {}
+    __device__ __forceinline__ void cell(const fr_t &) {}
+    __device__ __forceinline__ void skip(uint64_t, uint64_t) {}
+    __device__ __forceinline__ void compare(bool differ) { acc.compare(differ); }
+    __device__ __forceinline__ void site(int s) { acc.cur = s; }
+};
+
+struct VerdictArgs { BatchArgs A; h2w_verdict_t *verdict; uint32_t *lflag; };
+
+__global__ __launch_bounds__(256) void k_verdict_init(VerdictArgs V) {
+    const unsigned p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= (unsigned)V.A.nproofs) return;
+    const int pb = V.A.shape.pow_bits;
+    const uint64_t resp = V.A.cbs[p].fri_pow_response;
+    h2w_verdict_t v;
+    v.flags = (pb > 0 && (resp >> (64 - pb)) != 0) ? (uint32_t)H2W_VERDICT_POW : 0u;      // (pow_bits 0: a 64-bit range check of a 64-bit word)
+    // RangeChip::range_check decomposes the response into ceil((64 - pow_bits) / lookup_bits) limbs and constrains their sum to equal it: a response
+    // that does not fit the limbs breaks that copy constraint too - the one failing equality of a proof that no query owns
+    const int L = V.A.shape.lookup_bits, nl = (64 - pb + L - 1) / L;
+    v.n_failed = (nl > 1 && nl * L < 64 && (resp >> (nl * L)) != 0) ? 1u : 0u;
+    v.first_query = 0xFFFFFFFFu; v.status = V.A.status[p];
+    V.verdict[p] = v;
+}
+
+__global__ __launch_bounds__(256) void k_verdict_check(VerdictArgs V) {
+    const uint32_t items = V.A.n_load_items;      // (kinds 0-3; the cap hashes' limb decompositions behind them check nothing)
+    const uint64_t g = (uint64_t)blockIdx.x * 256 + threadIdx.x, p = g / items; const uint32_t i = (uint32_t)(g % items);
+    if (p >= (uint64_t)V.A.nproofs) return;
+    const uint64_t wk = g_load_u64(reinterpret_cast<const uint64_t *>(V.A.load_items + i));
+    const uint32_t word = (uint32_t)wk, kind = (uint32_t)(wk >> 32);
+    const uint64_t *w = V.A.proofs + p * V.A.proof_words + word; const uint64_t w0 = g_load_u64(w);
+    bool bad;
+    if (kind <= 1) bad = w0 >= GL_P;
+    else {
+        fr_t v; v.l[0] = w0; v.l[1] = g_load_u64(w + 1); v.l[2] = g_load_u64(w + 2); v.l[3] = g_load_u64(w + 3);
+        bad = kind == 2 ? (v.l[0] >= GL_P || v.l[1] >= GL_P || v.l[2] >= GL_P || v.l[3] >= GL_P) : kind == 3 ? fr_geq_mod(v) : false;
+    }
+    if (bad) atomicOr(&V.lflag[p], 4u);
+}
+
+__global__ __launch_bounds__(256) void k_verdict_finish(VerdictArgs V) {
+    const unsigned p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= (unsigned)V.A.nproofs) return;
+    if (V.verdict[p].status == 0) V.verdict[p].status = V.lflag[p];      // (the strands' conditions come first: h2w_plan_status)
+}
+
+__global__ __launch_bounds__(64) __attribute__((flatten)) void k_verdict_glue(VerdictArgs V) {
+    typedef ValBackend<VerdictGlueSink> GlueB;
+    int p, q;
+    if (!own_unit_at(V.A, blockIdx.x * blockDim.x + threadIdx.x, p, q)) return;
+    VerdictGlueSink sink; sink.acc.init(V.verdict, p, q, V.A.shape.n_perm_z, true);
+    const ChallengeBlock<GlueB> &cb = *reinterpret_cast<const ChallengeBlock<GlueB> *>(&V.A.cbs[p]);
+    ValCfg cfg = make_cfg(V.A, p); cfg.split = false;      // (kSplitOnly: the Merkle calls are the kernels' below; nothing to step over)
+    GlueB be(sink, cfg, true);
+    const h2w_shape_t shp = V.A.shape;      // (a reference into the kernel arguments would put all of them on every lane's stack)
+    Verifier<GlueB> Vf(be, shp, V.A.consts);
+    Vf.query_round(q, cb);
+    sink.acc.status(be.status);
+}
+
+__global__ __launch_bounds__(64) __attribute__((flatten)) void k_verdict_merkle_gl(VerdictArgs V) {
+    typedef ValBackend<VerdictCoopSink> CoopB;
+    __builtin_amdgcn_s_setprio(3);
+    stage_glp_consts<true>(V.A.consts, threadIdx.x, 64);
+    int p, q;
+    if (!own_unit_at(V.A, blockIdx.x, p, q)) return;
+    const int kind = merkle_kind(V.A.shape.n_perm_z, blockIdx.y);
+    VerdictCoopSink sink; coop_sink_init(sink, V.A, p, q); sink.emit = false; sink.nrec = 0; sink.cell_off = 0; sink.glp_slot = 0;
+    sink.acc.init(V.verdict, p, q, V.A.shape.n_perm_z, threadIdx.x == 0);      // wave-uniform values: lane 0 speaks
+    CoopB be(sink, make_cfg(V.A, p), true);
+    const h2w_shape_t shp = V.A.shape;
+    Verifier<CoopB> Vf(be, shp, V.A.consts);
+    Vf.merkle_strand_at(q, kind, V.A.cbs[p].fri_query_indices[q]);
+    sink.acc.status(be.status);
+}
+
+// LDS: the nine-limb tables alone.  The quads of a wavefront run in lockstep: no wavefront leaves early, tail quads redo the last strand and keep silent
+__global__ __launch_bounds__(QUAD_BLOCK) __attribute__((flatten)) void k_verdict_merkle_bn(VerdictArgs V) {
+    typedef ValBackend<VerdictQuadSink> QuadB;
+    stage_bn_consts9(V.A.bn_tab9, threadIdx.x, QUAD_BLOCK);    // (block-wide barrier inside: before any wavefront leaves)
+    const unsigned total = V.A.sh.n_own_units;
+    if (((blockIdx.x * QUAD_BLOCK + (threadIdx.x & ~63u)) >> 2) >= total) return;      // a wavefront past the last strand
+    unsigned idx = (blockIdx.x * QUAD_BLOCK + threadIdx.x) >> 2;
+    const bool tail = idx >= total;
+    if (tail) idx = total - 1;
+    int p, q; own_unit_at(V.A, idx, p, q);
+    const int kind = merkle_kind(V.A.shape.n_perm_z, blockIdx.y);
+    VerdictQuadSink sink; sink.recs = nullptr; sink.nrec = 0; sink.out = nullptr; sink.cell_off = 0; sink.ncells = nullptr; sink.l4 = threadIdx.x & 3; sink.ustate = nullptr; sink.sbx = nullptr;
+    sink.acc.init(V.verdict, p, q, V.A.shape.n_perm_z, !tail && (threadIdx.x & 3) == 0);      // quad-uniform values: lane 0 of the quad speaks
+    ValCfg mc = make_cfg(V.A, p); mc.split_bn = true;
+    QuadB be(sink, mc, true);
+    const h2w_shape_t shp = V.A.shape;
+    Verifier<QuadB> Vf(be, shp, V.A.consts);
+    Vf.merkle_strand_at(q, kind, V.A.cbs[p].fri_query_indices[q]);
+    sink.acc.status(be.status);
+}
+
+static size_t up256(size_t x) { return (x + 255) / 256 * 256; }
+
+}  // namespace h2w
+
+extern "C" {
+
+int h2w_fri_verdict_batch(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, h2w_verdict_t *verdict_dev, void *stream_) {
+    if (!p) { set_error("h2w_fri_verdict_batch: null plan"); return -1; }
+    if (p->traced) { set_error("h2w_fri_verdict_batch: a traced plan (h2w_plan_from_trace) replays a tape and has no verifier strands to judge: use a plan of h2w_plan_compile"); return -1; }
+    if (p->device < 0) { set_error("h2w_fri_verdict_batch: no HIP device — the verdict kernels only run on the GPU (no CPU fallback)"); return -1; }
+    if (n_proofs == 0) return 0;
+    if (!proofs_dev || !verdict_dev) { set_error("h2w_fri_verdict_batch: null buffer"); return -1; }
+    const uint64_t nq = (uint64_t)p->shape.num_queries;
+    if (n_proofs > 0x3fffffffull / (4 * nq)) { set_error("h2w_fri_verdict_batch: batch too large; split the batch"); return -1; }
+    DeviceGuard dg(p->device);
+    hipStream_t stream = (hipStream_t)stream_;
+    // the call's workspace: challenge blocks, the prologue's status words, the range flags
+    const size_t o_status = up256((size_t)n_proofs * sizeof(DevCB)), o_lflag = o_status + up256((size_t)n_proofs * sizeof(uint32_t)), total = o_lflag + up256((size_t)n_proofs * sizeof(uint32_t));
+    char *ws = nullptr;
+    H2W_HIP(hipMallocAsync((void **)&ws, total, stream));
+    auto run = [&]() -> int {
+        VerdictArgs V; BatchArgs &A = V.A;
+        A.shape = p->shape; A.consts = p->d_consts.get(); A.proofs = proofs_dev; A.proof_words = p->pl.total;
+        A.recs = nullptr; A.rec_stride = 0; A.out = nullptr; A.cell_stride = 0; A.cm = flat_cols();
+        A.cbs = (DevCB *)ws; A.status = (uint32_t *)(ws + o_status);
+        A.unit_state = nullptr; A.unit_sbox = nullptr; A.unit_sbox9 = nullptr; A.rowk = p->d_rowk.get(); A.glp_list = nullptr; A.glp_small_mds = p->small_mds ? 1 : 0;
+        A.bn_tab = p->d_bn_tab.get(); A.bn_tab9 = p->d_bn_tab9.get(); A.fri = p->d_fri.get();
+        A.load_items = p->d_items.get(); A.n_load_items = p->n_items; A.n_cap_items = p->n_cap_items; A.load_nrec = p->load_nrec; A.load_ncell = p->load_ncell; A.load_flag = (uint32_t *)(ws + o_lflag);
+        A.ncells = p->d_ncells.get(); A.inv_pos = p->d_inv.get(); A.inv_neg = p->d_inv.get() + INV_TAB; A.st = p->d_st.get(); A.P = p->P; A.nproofs = (int)n_proofs;
+        A.sh.compact = 0; A.sh.q_slot = 0; A.sh.unit_slot = 0; A.sh.n_own_units = 0; A.sh.n_own_proofs = 0;
+        V.verdict = verdict_dev; V.lflag = A.load_flag;
+        H2W_HIP(hipMemsetAsync(V.lflag, 0, n_proofs * sizeof(uint32_t), stream));
+        // the prologue on values: a world in which this rank owns no proof's block (own_prologue: p % world == rank never holds below 2^30 proofs)
+        A.sh.world = 0x40000000; A.sh.rank = 0x3fffffff;
+        launch_prologue_values(A, stream);
+        // every (proof, query) unit is this call's
+        A.sh.world = 1; A.sh.rank = 0; A.sh.n_own_units = (uint32_t)(n_proofs * nq); A.sh.n_own_proofs = (uint32_t)n_proofs;
+        const unsigned pgrid = (unsigned)((n_proofs + 255) / 256), nunits = A.sh.n_own_units, nkinds = (unsigned)(p->d.n_oracles + p->d.n_steps);
+        hipLaunchKernelGGL(k_verdict_init, dim3(pgrid), dim3(256), 0, stream, V);
+        if (p->n_items) hipLaunchKernelGGL(k_verdict_check, dim3((unsigned)((n_proofs * p->n_items + 255) / 256)), dim3(256), 0, stream, V);
+        hipLaunchKernelGGL(k_verdict_glue, dim3((nunits + 63) / 64), dim3(64), 0, stream, V);
+        if (p->shape.hash_mode == 0) hipLaunchKernelGGL(k_verdict_merkle_gl, dim3(nunits, nkinds), dim3(64), 0, stream, V);
+        else hipLaunchKernelGGL(k_verdict_merkle_bn, dim3((nunits * 4 + QUAD_BLOCK - 1) / QUAD_BLOCK, nkinds), dim3(QUAD_BLOCK), 0, stream, V);
+        hipLaunchKernelGGL(k_verdict_finish, dim3(pgrid), dim3(256), 0, stream, V);
+        H2W_HIP(hipGetLastError());
+        return 0;
+    };
+    const int rc = run();
+    (void)hipFreeAsync(ws, stream);
+    return rc;
+}
+
+int h2w_plan_proof_layout(const h2w_plan *p, uint64_t *out, size_t n_out) {
+    if (!p) { set_error("h2w_plan_proof_layout: null plan"); return -1; }
+    if (p->traced) { set_error("h2w_plan_proof_layout: not for traced plans (a tape names proof words, not a shape's layout)"); return -1; }
+    const ProofLayout &L = p->pl; const Derived &d = p->d;
+    const size_t need = 12 + 1 + 3 * (size_t)d.n_oracles + 1 + 3 * (size_t)d.n_steps;
+    if (!out) return (int)need;
+    if (n_out < need) { set_error("h2w_plan_proof_layout: " + std::to_string(need) + " words needed"); return -1; }
+    size_t k = 0;
+    const uint64_t head[12] = {L.trace_cap, L.quotient_cap, L.openings, L.perm_cap, L.pow_witness, L.final_poly, L.commit_caps, L.queries, L.query_words, L.pis, L.total, (uint64_t)d.cap_size};
+    for (uint64_t w : head) out[k++] = w;
+    out[k++] = (uint64_t)d.n_oracles;
+    for (int o = 0; o < d.n_oracles; o++) { out[k++] = L.init_off[o]; out[k++] = (uint64_t)d.oracle_polys[o]; out[k++] = (uint64_t)L.init_sibs; }
+    out[k++] = (uint64_t)d.n_steps;
+    for (int i = 0; i < d.n_steps; i++) { out[k++] = L.step_off[i]; out[k++] = 2ull << d.arity[i]; out[k++] = (uint64_t)L.step_sibs[i]; }
+    return (int)need;
+}
+
+}  // extern "C"

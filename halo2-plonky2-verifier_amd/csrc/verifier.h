@@ -18,6 +18,10 @@ constexpr int MK_KINDS = 3 + MAX_STEPS;   // merkle strand kinds: initial oracle
 // the kind of Merkle-strand slot `slot` (blockIdx.y of the strand kernels; the plan's emission items): the shape's initial oracles - two without
 // permutation Zs (trace, quotient), three with them - then its fold steps
 HF int merkle_kind(int n_perm_z, int slot) { const int n_or = n_perm_z > 0 ? 3 : 2; return slot < n_or ? slot : 3 + (slot - n_or); }
+// the protocol checks whose assert_equals a sink may tell apart (be.site(s), valbackend.h SinkBase): the root of Merkle strand kind k against its cap
+// entry, the consistency check of fold step i, the final polynomial's evaluation; hint checks made in between (GoldilocksChip::div, the extension
+// inverse) never fail
+enum { SITE_NONE = 0, SITE_MERKLE = 1, SITE_FOLD = SITE_MERKLE + MK_KINDS, SITE_FINAL = SITE_FOLD + MAX_STEPS };
 
 // wires produced by the prologue and consumed by the query strands (fri/mod.rs:64-69 FriChallengesWire + instance points)
 template <class B> struct ChallengeBlock {
@@ -199,6 +203,7 @@ template <class B> struct Verifier {
     struct ProofGl { B *be; uint64_t base; HF Gl operator[](int i) const { return be->proof_gl(base + (uint64_t)i); } };
     template <class BitsT> HF void merkle_strand(int q, int kind, const BitsT &bits, int n_bits, Gl cap_index) {
         const uint64_t qw = query_word(q);
+        be.site(SITE_MERKLE + kind);
         if (kind < 3) {
             const int o = kind; const uint64_t base = qw + pl.init_off[o]; const int ne = d.oracle_polys[o];
             const uint64_t capw = initial_cap_word(o), sibw = base + ne;
@@ -308,6 +313,7 @@ template <class B> struct Verifier {
             Bool *coset_index_bits = x_index_bits + ab; const int ncb = nb - ab;
             Gl within = gl.bits_to_num(x_index_bits, ab);
             Ex new_eval = ext.select_from_idx(evals, ne, within);
+            be.site(SITE_FOLD + i);
             be.assert_equal(new_eval.e[0], old_eval.e[0]); be.assert_equal(new_eval.e[1], old_eval.e[1]);       // no cells
             old_eval = compute_evaluation(subgroup_x, x_index_bits, ab, evals, cb.fri_betas[i]);
             merkle_call(q, 3 + i, coset_index_bits, ncb, cap_index);
@@ -317,6 +323,7 @@ template <class B> struct Verifier {
         {   // eval_scalar (:324-335)
             Ex point = ext.load_base(subgroup_x);
             Ex eval = ext.reduce_with_powers(d.final_poly_len, [&](int i) { return proof_ext(pl.final_poly + 2ull * i); }, point);
+            be.site(SITE_FINAL);
             be.assert_equal(eval.e[0], old_eval.e[0]); be.assert_equal(eval.e[1], old_eval.e[1]);               // no cells
         }
     }

@@ -458,6 +458,42 @@ uint64_t h2w_plan_num_record_cells(const h2w_plan *);
  * caps these are the cells the chain kernel writes itself (its permutations' 4,032 cells each, the selects, the cap lookup). */
 uint64_t h2w_plan_num_chain_cells(const h2w_plan *);
 
+/* ------------------------------------------------------------------ 3b. per-proof verdicts without a witness
+ * The verifier gadget's protocol checks are assert_equal copy constraints: they emit no cells, so the stream of a proof the circuit will reject
+ * looks like any other (only the proof-of-work range check shows in it, as a failing lookup).  h2w_fri_verdict_batch runs the VALUES of
+ * StarkChip::verify_proof alone - the Fiat-Shamir prologue, the query glue, the Merkle paths - and stores nothing but one verdict per proof:
+ * what a service runs in front of h2w_fri_witness_batch to drop the proofs that would waste a prover.
+ *   flags        H2W_VERDICT_* bits of the checks that fail
+ *   n_failed     chip-level assert_equal / assert_equal_fr calls of the proof's verify_proof whose two sides differ (a Goldilocks-Poseidon root counts
+ *                four times, hash/poseidon/hash.rs:148-159; a PoseidonBN254 root once; an extension element twice; the hint checks of
+ *                GoldilocksChip::div and the extension inverse count like any other and never fail; the PoW range check is in flags only - but
+ *                RangeChip::range_check also constrains the response to equal the sum of the ceil((64 - pow_bits) / lookup_bits) limbs it is
+ *                decomposed into, and a response that does not fit those limbs breaks that one copy constraint too: it is counted, and no query owns it)
+ *   first_query  the lowest query index that owns a failing equality, 0xFFFFFFFF if there is none
+ *   status       the word h2w_plan_status reports after h2w_fri_witness_batch on the same proofs
+ * A proof is accepted iff flags == 0 && status == 0.  Without permutation Zs (n_perm_z == 0) initial oracle 1 is the quotient tree.
+ * Stream-ordered, no synchronisation; whole proofs only (no sharded form); the call's workspace (challenge blocks) is a stream-ordered allocation
+ * inside it; the result depends on no h2w_plan_configure option; the plan's device is current for the duration of the call only.
+ * verdict_dev: [n_proofs], device.  n_proofs == 0: 0.  A plan of h2w_plan_from_trace: -1.  Without a device: -1 ("no HIP device"). */
+typedef struct { uint32_t flags, n_failed, first_query, status; } h2w_verdict_t;
+#define H2W_VERDICT_POW              1   /* pow_response does not fit 64 - pow_bits bits (fri/mod.rs:130-145) */
+#define H2W_VERDICT_MERKLE_TRACE     2   /* a root != cap entry, per tree (merkle/mod.rs:57-78) */
+#define H2W_VERDICT_MERKLE_PERM_Z    4
+#define H2W_VERDICT_MERKLE_QUOTIENT  8
+#define H2W_VERDICT_MERKLE_STEP     16   /* a commit-phase tree */
+#define H2W_VERDICT_FOLD            32   /* fri/mod.rs:403-438, the consistency check of a fold step */
+#define H2W_VERDICT_FINAL           64   /* final-polynomial evaluation */
+int h2w_fri_verdict_batch(h2w_plan *, const uint64_t *proofs_dev, uint64_t n_proofs, h2w_verdict_t *verdict_dev, void *stream);
+/* The flat proof layout of the plan's shape (WitnessChip load order, witness/mod.rs:236-294; every hash is 4 words), in u64 words:
+ *   out[0..11]  trace_cap, quotient_cap, openings, perm_cap, pow_witness, final_poly, commit_caps, queries (start of query 0), query_words (words per
+ *               query), pis, total, cap_size (hashes per cap)
+ *   out[12]     n_oracles, then per initial oracle o three words: init_off (start of its leaf within a query; its siblings follow the leaf), the leaf's
+ *               length, init_sibs (siblings, 4 words each)
+ *   then        n_steps, then per fold step i three words: step_off, the leaf's length (2 words per evaluation), step_sibs
+ * so sibling j of tree t of query q starts at queries + q * query_words + off_t + len_t + 4 j.  Returns the number of words (14 + 3 n_oracles + 3 n_steps);
+ * out == NULL: that number alone.  No device needed.  Not for traced plans (-1). */
+int h2w_plan_proof_layout(const h2w_plan *, uint64_t *out, size_t n_out);
+
 /* ------------------------------------------------------------------ 2c. batched chip ops on the device
  * n independent instances of ONE GoldilocksChip / GoldilocksQuadExtChip operation, each in a fresh Context: the operands are loaded
  * as witnesses (GoldilocksChip::load_witness, 28 cells each at lookup_bits 21; extension elements as two), then the op - the shape
@@ -496,7 +532,8 @@ int            h2w_chipbatch_run(h2w_chipbatch *, const uint64_t *operands_dev, 
  * 1 <= depth <= 32; cap_height <= min(depth, 6).
  * status_dev[i]: 0, or 4 where an operand word is outside its field (a Goldilocks word >= p, an Fr >= r: the cells are still produced,
  * from the raw value, as h2w_plan_status defines 4) or the leaf index is >= 2^depth (the cells of that instance are unspecified).
- * The chips' assert_equal emits no cells: a Merkle verdict is not part of this (h2w_check_equalities is the check).
+ * The chips' assert_equal emits no cells: a Merkle verdict is not part of this (h2w_check_equalities is the check; for whole proofs,
+ * h2w_fri_verdict_batch).
  * hash_mode 0 and GL_PERMUTE: one wavefront per instance, its permutations' records written by one wavefront per permutation;
  * hash_mode 1 and BN_PERMUTE: four lanes per instance, which emit every permutation's 4,032 cells themselves. */
 #define H2W_OP_GL_PERMUTE     9   /* PoseidonPermutationChip::permute           hash/poseidon/permutation.rs:270-284 */
