@@ -37,8 +37,10 @@ int h2w_layout_columns(const void *advice_dev, uint64_t n_cells, uint64_t proof_
     if (n_proofs == 0) return 0;
     const uint64_t ncols = n_bp + 1; std::vector<uint64_t> h(2 * ncols); uint64_t start = 0;
     for (uint64_t c = 0; c < ncols; c++) {      // column c holds cells [start, start + len); consecutive columns share their boundary cell
+        // a break point is a row 1 .. 2^k - 1: a column that breaks holds its first cell and the breaking one at least, and bp + 1 cannot wrap
+        if (c < n_bp && (break_points[c] == 0 || break_points[c] >= ((uint64_t)1 << k))) { set_error("h2w_layout_columns: break points do not fit the stream"); return -1; }
         const uint64_t len = c < n_bp ? break_points[c] + 1 : n_cells - start;
-        if (start + len > n_cells || len > ((uint64_t)1 << k)) { set_error("h2w_layout_columns: break points do not fit the stream"); return -1; }
+        if (start > n_cells || len > n_cells - start || len > ((uint64_t)1 << k)) { set_error("h2w_layout_columns: break points do not fit the stream"); return -1; }
         h[c] = start; h[ncols + c] = len; start += len - (c < n_bp ? 1 : 0);
     }
     if (ncols > 65535 || n_proofs > 65535) { set_error("h2w_layout_columns: too many columns / proofs per call"); return -1; }
@@ -65,7 +67,8 @@ __global__ void k_layout_lookup(const ulonglong2 *advice, uint64_t proof_stride,
 }
 static int ensure_lookup_cells(h2w_plan *p);
 int h2w_layout_lookup_columns(h2w_plan *p, const void *advice_dev, uint64_t proof_stride_cells, uint64_t n_proofs, int k, int unusable_rows, void *out_dev, uint64_t *n_cols_out, void *stream_) {
-    if (!p || k < 3 || k > 34 || unusable_rows < 0) { set_error("h2w_layout_lookup_columns: bad argument"); return -1; }
+    // the rule of h2w_break_points: a column keeps at least five usable rows (max_rows below is never zero and never wraps)
+    if (!p || k < 3 || k > 34 || unusable_rows < 0 || ((uint64_t)1 << k) <= (uint64_t)unusable_rows + 4) { set_error("h2w_layout_lookup_columns: bad argument"); return -1; }
     if (h2w_plan_metadata(p) != 0) return -1;
     const uint64_t max_rows = ((uint64_t)1 << k) - (uint64_t)unusable_rows, ncols = (p->n_lookups + max_rows - 1) / max_rows;
     if (n_cols_out) *n_cols_out = ncols;
@@ -91,7 +94,9 @@ __global__ void k_check_gates(const fr_t *advice, uint64_t proof_stride, uint64_
             const int b = __ffs((int)m) - 1; m &= m - 1; const uint64_t i = byte * 8 + (uint64_t)b;
             if (i + 3 >= n_cells) { nb++; continue; }
             const fr_t a = g_load_fr(adv + i), x = g_load_fr(adv + i + 1), y = g_load_fr(adv + i + 2), d = g_load_fr(adv + i + 3);
-            if (!fr_eq(fr_add(a, fr_mul(x, y, P)), d)) nb++;
+            // a, x, y >= r are no field elements: a + r or x + r would pass below (one conditional subtraction, a reduced product).  With the
+            // three canonical the sum is canonical, so the bitwise compare refuses a d >= r by itself.
+            if (fr_geq_mod(a) || fr_geq_mod(x) || fr_geq_mod(y) || !fr_eq(fr_add(a, fr_mul(x, y, P)), d)) nb++;
         }
     }
     if (nb) atomicAdd(bad, nb);

@@ -303,7 +303,8 @@ int h2w_plan_const_equalities(h2w_plan *, const uint64_t *proof_words, uint64_t 
  * out may be NULL to query *n_out. */
 int h2w_break_points(const uint8_t *selectors, uint64_t n_cells, int k, int unusable_rows,
                      uint64_t *out, uint64_t cap, uint64_t *n_out);
-/* flat advice (device) -> columns[n_proofs][n_bp + 1][2^k] (device, 32-byte canonical Fr, unassigned rows zero) */
+/* flat advice (device) -> columns[n_proofs][n_bp + 1][2^k] (device, 32-byte canonical Fr, unassigned rows zero).  Every break point
+ * is a row 1 .. 2^k - 1 and the columns must fit n_cells (the last one takes the rest, at most 2^k cells): anything else is -1. */
 int h2w_layout_columns(const void *advice_dev, uint64_t n_cells, uint64_t proof_stride_cells, uint64_t n_proofs,
                        const uint64_t *break_points, uint64_t n_bp, int k, void *columns_dev, void *stream);
 /* The same result as h2w_fri_witness_batch + h2w_layout_columns without materialising the flat stream: every kernel writes its
@@ -311,13 +312,16 @@ int h2w_layout_columns(const void *advice_dev, uint64_t n_cells, uint64_t proof_
  * the boundary cells and zeroes the unused rows).  k >= 12.  Workspace as for h2w_fri_witness_batch. */
 int h2w_fri_witness_batch_columns(h2w_plan *, const uint64_t *proofs_dev, uint64_t n_proofs, const uint64_t *break_points, uint64_t n_bp,
                                   int k, void *columns_dev, void *workspace_dev, void *stream);
-/* lookup advice columns: out[n_proofs][*n_cols_out][2^k]; out_dev may be NULL to query *n_cols_out */
+/* lookup advice columns: out[n_proofs][*n_cols_out][2^k]; out_dev may be NULL to query *n_cols_out.  unusable_rows as for
+ * h2w_break_points: 2^k > unusable_rows + 4, or -1. */
 int h2w_layout_lookup_columns(h2w_plan *, const void *advice_dev, uint64_t proof_stride_cells, uint64_t n_proofs,
                               int k, int unusable_rows, void *out_dev, uint64_t *n_cols_out, void *stream);
 
 /* Device-side constraint check of advice streams (restated MockProver gate + lookup checks): bad[0] = vertical
  * gates a[i] + a[i+1]*a[i+2] != a[i+3] over the selector-enabled cells, bad[1] = looked-up cells >= 2^lookup_bits, summed over
- * the n_proofs streams.  Synchronises the stream.  Covers every cell of full-size streams without the CPU oracle. */
+ * the n_proofs streams.  A gate also counts as failed when one of its four cells is not a field element (>= r: the unreduced
+ * cells of a status-4 stream), whatever it is congruent to, and when it starts in the last three cells of the stream.
+ * Synchronises the stream.  Covers every cell of full-size streams without the CPU oracle. */
 int h2w_check_constraints(h2w_plan *, const void *advice_dev, uint64_t proof_stride_cells, uint64_t n_proofs,
                           uint64_t bad[2], void *stream);
 

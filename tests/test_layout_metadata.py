@@ -147,19 +147,38 @@ def test_device_constraint_check(h2w, h2w_api, oracle, consts, mode):
     bad_g, bad_l = plan.check_constraints(advice.data_ptr(), n, stream)
     assert bad_g == 0
     assert bad_l <= 2 * 4                      # at most the PoW limbs of each proof
-    sel = np.unpackbits(np.frombuffer(plan.selectors(), dtype=np.uint8), bitorder="little")
+    import advicetools_ref as ref                  # Python integers (tests/test_advicetools_refs.py holds them to the oracle)
+    selb = plan.selectors()
+    sel = np.unpackbits(np.frombuffer(selb, dtype=np.uint8), bitorder="little")
     gate_cells = np.nonzero(sel)[0]
     a = advice.view(torch.int64)
+    ncells = plan.num_cells
+
+    def window(proof, cell):                       # the cells around `cell` as the device holds them now: {cell index: value}
+        lo, hi = max(0, cell - 3), min(ncells, cell + 4)
+        rows = a[(proof * ncells + lo) * 4:(proof * ncells + hi) * 4].cpu().numpy().view(np.uint64).reshape(-1, 4)
+        return dict(zip(range(lo, hi), ref.ints(rows)))
+
+    def touching(cell):                            # the enabled gates that read `cell`
+        return [g for g in range(max(0, cell - 3), cell + 1) if sel[g]]
+
     for g in (gate_cells[5], gate_cells[len(gate_cells) // 2], gate_cells[-1]):
-        idx = (plan.num_cells + int(g) + 3) * 4          # proof 1, the gate's output cell, low limb
+        idx = (ncells + int(g) + 3) * 4            # proof 1, the gate's output cell, low limb
         old = a[idx].item(); a[idx] = old ^ 1
-        assert plan.check_constraints(advice.data_ptr(), n, stream)[0] >= 1
+        want = ref.bad_gates(window(1, int(g) + 3), selb, ncells, gates=touching(int(g) + 3))      # all other gates hold: bad_g == 0 above
+        assert want >= 1
+        assert plan.check_constraints(advice.data_ptr(), n, stream)[0] == want
         a[idx] = old
-    assert plan.check_constraints(advice.data_ptr(), n, stream)[0] == 0
+    assert plan.check_constraints(advice.data_ptr(), n, stream) == (0, bad_l)
     lk = plan.lookup_cells()
-    idx = int(lk[len(lk) // 3]) * 4 + 1                  # proof 0: a looked-up limb gets a high word
+    j = len(lk) // 3
+    cell = int(lk[j])
+    idx = cell * 4 + 1                             # proof 0: a looked-up limb gets a high word
+    before = ref.bad_lookups(window(0, cell), lk, 21, registrations=[j])
     a[idx] = 1
-    assert plan.check_constraints(advice.data_ptr(), n, stream)[1] >= bad_l + 1
+    after = window(0, cell)
+    assert lk.count(cell) == 1 and before == 0 and ref.bad_lookups(after, lk, 21, registrations=[j]) == 1
+    assert plan.check_constraints(advice.data_ptr(), n, stream) == (ref.bad_gates(after, selb, ncells, gates=touching(cell)), bad_l + 1)
     plan.close()
 
 
