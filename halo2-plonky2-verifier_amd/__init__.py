@@ -83,6 +83,8 @@ H2W_CHIPBATCH_OPT_CHUNK = 1
 # flags of h2w_verdict_t (include/h2w.h 3b)
 (H2W_VERDICT_POW, H2W_VERDICT_MERKLE_TRACE, H2W_VERDICT_MERKLE_PERM_Z, H2W_VERDICT_MERKLE_QUOTIENT, H2W_VERDICT_MERKLE_STEP, H2W_VERDICT_FOLD,
  H2W_VERDICT_FINAL) = 1, 2, 4, 8, 16, 32, 64
+# flags of h2w_fri_verdict_batch_ex
+H2W_VERDICT_FORM_AUTO, H2W_VERDICT_FORM_QUAD, H2W_VERDICT_FORM_ROW, H2W_VERDICT_FORM_MASK, H2W_VERDICT_FORK = 0, 1, 2, 0xFF, 0x100
 
 SYMBOLS = {
     "h2w_abi_version": (C.c_int, []),
@@ -209,6 +211,8 @@ SYMBOLS = {
     "h2w_plan_direct_cells": (C.c_int, [_vp, _vp]),
     "h2w_plan_record_ranges": (C.c_int, [_vp, _vp]),
     "h2w_fri_verdict_batch": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp]),
+    "h2w_fri_verdict_batch_ex": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, C.c_uint32]),
+    "h2w_plan_verdict_form": (C.c_int, [_vp, C.c_uint64]),
     "h2w_plan_proof_layout": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.c_size_t]),
     "h2w_prover_new": (_vp, [C.POINTER(Shape), C.POINTER(PoseidonConsts), C.c_int]),
     "h2w_prover_free": (None, [_vp]),

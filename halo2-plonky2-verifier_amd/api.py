@@ -13,6 +13,7 @@ GL_P = 0xFFFFFFFF00000001
 FR_MODULUS = 21888242871839275222246405745257275088548364400416034343698204186575808495617
 # Plan.configure options (include/h2w.h)
 OPT_FORK_CHAINS, OPT_SERIAL_EXPAND, OPT_CHAIN_PASSES, OPT_VALUES_FORM, OPT_OUTPUT_FORM = 1, 2, 3, 4, 5
+VERDICT_FORM_AUTO, VERDICT_FORM_QUAD, VERDICT_FORM_ROW, VERDICT_FORK = 0, 1, 2, 0x100      # flags of Plan.verdict (h2w_fri_verdict_batch_ex)
 FORM_CANONICAL, FORM_MONTGOMERY = 0, 1      # OPT_OUTPUT_FORM: canonical little-endian Fr / v * 2^256 mod r (halo2curves' in-memory form)
 
 
@@ -381,23 +382,37 @@ class Plan:
         return list(st)
 
     # ---- verdicts without a witness (include/h2w.h 3b)
-    def verdict(self, proofs_ptr, n, stream=0, verdict_ptr=None):
+    def verdict(self, proofs_ptr, n, stream=0, verdict_ptr=None, flags=None):
         """h2w_fri_verdict_batch: per proof (flags, n_failed, first_query, status); a proof is accepted iff flags == 0 and status == 0.
         verdict_ptr: device memory of n x 4 uint32 - the call is then enqueued on `stream` and nothing is returned (no synchronisation).
-        Without it the verdicts go to a torch buffer on the plan's device, the device is synchronised and they come back as a list of tuples."""
+        Without it the verdicts go to a torch buffer on the plan's device, the device is synchronised and they come back as a list of tuples.
+        flags: None - h2w_fri_verdict_batch; a value - h2w_fri_verdict_batch_ex with it: one VERDICT_FORM_* (AUTO: by the number of Merkle paths,
+        QUAD: the kernels of the plain call, ROW: one wavefront per path, PoseidonBN254 caps), optionally | VERDICT_FORK (the glue kernel on the plan's
+        side stream beside the Merkle kernel).  The verdicts are the same under every value."""
+        if flags is None:
+            call = lambda np_, out: _ck(self.L.h2w_fri_verdict_batch(self.p, proofs_ptr, np_, out, stream), "h2w_fri_verdict_batch")
+        else:
+            call = lambda np_, out: _ck(self.L.h2w_fri_verdict_batch_ex(self.p, proofs_ptr, np_, out, stream, flags), "h2w_fri_verdict_batch_ex")
         if verdict_ptr is not None:
-            _ck(self.L.h2w_fri_verdict_batch(self.p, proofs_ptr, n, verdict_ptr, stream), "h2w_fri_verdict_batch")
+            call(n, verdict_ptr)
             return None
         if n == 0:
-            _ck(self.L.h2w_fri_verdict_batch(self.p, proofs_ptr, 0, None, stream), "h2w_fri_verdict_batch")
+            call(0, None)
             return []
         import torch
         dev = f"cuda:{self.device_id}"
         buf = torch.empty(4 * n, dtype=torch.int32, device=dev) if torch.cuda.is_available() else None      # (no device: the library says so)
-        _ck(self.L.h2w_fri_verdict_batch(self.p, proofs_ptr, n, buf.data_ptr() if buf is not None else None, stream), "h2w_fri_verdict_batch")
+        call(n, buf.data_ptr() if buf is not None else None)
         torch.cuda.synchronize(dev)
         w = [int(x) & 0xFFFFFFFF for x in buf.cpu().tolist()]
         return [tuple(w[4 * i:4 * i + 4]) for i in range(n)]
+
+    def verdict_form(self, n):
+        """h2w_plan_verdict_form: what VERDICT_FORM_AUTO resolves to for n proofs of this plan's shape (VERDICT_FORM_QUAD or VERDICT_FORM_ROW)."""
+        form = self.L.h2w_plan_verdict_form(self.p, n)
+        if form < 0:
+            raise H2WError("h2w_plan_verdict_form: " + last_error())
+        return form
 
     def proof_layout(self):
         """h2w_plan_proof_layout: the flat proof layout of the shape, in u64 words, as a dict - the scalar fields, and per initial oracle

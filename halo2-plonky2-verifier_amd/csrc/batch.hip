@@ -334,13 +334,9 @@ static int run_batch(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs,
     A.sh.n_own_proofs = (uint32_t)own_count(n_proofs, sh.rank, sh.world);
     hipStream_t cstream = stream;      // chain kernels' stream
     if (p->fork_chains) {
-        int k = 0; while (k < p->n_side && p->side_of[k] != stream) k++;
-        if (k == p->n_side && p->n_side < h2w_plan::N_SIDE) {
-            int lo_pri = 0, hi_pri = 0; (void)hipDeviceGetStreamPriorityRange(&lo_pri, &hi_pri);      // the chain is the longest dependent piece of a launch: let its blocks be placed first
-            if (p->side[k].create(hipStreamNonBlocking, hi_pri) != 0) return -1;
-            p->side_of[k] = stream; p->n_side++;
-        }
-        if (k < p->n_side) cstream = p->side[k];      // (more caller streams than side streams: the extra ones do not fork)
+        const int k = plan_side_slot(p, stream);
+        if (k == -2) return -1;
+        if (k >= 0) cstream = p->side[k];      // (more caller streams than side streams: the extra ones do not fork)
     }
     const DevEvent *prev_ev = (p->n_batches && p->ev_recorded) ? p->evr[(p->n_batches - 1) % h2w_plan::EV_RING] : nullptr;
     const DevEvent *ev = p->evr[p->n_batches % h2w_plan::EV_RING];

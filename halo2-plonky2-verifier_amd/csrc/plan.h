@@ -31,6 +31,7 @@ struct h2w_plan {
     enum { EV_PROLOGUE_VALUES_END = H2W_EV_COUNT, EV_CHAIN_VALUES_END, EV_GLP_START, EV_GLP_END, EV_DIRECT_END, N_EV };
     DevEvent evr[EV_RING][N_EV]; int passes_of[EV_RING] = {0};      // (created by h2w_plan_compile; a traced plan has none)
     DevStream side[N_SIDE]; hipStream_t side_of[N_SIDE]; int n_side = 0;   // PoseidonBN254 chain kernels run beside the glue + expansion kernels
+    DevEvent vev[N_SIDE][2];         // h2w_fri_verdict_batch_ex, H2W_VERDICT_FORK: fork / join of the call on side stream k (created with the first such call)
     int chain_passes = 0;            // H2W_OPT_CHAIN_PASSES (0: by the size of the launch)
     int values_form = 0;             // H2W_OPT_VALUES_FORM (0: by the size of the launch)
     int serial_expand = 1;           // H2W_OPT_SERIAL_EXPAND: the expansion kernel of a call waits for the previous call's
@@ -44,6 +45,18 @@ struct h2w_plan {
 };
 extern "C" int h2w_plan_metadata(h2w_plan *pl);      // plancompile.cpp: the keygen-metadata replay, once per plan (the selector / lookup queries and advicetools.hip call it)
 namespace h2w {
+// The plan's side stream for the caller's stream `s` (batch.hip run_batch: the chain kernels; verdict.hip: the forked glue kernel - a witness call and a
+// forked verdict call on one caller stream share it, in order): slot k of side[] / side_of[], created when `s` is first seen.  -1: every side stream is
+// another caller stream's (the call does not fork); -2: the stream could not be created (the reason is in the last error).
+inline int plan_side_slot(h2w_plan *p, hipStream_t s) {
+    int k = 0; while (k < p->n_side && p->side_of[k] != s) k++;
+    if (k < p->n_side) return k;
+    if (p->n_side == h2w_plan::N_SIDE) return -1;
+    int lo_pri = 0, hi_pri = 0; (void)hipDeviceGetStreamPriorityRange(&lo_pri, &hi_pri);      // the chain is the longest dependent piece of a launch: let its blocks be placed first
+    if (p->side[k].create(hipStreamNonBlocking, hi_pri) != 0) return -2;
+    p->side_of[k] = s; p->n_side++;
+    return k;
+}
 // The expansion launch of a plan's call (batch.hip: run_batch, h2w_fri_expand_records; replay.hip traced_run): records[n_proofs][p->nrec] -> cells
 // out[n_proofs][cell_stride] through cm.  sh: the (proof, query) sharding of the record ranges; null: every proof is one block (a traced plan has
 // no strand table).  tile_ctr: n_proofs words of workspace, zeroed here.  roam_per_cu: ExpandArgs.

@@ -54,7 +54,11 @@ RF_FN fr_t gather_canonical(const V &v, int row) {
 RF_FN V all_rows_of_row0(const V &v) { V e, o, lo, hi; pair_bcast(v, e, o); half_bcast(e, lo, hi); return lo; }
 
 // st: the state, canonical, the same on every lane; on return the permuted state.  sbx9: [56][3][SBX9_W] dwords of this unit (global memory).
-RF_FN void bn_permute_rows(fr_t st[4], const RowConst &K, const LaneK &L, uint32_t *sbx9) {
+// store = false: the permutation alone (verdict.hip k_verdict_merkle_row) - the same schedule without its three stores; sbx9 is never read and no address is
+// formed from it: callers pass nullptr.  (The products a store was the only consumer of are the next slot's operands: the round is the same.)
+// Callers use the template below; `store` is its argument, a constant wherever this body is inlined.  (The body is no template itself: as one, with its
+// lambdas instantiated, the compiler allocated k_merkle_bn_values_row's registers differently - this way that kernel's code is what it was.)
+RF_FN void bn_permute_rows_as(fr_t st[4], const RowConst &K, const LaneK &L, uint32_t *sbx9, const bool store) {
     const V row = lane_index() >> 4;                         // = the state element this lane works on
     const V km1 = sel(row < V(2u), V(0u), sel(row == V(2u), V(1u), V(2u)));      // k - 1 on rows 1..3 (0 on row 0)
     // the state, one limb per lane, to Montgomery form (times R)
@@ -107,24 +111,25 @@ RF_FN void bn_permute_rows(fr_t st[4], const RowConst &K, const LaneK &L, uint32
             for (int r = 0; r < BN_PARTIAL_ROUNDS; r++) {
                 const RoundK kn = round_k(r + 1 < BN_PARTIAL_ROUNDS ? r + 1 : r);
                 uint32_t t[9];
-                uint32_t *const sb = sbx9 + (size_t)r * 3 * SBX9_W;
+                uint32_t *sb = nullptr;
+                if (store) sb = sbx9 + (size_t)r * 3 * SBX9_W;
                 // slot 1
                 A9 A = kr.kp;
                 replicate(S, 0, t); put_rows(A, L.row0, t);
                 const V P1 = mont(A, sel(L.row0, S, s0p_all), K, L);                           // row 0: X2 | rows k: U_k
-                st_row(sb, P1, L.row0, L);
+                if (store) st_row(sb, P1, L.row0, L);
                 S = sel(L.row0, S, tighten(S + P1));
                 // slot 2
                 A = kr.k2;
                 replicate(P1, 0, t); put_rows(A, L.row0, t);
                 const V P2 = mont(A, sel(L.row0, P1, sel(L.row1, s0_all, S)), K, L);           // row 0: X4 | row 1: XA = S_0 s0 | rows j: W_j = S_j s_j
-                st_row(sb + SBX9_W, P2, L.row0, L);
+                if (store) st_row(sb + SBX9_W, P2, L.row0, L);
                 // slot 3
                 A = kr.k1;
                 replicate(P2, 0, t); put_rows(A, !L.row1, t);                                  // rows 0, 2, 3: X4
                 V e, o; pair_bcast(P2, e, o);                                                  // o: XA (row 1) on row 0
                 const V P3 = mont(A, sel(L.row0, o, sel(L.row1, S, s0_all)), K, L);            // row 0: T0 = X4 XA | row 1: W_1 | rows 2, 3: X5 = X4 s0
-                st_row(sb + 2 * SBX9_W, P3, row == V(2u), L);
+                if (store) st_row(sb + 2 * SBX9_W, P3, row == V(2u), L);
                 // s0' = X5 + c on rows 2, 3 -> rows 1, 2, 3
                 V lo, hi; half_bcast(P3 + kr.kc, lo, hi); s0p_all = hi;
                 // new s0 = (T0 + S_0 c) + W_1 + W_2 + W_3, on every row
@@ -159,6 +164,15 @@ RF_FN void bn_permute_rows(fr_t st[4], const RowConst &K, const LaneK &L, uint32
     }
     for (int i = 0; i < 4; i++) st[i] = gather_canonical(S, i);
 }
+
+// (RF_TFN: in the host pass of a HIP compilation the simulated-lane form of a function TEMPLATE is a candidate for a call from a kernel's sink only if it
+// is callable from there; nothing runs it)
+#if defined(__HIP__) && !defined(__HIP_DEVICE_COMPILE__)
+#define RF_TFN __host__ __device__ inline
+#else
+#define RF_TFN RF_FN
+#endif
+template <bool STORE = true> RF_TFN void bn_permute_rows(fr_t st[4], const RowConst &K, const LaneK &L, uint32_t *sbx9) { bn_permute_rows_as(st, K, L, sbx9, STORE); }
 
 }  // namespace rf
 }  // namespace h2w

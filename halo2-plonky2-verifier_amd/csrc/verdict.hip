@@ -1,4 +1,4 @@
-// verdict.hip - per-proof verdicts without a witness (include/h2w.h 3b): h2w_fri_verdict_batch, h2w_plan_proof_layout.
+// verdict.hip - per-proof verdicts without a witness (include/h2w.h 3b): h2w_fri_verdict_batch, h2w_fri_verdict_batch_ex, h2w_plan_verdict_form, h2w_plan_proof_layout.
 //
 // The verifier gadget's protocol checks are assert_equal copy constraints (chips.h MerkleTreeChip, verifier.h query_round): they emit no cells, so a
 // stream made from a rejected proof looks like one made from an accepted proof.  Every value those checks compare is computed by the value kernels
@@ -13,12 +13,19 @@
 //   k_verdict_merkle_gl     Goldilocks caps: one wavefront per (proof, query, tree), permutations on glp_permute_lanes (k_merkle_gl_values without list or records)
 //   k_verdict_merkle_bn     PoseidonBN254 caps: four lanes per (proof, query, tree) on the lazy nine-limb values walk (coop.h QuadSinkT bn_values, QUAD_VERDICT:
 //                           no unit states, no S-box values; the cap lookup's value is taken)
+//   k_verdict_merkle_row    PoseidonBN254 caps, few paths (h2w_fri_verdict_batch_ex, H2W_VERDICT_FORM_ROW): one wavefront per (proof, query, tree), the four rows
+//                           of the wavefront = the four state elements (rowfr.h; rowperm.h bn_permute_rows<false>: the permutation of k_merkle_bn_values_row
+//                           without its S-box stores).  A path's 18 dependent permutations take half the time of the four-lane form's
 //   k_verdict_finish        one lane per proof: status 4 where no strand reported a condition of its own (h2w_plan_status's order)
+// h2w_fri_verdict_batch_ex picks the PoseidonBN254 form by the number of paths (VERDICT_ROW_MAX_PATHS) and may run k_verdict_glue on the plan's side
+// stream beside the Merkle kernel (H2W_VERDICT_FORK): the two read the challenge blocks and meet in the verdict words' atomics alone.
 // Flattened like glue.hip: the sinks below exist in this unit alone (field.h HNI).
 #define H2W_FLATTEN_CHIPS 1
 #include <hip/hip_runtime.h>
 #include <string>
 #include "plan.h"
+#define RF_TAB9 s_bn_tab9
+#include "rowperm.h"
 
 namespace h2w {
 
@@ -64,6 +71,31 @@ struct VerdictQuadSink : QuadSinkT<false, QUAD_VERDICT> {
     __device__ __forceinline__ void rec(int, uint64_t, uint64_t, uint64_t, uint64_t) {}
     __device__ __forceinline__ void cell(const fr_t &) {}
     __device__ __forceinline__ void skip(uint64_t, uint64_t) {}
+    __device__ __forceinline__ void compare(bool differ) { acc.compare(differ); }
+    __device__ __forceinline__ void site(int s) { acc.cur = s; }
+};
+
+// one wavefront per path, every lane on the same values (glue.hip RowSink without anything it leaves for an emission pass): no unit states, no S-box
+// values - the permutation stores nothing -, and the cap lookup's value is taken; lane 0 speaks
+struct VerdictRowSink : SinkBase {
+    static constexpr bool kBnUnits = true; static constexpr int kHashMode = 1;
+    const rf::RowConst *rowk; VerdictAcc acc;
+    __device__ __forceinline__ void rec(int, uint64_t, uint64_t, uint64_t, uint64_t) {}
+    __device__ __forceinline__ void cell(const fr_t &) {}
+    __device__ __forceinline__ void skip(uint64_t, uint64_t) {}
+    __device__ __forceinline__ bool level_skip(fr_t &, bool &) { return false; }
+    __device__ __forceinline__ bool tail_skip() const { return false; }
+    __device__ __forceinline__ void permute_unit(fr_t *st) {
+        rf::RowConst K;
+        {   // wave-uniform: scalar loads
+            const uint32_t *src = reinterpret_cast<const uint32_t *>(rowk); uint32_t *dst = reinterpret_cast<uint32_t *>(&K);
+#pragma unroll
+            for (unsigned i = 0; i < sizeof(rf::RowConst) / 4; i++) dst[i] = *(const __attribute__((address_space(4))) uint32_t *)(src + i);
+        }
+        const rf::LaneK L = rf::lane_consts();
+        rf::bn_permute_rows<false>(st, K, L, nullptr);
+    }
+    __device__ __forceinline__ bool bn_emit_inline(fr_t *st, const ValCfg &, bool &) { permute_unit(st); return true; }
     __device__ __forceinline__ void compare(bool differ) { acc.compare(differ); }
     __device__ __forceinline__ void site(int s) { acc.cur = s; }
 };
@@ -158,26 +190,63 @@ __global__ __launch_bounds__(QUAD_BLOCK) __attribute__((flatten)) void k_verdict
     sink.acc.status(be.status);
 }
 
+// LDS: the nine-limb tables alone.  Global memory is written through the VerdictAcc atomics only
+__global__ __launch_bounds__(QUAD_BLOCK) __attribute__((flatten)) void k_verdict_merkle_row(VerdictArgs V) {
+    typedef ValBackend<VerdictRowSink> RowB;
+    stage_bn_consts9(V.A.bn_tab9, threadIdx.x, QUAD_BLOCK);    // (block-wide barrier inside: before any wavefront leaves)
+    const unsigned idx = blockIdx.x * QUAD_WAVES + (threadIdx.x >> 6);      // this wavefront's (proof, query) unit
+    int p, q;
+    if (!own_unit_at(V.A, idx, p, q)) return;      // a wavefront past the last unit
+    const int kind = merkle_kind(V.A.shape.n_perm_z, blockIdx.y);
+    VerdictRowSink sink; sink.rowk = V.A.rowk;
+    sink.acc.init(V.verdict, p, q, V.A.shape.n_perm_z, (threadIdx.x & 63) == 0);      // wave-uniform values: lane 0 speaks
+    ValCfg mc = make_cfg(V.A, p); mc.split_bn = true;
+    RowB be(sink, mc, true);
+    const h2w_shape_t shp = V.A.shape;
+    Verifier<RowB> Vf(be, shp, V.A.consts);
+    Vf.merkle_strand_at(q, kind, V.A.cbs[p].fri_query_indices[q]);
+    sink.acc.status(be.status);
+}
+
 static size_t up256(size_t x) { return (x + 255) / 256 * 256; }
 
-}  // namespace h2w
+// H2W_VERDICT_FORM_AUTO: the wavefront-per-path form up to this many Merkle paths = n_proofs x num_queries x (n_oracles + n_steps) of a call with
+// PoseidonBN254 caps.  A path is 18 dependent permutations in either form; the row form walks it in half the time with sixteen times the lanes, so it
+// wins while the four-lane form leaves the chip idle.  The largest path count of the sweep at which it was not the slower one, a call alone on the
+// chip (cfg 3, 196 paths per proof: 12 proofs 2.96 against 3.43 ms, 16 proofs 3.55 against 3.42; DESIGN 5g, profiles/verdict_forms_cfg3.json).  A caller
+// that keeps other launches in flight pays for the row form's instructions earlier (batch.hip on H2W_OPT_VALUES_FORM): it names its form itself.
+constexpr uint64_t VERDICT_ROW_MAX_PATHS = 2352;
 
-extern "C" {
+static unsigned verdict_form_of(const h2w_plan *p, uint64_t n_proofs) {
+    if (p->shape.hash_mode == 0) return H2W_VERDICT_FORM_QUAD;      // Goldilocks caps: the one kernel there is already one wavefront per path
+    const uint64_t per_proof = (uint64_t)p->shape.num_queries * (uint64_t)(p->d.n_oracles + p->d.n_steps);
+    return per_proof == 0 || n_proofs <= VERDICT_ROW_MAX_PATHS / per_proof ? H2W_VERDICT_FORM_ROW : H2W_VERDICT_FORM_QUAD;
+}
 
-int h2w_fri_verdict_batch(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, h2w_verdict_t *verdict_dev, void *stream_) {
-    if (!p) { set_error("h2w_fri_verdict_batch: null plan"); return -1; }
-    if (p->traced) { set_error("h2w_fri_verdict_batch: a traced plan (h2w_plan_from_trace) replays a tape and has no verifier strands to judge: use a plan of h2w_plan_compile"); return -1; }
-    if (p->device < 0) { set_error("h2w_fri_verdict_batch: no HIP device — the verdict kernels only run on the GPU (no CPU fallback)"); return -1; }
+// the checks both entry points share, in h2w_fri_verdict_batch's order, and the call itself.  form: H2W_VERDICT_FORM_QUAD or _ROW
+static int verdict_call(const char *who, h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, h2w_verdict_t *verdict_dev, void *stream_, unsigned form, bool fork) {
+    const std::string w(who);
+    if (p->device < 0) { set_error(w + ": no HIP device — the verdict kernels only run on the GPU (no CPU fallback)"); return -1; }
     if (n_proofs == 0) return 0;
-    if (!proofs_dev || !verdict_dev) { set_error("h2w_fri_verdict_batch: null buffer"); return -1; }
+    if (!proofs_dev || !verdict_dev) { set_error(w + ": null buffer"); return -1; }
     const uint64_t nq = (uint64_t)p->shape.num_queries;
-    if (n_proofs > 0x3fffffffull / (4 * nq)) { set_error("h2w_fri_verdict_batch: batch too large; split the batch"); return -1; }
+    if (n_proofs > 0x3fffffffull / (4 * nq)) { set_error(w + ": batch too large; split the batch"); return -1; }
     DeviceGuard dg(p->device);
-    hipStream_t stream = (hipStream_t)stream_;
+    hipStream_t stream = (hipStream_t)stream_, gstream = stream;      // gstream: the glue kernel's
+    int slot = -1;
+    if (fork) {
+        slot = plan_side_slot(p, stream);      // (-1: every side stream is another caller stream's - this one does not fork)
+        if (slot == -2) return -1;
+        if (slot >= 0) {
+            for (DevEvent &e : p->vev[slot]) if (!(hipEvent_t)e && e.create() != 0) return -1;
+            gstream = p->side[slot];
+        }
+    }
     // the call's workspace: challenge blocks, the prologue's status words, the range flags
     const size_t o_status = up256((size_t)n_proofs * sizeof(DevCB)), o_lflag = o_status + up256((size_t)n_proofs * sizeof(uint32_t)), total = o_lflag + up256((size_t)n_proofs * sizeof(uint32_t));
     char *ws = nullptr;
     H2W_HIP(hipMallocAsync((void **)&ws, total, stream));
+    bool forked = false;
     auto run = [&]() -> int {
         VerdictArgs V; BatchArgs &A = V.A;
         A.shape = p->shape; A.consts = p->d_consts.get(); A.proofs = proofs_dev; A.proof_words = p->pl.total;
@@ -198,16 +267,55 @@ int h2w_fri_verdict_batch(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_pr
         const unsigned pgrid = (unsigned)((n_proofs + 255) / 256), nunits = A.sh.n_own_units, nkinds = (unsigned)(p->d.n_oracles + p->d.n_steps);
         hipLaunchKernelGGL(k_verdict_init, dim3(pgrid), dim3(256), 0, stream, V);
         if (p->n_items) hipLaunchKernelGGL(k_verdict_check, dim3((unsigned)((n_proofs * p->n_items + 255) / 256)), dim3(256), 0, stream, V);
-        hipLaunchKernelGGL(k_verdict_glue, dim3((nunits + 63) / 64), dim3(64), 0, stream, V);
+        // the glue kernel and the Merkle kernel read the challenge blocks and meet in the verdict words' atomics alone: forked, the glue kernel runs on the
+        // plan's side stream beside the Merkle kernel and the caller's stream waits for it before k_verdict_finish and before the workspace is released
+        if (gstream != stream) {
+            H2W_HIP(hipEventRecord(p->vev[slot][0], stream));
+            H2W_HIP(hipStreamWaitEvent(gstream, p->vev[slot][0], 0)); forked = true;
+        }
+        hipLaunchKernelGGL(k_verdict_glue, dim3((nunits + 63) / 64), dim3(64), 0, gstream, V);
+        if (forked) H2W_HIP(hipEventRecord(p->vev[slot][1], gstream));
         if (p->shape.hash_mode == 0) hipLaunchKernelGGL(k_verdict_merkle_gl, dim3(nunits, nkinds), dim3(64), 0, stream, V);
+        else if (form == H2W_VERDICT_FORM_ROW) hipLaunchKernelGGL(k_verdict_merkle_row, dim3((nunits + QUAD_WAVES - 1) / QUAD_WAVES, nkinds), dim3(QUAD_BLOCK), 0, stream, V);
         else hipLaunchKernelGGL(k_verdict_merkle_bn, dim3((nunits * 4 + QUAD_BLOCK - 1) / QUAD_BLOCK, nkinds), dim3(QUAD_BLOCK), 0, stream, V);
+        if (forked) { H2W_HIP(hipStreamWaitEvent(stream, p->vev[slot][1], 0)); forked = false; }
         hipLaunchKernelGGL(k_verdict_finish, dim3(pgrid), dim3(256), 0, stream, V);
         H2W_HIP(hipGetLastError());
         return 0;
     };
     const int rc = run();
+    // a failed enqueue after the fork: the glue kernel may still read the workspace on the side stream and nothing orders the caller's stream behind it
+    // any more - wait for it here (as h2w_fri_witness_batch does), before the workspace is released and the caller sees the error
+    if (forked) (void)hipStreamSynchronize(gstream);
     (void)hipFreeAsync(ws, stream);
     return rc;
+}
+
+}  // namespace h2w
+
+extern "C" {
+
+int h2w_fri_verdict_batch(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, h2w_verdict_t *verdict_dev, void *stream_) {
+    if (!p) { set_error("h2w_fri_verdict_batch: null plan"); return -1; }
+    if (p->traced) { set_error("h2w_fri_verdict_batch: a traced plan (h2w_plan_from_trace) replays a tape and has no verifier strands to judge: use a plan of h2w_plan_compile"); return -1; }
+    return verdict_call("h2w_fri_verdict_batch", p, proofs_dev, n_proofs, verdict_dev, stream_, H2W_VERDICT_FORM_QUAD, false);
+}
+
+int h2w_fri_verdict_batch_ex(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, h2w_verdict_t *verdict_dev, void *stream_, uint32_t flags) {
+    if (!p) { set_error("h2w_fri_verdict_batch_ex: null plan"); return -1; }
+    if (flags & ~(H2W_VERDICT_FORM_MASK | H2W_VERDICT_FORK)) { set_error("h2w_fri_verdict_batch_ex: unknown flag bits " + std::to_string(flags & ~(H2W_VERDICT_FORM_MASK | H2W_VERDICT_FORK)) + " (H2W_VERDICT_FORM_* | H2W_VERDICT_FORK)"); return -1; }
+    unsigned form = flags & H2W_VERDICT_FORM_MASK;
+    if (form > H2W_VERDICT_FORM_ROW) { set_error("h2w_fri_verdict_batch_ex: unknown form " + std::to_string(form) + " (H2W_VERDICT_FORM_AUTO, _QUAD, _ROW)"); return -1; }
+    if (p->traced) { set_error("h2w_fri_verdict_batch_ex: a traced plan (h2w_plan_from_trace) replays a tape and has no verifier strands to judge: use a plan of h2w_plan_compile"); return -1; }
+    if (form == H2W_VERDICT_FORM_ROW && p->shape.hash_mode == 0) { set_error("h2w_fri_verdict_batch_ex: H2W_VERDICT_FORM_ROW is a PoseidonBN254 form and the plan's hash_mode is 0 (Goldilocks caps have one kernel: H2W_VERDICT_FORM_QUAD or _AUTO)"); return -1; }
+    if (form == H2W_VERDICT_FORM_AUTO) form = verdict_form_of(p, n_proofs);
+    return verdict_call("h2w_fri_verdict_batch_ex", p, proofs_dev, n_proofs, verdict_dev, stream_, form, (flags & H2W_VERDICT_FORK) != 0);
+}
+
+int h2w_plan_verdict_form(const h2w_plan *p, uint64_t n_proofs) {
+    if (!p) { set_error("h2w_plan_verdict_form: null plan"); return -1; }
+    if (p->traced) { set_error("h2w_plan_verdict_form: a traced plan (h2w_plan_from_trace) has no verdict call"); return -1; }
+    return (int)verdict_form_of(p, n_proofs);
 }
 
 int h2w_plan_proof_layout(const h2w_plan *p, uint64_t *out, size_t n_out) {

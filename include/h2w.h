@@ -488,6 +488,26 @@ typedef struct { uint32_t flags, n_failed, first_query, status; } h2w_verdict_t;
 #define H2W_VERDICT_FOLD            32   /* fri/mod.rs:403-438, the consistency check of a fold step */
 #define H2W_VERDICT_FINAL           64   /* final-polynomial evaluation */
 int h2w_fri_verdict_batch(h2w_plan *, const uint64_t *proofs_dev, uint64_t n_proofs, h2w_verdict_t *verdict_dev, void *stream);
+/* The same verdict words from other kernels and streams: `flags` = one H2W_VERDICT_FORM_*, optionally | H2W_VERDICT_FORK.  Every accepted value gives the
+ * words h2w_fri_verdict_batch gives; flags == H2W_VERDICT_FORM_QUAD enqueues exactly what it enqueues.
+ *   FORM_ROW   PoseidonBN254 caps only: one wavefront per Merkle path (the four rows of the wavefront hold the four state elements) instead of four lanes -
+ *              a path's 18 dependent permutations in half the time with sixteen times the lanes: the form for a caller that judges a proof as it arrives
+ *   FORM_AUTO  FORM_ROW while n_proofs x num_queries x (n_oracles + n_steps) is at most the crossover the library keeps (h2w_plan_verdict_form reports the
+ *              choice), FORM_QUAD beyond it and always with hash_mode 0 (whose one Merkle kernel is a wavefront per path already)
+ *   FORK       the query-glue kernel runs on a side stream of the plan beside the Merkle kernel (either hash mode) and the caller's stream waits for it before
+ *              the verdicts are final and the call's workspace is released: still stream-ordered for the caller, no synchronisation.  The side stream is the
+ *              one h2w_fri_witness_batch forks its chain kernels to from the same caller stream (work of the two is ordered on it); a plan serves at most 16
+ *              caller streams with side streams - a further one runs the call unforked.
+ * -1 before any device work, the reason in h2w_last_error(): a bit outside FORM_MASK | FORK, a form above FORM_ROW, FORM_ROW on a plan with hash_mode 0, a
+ * plan of h2w_plan_from_trace.  Everything else as h2w_fri_verdict_batch. */
+#define H2W_VERDICT_FORM_AUTO 0u      /* the library picks by the number of Merkle paths of the call */
+#define H2W_VERDICT_FORM_QUAD 1u      /* the Merkle kernels of h2w_fri_verdict_batch */
+#define H2W_VERDICT_FORM_ROW  2u      /* PoseidonBN254 caps: one wavefront per (proof, query, tree) */
+#define H2W_VERDICT_FORM_MASK 0xFFu
+#define H2W_VERDICT_FORK      0x100u  /* k_verdict_glue on a side stream of the plan, beside the Merkle kernel */
+int h2w_fri_verdict_batch_ex(h2w_plan *, const uint64_t *proofs_dev, uint64_t n_proofs, h2w_verdict_t *verdict_dev, void *stream, uint32_t flags);
+/* What FORM_AUTO resolves to for n_proofs of this plan's shape: H2W_VERDICT_FORM_QUAD or _ROW.  No device needed.  -1 for a traced plan. */
+int h2w_plan_verdict_form(const h2w_plan *, uint64_t n_proofs);
 /* The flat proof layout of the plan's shape (WitnessChip load order, witness/mod.rs:236-294; every hash is 4 words), in u64 words:
  *   out[0..11]  trace_cap, quotient_cap, openings, perm_cap, pow_witness, final_poly, commit_caps, queries (start of query 0), query_words (words per
  *               query), pis, total, cap_size (hashes per cap)

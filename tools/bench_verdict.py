@@ -5,6 +5,9 @@ from random polynomials; no oracle involved), each alone on the chip, in one pro
   witness_ms   h2w_fri_witness_batch of the same batch                       h2w_plan_timing, whole call
   route_ms     the only verdict there was before: the stream, then h2w_check_equalities (the static lists uploaded by the call) and h2w_check_constraints
                over it                                                        wall clock between device synchronisations (both checks synchronise)
+--forms: h2w_fri_verdict_batch_ex under each of the listed flags as well - quad, row, auto, each with an optional +fork (the glue kernel on the plan's
+side stream) -, timed like verdict_ms on the same proofs, into the batch's "forms" (row is a PoseidonBN254 form: left out with Goldilocks caps).
+--witness-batches: the batches the witness leg is run for (default: all of them).
 A warm-up, then the median of --reps calls.  A batch whose advice does not fit --advice-gb is run in chunks of whole proofs, the chunks' times summed
 (the verdict call itself always takes the whole batch).  --route: the hash modes the route leg is run for (its equality lists come from a keygen replay of
 the shape on the host: 24 s with Goldilocks caps, and one proof per check call there - half a minute for 64 proofs).  Writes one JSON document (--out)."""
@@ -21,11 +24,18 @@ ap.add_argument("--batches", default="1,64")
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--advice-gb", type=float, default=58.0, help="advice per witness call at most (bench.py's automatic batch size)")
 ap.add_argument("--route", default="both", choices=["none", "bn254", "gl", "both"])
+ap.add_argument("--forms", default="", help="comma list of quad|row|auto[+fork]: h2w_fri_verdict_batch_ex under these flags too")
+ap.add_argument("--witness-batches", default="", help="comma list of the batches the witness leg is run for (default: all)")
 ap.add_argument("--degree-bits", type=int, default=20); ap.add_argument("--queries", type=int, default=28)
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "verdict_cfg3.json"))
 args = ap.parse_args()
 kh = h2w.published_consts()
 med = statistics.median
+FORM_FLAGS = {"quad": api.VERDICT_FORM_QUAD, "row": api.VERDICT_FORM_ROW, "auto": api.VERDICT_FORM_AUTO}
+forms = [f for f in args.forms.split(",") if f]
+for f in forms:
+    assert f.split("+")[0] in FORM_FLAGS and f.split("+")[1:] in ([], ["fork"]), "--forms: quad|row|auto[+fork], not " + f
+witness_batches = [int(x) for x in args.witness_batches.split(",") if x]
 result = {"workload": "2^%d rows, %d queries, lookup_bits 21; valid proofs from h2w_prove_fri_batch; warm-up + median of %d" % (args.degree_bits, args.queries, args.reps), "modes": {}}
 
 
@@ -55,15 +65,33 @@ for name, mode in (("bn254", 1), ("gl", 0)):
         s = torch.cuda.current_stream().cuda_stream
         out = torch.zeros(4 * B, dtype=torch.int32, device="cuda")
         # ---- the verdict call
-        ms = []
-        for r in range(args.reps + 1):
-            e0, e1 = torch.cuda.Event(True), torch.cuda.Event(True)
-            e0.record(); plan.verdict(proofs.data_ptr(), B, s, verdict_ptr=out.data_ptr()); e1.record(); torch.cuda.synchronize()
-            if r:
-                ms.append(e0.elapsed_time(e1))
-        v = out.cpu().numpy().view(np.uint32).reshape(B, 4)
-        assert (v == np.array([0, 0, 0xFFFFFFFF, 0], dtype=np.uint32)).all(), v      # every proof is accepted
+        def verdict_ms(flags):
+            ms = []
+            out.zero_(); torch.cuda.synchronize()
+            for r in range(args.reps + 1):
+                e0, e1 = torch.cuda.Event(True), torch.cuda.Event(True)
+                e0.record(); plan.verdict(proofs.data_ptr(), B, s, verdict_ptr=out.data_ptr(), flags=flags); e1.record(); torch.cuda.synchronize()
+                if r:
+                    ms.append(e0.elapsed_time(e1))
+            v = out.cpu().numpy().view(np.uint32).reshape(B, 4)
+            assert (v == np.array([0, 0, 0xFFFFFFFF, 0], dtype=np.uint32)).all(), v      # every proof is accepted
+            return ms
+        ms = verdict_ms(None)
         row = {"verdict_ms": round(med(ms), 4), "verdict_ms_all": [round(x, 4) for x in ms]}
+        if forms:
+            row["paths"] = B * args.queries * (len(plan.proof_layout()["oracles"]) + len(plan.proof_layout()["steps"]))
+            row["auto_is"] = {api.VERDICT_FORM_QUAD: "quad", api.VERDICT_FORM_ROW: "row"}[plan.verdict_form(B)]
+            row["forms"] = {}
+            for f in forms:
+                if mode == 0 and f.startswith("row"):
+                    continue
+                fms = verdict_ms(FORM_FLAGS[f.split("+")[0]] | (api.VERDICT_FORK if f.endswith("+fork") else 0))
+                row["forms"][f] = {"ms": round(med(fms), 4), "ms_all": [round(x, 4) for x in fms]}
+        if witness_batches and B not in witness_batches:
+            per_mode["batches"][str(B)] = row
+            print(json.dumps({name: {str(B): row}}), flush=True)
+            del proofs, out; torch.cuda.empty_cache()
+            continue
         # ---- the witness call, in chunks that fit
         chunk = max(1, min(B, int(args.advice_gb * 1e9 / (plan.num_cells * 32))))
         advice = torch.empty(chunk * plan.num_cells * 32, dtype=torch.uint8, device="cuda"); ws = torch.zeros(plan.workspace_bytes(chunk), dtype=torch.uint8, device="cuda")
