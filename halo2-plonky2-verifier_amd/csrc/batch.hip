@@ -34,22 +34,19 @@ template <bool COLS> __global__ __launch_bounds__(256) void k_prologue_load(Batc
     const uint64_t *ip = reinterpret_cast<const uint64_t *>(A.load_items + i);
     const uint64_t wk = g_load_u64(ip), irec = g_load_u64(ip + 1), icell = g_load_u64(ip + 2);
     const uint32_t word = (uint32_t)wk, kind = (uint32_t)(wk >> 32);
-    const uint64_t *w = A.proofs + (uint64_t)p * A.proof_words + word; const uint64_t w0 = g_load_u64(w);
-    bool bad = false;
-    if (kind <= 1) { if (emit) g_store_rec(recs + irec, w0, 0, 0, 0); bad = w0 >= GL_P; }
-    else {
-        const uint64_t w1 = g_load_u64(w + 1), w2 = g_load_u64(w + 2), w3 = g_load_u64(w + 3);
-        if (kind == 2) { if (emit) g_store_rec(recs + irec, w0, w1, w2, w3); bad = w0 >= GL_P || w1 >= GL_P || w2 >= GL_P || w3 >= GL_P; }
-        else {
-            fr_t v; v.l[0] = w0; v.l[1] = w1; v.l[2] = w2; v.l[3] = w3;
-            if (kind == 3) { ColPolicy<COLS> cc; cc.init(A.cm); if (emit) g_store_fr(out + cc.map(icell), v); bad = fr_geq_mod(v); }
-            else if (emit) {      // kind 4: RangeChip::decompose_le(x, 56, 5) - 13 cells of limb sums + 5 range checks
-                DevSinkT<COLS> sink; sink.recs = recs; sink.nrec = irec; sink.out = out; sink.cell_off = icell; sink.ncells = A.ncells; sink.cc.init(A.cm);
-                ValBackend<DevSinkT<COLS>> be(sink, make_cfg(A, p), true);
-                uint64_t limbs[5]; be.decompose_le_56_5(v, limbs);
-            }
+    const uint64_t *w = A.proofs + (uint64_t)p * A.proof_words + word;
+    fr_t v; v.l[0] = g_load_u64(w); v.l[1] = v.l[2] = v.l[3] = 0;
+    if (kind >= 2) { v.l[1] = g_load_u64(w + 1); v.l[2] = g_load_u64(w + 2); v.l[3] = g_load_u64(w + 3); }
+    if (emit) {
+        if (kind <= 2) g_store_rec(recs + irec, v.l[0], v.l[1], v.l[2], v.l[3]);      // (kinds 0-1: the one word, three zeros)
+        else if (kind == 3) { ColPolicy<COLS> cc; cc.init(A.cm); g_store_fr(out + cc.map(icell), v); }
+        else {      // kind 4: RangeChip::decompose_le(x, 56, 5) - 13 cells of limb sums + 5 range checks
+            DevSinkT<COLS> sink; sink.recs = recs; sink.nrec = irec; sink.out = out; sink.cell_off = icell; sink.ncells = A.ncells; sink.cc.init(A.cm);
+            ValBackend<DevSinkT<COLS>> be(sink, make_cfg(A, p), true);
+            uint64_t limbs[5]; be.decompose_le_56_5(v, limbs);
         }
     }
+    const bool bad = load_item_out_of_field(kind, v);
     if (bad) atomicOr(&A.load_flag[p], 4u);
 }
 
@@ -171,19 +168,24 @@ template <bool COLS> __global__ __launch_bounds__(256) void k_direct_to_montgome
 
 }  // namespace h2w
 
+// column-major emission: boundary cells repeated in the previous column, unused rows zeroed
+extern "C" __global__ void k_columns_fixup(ulonglong2 *cols, const uint64_t *lens, uint32_t ncols, uint32_t k) {
+    const uint64_t rows2 = (uint64_t)2 << k; const uint32_t p = blockIdx.z, c = blockIdx.y;
+    ulonglong2 *col = cols + ((uint64_t)p * ncols + c) * rows2; const uint64_t len2 = lens[c] * 2;
+    if (c + 1 < ncols && blockIdx.x == 0 && threadIdx.x < 2) col[len2 - 2 + threadIdx.x] = col[rows2 + threadIdx.x];       // (c, len-1) <- (c+1, 0)
+    for (uint64_t h = len2 + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; h < rows2; h += (uint64_t)gridDim.x * blockDim.x) col[h] = make_ulonglong2(0, 0);
+}
+
 namespace h2w {
 // a traced plan (replay.hip)
 uint64_t traced_workspace_bytes(const h2w_plan *p, uint64_t n);
 uint64_t traced_status_offset(const h2w_plan *p, uint64_t n, bool flags);
 int traced_run(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void *advice_dev, void *workspace_dev, void *stream_, ColMap cm, uint64_t cell_stride, const ShardSpec &sh);
 const char *traced_shard_refusal(const h2w_plan *p);      // null: the traced plan shards by its depth-1 parallel instances
-}
-static size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
-extern "C" {
 
 static uint64_t own_count(uint64_t total, int rank, int world) { return total > (uint64_t)rank ? (total - (uint64_t)rank + (uint64_t)world - 1) / (uint64_t)world : 0; }
 static uint32_t unit_slot_of(const h2w_plan *p) { return (uint32_t)(p->st.q_nunit[0] > p->st.q_nunit[1] ? p->st.q_nunit[0] : p->st.q_nunit[1]); }
+static uint64_t shard_q_slot(const h2w_plan *p) { return p->st.q_ncell[0] > p->st.q_ncell[1] ? p->st.q_ncell[0] : p->st.q_ncell[1]; }      // a query block's slot in the packed layout (ShardMap)
 // Per-proof pieces first (their offsets do not depend on the sharding: h2w_plan_status finds the status words whatever call filled them), then the
 // PoseidonBN254 unit buffers, which hold the units of THIS RANK's (proof, query) units only.
 struct WsLayout { size_t recs, cbs, status, lflag, units, sbox, sbox9, glp, ctr, total; };
@@ -202,100 +204,14 @@ static WsLayout ws_layout(const h2w_plan *p, uint64_t n, const ShardSpec &sh = S
     w.total = o;
     return w;
 }
-uint64_t h2w_plan_workspace_bytes(const h2w_plan *p, uint64_t n_proofs) { return !p ? 0 : p->traced ? traced_workspace_bytes(p, n_proofs) : ws_layout(p, n_proofs).total; }
-uint64_t h2w_plan_shard_workspace_bytes(const h2w_plan *p, uint64_t n_proofs, int rank, int world) {
-    if (!p || world < 1 || rank < 0 || rank >= world) return 0;
-    if (const char *why = traced_shard_refusal(p)) { set_error(std::string("h2w_plan_shard_workspace_bytes: ") + why); return 0; }
-    if (p->traced) return traced_workspace_bytes(p, n_proofs);      // (value store and records per proof: the unsharded size)
-    ShardSpec sh; sh.rank = rank; sh.world = world;
-    return ws_layout(p, n_proofs, sh).total;
-}
-static int run_batch(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void *advice_dev, void *workspace_dev, void *stream_, void *emit_stream_, ColMap cm, uint64_t cell_stride, ShardSpec sh = ShardSpec());
-int h2w_fri_witness_batch(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void *advice_dev, void *workspace_dev, void *stream_) {
-    return run_batch(p, proofs_dev, n_proofs, advice_dev, workspace_dev, stream_, stream_, flat_cols(), p ? p->ncells : 0);
-}
-int h2w_fri_witness_batch2(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void *advice_dev, void *workspace_dev, void *stream_, void *emit_stream_) {
-    return run_batch(p, proofs_dev, n_proofs, advice_dev, workspace_dev, stream_, emit_stream_, flat_cols(), p ? p->ncells : 0);
-}
-// column-major emission: boundary cells repeated in the previous column, unused rows zeroed
-__global__ void k_columns_fixup(ulonglong2 *cols, const uint64_t *lens, uint32_t ncols, uint32_t k) {
-    const uint64_t rows2 = (uint64_t)2 << k; const uint32_t p = blockIdx.z, c = blockIdx.y;
-    ulonglong2 *col = cols + ((uint64_t)p * ncols + c) * rows2; const uint64_t len2 = lens[c] * 2;
-    if (c + 1 < ncols && blockIdx.x == 0 && threadIdx.x < 2) col[len2 - 2 + threadIdx.x] = col[rows2 + threadIdx.x];       // (c, len-1) <- (c+1, 0)
-    for (uint64_t h = len2 + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; h < rows2; h += (uint64_t)gridDim.x * blockDim.x) col[h] = make_ulonglong2(0, 0);
-}
-int h2w_fri_witness_batch_columns(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, const uint64_t *break_points, uint64_t n_bp, int k,
-                                  void *columns_dev, void *workspace_dev, void *stream_) {
-    if (!p || (!break_points && n_bp) || !columns_dev) { set_error("h2w_fri_witness_batch_columns: null argument"); return -1; }
-    if (k < 12 || k > 34 || n_bp + 1 > 4096) { set_error("h2w_fri_witness_batch_columns: k must be in [12, 34] and at most 4096 columns"); return -1; }
-    if (p->device < 0) { set_error("h2w_fri_witness_batch_columns: no HIP device — the hot path only runs on the GPU (no CPU fallback)"); return -1; }
-    const uint64_t ncols = n_bp + 1; std::vector<uint64_t> h(2 * ncols); uint64_t start = 0;
-    for (uint64_t c = 0; c < ncols; c++) {
-        const uint64_t len = c < n_bp ? break_points[c] + 1 : p->ncells - start;
-        if (start + len > p->ncells || len > ((uint64_t)1 << k) || len < 2) { set_error("h2w_fri_witness_batch_columns: break points do not fit the stream"); return -1; }
-        h[c] = start; h[ncols + c] = len; start += len - (c < n_bp ? 1 : 0);
-    }
-    DeviceGuard dg(p->device);
-    hipStream_t stream = (hipStream_t)stream_;
-    if (h != p->h_col_tab || k != p->col_k) {      // (re)upload the column table; plans are single-threaded handles (include/h2w.h)
-        H2W_HIP(hipDeviceSynchronize());             // a previous call on another stream may still read the old table
-        p->h_col_tab.clear();                        // (a failed upload leaves no table: the next call starts over)
-        if (p->d_col_tab.upload(h) != 0) return -1;
-        p->h_col_tab = h; p->col_k = k;
-    }
-    ColMap cm; cm.starts = p->d_col_tab.get(); cm.ncols = (uint32_t)ncols; cm.k = (uint32_t)k;
-    if (run_batch(p, proofs_dev, n_proofs, columns_dev, workspace_dev, stream_, stream_, cm, ncols << k) != 0) return -1;
-    if (n_proofs) {
-        if (n_proofs > 65535) { set_error("h2w_fri_witness_batch_columns: too many proofs per call"); return -1; }
-        hipLaunchKernelGGL(k_columns_fixup, dim3(64, (unsigned)ncols, (unsigned)n_proofs), dim3(256), 0, stream, (ulonglong2 *)columns_dev, p->d_col_tab.get() + ncols, (uint32_t)ncols, (uint32_t)k);
-        H2W_HIP(hipGetLastError());
-    }
-    return 0;
-}
-// (proof, query) sharding (SURVEY §8e): this rank LAUNCHES only what it owns - the prologue block of the proofs p % world == rank and the
-// query blocks of the units (proof * num_queries + query) % world == rank (every rank runs every prologue's values: it needs the
-// challenges) - at their global offsets in advice_dev[n_proofs][num_cells]; the other blocks are left untouched.
-int h2w_fri_witness_batch_shard(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void *advice_dev, void *workspace_dev, void *stream_, int rank, int world) {
-    if (world < 1 || rank < 0 || rank >= world) { set_error("h2w_fri_witness_batch_shard: bad rank / world"); return -1; }
-    if (const char *why = p ? traced_shard_refusal(p) : nullptr) { set_error(std::string("h2w_fri_witness_batch_shard: ") + why); return -1; }
-    ShardSpec sh; sh.rank = rank; sh.world = world;
-    return run_batch(p, proofs_dev, n_proofs, advice_dev, workspace_dev, stream_, stream_, flat_cols(), p ? p->ncells : 0, sh);
-}
-// The same blocks packed into a buffer of h2w_plan_shard_cells cells: the rank's owned blocks back to back in (proof, block) order.
-static uint64_t shard_q_slot(const h2w_plan *p) { return p->st.q_ncell[0] > p->st.q_ncell[1] ? p->st.q_ncell[0] : p->st.q_ncell[1]; }
-uint64_t h2w_plan_shard_cells(const h2w_plan *p, uint64_t n_proofs, int rank, int world) {
-    if (!p || world < 1 || rank < 0 || rank >= world) return 0;
-    if (const char *why = traced_shard_refusal(p)) { set_error(std::string("h2w_plan_shard_cells: ") + why); return 0; }
-    return own_count(n_proofs, rank, world) * p->st.pro_ncell + own_count(n_proofs * (uint64_t)p->shape.num_queries, rank, world) * shard_q_slot(p);
-}
-int h2w_plan_shard_block(const h2w_plan *p, int rank, int world, uint64_t proof, int query, uint64_t *local_cell, uint64_t *n_cells, uint64_t *global_cell) {
-    if (!p || world < 1 || rank < 0 || rank >= world || query >= p->shape.num_queries) { set_error("h2w_plan_shard_block: bad argument"); return -1; }
-    if (const char *why = traced_shard_refusal(p)) { set_error(std::string("h2w_plan_shard_block: ") + why); return -1; }
-    const uint64_t W = (uint64_t)world, r = (uint64_t)rank, nq = (uint64_t)p->shape.num_queries, u0 = proof * nq;
-    const bool owned = query < 0 ? proof % W == r : (u0 + (uint64_t)query) % W == r;
-    if (!owned) return 1;
-    const uint64_t local = packed_block_start(W, r, nq, p->st.pro_ncell, shard_q_slot(p), proof, query);
-    uint64_t n = p->st.pro_ncell, g = 0;
-    if (query >= 0) { n = p->st.q_ncell[query == 0 ? 0 : 1]; g = strand_q_cell(p->st, query); }
-    if (local_cell) *local_cell = local; if (n_cells) *n_cells = n; if (global_cell) *global_cell = g;
-    return 0;
-}
-int h2w_fri_witness_batch_shard_compact(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void *shard_advice_dev, void *workspace_dev, void *stream_, int rank, int world) {
-    if (world < 1 || rank < 0 || rank >= world) { set_error("h2w_fri_witness_batch_shard_compact: bad rank / world"); return -1; }
-    if (const char *why = p ? traced_shard_refusal(p) : nullptr) { set_error(std::string("h2w_fri_witness_batch_shard_compact: ") + why); return -1; }
-    if (p && !(p->shape.lookup_bits == 21 || p->shape.lookup_bits == 13 || p->shape.lookup_bits == 8)) { set_error("h2w_fri_witness_batch_shard_compact: lookup_bits must be 21, 13 or 8 (the packed layout is written by expand_fast)"); return -1; }
-    ShardSpec sh; sh.rank = rank; sh.world = world; sh.compact = 1;
-    return run_batch(p, proofs_dev, n_proofs, shard_advice_dev, workspace_dev, stream_, stream_, flat_cols(), 0, sh);
-}
 static void fill_expand_shard(const h2w_plan *p, ExpandArgs &E, const ShardSpec &sh) {
     E.shard_rank = (uint32_t)sh.rank; E.shard_world = (uint32_t)sh.world; E.shard_compact = (uint32_t)sh.compact; E.nq = (uint32_t)p->shape.num_queries;
     E.pro_nrec = p->st.pro_nrec; E.q_rec0_first = p->st.q_rec0[0]; E.q_rec0_rest = p->st.q_rec0[1]; E.q_nrec_first = p->st.q_nrec[0]; E.q_nrec_rest = p->st.q_nrec[1] ? p->st.q_nrec[1] : 1;
     if (p->shape.num_queries == 1) E.q_rec0_rest = ~0ull;
     E.pro_ncell = p->st.pro_ncell; E.q_cell0_first = p->st.q_cell0[0]; E.q_cell0_rest = p->st.q_cell0[1]; E.q_ncell_rest = p->st.q_ncell[1]; E.q_slot = shard_q_slot(p);
 }
-}  // extern "C"
-int h2w::launch_plan_expand(const h2w_plan *p, uint64_t n_proofs, const rec_t *recs, uint32_t *tile_ctr, fr_t *out, uint64_t cell_stride, ColMap cm,
-                            const ShardSpec *sh, uint32_t roam_per_cu, hipStream_t stream) {
+int launch_plan_expand(const h2w_plan *p, uint64_t n_proofs, const rec_t *recs, uint32_t *tile_ctr, fr_t *out, uint64_t cell_stride, ColMap cm,
+                       const ShardSpec *sh, uint32_t roam_per_cu, hipStream_t stream) {
     ExpandArgs E;
     E.meta = p->d_meta.get(); E.recs = recs; E.nrec = p->nrec; E.rec_stride = p->nrec; E.out = out; E.cell_stride = cell_stride; E.pool = nullptr; E.cm = cm;
     if (sh) fill_expand_shard(p, E, *sh); else expand_unsharded(E);
@@ -305,8 +221,19 @@ int h2w::launch_plan_expand(const h2w_plan *p, uint64_t n_proofs, const rec_t *r
     int gx = (int)(2048 / (n_proofs < 2048 ? n_proofs : 2048)); if (gx < 8) gx = 8;
     return launch_expand(E, n_proofs, gx, stream);
 }
-extern "C" {
-static int run_batch(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void *advice_dev, void *workspace_dev, void *stream_, void *emit_stream_, ColMap cm, uint64_t cell_stride, ShardSpec sh) {
+// roam_per_cu of the plan's expansion launches (profiles/r02_expand_grid.txt); the Montgomery form's kernel is bound by instruction issue, not by stores:
+// it needs every wavefront a CU holds (profiles/montgomery_form_cfg3.json)
+static uint32_t plan_roam_per_cu(const h2w_plan *p) { return (p->shape.hash_mode == 0 || p->output_form == H2W_FORM_MONTGOMERY) ? 2 : 1; }
+// k_direct_to_montgomery's arguments for a call: the plan's bitmap and block sizes, the call's output buffer, column map and sharding
+static DirectArgs direct_args(const h2w_plan *p, const BatchArgs &A, const ShardSpec &sh) {
+    DirectArgs D;
+    D.bits = p->d_direct_bits.get(); D.ncells = p->ncells; D.out = A.out; D.cell_stride = A.cell_stride; D.cm = A.cm;
+    D.rank = sh.rank; D.world = sh.world; D.compact = sh.compact; D.nq = (uint32_t)p->shape.num_queries;
+    D.pro_ncell = p->st.pro_ncell; D.q_cell0_first = p->st.q_cell0[0]; D.q_cell0_rest = p->st.q_cell0[1]; D.q_ncell_rest = p->st.q_ncell[1]; D.q_slot = shard_q_slot(p);
+    D.kconst = mont_k(); D.ninv = p->P.ninv;
+    return D;
+}
+static int run_batch(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void *advice_dev, void *workspace_dev, void *stream_, void *emit_stream_, ColMap cm, uint64_t cell_stride, const ShardSpec &sh) {
     if (!p) { set_error("h2w_fri_witness_batch: null plan"); return -1; }
     if (p->device < 0) { set_error("h2w_fri_witness_batch: no HIP device — the hot path only runs on the GPU (no CPU fallback)"); return -1; }
     if (!proofs_dev || !advice_dev || !workspace_dev) { set_error("h2w_fri_witness_batch: null buffer"); return -1; }
@@ -321,14 +248,10 @@ static int run_batch(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs,
     hipStream_t stream = (hipStream_t)stream_, estream = (hipStream_t)emit_stream_;
     const WsLayout wl = ws_layout(p, n_proofs, sh);
     char *ws = (char *)workspace_dev;
-    BatchArgs A;
-    A.shape = p->shape; A.consts = p->d_consts.get(); A.proofs = proofs_dev; A.proof_words = p->pl.total;
+    BatchArgs A = plan_batch_args(p, proofs_dev, n_proofs);
     A.recs = (rec_t *)(ws + wl.recs); A.rec_stride = p->nrec; A.out = (fr_t *)advice_dev; A.cell_stride = cell_stride; A.cm = cm;
-    A.cbs = (DevCB *)(ws + wl.cbs); A.status = (uint32_t *)(ws + wl.status);
-    A.unit_state = (fr_t *)(ws + wl.units); A.unit_sbox = (fr_t *)(ws + wl.sbox); A.unit_sbox9 = (uint32_t *)(ws + wl.sbox9); A.rowk = p->d_rowk.get(); A.glp_list = (uint64_t *)(ws + wl.glp); A.glp_small_mds = p->small_mds ? 1 : 0;
-    A.bn_tab = p->d_bn_tab.get(); A.bn_tab9 = p->d_bn_tab9.get(); A.fri = p->d_fri.get();
-    A.load_items = p->d_items.get(); A.n_load_items = p->n_items; A.n_cap_items = p->n_cap_items; A.load_nrec = p->load_nrec; A.load_ncell = p->load_ncell; A.load_flag = (uint32_t *)(ws + wl.lflag);
-    A.ncells = p->d_ncells.get(); A.inv_pos = p->d_inv.get(); A.inv_neg = p->d_inv.get() + INV_TAB; A.st = p->d_st.get(); A.P = p->P; A.nproofs = (int)n_proofs;
+    A.cbs = (DevCB *)(ws + wl.cbs); A.status = (uint32_t *)(ws + wl.status); A.load_flag = (uint32_t *)(ws + wl.lflag);
+    A.unit_state = (fr_t *)(ws + wl.units); A.unit_sbox = (fr_t *)(ws + wl.sbox); A.unit_sbox9 = (uint32_t *)(ws + wl.sbox9); A.glp_list = (uint64_t *)(ws + wl.glp);
     A.sh.rank = sh.rank; A.sh.world = sh.world; A.sh.compact = sh.compact; A.sh.q_slot = shard_q_slot(p); A.sh.unit_slot = unit_slot_of(p);
     A.sh.n_own_units = (uint32_t)own_count(n_proofs * (uint64_t)p->shape.num_queries, sh.rank, sh.world);
     A.sh.n_own_proofs = (uint32_t)own_count(n_proofs, sh.rank, sh.world);
@@ -354,14 +277,14 @@ static int run_batch(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs,
         H2W_HIP(hipMemsetAsync(A.load_flag, 0, n_proofs * sizeof(uint32_t), stream));
         if (p->n_items + p->n_cap_items) {
             const dim3 lgrid((p->n_items + p->n_cap_items + 255) / 256, (unsigned)n_proofs);
-            if (cm.starts) hipLaunchKernelGGL(k_prologue_load<true>, lgrid, dim3(256), 0, stream, A); else hipLaunchKernelGGL(k_prologue_load<false>, lgrid, dim3(256), 0, stream, A);
+            launch_cols(cm.starts != nullptr, k_prologue_load<true>, k_prologue_load<false>, lgrid, dim3(256), 0, stream, A);
         }
         // 2. the records of the listed Goldilocks-Poseidon permutations: with PoseidonBN254 caps the prologues' (now); with Goldilocks caps
         //    together with the Merkle strands' (below)
         const unsigned n_pro_perms = A.sh.n_own_proofs * p->st.pro_nglp, n_mk_perms = nunits * p->st.q_nglp;
         auto glp_emit = [&](unsigned n) -> int {
             H2W_HIP(hipEventRecord(ev[h2w_plan::EV_GLP_START], stream));
-            if (n) { if (cm.starts) hipLaunchKernelGGL(k_glp_emit<true>, dim3(n), dim3(64), 0, stream, A); else hipLaunchKernelGGL(k_glp_emit<false>, dim3(n), dim3(64), 0, stream, A); }
+            if (n) launch_cols(cm.starts != nullptr, k_glp_emit<true>, k_glp_emit<false>, dim3(n), dim3(64), 0, stream, A);
             H2W_HIP(hipEventRecord(ev[h2w_plan::EV_GLP_END], stream));
             return 0;
         };
@@ -377,7 +300,7 @@ static int run_batch(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs,
             // one pass or two (include/h2w.h H2W_OPT_CHAIN_PASSES): a launch whose paths do not fill the chip is bound by the depth of a path - split it
             const int passes = p->chain_passes ? p->chain_passes : (nunits <= 512 ? 2 : 1);
             p->passes_of[p->n_batches % h2w_plan::EV_RING] = passes;
-            if (nunits && passes == 1) { if (cm.starts) hipLaunchKernelGGL(k_merkle_bn_fused<true>, sgrid, dim3(QUAD_BLOCK), 0, cstream, A); else hipLaunchKernelGGL(k_merkle_bn_fused<false>, sgrid, dim3(QUAD_BLOCK), 0, cstream, A); }
+            if (nunits && passes == 1) launch_cols(cm.starts != nullptr, k_merkle_bn_fused<true>, k_merkle_bn_fused<false>, sgrid, dim3(QUAD_BLOCK), 0, cstream, A);
             if (nunits && passes != 1) {
                 // the values of the paths: one wavefront per path (rowperm.h: a path's 18 permutations in 1.3 ms instead of 2.6) for a launch of a few proofs - the form for
                 // one proof's latency; four lanes per path (coop.h bn_values: a sixth of the instructions per path) beyond that: alone on the chip the wavefront form
@@ -427,23 +350,15 @@ static int run_batch(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs,
         // runs on a grid of resident blocks there and reaches its rate alone, profiles/r02_expand_grid.txt).
         if (p->serial_expand != 0 && prev_ev) H2W_HIP(hipStreamWaitEvent(estream, prev_ev[H2W_EV_EXPAND_END], 0));
         H2W_HIP(hipEventRecord(ev[H2W_EV_EXPAND_START], estream));
-        if (launch_plan_expand(p, n_proofs, A.recs, (uint32_t *)(ws + wl.ctr), A.out, cell_stride, cm, &sh,
-                               (p->shape.hash_mode == 0 || p->output_form == H2W_FORM_MONTGOMERY) ? 2 : 1, estream) != 0) return -1;      // roam_per_cu: profiles/r02_expand_grid.txt;
-                               // the Montgomery form's kernel is bound by instruction issue, not by stores: it needs every wavefront a CU holds (profiles/montgomery_form_cfg3.json)
+        if (launch_plan_expand(p, n_proofs, A.recs, (uint32_t *)(ws + wl.ctr), A.out, cell_stride, cm, &sh, plan_roam_per_cu(p), estream) != 0) return -1;
         H2W_HIP(hipEventRecord(ev[H2W_EV_EXPAND_END], estream));
         // 6. Montgomery form: the direct cells, behind the chain kernels on the stream they ran on, beside the expansion kernel (which converts its own cells
         //    as it writes them).  The glue strands' and the prologue's direct cells were written on the caller's stream: the side stream waits for them.
         const bool mont = p->output_form == H2W_FORM_MONTGOMERY;
         if (mont) {
             if (cstream != stream) { H2W_HIP(hipStreamWaitEvent(cstream, ev[H2W_EV_GLUE_END], 0)); forked = true; }
-            DirectArgs D;
-            D.bits = p->d_direct_bits.get(); D.ncells = p->ncells; D.out = A.out; D.cell_stride = cell_stride; D.cm = cm;
-            D.rank = sh.rank; D.world = sh.world; D.compact = sh.compact; D.nq = (uint32_t)p->shape.num_queries;
-            D.pro_ncell = p->st.pro_ncell; D.q_cell0_first = p->st.q_cell0[0]; D.q_cell0_rest = p->st.q_cell0[1]; D.q_ncell_rest = p->st.q_ncell[1]; D.q_slot = shard_q_slot(p);
-            D.kconst = mont_k(); D.ninv = p->P.ninv;
             const uint64_t nwaves = ((p->ncells + 63) / 64 + 63) / 64;
-            const dim3 dgrid((unsigned)((nwaves + 3) / 4), (unsigned)n_proofs);
-            if (cm.starts) hipLaunchKernelGGL(k_direct_to_montgomery<true>, dgrid, dim3(256), 0, cstream, D); else hipLaunchKernelGGL(k_direct_to_montgomery<false>, dgrid, dim3(256), 0, cstream, D);
+            launch_cols(cm.starts != nullptr, k_direct_to_montgomery<true>, k_direct_to_montgomery<false>, dim3((unsigned)((nwaves + 3) / 4), (unsigned)n_proofs), dim3(256), 0, cstream, direct_args(p, A, sh));
             if (cstream != stream) H2W_HIP(hipEventRecord(ev[h2w_plan::EV_DIRECT_END], cstream));
         }
         if (estream != stream) H2W_HIP(hipStreamWaitEvent(stream, ev[H2W_EV_EXPAND_END], 0));    // the caller's stream completes when the advice is complete
@@ -461,6 +376,92 @@ static int run_batch(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs,
     p->n_batches++; p->ev_recorded = true;
     return 0;
 }
+// the event row of the call `back` calls before the last one (a ring of EV_RING); null, and `error` set, where there is none
+static const DevEvent *call_events(h2w_plan *p, uint64_t back, const char *error) {
+    if (!p || !p->ev_recorded || back >= p->n_batches || back >= (uint64_t)h2w_plan::EV_RING) { set_error(error); return nullptr; }
+    return p->evr[(p->n_batches - 1 - back) % h2w_plan::EV_RING];
+}
+
+}  // namespace h2w
+
+extern "C" {
+
+uint64_t h2w_plan_workspace_bytes(const h2w_plan *p, uint64_t n_proofs) { return !p ? 0 : p->traced ? traced_workspace_bytes(p, n_proofs) : ws_layout(p, n_proofs).total; }
+uint64_t h2w_plan_shard_workspace_bytes(const h2w_plan *p, uint64_t n_proofs, int rank, int world) {
+    if (!p || world < 1 || rank < 0 || rank >= world) return 0;
+    if (const char *why = traced_shard_refusal(p)) { set_error(std::string("h2w_plan_shard_workspace_bytes: ") + why); return 0; }
+    if (p->traced) return traced_workspace_bytes(p, n_proofs);      // (value store and records per proof: the unsharded size)
+    ShardSpec sh; sh.rank = rank; sh.world = world;
+    return ws_layout(p, n_proofs, sh).total;
+}
+int h2w_fri_witness_batch(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void *advice_dev, void *workspace_dev, void *stream_) {
+    return run_batch(p, proofs_dev, n_proofs, advice_dev, workspace_dev, stream_, stream_, flat_cols(), p ? p->ncells : 0, ShardSpec());
+}
+int h2w_fri_witness_batch2(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void *advice_dev, void *workspace_dev, void *stream_, void *emit_stream_) {
+    return run_batch(p, proofs_dev, n_proofs, advice_dev, workspace_dev, stream_, emit_stream_, flat_cols(), p ? p->ncells : 0, ShardSpec());
+}
+int h2w_fri_witness_batch_columns(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, const uint64_t *break_points, uint64_t n_bp, int k,
+                                  void *columns_dev, void *workspace_dev, void *stream_) {
+    if (!p || (!break_points && n_bp) || !columns_dev) { set_error("h2w_fri_witness_batch_columns: null argument"); return -1; }
+    if (k < 12 || k > 34 || n_bp + 1 > 4096) { set_error("h2w_fri_witness_batch_columns: k must be in [12, 34] and at most 4096 columns"); return -1; }
+    if (p->device < 0) { set_error("h2w_fri_witness_batch_columns: no HIP device — the hot path only runs on the GPU (no CPU fallback)"); return -1; }
+    const uint64_t ncols = n_bp + 1; std::vector<uint64_t> h(2 * ncols); uint64_t start = 0;
+    for (uint64_t c = 0; c < ncols; c++) {
+        const uint64_t len = c < n_bp ? break_points[c] + 1 : p->ncells - start;
+        if (start + len > p->ncells || len > ((uint64_t)1 << k) || len < 2) { set_error("h2w_fri_witness_batch_columns: break points do not fit the stream"); return -1; }
+        h[c] = start; h[ncols + c] = len; start += len - (c < n_bp ? 1 : 0);
+    }
+    DeviceGuard dg(p->device);
+    hipStream_t stream = (hipStream_t)stream_;
+    if (h != p->h_col_tab || k != p->col_k) {      // (re)upload the column table; plans are single-threaded handles (include/h2w.h)
+        H2W_HIP(hipDeviceSynchronize());             // a previous call on another stream may still read the old table
+        p->h_col_tab.clear();                        // (a failed upload leaves no table: the next call starts over)
+        if (p->d_col_tab.upload(h) != 0) return -1;
+        p->h_col_tab = h; p->col_k = k;
+    }
+    ColMap cm; cm.starts = p->d_col_tab.get(); cm.ncols = (uint32_t)ncols; cm.k = (uint32_t)k;
+    if (run_batch(p, proofs_dev, n_proofs, columns_dev, workspace_dev, stream_, stream_, cm, ncols << k, ShardSpec()) != 0) return -1;
+    if (n_proofs) {
+        if (n_proofs > 65535) { set_error("h2w_fri_witness_batch_columns: too many proofs per call"); return -1; }
+        hipLaunchKernelGGL(k_columns_fixup, dim3(64, (unsigned)ncols, (unsigned)n_proofs), dim3(256), 0, stream, (ulonglong2 *)columns_dev, p->d_col_tab.get() + ncols, (uint32_t)ncols, (uint32_t)k);
+        H2W_HIP(hipGetLastError());
+    }
+    return 0;
+}
+// (proof, query) sharding (SURVEY §8e): this rank LAUNCHES only what it owns - the prologue block of the proofs p % world == rank and the
+// query blocks of the units (proof * num_queries + query) % world == rank (every rank runs every prologue's values: it needs the
+// challenges) - at their global offsets in advice_dev[n_proofs][num_cells]; the other blocks are left untouched.
+int h2w_fri_witness_batch_shard(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void *advice_dev, void *workspace_dev, void *stream_, int rank, int world) {
+    if (world < 1 || rank < 0 || rank >= world) { set_error("h2w_fri_witness_batch_shard: bad rank / world"); return -1; }
+    if (const char *why = p ? traced_shard_refusal(p) : nullptr) { set_error(std::string("h2w_fri_witness_batch_shard: ") + why); return -1; }
+    ShardSpec sh; sh.rank = rank; sh.world = world;
+    return run_batch(p, proofs_dev, n_proofs, advice_dev, workspace_dev, stream_, stream_, flat_cols(), p ? p->ncells : 0, sh);
+}
+// The same blocks packed into a buffer of h2w_plan_shard_cells cells: the rank's owned blocks back to back in (proof, block) order.
+uint64_t h2w_plan_shard_cells(const h2w_plan *p, uint64_t n_proofs, int rank, int world) {
+    if (!p || world < 1 || rank < 0 || rank >= world) return 0;
+    if (const char *why = traced_shard_refusal(p)) { set_error(std::string("h2w_plan_shard_cells: ") + why); return 0; }
+    return own_count(n_proofs, rank, world) * p->st.pro_ncell + own_count(n_proofs * (uint64_t)p->shape.num_queries, rank, world) * shard_q_slot(p);
+}
+int h2w_plan_shard_block(const h2w_plan *p, int rank, int world, uint64_t proof, int query, uint64_t *local_cell, uint64_t *n_cells, uint64_t *global_cell) {
+    if (!p || world < 1 || rank < 0 || rank >= world || query >= p->shape.num_queries) { set_error("h2w_plan_shard_block: bad argument"); return -1; }
+    if (const char *why = traced_shard_refusal(p)) { set_error(std::string("h2w_plan_shard_block: ") + why); return -1; }
+    const uint64_t W = (uint64_t)world, r = (uint64_t)rank, nq = (uint64_t)p->shape.num_queries, u0 = proof * nq;
+    const bool owned = query < 0 ? proof % W == r : (u0 + (uint64_t)query) % W == r;
+    if (!owned) return 1;
+    const uint64_t local = packed_block_start(W, r, nq, p->st.pro_ncell, shard_q_slot(p), proof, query);
+    uint64_t n = p->st.pro_ncell, g = 0;
+    if (query >= 0) { n = p->st.q_ncell[query == 0 ? 0 : 1]; g = strand_q_cell(p->st, query); }
+    if (local_cell) *local_cell = local; if (n_cells) *n_cells = n; if (global_cell) *global_cell = g;
+    return 0;
+}
+int h2w_fri_witness_batch_shard_compact(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void *shard_advice_dev, void *workspace_dev, void *stream_, int rank, int world) {
+    if (world < 1 || rank < 0 || rank >= world) { set_error("h2w_fri_witness_batch_shard_compact: bad rank / world"); return -1; }
+    if (const char *why = p ? traced_shard_refusal(p) : nullptr) { set_error(std::string("h2w_fri_witness_batch_shard_compact: ") + why); return -1; }
+    if (p && !(p->shape.lookup_bits == 21 || p->shape.lookup_bits == 13 || p->shape.lookup_bits == 8)) { set_error("h2w_fri_witness_batch_shard_compact: lookup_bits must be 21, 13 or 8 (the packed layout is written by expand_fast)"); return -1; }
+    ShardSpec sh; sh.rank = rank; sh.world = world; sh.compact = 1;
+    return run_batch(p, proofs_dev, n_proofs, shard_advice_dev, workspace_dev, stream_, stream_, flat_cols(), 0, sh);
+}
 // Re-expands the block records a previous h2w_fri_witness_batch* call left in `workspace_dev` (same n_proofs) into advice_dev: the
 // expansion kernel alone, for measuring its streaming rate (bench.py roofline).  Cells written by the value kernels are not touched.
 int h2w_fri_expand_records(h2w_plan *p, uint64_t n_proofs, void *advice_dev, void *workspace_dev, void *stream_) {
@@ -473,8 +474,7 @@ int h2w_fri_expand_records(h2w_plan *p, uint64_t n_proofs, void *advice_dev, voi
     const WsLayout wl = ws_layout(p, n_proofs);
     char *ws = (char *)workspace_dev;
     const ShardSpec one_rank{};
-    if (launch_plan_expand(p, n_proofs, (rec_t *)(ws + wl.recs), (uint32_t *)(ws + wl.ctr), (fr_t *)advice_dev, p->ncells, flat_cols(), &one_rank,
-                           (p->shape.hash_mode == 0 || p->output_form == H2W_FORM_MONTGOMERY) ? 2 : 1, stream) != 0) return -1;      // (as run_batch)
+    if (launch_plan_expand(p, n_proofs, (rec_t *)(ws + wl.recs), (uint32_t *)(ws + wl.ctr), (fr_t *)advice_dev, p->ncells, flat_cols(), &one_rank, plan_roam_per_cu(p), stream) != 0) return -1;
     H2W_HIP(hipGetLastError());
     return 0;
 }
@@ -492,8 +492,8 @@ int h2w_plan_status(h2w_plan *p, const void *workspace_dev, uint64_t n_proofs, u
     return 0;
 }
 int h2w_plan_timing(h2w_plan *p, uint64_t back, float ms[5]) {   // `back` batches before the last one (ring of 64)
-    if (!p || !p->ev_recorded || back >= p->n_batches || back >= (uint64_t)h2w_plan::EV_RING) { set_error("h2w_plan_timing: no such batch"); return -1; }
-    const DevEvent *ev = p->evr[(p->n_batches - 1 - back) % h2w_plan::EV_RING];
+    const DevEvent *ev = call_events(p, back, "h2w_plan_timing: no such batch");
+    if (!ev) return -1;
     DeviceGuard dg(p->device);
     H2W_HIP(hipEventSynchronize(ev[H2W_EV_CALL_END]));
     H2W_HIP(hipEventElapsedTime(&ms[0], ev[H2W_EV_CALL_START], ev[H2W_EV_PROLOGUE_END]));   // prologue strands: values (+ with PoseidonBN254 caps: their permutations' records)
@@ -504,8 +504,8 @@ int h2w_plan_timing(h2w_plan *p, uint64_t back, float ms[5]) {   // `back` batch
     return 0;
 }
 int h2w_plan_timing_ex(h2w_plan *p, uint64_t back, float ms[8]) {
-    if (!p || !p->ev_recorded || back >= p->n_batches || back >= (uint64_t)h2w_plan::EV_RING) { set_error("h2w_plan_timing_ex: no such batch"); return -1; }
-    const DevEvent *ev = p->evr[(p->n_batches - 1 - back) % h2w_plan::EV_RING];
+    const DevEvent *ev = call_events(p, back, "h2w_plan_timing_ex: no such batch");
+    if (!ev) return -1;
     DeviceGuard dg(p->device);
     H2W_HIP(hipEventSynchronize(ev[H2W_EV_CALL_END]));
     H2W_HIP(hipEventElapsedTime(&ms[0], ev[H2W_EV_CALL_START], ev[h2w_plan::EV_PROLOGUE_VALUES_END]));    // k_prologue_values
@@ -520,10 +520,12 @@ int h2w_plan_timing_ex(h2w_plan *p, uint64_t back, float ms[8]) {
 }
 int h2w_plan_last_timing(h2w_plan *p, float ms[5]) { return h2w_plan_timing(p, 0, ms); }
 int h2w_plan_event_gap(h2w_plan *p, uint64_t back_a, int which_a, uint64_t back_b, int which_b, float *ms) {
-    if (!p || !ms || !p->ev_recorded || back_a >= p->n_batches || back_b >= p->n_batches || back_a >= (uint64_t)h2w_plan::EV_RING || back_b >= (uint64_t)h2w_plan::EV_RING ||
-        which_a < 0 || which_a >= H2W_EV_COUNT || which_b < 0 || which_b >= H2W_EV_COUNT) { set_error("h2w_plan_event_gap: no such batch / event"); return -1; }
+    const char *none = "h2w_plan_event_gap: no such batch / event";
+    if (!ms || which_a < 0 || which_a >= H2W_EV_COUNT || which_b < 0 || which_b >= H2W_EV_COUNT) { set_error(none); return -1; }
+    const DevEvent *ev_a = call_events(p, back_a, none), *ev_b = call_events(p, back_b, none);
+    if (!ev_a || !ev_b) return -1;
     if (p->shape.hash_mode == 0 && (which_a == H2W_EV_CHAINS_START || which_a == H2W_EV_CHAINS_END || which_b == H2W_EV_CHAINS_START || which_b == H2W_EV_CHAINS_END)) { set_error("h2w_plan_event_gap: no chain kernel with Goldilocks-Poseidon caps"); return -1; }
-    hipEvent_t a = p->evr[(p->n_batches - 1 - back_a) % h2w_plan::EV_RING][which_a], b = p->evr[(p->n_batches - 1 - back_b) % h2w_plan::EV_RING][which_b];
+    hipEvent_t a = ev_a[which_a], b = ev_b[which_b];
     DeviceGuard dg(p->device);
     H2W_HIP(hipEventSynchronize(a)); H2W_HIP(hipEventSynchronize(b));
     H2W_HIP(hipEventElapsedTime(ms, a, b));
@@ -551,4 +553,3 @@ int h2w_plan_configure(h2w_plan *p, int option, int value) {
 }
 
 }  // extern "C"
-

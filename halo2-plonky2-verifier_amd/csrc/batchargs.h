@@ -76,6 +76,21 @@ __device__ __forceinline__ ValCfg make_cfg(const BatchArgs &A, int p) {
     c.split_bn = false;
     return c;
 }
+// status 4: the proof words of a load item are outside their field - kinds 0-1: one Goldilocks word, v.l[0]; 2: four of them; 3: a BN254 element; kind 4
+// (the limb decomposition of a cap hash) checks nothing.  The one place that decides it: k_prologue_load (batch.hip) and k_verdict_check (verdict.hip)
+__device__ __forceinline__ bool load_item_out_of_field(uint32_t kind, const fr_t &v) {
+    if (kind <= 1) return v.l[0] >= GL_P;
+    if (kind == 2) return v.l[0] >= GL_P || v.l[1] >= GL_P || v.l[2] >= GL_P || v.l[3] >= GL_P;
+    return kind == 3 && fr_geq_mod(v);
+}
+// the row-cooperative permutation's constants (rowfr.h) from the plan's device copy: wave-uniform, scalar loads
+__device__ __forceinline__ rf::RowConst load_row_consts(const rf::RowConst *rowk) {
+    rf::RowConst K;
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(rowk); uint32_t *dst = reinterpret_cast<uint32_t *>(&K);
+#pragma unroll
+    for (unsigned i = 0; i < sizeof(rf::RowConst) / 4; i++) dst[i] = *(const __attribute__((address_space(4))) uint32_t *)(src + i);
+    return K;
+}
 
 template <bool COLS, bool VALPH, int HM> __device__ __forceinline__ void coop_sink_init(CoopSinkT<COLS, VALPH, HM> &sink, const BatchArgs &A, int p, int q) {
     sink.recs = A.recs + (uint64_t)p * A.rec_stride; sink.out = block_out(A, p, q); sink.ncells = A.ncells; sink.lane = threadIdx.x; sink.cc.init(A.cm);

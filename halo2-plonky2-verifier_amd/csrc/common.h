@@ -26,6 +26,11 @@ inline int device_of(const void *ptr) {
     if (!ptr || hipPointerGetAttributes(&a, ptr) != hipSuccess) { (void)hipGetLastError(); return -1; }
     return a.type == hipMemoryTypeDevice ? a.device : -1;
 }
+inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+// a kernel with a column-layout template parameter: the instantiation for column-major emission (ColMap.starts set) or the flat one
+template <class Args> inline void launch_cols(bool cols, void (*k_cols)(Args), void (*k_flat)(Args), dim3 grid, dim3 block, size_t dyn, hipStream_t s, const Args &a) {
+    if (cols) hipLaunchKernelGGL(k_cols, grid, block, dyn, s, a); else hipLaunchKernelGGL(k_flat, grid, block, dyn, s, a);
+}
 
 // keygen lists of a plan's cell stream that need wires with cell identities (copy constraints, constant equalities): built once, on
 // demand, by abi_backend.cpp (the eager keygen context replays the shape) and cached in the plan

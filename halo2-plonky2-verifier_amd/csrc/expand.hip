@@ -570,11 +570,8 @@ int launch_expand(const ExpandArgs &A, uint64_t nproofs, int grid_x, hipStream_t
     uint64_t gx = (uint64_t)grid_x; if (gx > ntiles) gx = ntiles; if (gx < 1) gx = 1;
     const dim3 grid((unsigned)gx, (unsigned)nproofs);
     const size_t dyn = ((size_t)A.nconsts * 32 + (size_t)A.nslots * 4 + 15) & ~(size_t)15;      // expand_kernel_t's tables
-    if (A.mont) {
-        if (A.cm.starts) hipLaunchKernelGGL((expand_kernel_mont<32, 5, true>), grid, dim3(EXPAND_THREADS), dyn, stream, A);
-        else hipLaunchKernelGGL((expand_kernel_mont<32, 5, false>), grid, dim3(EXPAND_THREADS), dyn, stream, A);
-    } else if (A.cm.starts) hipLaunchKernelGGL((expand_kernel_t<32, 5, true>), grid, dim3(EXPAND_THREADS), dyn, stream, A);
-    else hipLaunchKernelGGL((expand_kernel_t<32, 5, false>), grid, dim3(EXPAND_THREADS), dyn, stream, A);
+    if (A.mont) launch_cols(A.cm.starts != nullptr, expand_kernel_mont<32, 5, true>, expand_kernel_mont<32, 5, false>, grid, dim3(EXPAND_THREADS), dyn, stream, A);
+    else launch_cols(A.cm.starts != nullptr, expand_kernel_t<32, 5, true>, expand_kernel_t<32, 5, false>, grid, dim3(EXPAND_THREADS), dyn, stream, A);
     return 0;
 }
 

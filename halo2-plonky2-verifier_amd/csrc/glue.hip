@@ -34,12 +34,7 @@ struct RowSink : SinkBase {
     __device__ __forceinline__ bool level_skip(fr_t &, bool &) { return false; }
     __device__ __forceinline__ bool tail_skip() const { return true; }      // the cap lookup: cells only (no value anyone uses)
     __device__ __forceinline__ void permute_unit(fr_t *st) {
-        rf::RowConst K;
-        {   // wave-uniform: scalar loads
-            const uint32_t *src = reinterpret_cast<const uint32_t *>(rowk); uint32_t *dst = reinterpret_cast<uint32_t *>(&K);
-#pragma unroll
-            for (unsigned i = 0; i < sizeof(rf::RowConst) / 4; i++) dst[i] = *(const __attribute__((address_space(4))) uint32_t *)(src + i);
-        }
+        const rf::RowConst K = load_row_consts(rowk);
         const rf::LaneK L = rf::lane_consts();
         rf::bn_permute_rows(st, K, L, sbx9 + (size_t)unit_local * (BN_PARTIAL_ROUNDS * 3 * rf::SBX9_W));
         const unsigned lane = threadIdx.x & 63u;
@@ -141,10 +136,7 @@ __global__ __launch_bounds__(QUAD_BLOCK) __attribute__((flatten)) void k_merkle_
 }
 void launch_merkle_bn_values(const BatchArgs &A, dim3 grid, hipStream_t stream) { hipLaunchKernelGGL(k_merkle_bn_values, grid, dim3(QUAD_BLOCK), 0, stream, A); }
 
-void launch_merkle_bn_emit(const BatchArgs &A, dim3 grid, hipStream_t stream) {
-    if (A.cm.starts) hipLaunchKernelGGL(k_merkle_bn_emit<true>, grid, dim3(QUAD_BLOCK), 0, stream, A);
-    else hipLaunchKernelGGL(k_merkle_bn_emit<false>, grid, dim3(QUAD_BLOCK), 0, stream, A);
-}
+void launch_merkle_bn_emit(const BatchArgs &A, dim3 grid, hipStream_t stream) { launch_cols(A.cm.starts != nullptr, k_merkle_bn_emit<true>, k_merkle_bn_emit<false>, grid, dim3(QUAD_BLOCK), 0, stream, A); }
 
 // Goldilocks-Poseidon Merkle strands (hash_mode 0), values phase: one wavefront per (owned unit, kind); blockIdx.y = kind slot.  Flattened like the
 // prologue (round 4): out of line, every hash of a path handed its state to the permutation through scratch memory and the sink lived there
@@ -166,18 +158,8 @@ template <bool COLS> __global__ __launch_bounds__(64) __attribute__((flatten)) v
     if (threadIdx.x == 0 && be.status) atomicCAS(&A.status[p], 0u, be.status);
 }
 
-void launch_merkle_gl_values(const BatchArgs &A, unsigned nunits, unsigned nkinds, hipStream_t stream) {
-    if (A.cm.starts) hipLaunchKernelGGL(k_merkle_gl_values<true>, dim3(nunits, nkinds), dim3(64), 0, stream, A); else hipLaunchKernelGGL(k_merkle_gl_values<false>, dim3(nunits, nkinds), dim3(64), 0, stream, A);
-}
-void launch_prologue_values(const BatchArgs &A, hipStream_t stream) {
-    if (A.cm.starts) hipLaunchKernelGGL(k_prologue_values<true>, dim3((unsigned)A.nproofs), dim3(64), 0, stream, A);
-    else hipLaunchKernelGGL(k_prologue_values<false>, dim3((unsigned)A.nproofs), dim3(64), 0, stream, A);
-}
-
-void launch_glue_strands(const BatchArgs &A, hipStream_t stream) {
-    const unsigned nlanes = A.sh.n_own_units;
-    if (A.cm.starts) hipLaunchKernelGGL(k_strands<true>, dim3((nlanes + 63) / 64, 1), dim3(64), 0, stream, A);
-    else hipLaunchKernelGGL(k_strands<false>, dim3((nlanes + 63) / 64, 1), dim3(64), 0, stream, A);
-}
+void launch_merkle_gl_values(const BatchArgs &A, unsigned nunits, unsigned nkinds, hipStream_t stream) { launch_cols(A.cm.starts != nullptr, k_merkle_gl_values<true>, k_merkle_gl_values<false>, dim3(nunits, nkinds), dim3(64), 0, stream, A); }
+void launch_prologue_values(const BatchArgs &A, hipStream_t stream) { launch_cols(A.cm.starts != nullptr, k_prologue_values<true>, k_prologue_values<false>, dim3((unsigned)A.nproofs), dim3(64), 0, stream, A); }
+void launch_glue_strands(const BatchArgs &A, hipStream_t stream) { launch_cols(A.cm.starts != nullptr, k_strands<true>, k_strands<false>, dim3((A.sh.n_own_units + 63) / 64, 1), dim3(64), 0, stream, A); }
 
 }  // namespace h2w

@@ -57,6 +57,17 @@ inline int plan_side_slot(h2w_plan *p, hipStream_t s) {
     p->side_of[k] = s; p->n_side++;
     return k;
 }
+// The plan's part of a call's kernel arguments (batch.hip run_batch, verdict.hip verdict_call): the shape, its device tables, the proofs.  What belongs to
+// the call - workspace pointers, the output buffer and its stride, cm, sh - is value-initialised here and the caller's to set.
+inline BatchArgs plan_batch_args(const h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs) {
+    BatchArgs A{};
+    A.shape = p->shape; A.consts = p->d_consts.get(); A.proofs = proofs_dev; A.proof_words = p->pl.total;
+    A.rowk = p->d_rowk.get(); A.glp_small_mds = p->small_mds ? 1 : 0;
+    A.bn_tab = p->d_bn_tab.get(); A.bn_tab9 = p->d_bn_tab9.get(); A.fri = p->d_fri.get();
+    A.load_items = p->d_items.get(); A.n_load_items = p->n_items; A.n_cap_items = p->n_cap_items; A.load_nrec = p->load_nrec; A.load_ncell = p->load_ncell;
+    A.ncells = p->d_ncells.get(); A.inv_pos = p->d_inv.get(); A.inv_neg = p->d_inv.get() + INV_TAB; A.st = p->d_st.get(); A.P = p->P; A.nproofs = (int)n_proofs;
+    return A;
+}
 // The expansion launch of a plan's call (batch.hip: run_batch, h2w_fri_expand_records; replay.hip traced_run): records[n_proofs][p->nrec] -> cells
 // out[n_proofs][cell_stride] through cm.  sh: the (proof, query) sharding of the record ranges; null: every proof is one block (a traced plan has
 // no strand table).  tile_ctr: n_proofs words of workspace, zeroed here.  roam_per_cu: ExpandArgs.

@@ -465,7 +465,7 @@ int traced_run(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void 
         } else { E.items = nullptr; E.nitems = (uint64_t)n_proofs * t->nbnp; }
         const uint64_t nblk = (E.nitems * 4 + QUAD_BLOCK - 1) / QUAD_BLOCK;
         if (nblk >= 0x7fffffffull) { set_error("h2w_fri_witness_batch: too many fused permutations in one call"); return -1; }
-        if (nblk) { if (cm.starts) hipLaunchKernelGGL(k_bn_emit_traced<true>, dim3((uint32_t)nblk), dim3(QUAD_BLOCK), 0, stream, E); else hipLaunchKernelGGL(k_bn_emit_traced<false>, dim3((uint32_t)nblk), dim3(QUAD_BLOCK), 0, stream, E); }
+        if (nblk) launch_cols(cm.starts != nullptr, k_bn_emit_traced<true>, k_bn_emit_traced<false>, dim3((uint32_t)nblk), dim3(QUAD_BLOCK), 0, stream, E);
     }
     if (t->timing) H2W_HIP(hipEventRecord(t->tev[t->tev_used++], stream));
     // expansion of the block records

@@ -7,7 +7,7 @@
 //   launch_prologue_values  k_prologue_values as it is (glue.hip), with a shard map under which no proof's block is owned: what a non-owner rank of a
 //                           sharded run does - values only -> challenge blocks, the prologue's status word
 //   k_verdict_init          one lane per proof: the verdict's start value, the PoW bit (fri/mod.rs:130-145) from the challenge block
-//   k_verdict_check         one lane per (proof, load item): status 4, as k_prologue_load (batch.hip) decides it
+//   k_verdict_check         one lane per (proof, load item): status 4, by k_prologue_load's (batch.hip) predicate: batchargs.h load_item_out_of_field
 //   k_verdict_glue          one lane per (proof, query): Verifier::query_round on a sink without cells - the fold steps' consistency checks and the
 //                           final polynomial's evaluation
 //   k_verdict_merkle_gl     Goldilocks caps: one wavefront per (proof, query, tree), permutations on glp_permute_lanes (k_merkle_gl_values without list or records)
@@ -49,8 +49,8 @@ struct VerdictAcc {
     __device__ __forceinline__ void status(uint32_t s) { if (s && on) atomicCAS(&v->status, 0u, s); }
 };
 
-struct VerdictGlueSink : SinkBase {
-    static constexpr bool kSplitOnly = true;
+// a sink of this unit: Base's walk on values with no record, no cell and no cursor - the comparisons alone, to the accumulator
+template <class Base> struct VerdictSinkT : Base {
     VerdictAcc acc;
     __device__ __forceinline__ void rec(int, uint64_t, uint64_t, uint64_t, uint64_t) {}
     __device__ __forceinline__ void cell(const fr_t &) {}
@@ -58,47 +58,25 @@ struct VerdictGlueSink : SinkBase {
     __device__ __forceinline__ void compare(bool differ) { acc.compare(differ); }
     __device__ __forceinline__ void site(int s) { acc.cur = s; }
 };
-struct VerdictCoopSink : CoopSinkT<false, true, 0> {      // (emit = false: no list entry; rec / cell hidden: no cursor either)
-    VerdictAcc acc;
-    __device__ __forceinline__ void rec(int, uint64_t, uint64_t, uint64_t, uint64_t) {}
-    __device__ __forceinline__ void cell(const fr_t &) {}
-    __device__ __forceinline__ void skip(uint64_t, uint64_t) {}
-    __device__ __forceinline__ void compare(bool differ) { acc.compare(differ); }
-    __device__ __forceinline__ void site(int s) { acc.cur = s; }
-};
-struct VerdictQuadSink : QuadSinkT<false, QUAD_VERDICT> {
-    VerdictAcc acc;
-    __device__ __forceinline__ void rec(int, uint64_t, uint64_t, uint64_t, uint64_t) {}
-    __device__ __forceinline__ void cell(const fr_t &) {}
-    __device__ __forceinline__ void skip(uint64_t, uint64_t) {}
-    __device__ __forceinline__ void compare(bool differ) { acc.compare(differ); }
-    __device__ __forceinline__ void site(int s) { acc.cur = s; }
-};
-
+struct VerdictGlueBase : SinkBase { static constexpr bool kSplitOnly = true; };
 // one wavefront per path, every lane on the same values (glue.hip RowSink without anything it leaves for an emission pass): no unit states, no S-box
 // values - the permutation stores nothing -, and the cap lookup's value is taken; lane 0 speaks
-struct VerdictRowSink : SinkBase {
+struct VerdictRowBase : SinkBase {
     static constexpr bool kBnUnits = true; static constexpr int kHashMode = 1;
-    const rf::RowConst *rowk; VerdictAcc acc;
-    __device__ __forceinline__ void rec(int, uint64_t, uint64_t, uint64_t, uint64_t) {}
-    __device__ __forceinline__ void cell(const fr_t &) {}
-    __device__ __forceinline__ void skip(uint64_t, uint64_t) {}
+    const rf::RowConst *rowk;
     __device__ __forceinline__ bool level_skip(fr_t &, bool &) { return false; }
     __device__ __forceinline__ bool tail_skip() const { return false; }
     __device__ __forceinline__ void permute_unit(fr_t *st) {
-        rf::RowConst K;
-        {   // wave-uniform: scalar loads
-            const uint32_t *src = reinterpret_cast<const uint32_t *>(rowk); uint32_t *dst = reinterpret_cast<uint32_t *>(&K);
-#pragma unroll
-            for (unsigned i = 0; i < sizeof(rf::RowConst) / 4; i++) dst[i] = *(const __attribute__((address_space(4))) uint32_t *)(src + i);
-        }
+        const rf::RowConst K = load_row_consts(rowk);
         const rf::LaneK L = rf::lane_consts();
         rf::bn_permute_rows<false>(st, K, L, nullptr);
     }
     __device__ __forceinline__ bool bn_emit_inline(fr_t *st, const ValCfg &, bool &) { permute_unit(st); return true; }
-    __device__ __forceinline__ void compare(bool differ) { acc.compare(differ); }
-    __device__ __forceinline__ void site(int s) { acc.cur = s; }
 };
+typedef VerdictSinkT<VerdictGlueBase> VerdictGlueSink;
+typedef VerdictSinkT<CoopSinkT<false, true, 0>> VerdictCoopSink;      // (emit = false: no list entry; rec / cell hidden: no cursor either)
+typedef VerdictSinkT<QuadSinkT<false, QUAD_VERDICT>> VerdictQuadSink;
+typedef VerdictSinkT<VerdictRowBase> VerdictRowSink;
 
 struct VerdictArgs { BatchArgs A; h2w_verdict_t *verdict; uint32_t *lflag; };
 
@@ -124,12 +102,9 @@ __global__ __launch_bounds__(256) void k_verdict_check(VerdictArgs V) {
     const uint64_t wk = g_load_u64(reinterpret_cast<const uint64_t *>(V.A.load_items + i));
     const uint32_t word = (uint32_t)wk, kind = (uint32_t)(wk >> 32);
     const uint64_t *w = V.A.proofs + p * V.A.proof_words + word; const uint64_t w0 = g_load_u64(w);
-    bool bad;
-    if (kind <= 1) bad = w0 >= GL_P;
-    else {
-        fr_t v; v.l[0] = w0; v.l[1] = g_load_u64(w + 1); v.l[2] = g_load_u64(w + 2); v.l[3] = g_load_u64(w + 3);
-        bad = kind == 2 ? (v.l[0] >= GL_P || v.l[1] >= GL_P || v.l[2] >= GL_P || v.l[3] >= GL_P) : kind == 3 ? fr_geq_mod(v) : false;
-    }
+    fr_t v; v.l[0] = w0;
+    if (kind >= 2) { v.l[1] = g_load_u64(w + 1); v.l[2] = g_load_u64(w + 2); v.l[3] = g_load_u64(w + 3); }
+    const bool bad = load_item_out_of_field(kind, v);
     if (bad) atomicOr(&V.lflag[p], 4u);
 }
 
@@ -208,8 +183,6 @@ __global__ __launch_bounds__(QUAD_BLOCK) __attribute__((flatten)) void k_verdict
     sink.acc.status(be.status);
 }
 
-static size_t up256(size_t x) { return (x + 255) / 256 * 256; }
-
 // H2W_VERDICT_FORM_AUTO: the wavefront-per-path form up to this many Merkle paths = n_proofs x num_queries x (n_oracles + n_steps) of a call with
 // PoseidonBN254 caps.  A path is 18 dependent permutations in either form; the row form walks it in half the time with sixteen times the lanes, so it
 // wins while the four-lane form leaves the chip idle.  The largest path count of the sweep at which it was not the slower one, a call alone on the
@@ -243,20 +216,14 @@ static int verdict_call(const char *who, h2w_plan *p, const uint64_t *proofs_dev
         }
     }
     // the call's workspace: challenge blocks, the prologue's status words, the range flags
-    const size_t o_status = up256((size_t)n_proofs * sizeof(DevCB)), o_lflag = o_status + up256((size_t)n_proofs * sizeof(uint32_t)), total = o_lflag + up256((size_t)n_proofs * sizeof(uint32_t));
+    const size_t o_status = align_up((size_t)n_proofs * sizeof(DevCB), 256), o_lflag = o_status + align_up((size_t)n_proofs * sizeof(uint32_t), 256), total = o_lflag + align_up((size_t)n_proofs * sizeof(uint32_t), 256);
     char *ws = nullptr;
     H2W_HIP(hipMallocAsync((void **)&ws, total, stream));
     bool forked = false;
     auto run = [&]() -> int {
         VerdictArgs V; BatchArgs &A = V.A;
-        A.shape = p->shape; A.consts = p->d_consts.get(); A.proofs = proofs_dev; A.proof_words = p->pl.total;
-        A.recs = nullptr; A.rec_stride = 0; A.out = nullptr; A.cell_stride = 0; A.cm = flat_cols();
-        A.cbs = (DevCB *)ws; A.status = (uint32_t *)(ws + o_status);
-        A.unit_state = nullptr; A.unit_sbox = nullptr; A.unit_sbox9 = nullptr; A.rowk = p->d_rowk.get(); A.glp_list = nullptr; A.glp_small_mds = p->small_mds ? 1 : 0;
-        A.bn_tab = p->d_bn_tab.get(); A.bn_tab9 = p->d_bn_tab9.get(); A.fri = p->d_fri.get();
-        A.load_items = p->d_items.get(); A.n_load_items = p->n_items; A.n_cap_items = p->n_cap_items; A.load_nrec = p->load_nrec; A.load_ncell = p->load_ncell; A.load_flag = (uint32_t *)(ws + o_lflag);
-        A.ncells = p->d_ncells.get(); A.inv_pos = p->d_inv.get(); A.inv_neg = p->d_inv.get() + INV_TAB; A.st = p->d_st.get(); A.P = p->P; A.nproofs = (int)n_proofs;
-        A.sh.compact = 0; A.sh.q_slot = 0; A.sh.unit_slot = 0; A.sh.n_own_units = 0; A.sh.n_own_proofs = 0;
+        A = plan_batch_args(p, proofs_dev, n_proofs);      // (no records, no advice, no unit buffers, no permutation list: those stay null)
+        A.cm = flat_cols(); A.cbs = (DevCB *)ws; A.status = (uint32_t *)(ws + o_status); A.load_flag = (uint32_t *)(ws + o_lflag);
         V.verdict = verdict_dev; V.lflag = A.load_flag;
         H2W_HIP(hipMemsetAsync(V.lflag, 0, n_proofs * sizeof(uint32_t), stream));
         // the prologue on values: a world in which this rank owns no proof's block (own_prologue: p % world == rank never holds below 2^30 proofs)

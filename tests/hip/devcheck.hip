@@ -190,7 +190,7 @@ __global__ __launch_bounds__(64) void k_bn(const uint32_t *tab9s, const rf::RowC
     const int tab = __builtin_amdgcn_readfirstlane((int)cs[0]);
     stage_bn_consts9(tab9s + (size_t)tab * (BK9_N * BK9_W), threadIdx.x, 64);
     rf::RowConst K;
-    {   // wave-uniform: scalar loads (glue.hip RowSink::permute_unit)
+    {   // wave-uniform: scalar loads (batchargs.h load_row_consts)
         const uint32_t *src = reinterpret_cast<const uint32_t *>(rowk); uint32_t *dst = reinterpret_cast<uint32_t *>(&K);
 #pragma unroll
         for (unsigned i = 0; i < sizeof(rf::RowConst) / 4; i++) dst[i] = *(const __attribute__((address_space(4))) uint32_t *)(src + i);

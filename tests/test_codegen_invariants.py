@@ -4,43 +4,15 @@ On this family loads and stores retire in order on one counter (vmcnt): a scratc
 wait for every cell store it has in flight.  Twice in round 2 a source change that "did not touch the arithmetic" (a struct select, a
 refactoring of the Montgomery product into helper functions) put spill reloads into the PoseidonBN254 partial-round loop and cost 3-8 % of the
 chain kernel; this test is the guard."""
-import os
 import re
-import shutil
-import subprocess
 
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "halo2-plonky2-verifier_amd", "csrc")
-FLAGS = "-O3 -std=c++17 --offload-arch=gfx950 -fPIC -Wno-unused-function -Wno-unused-value -x hip -S --cuda-device-only".split()
-
-
-def _asm(src, tmp_path):
-    if not shutil.which("hipcc"):
-        pytest.skip("no hipcc")
-    out = os.path.join(str(tmp_path), src + ".s")
-    subprocess.run(["hipcc", *FLAGS, os.path.join(CSRC, src), "-o", out], check=True, capture_output=True, cwd=CSRC)
-    return open(out).read().split("\n")
+from codegen_util import compile_asm as _asm, count as _count, loops as _loops
 
 
 def _function(lines, mangled_prefix):
     start = next(i for i, l in enumerate(lines) if re.match("^" + re.escape(mangled_prefix) + r"\w*:", l))
     end = next(i for i in range(start, len(lines)) if "s_setpc_b64" in lines[i] or "s_endpgm" in lines[i])
     return start, end
-
-
-def _loops(lines, lo, hi):
-    """(first, last) line of every natural loop = backward branch (conditional or not) to a label inside [lo, hi)."""
-    labels = {m.group(1): i for i in range(lo, hi) for m in [re.match(r"^(\.LBB\d+_\d+):", lines[i])] if m}
-    for i in range(lo, hi):
-        m = re.search(r"^\s+s_c?branch\w*\s+(\.LBB\d+_\d+)", lines[i])
-        if m and m.group(1) in labels and labels[m.group(1)] < i:
-            yield labels[m.group(1)], i
-
-
-def _count(lines, a, b, pat):
-    return sum(1 for l in lines[a:b + 1] if re.match(r"^\s+" + pat, l))
 
 
 def _clean(lines, a, b, what):

@@ -1,20 +1,15 @@
 """Code generation of the expansion kernel's two output forms, on the cross-compiled gfx950 assembly (no GPU needed; the model is
 test_codegen_invariants.py): the Montgomery instantiation converts in registers - no scratch or flat access anywhere, its flush loop included -
 and the canonical instantiations are what they were before the form existed."""
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "halo2-plonky2-verifier_amd", "csrc")
-FLAGS = "-O3 -std=c++17 --offload-arch=gfx950 -fPIC -Wno-unused-function -Wno-unused-value -x hip -S --cuda-device-only".split()
+from codegen_util import compile_asm, count as _count, loops as _loops
 
 # Instructions of the canonical kernels at the commit before the output form, c4c5383 ("Traced plans: (proof, query) sharding, keygen metadata and
 # status 4"): `git archive c4c5383 halo2-plonky2-verifier_amd/csrc include | tar -x -C DIR`, then in DIR/halo2-plonky2-verifier_amd/csrc
-# `hipcc <FLAGS below> expand.hip -o expand.s`, counted with _function / _count below.  The body now takes its arguments by reference from a one-line
+# `hipcc <codegen_util.FLAGS> expand.hip -o expand.s`, counted with _function / _count below.  The body now takes its arguments by reference from a one-line
 # kernel; the scheduler answers with up to nine instructions fewer here; 16 (under 1 % of the smallest kernel) is allowed.
 PARENT = {"_ZN3h2w11expand_fastILi21ELb0ELb0EE": 1722, "_ZN3h2w11expand_fastILi21ELb1ELb0EE": 1908, "_ZN3h2w11expand_fastILi21ELb1ELb1EE": 2210,
           "_ZN3h2w11expand_fastILi13ELb1ELb0EE": 1949, "_ZN3h2w11expand_fastILi8ELb1ELb0EE": 2096, "_ZN3h2w15expand_kernel_tILi32ELi5ELb0EE": 1135}
@@ -23,28 +18,12 @@ TOLERANCE = 16
 
 @pytest.fixture(scope="module")
 def asm(tmp_path_factory):
-    if not shutil.which("hipcc"):
-        pytest.skip("no hipcc")
-    out = os.path.join(str(tmp_path_factory.mktemp("asm")), "expand.s")
-    subprocess.run(["hipcc", *FLAGS, os.path.join(CSRC, "expand.hip"), "-o", out], check=True, capture_output=True, cwd=CSRC)
-    return open(out).read().split("\n")
+    return compile_asm("expand.hip", tmp_path_factory.mktemp("asm"))
 
 
 def _function(lines, prefix):
     start = next(i for i, l in enumerate(lines) if re.match("^" + re.escape(prefix) + r"\w*:", l))
     return start, next(i for i in range(start, len(lines)) if "s_endpgm" in lines[i])
-
-
-def _count(lines, a, b, pat=r"[a-z]"):
-    return sum(1 for l in lines[a:b + 1] if re.match(r"^\s+" + pat, l))
-
-
-def _loops(lines, lo, hi):
-    labels = {m.group(1): i for i in range(lo, hi) for m in [re.match(r"^(\.LBB\d+_\d+):", lines[i])] if m}
-    for i in range(lo, hi):
-        m = re.search(r"^\s+s_c?branch\w*\s+(\.LBB\d+_\d+)", lines[i])
-        if m and m.group(1) in labels and labels[m.group(1)] < i:
-            yield labels[m.group(1)], i
 
 
 def test_canonical_instantiations_are_unchanged(asm):

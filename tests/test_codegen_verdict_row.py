@@ -5,29 +5,17 @@ The kernel keeps nothing but comparisons: it writes global memory through the Ve
 it (the S-box stores of the storing form are gone, and nothing else took their place).  Dropping the stores must not have changed the round: its
 partial-round loop holds the three lane-cooperative products (3 x 29 multiply-adds) that k_merkle_bn_values_row's loop holds, without a scratch or
 flat access, with the table entries read ahead of the first product, and no longer than that loop; the seven-product full-round loops are there too."""
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "halo2-plonky2-verifier_amd", "csrc")
-FLAGS = "-O3 -std=c++17 --offload-arch=gfx950 -fPIC -Wno-unused-function -Wno-unused-value -x hip -S --cuda-device-only".split()
+from codegen_util import compile_asm, count as _count, loops as _loops
 
 
 @pytest.fixture(scope="module")
 def asm(tmp_path_factory):
-    if not shutil.which("hipcc"):
-        pytest.skip("no hipcc")
-    out = {}
-    d = str(tmp_path_factory.mktemp("asm"))
-    for src in ("verdict.hip", "glue.hip"):
-        s = os.path.join(d, src + ".s")
-        subprocess.run(["hipcc", *FLAGS, os.path.join(CSRC, src), "-o", s], check=True, capture_output=True, cwd=CSRC)
-        out[src] = open(s).read().split("\n")
-    return out
+    d = tmp_path_factory.mktemp("asm")
+    return {src: compile_asm(src, d) for src in ("verdict.hip", "glue.hip")}
 
 
 def _kernel(lines, mangled_prefix):
@@ -35,18 +23,6 @@ def _kernel(lines, mangled_prefix):
     start = next(i for i, l in enumerate(lines) if re.match("^" + re.escape(mangled_prefix) + r"\w*:", l))
     end = next(i for i in range(start, len(lines)) if re.match(r"^\.Lfunc_end\d+:", lines[i]))
     return start, end
-
-
-def _loops(lines, lo, hi):
-    labels = {m.group(1): i for i in range(lo, hi) for m in [re.match(r"^(\.LBB\d+_\d+):", lines[i])] if m}
-    for i in range(lo, hi):
-        m = re.search(r"^\s+s_c?branch\w*\s+(\.LBB\d+_\d+)", lines[i])
-        if m and m.group(1) in labels and labels[m.group(1)] < i:
-            yield labels[m.group(1)], i
-
-
-def _count(lines, a, b, pat):
-    return sum(1 for l in lines[a:b + 1] if re.match(r"^\s+" + pat, l))
 
 
 def _partial_loop(lines, lo, hi):

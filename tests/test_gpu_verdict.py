@@ -128,6 +128,49 @@ def test_one_proof_of_one_query(h2w, h2w_api, oracle, consts, mode):
     plan.close()
 
 
+BN_R = 21888242871839275222246405745257275088548364400416034343698204186575808495617      # the BN254 scalar field's modulus
+
+
+def _with(valid, at, values):
+    """A copy of the proof with the words from `at` on replaced by `values`."""
+    c = valid.copy()
+    c[at:at + len(values)] = np.array(values, dtype=np.uint64)
+    return c
+
+
+@pytest.mark.parametrize("mode", [1, 0])
+def test_status_4_at_the_field_boundaries_is_the_witness_calls(h2w, h2w_api, oracle, consts, mode):
+    """Status 4 (a proof word outside its field) is one predicate (csrc/batchargs.h load_item_out_of_field) that the witness call's k_prologue_load and
+    the verdict call's k_verdict_check both ask: the verdict's status word is the witness call's for every proof.  A `>=` that became `>` there would
+    move both alike, so the batch holds the boundary itself: every proof is the valid one with one place at the modulus (status 4) or one below it
+    (not 4) - an openings word and a final-polynomial word against p = 2^64 - 2^32 + 1; entry 0 of the trace cap and sibling 0 of query 1's first
+    tree against p in their limb 2 (Goldilocks caps: four Goldilocks words) or, as the four words of one BN254 element, against r (PoseidonBN254 caps)."""
+    ko, kh = consts
+    sh, osh = _shapes(h2w, oracle, mode, "one_fold_step")
+    plan = h2w_api.Plan(sh, kh)
+    L = plan.proof_layout()
+    valid = np.frombuffer(bytes(oracle.prove_fri(osh, ko, 77)), dtype=np.uint64)
+    limbs = lambda x: [(x >> (64 * i)) & (2**64 - 1) for i in range(4)]
+    hashes = {"trace cap entry 0": L["trace_cap"], "sibling 0 of query 1's first tree": R.sibling_word(L, 1, L["oracles"][0], 0)}
+    cases = [("valid", valid, False),
+             ("openings word = p", _with(valid, L["openings"] + 1, [R.GL_P]), True),
+             ("openings word = p - 1", _with(valid, L["openings"] + 1, [R.GL_P - 1]), False),
+             ("final-polynomial word = 2^64 - 1", _with(valid, L["final_poly"] + 1, [2**64 - 1]), True)]
+    for name, at in hashes.items():
+        if mode == 0:
+            cases += [(name + ": limb 2 = p", _with(valid, at + 2, [R.GL_P]), True), (name + ": limb 2 = p - 1", _with(valid, at + 2, [R.GL_P - 1]), False)]
+        else:
+            cases += [(name + " = r", _with(valid, at, limbs(BN_R)), True), (name + " = r - 1", _with(valid, at, limbs(BN_R - 1)), False)]
+    got, d = _device_verdicts(h2w_api, plan, [w for _, w, _ in cases])
+    status = _witness_status(plan, d, len(cases))
+    for (name, _, outside), g, s in zip(cases, got, status):
+        print(f"{name:50s} outside its field: {outside!s:5s} verdict status {g[3]} witness status {s}")
+    assert [g[3] for g in got] == status
+    for (name, _, outside), s in zip(cases, status):
+        assert (s == 4) == outside, (name, s)
+    plan.close()
+
+
 def test_no_proof(h2w, h2w_api, consts):
     import torch
     plan = h2w_api.Plan(h2w.fibonacci_shape(6, 2, rate_bits=1, cap_height=2), consts[1])
