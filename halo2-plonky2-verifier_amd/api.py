@@ -7,7 +7,7 @@ argument meaning and error behaviour (a non-zero status raises H2WError where th
 """
 import ctypes as C
 
-from . import (Assigned, Fr, H2W_CHIPBATCH_OPT_CHUNK, H2W_TRACE_FUSE_BN_PERMUTE, H2W_TRACE_FUSE_GL_PERMUTE, H2WError, PoseidonConsts, Shape, _ck, last_error, lib)
+from . import (Assigned, Fr, H2W_CHIPBATCH_OPT_CHUNK, H2W_TRACE_FUSE_BN_PERMUTE, H2W_TRACE_FUSE_GL_PERMUTE, H2W_TRACE_OUTPUT_FORMS, H2WError, PoseidonConsts, Shape, _ck, last_error, lib)
 
 GL_P = 0xFFFFFFFF00000001
 FR_MODULUS = 21888242871839275222246405745257275088548364400416034343698204186575808495617
@@ -252,7 +252,7 @@ class Plan:
         self.num_chain_cells = int(self.L.h2w_plan_num_chain_cells(self.p))
 
     @classmethod
-    def from_trace(cls, ctx, proof_words, parallel_scopes=("verify_query_round", "verify_proof_to_cap_with_cap_index"), device_id=0, fuse_consts=None, fuse_bn=False, fuse_gl=True):
+    def from_trace(cls, ctx, proof_words, parallel_scopes=("verify_query_round", "verify_proof_to_cap_with_cap_index"), device_id=0, fuse_consts=None, fuse_bn=False, fuse_gl=True, output_forms=False):
         """h2w_plan_from_trace: the tape `ctx` recorded (Context.trace_begin, then ONE run through the level-1 / level-2 calls) as a plan that
         h2w_fri_witness_batch replays on other proofs of the shape.  parallel_scopes: the #[count] scopes whose instances are independent
         (fri/mod.rs:488-501, merkle/mod.rs:57-78); the library checks the claim on the tape.  The depth-1 instances (the query rounds) are the
@@ -261,14 +261,19 @@ class Plan:
         fuse_consts: Poseidon tables (h2w_plan_from_trace_ex, H2W_TRACE_FUSE_GL_PERMUTE): every stretch of the tape that the library verifies to be
         a Goldilocks-Poseidon permutation on these tables runs as one device op; trace_info() says how many did.  The stream is the same.
         fuse_bn (with fuse_consts): H2W_TRACE_FUSE_BN_PERMUTE as well - the PoseidonBN254 permutations on these tables run as one op each, their cells
-        written by a kernel of their own; trace_info_bn() says how many did.  fuse_gl=False with fuse_bn: the PoseidonBN254 flag alone."""
+        written by a kernel of their own; trace_info_bn() says how many did.  fuse_gl=False with fuse_bn: the PoseidonBN254 flag alone.
+        output_forms: H2W_TRACE_OUTPUT_FORMS (with or without fuse_consts) - the lowering also maps the plan's direct cells, and set_output_form,
+        direct_cells and record_ranges work as on a compiled plan."""
         L = lib()
         names = (C.c_char_p * len(parallel_scopes))(*[s.encode() for s in parallel_scopes])
         if fuse_bn and fuse_consts is None:
             raise H2WError("Plan.from_trace: fuse_bn needs fuse_consts")
+        forms = H2W_TRACE_OUTPUT_FORMS if output_forms else 0
         if fuse_consts is not None:
-            flags = (H2W_TRACE_FUSE_GL_PERMUTE if fuse_gl else 0) | (H2W_TRACE_FUSE_BN_PERMUTE if fuse_bn else 0)
+            flags = (H2W_TRACE_FUSE_GL_PERMUTE if fuse_gl else 0) | (H2W_TRACE_FUSE_BN_PERMUTE if fuse_bn else 0) | forms
             h = L.h2w_plan_from_trace_ex(ctx.p, proof_words, names, len(parallel_scopes), device_id, C.byref(fuse_consts), flags)
+        elif forms:
+            h = L.h2w_plan_from_trace_ex(ctx.p, proof_words, names, len(parallel_scopes), device_id, None, forms)
         else:
             h = L.h2w_plan_from_trace(ctx.p, proof_words, names, len(parallel_scopes), device_id)
         if not h:
@@ -354,7 +359,7 @@ class Plan:
 
     def set_output_form(self, form):
         """FORM_CANONICAL (default) or FORM_MONTGOMERY: every cell the plan's batch calls write holds v * 2^256 mod r, halo2curves' bn256::Fr as it
-        lies in memory (H2W_OPT_OUTPUT_FORM; not for traced plans)."""
+        lies in memory (H2W_OPT_OUTPUT_FORM; of traced plans, those made with output_forms=True)."""
         self.configure(OPT_OUTPUT_FORM, form)
 
     def direct_cells(self):

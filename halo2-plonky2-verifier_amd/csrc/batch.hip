@@ -224,14 +224,16 @@ int launch_plan_expand(const h2w_plan *p, uint64_t n_proofs, const rec_t *recs, 
 // roam_per_cu of the plan's expansion launches (profiles/r02_expand_grid.txt); the Montgomery form's kernel is bound by instruction issue, not by stores:
 // it needs every wavefront a CU holds (profiles/montgomery_form_cfg3.json)
 static uint32_t plan_roam_per_cu(const h2w_plan *p) { return (p->shape.hash_mode == 0 || p->output_form == H2W_FORM_MONTGOMERY) ? 2 : 1; }
-// k_direct_to_montgomery's arguments for a call: the plan's bitmap and block sizes, the call's output buffer, column map and sharding
-static DirectArgs direct_args(const h2w_plan *p, const BatchArgs &A, const ShardSpec &sh) {
+// k_direct_to_montgomery for a call (plan.h): the plan's bitmap and block sizes, the call's output buffer, column map and sharding
+int launch_plan_direct(const h2w_plan *p, const uint64_t *bits, uint64_t n_proofs, fr_t *out, uint64_t cell_stride, ColMap cm, const ShardSpec &sh, hipStream_t stream) {
     DirectArgs D;
-    D.bits = p->d_direct_bits.get(); D.ncells = p->ncells; D.out = A.out; D.cell_stride = A.cell_stride; D.cm = A.cm;
+    D.bits = bits; D.ncells = p->ncells; D.out = out; D.cell_stride = cell_stride; D.cm = cm;
     D.rank = sh.rank; D.world = sh.world; D.compact = sh.compact; D.nq = (uint32_t)p->shape.num_queries;
     D.pro_ncell = p->st.pro_ncell; D.q_cell0_first = p->st.q_cell0[0]; D.q_cell0_rest = p->st.q_cell0[1]; D.q_ncell_rest = p->st.q_ncell[1]; D.q_slot = shard_q_slot(p);
     D.kconst = mont_k(); D.ninv = p->P.ninv;
-    return D;
+    const uint64_t nwaves = ((p->ncells + 63) / 64 + 63) / 64;
+    launch_cols(cm.starts != nullptr, k_direct_to_montgomery<true>, k_direct_to_montgomery<false>, dim3((unsigned)((nwaves + 3) / 4), (unsigned)n_proofs), dim3(256), 0, stream, D);
+    return 0;
 }
 static int run_batch(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void *advice_dev, void *workspace_dev, void *stream_, void *emit_stream_, ColMap cm, uint64_t cell_stride, const ShardSpec &sh) {
     if (!p) { set_error("h2w_fri_witness_batch: null plan"); return -1; }
@@ -357,8 +359,7 @@ static int run_batch(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs,
         const bool mont = p->output_form == H2W_FORM_MONTGOMERY;
         if (mont) {
             if (cstream != stream) { H2W_HIP(hipStreamWaitEvent(cstream, ev[H2W_EV_GLUE_END], 0)); forked = true; }
-            const uint64_t nwaves = ((p->ncells + 63) / 64 + 63) / 64;
-            launch_cols(cm.starts != nullptr, k_direct_to_montgomery<true>, k_direct_to_montgomery<false>, dim3((unsigned)((nwaves + 3) / 4), (unsigned)n_proofs), dim3(256), 0, cstream, direct_args(p, A, sh));
+            if (launch_plan_direct(p, p->d_direct_bits.get(), n_proofs, A.out, A.cell_stride, A.cm, sh, cstream) != 0) return -1;
             if (cstream != stream) H2W_HIP(hipEventRecord(ev[h2w_plan::EV_DIRECT_END], cstream));
         }
         if (estream != stream) H2W_HIP(hipStreamWaitEvent(stream, ev[H2W_EV_EXPAND_END], 0));    // the caller's stream completes when the advice is complete
@@ -539,13 +540,18 @@ int h2w_plan_configure(h2w_plan *p, int option, int value) {
     if (option == H2W_OPT_CHAIN_PASSES) { if (value < 0 || value > 2) { set_error("h2w_plan_configure: H2W_OPT_CHAIN_PASSES is 0 (by launch size), 1 or 2"); return -1; } p->chain_passes = value; return 0; }
     if (option == H2W_OPT_OUTPUT_FORM) {
         if (value != H2W_FORM_CANONICAL && value != H2W_FORM_MONTGOMERY) { set_error("h2w_plan_configure: H2W_OPT_OUTPUT_FORM is 0 (canonical cells) or 1 (Montgomery form, R = 2^256)"); return -1; }
-        if (value == H2W_FORM_MONTGOMERY && p->traced) { set_error("h2w_plan_configure: a traced plan (h2w_plan_from_trace) writes canonical cells only; convert its stream with h2w_advice_to_montgomery"); return -1; }
+        if (value == H2W_FORM_MONTGOMERY && p->traced && !p->trace_forms) { set_error("h2w_plan_configure: a traced plan (h2w_plan_from_trace) writes canonical cells only; convert its stream with h2w_advice_to_montgomery, or lower the trace with H2W_TRACE_OUTPUT_FORMS"); return -1; }
         if (value == H2W_FORM_MONTGOMERY && p->device >= 0 && !p->d_mont.get()) {      // first use: the form's constants (derived from r) and the direct-cell bitmap
             DeviceGuard dg(p->device);
             MontForm K; montform_init(K, p->tt.rb);
-            DevBuf<uint64_t> bits; DevBuf<MontForm> d;
+            DevBuf<uint64_t> bits, ranged; DevBuf<MontForm> d; DevBuf<fr_t> tabm;
             if (bits.upload(p->direct_bits) != 0 || d.upload(&K, 1) != 0) return -1;      // (nothing kept: the next call starts over)
-            p->d_direct_bits = std::move(bits); p->d_mont = std::move(d);
+            if (p->traced && p->d_bn_tab.get()) {      // a traced plan with fused PoseidonBN254 permutations: the emitter's Montgomery cell table, the ranged kernel's map
+                std::vector<fr_t> tab(BK_ALL); bn_table_build(p->h_consts, p->P, tab.data());
+                for (int i = 0; i < BK_T; i++) tab[(size_t)i] = fr_mont_mul(tab[(size_t)i], mont_k(), p->P.ninv);
+                if (tabm.upload(tab) != 0 || ranged.upload(p->ranged_bits) != 0) return -1;
+            }
+            p->d_direct_bits = std::move(bits); p->d_mont = std::move(d); p->d_bn_tab_mont = std::move(tabm); p->d_ranged_bits = std::move(ranged);
         }
         p->output_form = value; return 0;
     }

@@ -351,6 +351,17 @@ __device__ __forceinline__ fr_t bnkc(int r) {
     const sq16_t a = s_bn_tab[(BK_XC + r) * 2], b = s_bn_tab[(BK_XC + r) * 2 + 1];
     fr_t v; v.l[0] = a.x; v.l[1] = a.y; v.l[2] = b.x; v.l[3] = b.y; return v;
 }
+// QUAD_FUSED_MONT (below): s_bn_tab's canonical half holds the cell table in Montgomery form there, so the round constants the adds take come from a
+// canonical copy of their own (2.8 KB; only kernels that stage it have it)
+__shared__ sq16_t s_bn_c[(BK_S - BK_C) * 2];
+__device__ __forceinline__ void stage_bn_canon_c(const fr_t *tab, int tid, int nthreads) {      // (no barrier: stage_bn_consts follows)
+    const sq16_t *src = reinterpret_cast<const sq16_t *>(tab + BK_C);
+    for (int i = tid; i < (BK_S - BK_C) * 2; i += nthreads) { sq16_t v; v.x = H2W_GLOAD64(&src[i].x); v.y = H2W_GLOAD64(&src[i].y); s_bn_c[i] = v; }
+}
+__device__ __forceinline__ fr_t bnc(int idx) {      // canonical C_CONSTANTS[idx]
+    const sq16_t a = s_bn_c[idx * 2], b = s_bn_c[idx * 2 + 1];
+    fr_t r; r.l[0] = a.x; r.l[1] = a.y; r.l[2] = b.x; r.l[3] = b.y; return r;
+}
 __shared__ uint32_t s_bn_tab9[BK9_N * BK9_W];
 __device__ __forceinline__ void stage_bn_consts9(const uint32_t *tab9, int tid, int nthreads) {
     const sq16_t *src = reinterpret_cast<const sq16_t *>(tab9); sq16_t *dst = reinterpret_cast<sq16_t *>(s_bn_tab9);
@@ -440,8 +451,16 @@ constexpr BnSrc bn_map_partial(int c) {
 
 enum { QUAD_VALUES = 1, QUAD_EMIT = 2, QUAD_FUSED = 3 };      // QUAD_FUSED: one quad walks its strand AND emits every unit of it (one pass, serial in the path's depth)
 constexpr int QUAD_VERDICT = 4;      // the QUAD_VALUES walk with no store at all: no unit states, no S-box values, and the cap lookup's value taken (verdict.hip)
-template <bool COLS, int MODE> struct QuadSinkT : SinkBase {
-    static constexpr bool kBnUnits = true; static constexpr int kHashMode = 1;
+// QUAD_FUSED_MONT: the QUAD_FUSED emitter (bn_emit_cells<false>) whose cells leave in Montgomery form (H2W_OPT_OUTPUT_FORM on a traced plan,
+// bnemit_mont.hip k_bn_emit_traced_mont).  The flush code is the same - it moves 16-byte pieces -; what it reads differs: the kernel stages a Montgomery copy of the cell table
+// where the canonical half of s_bn_tab lies, and put() stores v * 2^256 (fr_mont_mul(v, mont_k, ninv), the product of the second pass: the same bytes).
+// What the arithmetic reads back stays canonical: the adds' round constants come from s_bn_c, mix takes s_j from the lanes' registers, not from the slots.
+// A mode, not a third template parameter: the other instantiations keep their names and their code.
+constexpr int QUAD_FUSED_MONT = 5;
+template <bool M> struct QuadMontK {};
+template <> struct QuadMontK<true> { fr_t mk; uint64_t mninv; };      // mont_k() (montform.h) and -r^-1
+template <bool COLS, int MODE> struct QuadSinkT : SinkBase, QuadMontK<MODE == QUAD_FUSED_MONT> {
+    static constexpr bool kBnUnits = true; static constexpr int kHashMode = 1; static constexpr bool kMont = MODE == QUAD_FUSED_MONT;
     rec_t *recs; uint64_t nrec; fr_t *out; uint64_t cell_off; const uint16_t *ncells; int l4; ColPolicy<COLS> cc;
     fr_t *ustate;                  // output states of this strand's permutation units, [unit][4] (written by QUAD_VALUES, read by QUAD_EMIT)
     fr_t *sbx;                     // the S-box chains of their partial rounds, [unit][BN_PARTIAL_ROUNDS][3] = canonical x^2, x^4, x^5 (QUAD_VALUES -> QUAD_EMIT)
@@ -457,7 +476,7 @@ template <bool COLS, int MODE> struct QuadSinkT : SinkBase {
     __device__ __forceinline__ void skip(uint64_t nr, uint64_t nc) { nrec += nr; cell_off += nc; }
     // The emitter's working set, by value (a member read behind an opaque call is a FLAT load of the sink object, and flat loads
     // wait for every cell store in flight).
-    struct Em {
+    struct Em : QuadMontK<kMont> {
         sq16_t *val;                   // this quad's value slots (slot s at val + s * BN_SLOT_SQ)
         const sq16_t *tabh;            // canonical table + (l & 1): the half this lane flushes
         unsigned long long gdst;       // byte address of this lane's first 16-byte piece of the current layer
@@ -465,9 +484,15 @@ template <bool COLS, int MODE> struct QuadSinkT : SinkBase {
         int l;
         ColPolicy<COLS> cc;            // column layout: the cursor, by value too (nothing in the flat layout)
     };
-    static __device__ __forceinline__ void put(const Em &e, int slot, const fr_t &v) {
+    static __device__ __forceinline__ void put_raw(const Em &e, int slot, const fr_t &v) {
         sq16_t *q = e.val + slot * BN_SLOT_SQ; q[0] = sq16_t{v.l[0], v.l[1]}; q[1] = sq16_t{v.l[2], v.l[3]};
     }
+    static __device__ __forceinline__ fr_t to_cell(const Em &e, const fr_t &v) { if constexpr (kMont) return fr_mont_mul(v, e.mk, e.mninv); else return v; }
+    static __device__ __forceinline__ void put(const Em &e, int slot, const fr_t &v) {
+        if constexpr (kMont) put_raw(e, slot, to_cell(e, v));
+        else { sq16_t *q = e.val + slot * BN_SLOT_SQ; q[0] = sq16_t{v.l[0], v.l[1]}; q[1] = sq16_t{v.l[2], v.l[3]}; }
+    }
+    static __device__ __forceinline__ fr_t kcanon(int idx) { if constexpr (kMont) return bnc(idx - BK_C); else return bnk(0, idx); }      // a round constant for an add
     static __device__ __forceinline__ void put_if(const Em &e, bool on, int slot, const fr_t &v) { if (on) put(e, slot, v); }
     template <class MapFn> static __device__ __forceinline__ const sq16_t *src_ptr(const Em &e, MapFn map, int c, const sq16_t *baseA, const sq16_t *baseB) {
         const BnSrc s = map(c);
@@ -711,6 +736,7 @@ template <bool COLS, int MODE> struct QuadSinkT : SinkBase {
         bool zc = zc_ref;                      // by value: a reference would be re-read with a flat load (vmcnt(0)) at every mix
         const int l = l4; const uint64_t ninv = cfg.P.ninv; const fr_t r2 = cfg.P.r2;
         Em e; e.l = l;
+        if constexpr (kMont) { static_assert(!PRE, "the Montgomery emitter is the one-pass form"); e.mk = this->mk; e.mninv = this->mninv; }
         const int val_off = ((threadIdx.x >> 6) * BN_NSLOT * BN_SLOT_SQ) + ((threadIdx.x & 63) >> 2) * 2;
         e.val = s_bn_val + val_off;
         e.tabh = s_bn_tab + (l & 1);
@@ -727,7 +753,7 @@ template <bool COLS, int MODE> struct QuadSinkT : SinkBase {
             s = x5;
         };
         auto ark = [&](int it) {
-            const fr_t ns = fr_add(s, bnk(0, BK_C + it + l));
+            const fr_t ns = fr_add(s, kcanon(BK_C + it + l));
             put(e, l, s); put(e, 4 + l, ns);
             flush_layer<20>(e, bn_map_ark, e.tabh + (BK_C + it) * 2, e.tabh);
             s = ns;
@@ -739,8 +765,14 @@ template <bool COLS, int MODE> struct QuadSinkT : SinkBase {
             fr_t acc = fr_zero();
 #pragma unroll 1
             for (int j = 0; j < 4; j++) {
-                const sq16_t a0 = e.val[j * BN_SLOT_SQ], a1 = e.val[j * BN_SLOT_SQ + 1];       // s_j, staged above (an LDS read: j is a loop index)
-                fr_t sj; sj.l[0] = a0.x; sj.l[1] = a0.y; sj.l[2] = a1.x; sj.l[3] = a1.y;
+                fr_t sj;
+                if constexpr (kMont) {      // (the slot holds s_j times 2^256: lane j's register instead)
+                    const fr_t b0 = quad_bcast<0>(s), b1 = quad_bcast<1>(s), b2 = quad_bcast<2>(s), b3 = quad_bcast<3>(s);
+                    sj = fr_sel(j < 2, fr_sel(j == 0, b0, b1), fr_sel(j == 2, b2, b3));
+                } else {
+                    const sq16_t a0 = e.val[j * BN_SLOT_SQ], a1 = e.val[j * BN_SLOT_SQ + 1];       // s_j, staged above (an LDS read: j is a loop index)
+                    sj.l[0] = a0.x; sj.l[1] = a0.y; sj.l[2] = a1.x; sj.l[3] = a1.y;
+                }
                 acc = fr_add(fr_mont_mul(sj, bnk(1, mb + 4 * j + l), ninv), acc);
                 put(e, 4 + 4 * l + j, acc);
             }
@@ -833,9 +865,14 @@ template <bool COLS, int MODE> struct QuadSinkT : SinkBase {
                         if (pend) { part_store<14, 20, 52>(e, t2); part_load<20, 26, 52>(e, bn_map_partial, pA, pB, t3); }
                         const fr_t D_ = fr_mont_mul(quad_bcast<0>(C_), fr_sel(l == 0, XSb, Xb), ninv);
                         if (pend) { part_store<20, 26, 52>(e, t3); e.cell0 += 52; e.gdst += 52ull * 32; }
-                        const fr_t s0n = fr_add(quad_bcast<1>(D_), bnk(0, ic));
+                        const fr_t s0n = fr_add(quad_bcast<1>(D_), kcanon(ic));
                         put(e, l, s);                                        // slots 0-3: the state before the round
-                        put_if(e, l == 1, 4, B_); put_if(e, l == 0, 5, C_); put_if(e, l == 1, 6, D_); put_if(e, l == 0, 7, s0n);
+                        if constexpr (kMont) {      // slots 4-7 in two products: lane 0's C_ and s0n beside lane 1's B_ and D_
+                            const fr_t w1 = to_cell(e, fr_sel(l == 0, C_, B_)), w2 = to_cell(e, fr_sel(l == 0, s0n, D_));
+                            if (l < 2) { put_raw(e, l == 0 ? 5 : 4, w1); put_raw(e, l == 0 ? 7 : 6, w2); }
+                        } else {
+                            put_if(e, l == 1, 4, B_); put_if(e, l == 0, 5, C_); put_if(e, l == 1, 6, D_); put_if(e, l == 0, 7, s0n);
+                        }
                         fr_t incl = fr_sel(l == 0, fr_add(D_, bnkc(r)), fr_sel(l == 3, B_, C_));      // S_0 s0', then S_j s_j: the running sums over the quad
                         { const fr_t t = quad_up1(incl); if (l >= 1) incl = fr_add(incl, t); }
                         { const fr_t t = quad_up2(incl); if (l >= 2) incl = fr_add(incl, t); }

@@ -37,7 +37,14 @@ struct h2w_plan {
     int serial_expand = 1;           // H2W_OPT_SERIAL_EXPAND: the expansion kernel of a call waits for the previous call's
     // H2W_OPT_OUTPUT_FORM.  The shape compiler marks the cells of a proof's stream that value kernels write themselves (one bit per cell, padded to whole
     // 64-word rows for k_direct_to_montgomery); the Montgomery form's constants and the bitmap go to the device when the form is first selected.
+    // A traced plan has the bitmap (made at lowering, tracelower.h direct_cell_map) and the option only when lowered with H2W_TRACE_OUTPUT_FORMS.
     int output_form = 0; std::vector<uint64_t> direct_bits, h_meta; uint64_t n_direct = 0; DevBuf<uint64_t> d_direct_bits; DevBuf<MontForm> d_mont;
+    bool trace_forms = false;        // traced with H2W_TRACE_OUTPUT_FORMS
+    // ... with fused PoseidonBN254 permutations: their cells leave k_bn_emit_traced in Montgomery form (d_bn_tab_mont: the plan's table with its canonical
+    // half converted, uploaded with the form's constants), and the ranged kernel works from ranged_bits, the direct map without those cells.
+    // trace_bn_ranged (H2W_TRACE_BN_RANGED set in the environment when the plan was lowered; measurement, tools/replay_timing.py): canonical emission and
+    // the ranged kernel over the full map instead.
+    std::vector<uint64_t> ranged_bits; DevBuf<uint64_t> d_ranged_bits; DevBuf<fr_t> d_bn_tab_mont; bool trace_bn_ranged = false;
     bool fork_chains = true;         // of their own batch (they share only the prologue): one side stream per caller stream seen (created on demand)
     uint64_t n_batches = 0; bool ev_recorded = false;
     h2w::TracedPlan *traced = nullptr;      // set: the plan replays a recorded tape (replay.hip); the strand tables above are unused
@@ -73,5 +80,9 @@ inline BatchArgs plan_batch_args(const h2w_plan *p, const uint64_t *proofs_dev, 
 // no strand table).  tile_ctr: n_proofs words of workspace, zeroed here.  roam_per_cu: ExpandArgs.
 int launch_plan_expand(const h2w_plan *p, uint64_t n_proofs, const rec_t *recs, uint32_t *tile_ctr, fr_t *out, uint64_t cell_stride, ColMap cm,
                        const ShardSpec *sh, uint32_t roam_per_cu, hipStream_t stream);
+// H2W_FORM_MONTGOMERY, the direct cells of a plan's call (batch.hip k_direct_to_montgomery; run_batch, replay.hip traced_run): the cells of the bitmap
+// `bits` (device; the plan's d_direct_bits or d_ranged_bits) in out[n_proofs][cell_stride] get the full product in place, through cm and, sharded, in this rank's blocks only (packed: at their local
+// addresses).  Behind every kernel that writes a direct cell; in front of the column fix-up, which copies converted boundary cells.
+int launch_plan_direct(const h2w_plan *p, const uint64_t *bits, uint64_t n_proofs, fr_t *out, uint64_t cell_stride, ColMap cm, const ShardSpec &sh, hipStream_t stream);
 }
 

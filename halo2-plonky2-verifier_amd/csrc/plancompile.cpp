@@ -161,13 +161,13 @@ uint64_t h2w_plan_num_records(const h2w_plan *p) { return p ? p->nrec : 0; }
 uint64_t h2w_plan_num_record_cells(const h2w_plan *p) { return p ? p->rec_cells : 0; }
 int h2w_plan_direct_cells(const h2w_plan *p, uint8_t *bitmap) {
     if (!p || !bitmap) { set_error("h2w_plan_direct_cells: null argument"); return -1; }
-    if (p->traced) { set_error("h2w_plan_direct_cells: not for traced plans"); return -1; }
+    if (p->traced && !p->trace_forms) { set_error("h2w_plan_direct_cells: not for traced plans lowered without H2W_TRACE_OUTPUT_FORMS"); return -1; }
     for (uint64_t i = 0; i < (p->ncells + 7) / 8; i++) bitmap[i] = (uint8_t)(p->direct_bits[i / 8] >> (8 * (i & 7)));
     return 0;
 }
 int h2w_plan_record_ranges(const h2w_plan *p, uint64_t *ranges) {
     if (!p || !ranges) { set_error("h2w_plan_record_ranges: null argument"); return -1; }
-    if (p->traced) { set_error("h2w_plan_record_ranges: not for traced plans"); return -1; }
+    if (p->traced && !p->trace_forms) { set_error("h2w_plan_record_ranges: not for traced plans lowered without H2W_TRACE_OUTPUT_FORMS"); return -1; }
     std::vector<uint64_t> back; const uint64_t *m = p->h_meta.data();
     if (p->device >= 0) {
         DeviceGuard dg(p->device); back.resize((size_t)p->nrec);

@@ -32,6 +32,7 @@
 #include "keygen.h"
 #include "glpval.h"
 #include "bnpval.h"
+#include "bnemit.h"
 
 struct h2w_ctx;
 namespace h2w {
@@ -70,7 +71,7 @@ struct TracedPlan {
     uint32_t nglp = 0; uint64_t n_candidates = 0; std::vector<uint32_t> h_glp_unit; DevBuf<uint32_t> d_glp_unit;
     // fused PoseidonBN254 permutations: per proof nbnp list entries; items: the (proof, entry) pairs of this rank's blocks (sharded calls, beside the lane table)
     bool bn_flag = false; uint32_t nbnp = 0; uint64_t n_bn_left = 0; std::vector<BnpD> h_bnp; DevBuf<BnpD> d_bnp; std::vector<uint32_t> h_bnp0; DevBuf<uint32_t> d_bnp0, d_bn_items; uint64_t n_bn_items = 0;
-    DevEvent tev[16]; int tev_used = 0; bool timing = false;      // h2w_plan_trace_timing: around every kernel of the last call
+    DevEvent tev[17]; int tev_used = 0; bool timing = false;      // h2w_plan_trace_timing: around every kernel of the last call (12 depths at most, three kernels, the expansion)
     // sharding: the depth-1 instances are the units (query q = the q-th in tape order); why_unshardable empty: they tile the stream behind the root's block
     std::string why_unshardable; std::vector<uint32_t> h_unit;      // h_unit: the unit of every instance (InstD order)
     std::vector<uint32_t> h_lanes, lane0; DevBuf<uint32_t> d_lanes; uint64_t lanes_n = 0; int lanes_rank = -1, lanes_world = 0;      // the lane table of the last (n, rank, world)
@@ -312,17 +313,8 @@ __global__ __launch_bounds__(64) void k_glp_emit_traced(GlpEmitArgs A) {
     sink.coop_poseidon_permute(st, A.consts);
 }
 
-// One QUAD per listed PoseidonBN254 permutation of the launch: its 4,032 cells from the entry's input state, by the one-pass emitter the compiled plan's
-// k_merkle_bn_fused runs (coop.h QuadSinkT::bn_emit_cells<false>: it walks the S-box chain itself; 64 contiguous bytes per quad and store).  The launch
-// works from a dense list of items: every (proof, entry) pair, or - sharded - `items`, the pairs of this rank's blocks (the others' entries were never
-// written).  The quads of a wavefront cooperate (cross-lane moves over the whole wavefront): none leaves early, tail quads redo the last item and write
-// identical bytes.  WHERE a permutation's cells go is static (BnpD, checked against the entry: status 97 if the interpreter listed another cell); only
-// the state comes from the list.  LDS: the tables (34.7 KB) + 10 KB of value slots per wavefront, as k_merkle_bn_fused: two blocks per CU.
-struct BnEmitArgs {
-    const fr_t *bn_tab; const uint64_t *list; const BnpD *bnp; const uint32_t *items; uint64_t nitems; uint32_t nbnp;
-    fr_t *out; uint64_t cell_stride; ColMap cm; FrParams P; uint32_t *status;
-    uint32_t sh_world, sh_rank, sh_compact, nq; uint64_t pro_ncell, q_slot;
-};
+// k_bn_emit_traced: one QUAD per listed PoseidonBN254 permutation of the launch (bnemit.h: how it works, its arguments).  Its Montgomery twin lives in
+// bnemit_mont.hip - a unit of its own, so that this unit's LDS layout and with it the code of k_replay and of this kernel stay what they are.
 template <bool COLS> __global__ __launch_bounds__(QUAD_BLOCK) H2W_QUAD_ATTR void k_bn_emit_traced(BnEmitArgs A) {
     typedef QuadSinkT<COLS, QUAD_FUSED> Sink;
     stage_bn_consts(A.bn_tab, threadIdx.x, QUAD_BLOCK);      // (block-wide barrier inside: before any wavefront leaves)
@@ -434,6 +426,8 @@ int traced_run(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void 
     H2W_HIP(hipMemsetAsync(ws + wl.lflag, 0, n_proofs * 4, stream));
     uint32_t maxd = 0; for (const TmplD &T : t->tmpls) if (T.depth > maxd) maxd = T.depth;
     uint64_t *const blist = (uint64_t *)(ws + wl.blist);
+    // Montgomery form: the fused PoseidonBN254 permutations' cells leave their emission kernel converted; the ranged kernel takes the other direct cells
+    const bool mont = p->output_form == H2W_FORM_MONTGOMERY, emit_mont = mont && t->nbnp && !p->trace_bn_ranged;
     t->tev_used = 0;
     for (uint32_t d = 0; d <= maxd; d++) {      // a segment reads its ancestors' values: depth by depth; the templates of one depth in one launch
         uint32_t nb = 0;
@@ -457,7 +451,8 @@ int traced_run(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void 
     }
     if (t->timing && t->bn_flag) H2W_HIP(hipEventRecord(t->tev[t->tev_used++], stream));
     if (t->nbnp) {      // the cells of the listed PoseidonBN254 permutations, a quad each (direct cells: nothing of the expansion depends on them, nor they on it)
-        BnEmitArgs E; memset(&E, 0, sizeof(E));
+        BnEmitMontArgs EM; memset(&EM, 0, sizeof(EM)); BnEmitArgs &E = EM;
+        EM.bn_tab_mont = p->d_bn_tab_mont.get(); EM.mont_k = mont_k();
         E.bn_tab = p->d_bn_tab.get(); E.list = blist; E.bnp = t->d_bnp.get(); E.nbnp = t->nbnp; E.out = R.out; E.cell_stride = cell_stride; E.cm = cm; E.P = p->P; E.status = R.status;
         if (sharded) {
             E.items = t->d_bn_items.get(); E.nitems = t->n_bn_items;
@@ -465,9 +460,15 @@ int traced_run(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void 
         } else { E.items = nullptr; E.nitems = (uint64_t)n_proofs * t->nbnp; }
         const uint64_t nblk = (E.nitems * 4 + QUAD_BLOCK - 1) / QUAD_BLOCK;
         if (nblk >= 0x7fffffffull) { set_error("h2w_fri_witness_batch: too many fused permutations in one call"); return -1; }
-        if (nblk) launch_cols(cm.starts != nullptr, k_bn_emit_traced<true>, k_bn_emit_traced<false>, dim3((uint32_t)nblk), dim3(QUAD_BLOCK), 0, stream, E);
+        if (nblk && emit_mont) launch_bn_emit_traced_mont(EM, cm.starts != nullptr, (uint32_t)nblk, stream);
+        else if (nblk) launch_cols(cm.starts != nullptr, k_bn_emit_traced<true>, k_bn_emit_traced<false>, dim3((uint32_t)nblk), dim3(QUAD_BLOCK), 0, stream, E);
     }
     if (t->timing) H2W_HIP(hipEventRecord(t->tev[t->tev_used++], stream));
+    // Montgomery form (plans lowered with H2W_TRACE_OUTPUT_FORMS): the direct cells - the interpreter's; the emission kernel's above too where it wrote
+    // canonical cells - in place, behind their writers on the call's stream; the expansion kernel converts its own cells as it writes them.  The column fix-up (h2w_fri_witness_batch_columns)
+    // follows the call, as on a compiled plan: it repeats converted boundary cells.
+    if (mont && launch_plan_direct(p, emit_mont ? p->d_ranged_bits.get() : p->d_direct_bits.get(), n_proofs, R.out, cell_stride, cm, sh, stream) != 0) return -1;
+    if (t->timing && p->trace_forms) H2W_HIP(hipEventRecord(t->tev[t->tev_used++], stream));
     // expansion of the block records
     if (launch_plan_expand(p, n_proofs, R.recs, (uint32_t *)(ws + wl.ctr), R.out, cell_stride, cm, sharded ? &sh : nullptr, 2, stream) != 0) return -1;
     if (t->timing) H2W_HIP(hipEventRecord(t->tev[t->tev_used++], stream));
@@ -483,7 +484,7 @@ static h2w_plan *plan_from_trace(h2w_ctx *ctx, uint64_t proof_words, const char 
     if (!tr->err.empty()) { set_error("h2w_plan_from_trace: " + tr->err); return nullptr; }
     if (tr->pending.kind) { set_error("h2w_plan_from_trace: a h2w_trace_input tag was never consumed"); return nullptr; }
     const bool fusing = (flags & H2W_TRACE_FUSE_GL_PERMUTE) != 0, fusing_bn = (flags & H2W_TRACE_FUSE_BN_PERMUTE) != 0;
-    if (flags & ~(uint32_t)(H2W_TRACE_FUSE_GL_PERMUTE | H2W_TRACE_FUSE_BN_PERMUTE)) { set_error("h2w_plan_from_trace_ex: unknown flag"); return nullptr; }
+    if (flags & ~(uint32_t)(H2W_TRACE_FUSE_GL_PERMUTE | H2W_TRACE_FUSE_BN_PERMUTE | H2W_TRACE_OUTPUT_FORMS)) { set_error("h2w_plan_from_trace_ex: unknown flag"); return nullptr; }
     if (fusing && !consts) { set_error("h2w_plan_from_trace_ex: H2W_TRACE_FUSE_GL_PERMUTE needs the Poseidon tables the permutations are claimed to use"); return nullptr; }
     if (fusing_bn && !consts) { set_error("h2w_plan_from_trace_ex: H2W_TRACE_FUSE_BN_PERMUTE needs the Poseidon tables the permutations are claimed to use"); return nullptr; }
     const int L = ctx_lookup_bits(ctx); const uint64_t ncells = ctx_num_cells(ctx);
@@ -520,6 +521,10 @@ static h2w_plan *plan_from_trace(h2w_ctx *ctx, uint64_t proof_words, const char 
     memset(&pl->shape, 0, sizeof(pl->shape)); pl->shape.lookup_bits = L; pl->shape.num_queries = U.num_queries; pl->shape.hash_mode = 1;
     pl->device = on_device ? device_id : -1; pl->P = fr_params_init(); memset(&pl->st, 0, sizeof(pl->st)); memset(&pl->pl, 0, sizeof(pl->pl)); memset(&pl->d, 0, sizeof(pl->d));
     pl->pl.total = proof_words; pl->nrec = LP.nrec; pl->ncells = ncells; pl->traced = tp;
+    if (flags & H2W_TRACE_OUTPUT_FORMS) {      // the direct-cell map of H2W_OPT_OUTPUT_FORM (the plan does not keep the tape: now)
+        if (!direct_cell_map(LP, pl->tt, ncells, pl->direct_bits, pl->n_direct, err) || !ranged_cell_map(LP, (uint64_t)BN_PERM_CELLS, pl->direct_bits, pl->ranged_bits, err)) { set_error(err); h2w_plan_free(pl); return nullptr; }
+        pl->trace_forms = true; pl->trace_bn_ranged = getenv("H2W_TRACE_BN_RANGED") != nullptr;
+    }
     if (consts) pl->h_consts = *consts;
     for (uint64_t m : LP.meta) pl->rec_cells += (uint64_t)pl->tt.ncells((int)meta_tmpl(m));
     // the block structure (StrandTable: what h2w_plan_strand_layout / _shard_cells / _shard_block and the sharded expansion read): unshardable, one block
@@ -544,7 +549,7 @@ static h2w_plan *plan_from_trace(h2w_ctx *ctx, uint64_t proof_words, const char 
         }
         E.ready = true;
     }
-    if (!on_device) return pl;
+    if (!on_device) { if (pl->trace_forms) pl->h_meta = LP.meta; return pl; }      // (h2w_plan_record_ranges: with a device it reads d_meta back)
     DeviceGuard dg(device_id);
     for (int k2 = 0; k2 < 16; k2++) LP.tape.push_back(DOP_END | (1u << 24));      // the interpreter reads a window ahead
     std::vector<uint64_t> prefix(tp->tmpls.size()); uint64_t acc = 0;
@@ -588,7 +593,8 @@ extern "C" int h2w_plan_trace_info_bn(const h2w_plan *p, uint64_t out[3]) {
     out[0] = t->nbnp; out[1] = t->n_bn_left; out[2] = t->nbnp;
     return 0;
 }
-// ms of the kernels of the last call: the k_replay launch of every depth, k_glp_emit_traced, (plans built with H2W_TRACE_FUSE_BN_PERMUTE) k_bn_emit_traced, the expansion.  The first call switches the events on
+// ms of the kernels of the last call: the k_replay launch of every depth, k_glp_emit_traced, (plans built with H2W_TRACE_FUSE_BN_PERMUTE) k_bn_emit_traced,
+// (plans built with H2W_TRACE_OUTPUT_FORMS) the direct cells' conversion - nothing in canonical form -, the expansion.  The first call switches the events on
 // (0 entries); later ones wait for the last call and report it.
 extern "C" int h2w_plan_trace_timing(h2w_plan *p, float *ms, uint32_t cap) {
     if (!p || !ms) { set_error("h2w_plan_trace_timing: null argument"); return -1; }

@@ -539,4 +539,38 @@ bool group_templates(Lowered &LW, const ShardUnits &U, LoweredPlan &P, std::stri
     return true;
 }
 
+bool direct_cell_map(const LoweredPlan &P, const TemplateTable &tt, uint64_t ncells, std::vector<uint64_t> &direct, uint64_t &n_direct, std::string &err) {
+    direct.assign((size_t)(((ncells + 63) / 64 + 63) / 64 * 64), 0);
+    for (uint64_t w = 0; w < ncells / 64; w++) direct[(size_t)w] = ~0ull;
+    if (ncells & 63) direct[(size_t)(ncells / 64)] = (1ull << (ncells & 63)) - 1;
+    uint64_t rec_cells = 0;
+    for (size_t i = 0; i < P.meta.size(); i++) {
+        const uint64_t c0 = meta_off(P.meta[i]), n = (uint64_t)tt.ncells((int)meta_tmpl(P.meta[i]));
+        if (c0 + n > ncells) { err = "h2w_plan_from_trace_ex: internal: record " + std::to_string(i) + " lies beyond the stream"; return false; }
+        for (uint64_t c = c0; c < c0 + n;) {      // word by word
+            const uint64_t k = c & 63, take = std::min<uint64_t>(64 - k, c0 + n - c), mask = (take == 64 ? ~0ull : ((1ull << take) - 1)) << k;
+            uint64_t &w = direct[(size_t)(c / 64)];
+            if ((w & mask) != mask) { err = "h2w_plan_from_trace_ex: internal: record " + std::to_string(i) + " overlaps another record"; return false; }
+            w &= ~mask; c += take;
+        }
+        rec_cells += n;
+    }
+    n_direct = 0;
+    for (uint64_t w : direct) n_direct += (uint64_t)__builtin_popcountll(w);
+    if (n_direct + rec_cells != ncells) { err = "h2w_plan_from_trace_ex: internal: direct cells + record cells != cells of the stream"; return false; }
+    return true;
+}
+
+bool ranged_cell_map(const LoweredPlan &P, uint64_t perm_cells, const std::vector<uint64_t> &direct, std::vector<uint64_t> &ranged, std::string &err) {
+    ranged = direct;
+    for (const BnpD &b : P.bnp)
+        for (uint64_t c = b.cell0; c < b.cell0 + perm_cells;) {
+            const uint64_t k = c & 63, take = std::min<uint64_t>(64 - k, b.cell0 + perm_cells - c), mask = (take == 64 ? ~0ull : ((1ull << take) - 1)) << k;
+            uint64_t &w = ranged[(size_t)(c / 64)];
+            if ((w & mask) != mask) { err = "h2w_plan_from_trace_ex: internal: a fused permutation's cell is a record's cell, or two permutations overlap"; return false; }
+            w &= ~mask; c += take;
+        }
+    return true;
+}
+
 }  // namespace h2w

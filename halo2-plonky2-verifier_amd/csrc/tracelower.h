@@ -78,5 +78,12 @@ struct LoweredPlan {
 };
 // false: err ("more than MAX_TMPL distinct scope shapes").  Takes the pools and the record meta list out of LW.
 bool group_templates(Lowered &LW, const ShardUnits &U, LoweredPlan &P, std::string &err);
+// H2W_TRACE_OUTPUT_FORMS: the direct cells of the lowered plan - what the interpreter and the fused PoseidonBN254 emission write themselves - as the
+// complement of the record ranges (P.meta: record i covers tt.ncells(template) cells from its offset), one bit per cell, padded to whole 64-word rows
+// (batch.hip k_direct_to_montgomery).  false: err - a record beyond the stream, two records on one cell, or direct + record cells != ncells.
+bool direct_cell_map(const LoweredPlan &P, const TemplateTable &tt, uint64_t ncells, std::vector<uint64_t> &direct, uint64_t &n_direct, std::string &err);
+// ... and the map the ranged kernel works from when the fused PoseidonBN254 permutations' cells leave their own kernel converted: `direct` without
+// [BnpD::cell0, + perm_cells) of every listed permutation.  false: err - one of those cells is not a direct cell.
+bool ranged_cell_map(const LoweredPlan &P, uint64_t perm_cells, const std::vector<uint64_t> &direct, std::vector<uint64_t> &ranged, std::string &err);
 
 }  // namespace h2w

@@ -232,9 +232,20 @@ h2w_plan *h2w_plan_from_trace(h2w_ctx *, uint64_t proof_words, const char *const
  * operands need more than 256 slots is refused by h2w_plan_from_trace, by name and with the count: in practice h2w_select_array_by_indicator /
  * h2w_select_from_idx on 52 to 64 wide (four-word) entries, whose 4 n + n operand words cannot all be at hand - a traced PoseidonBN254 verifier
  * with cap_height 6 (64 cap entries) is such a run; up to 51 wide entries (cap_height 5) replay, and so does any
- * length up to 64 of one-word entries. */
+ * length up to 64 of one-word entries.
+ * H2W_TRACE_OUTPUT_FORMS (combines freely with the fuse flags; alone, `consts` may be null): the lowering also builds, on the host, the map of the
+ * plan's direct cells - the cells the expansion kernel does not write: the interpreter's own and, with H2W_TRACE_FUSE_BN_PERMUTE, the 4,032 of every
+ * fused PoseidonBN254 permutation - as the complement of the record ranges, and checks that direct cells + record cells are the cells of the stream.
+ * Such a plan accepts H2W_OPT_OUTPUT_FORM as a compiled plan does (below: canonical by default, the form may change between calls, constants and
+ * bitmap uploaded when the Montgomery form is first selected), in every call that works on a traced plan (flat, _columns, _shard, _shard_compact), and
+ * answers h2w_plan_direct_cells / h2w_plan_record_ranges.  In Montgomery form the record cells leave the expansion kernel converted, the fused
+ * PoseidonBN254 permutations' cells leave their emission kernel converted (stored once: a Montgomery instantiation of that kernel, on a Montgomery copy
+ * of the plan's cell table), and one ranged kernel converts the remaining direct cells in place.  Its h2w_plan_trace_timing reports one more entry, the direct cells' conversion, between
+ * the PoseidonBN254 emission's slot and the expansion (0 in canonical form).  Sizes, status words and the stream in canonical form are those of the
+ * plan without the flag; a plan lowered without it is exactly as before.  (Flag value 4 is unassigned and refused.) */
 #define H2W_TRACE_FUSE_GL_PERMUTE 1
 #define H2W_TRACE_FUSE_BN_PERMUTE 2
+#define H2W_TRACE_OUTPUT_FORMS 8
 h2w_plan *h2w_plan_from_trace_ex(h2w_ctx *, uint64_t proof_words, const char *const *parallel_scopes, size_t n_scopes, int device_id,
                                  const h2w_poseidon_consts_t *consts, uint32_t flags);
 int h2w_plan_trace_info(const h2w_plan *, uint64_t out[6]);
@@ -397,15 +408,18 @@ int h2w_advice_to_montgomery(void *cells_dev, uint64_t n_cells, void *stream);
  * sharded calls (only this rank's blocks are touched) hold as in the canonical form.  Status words, workspace sizes, cell counts, layouts and the
  * keygen metadata do not depend on the form.  h2w_advice_digest, h2w_check_constraints, h2w_check_equalities, h2w_layout_columns and
  * h2w_layout_lookup_columns read cells as canonical values: they are meant for canonical streams (the layouts only move cells and work on either).
- * A plan made by h2w_plan_from_trace refuses H2W_FORM_MONTGOMERY (-1): its stream is canonical; convert it with h2w_advice_to_montgomery.
+ * A traced plan takes the option when it was lowered with H2W_TRACE_OUTPUT_FORMS (h2w_plan_from_trace_ex, 2d): its record cells leave the expansion
+ * kernel converted, so do the fused PoseidonBN254 permutations' cells their emission kernel, and the ranged kernel converts the other direct cells
+ * - the interpreter's - behind their writers and in front of the expansion, on the call's stream.  A plan made by h2w_plan_from_trace, or by h2w_plan_from_trace_ex without that flag,
+ * refuses H2W_FORM_MONTGOMERY (-1): its stream is canonical; convert it with h2w_advice_to_montgomery.
  * Any other value: -1.  The form may be changed between calls. */
 #define H2W_OPT_OUTPUT_FORM 5
 #define H2W_FORM_CANONICAL 0
 #define H2W_FORM_MONTGOMERY 1
 /* The cells of a proof's stream that value kernels write themselves (PoseidonBN254 permutation units, selects, inverses, ...): bit i of the bitmap
  * ((num_cells + 7) / 8 bytes) = cell i; the others - h2w_plan_num_record_cells of them - are written by the expansion kernel, record by record:
- * ranges[2 i] = first cell of record i, ranges[2 i + 1] = its cells (h2w_plan_num_records records).  Static per shape, no device needed; not for
- * traced plans. */
+ * ranges[2 i] = first cell of record i, ranges[2 i + 1] = its cells (h2w_plan_num_records records).  Static per shape, no device needed.  Of
+ * traced plans, those lowered with H2W_TRACE_OUTPUT_FORMS answer (the others: -1). */
 int h2w_plan_direct_cells(const h2w_plan *, uint8_t *bitmap);
 int h2w_plan_record_ranges(const h2w_plan *, uint64_t *ranges);
 /* Scheduling options of a plan.  H2W_OPT_FORK_CHAINS (default 1): with PoseidonBN254 Merkle caps the chain kernel of a batch call
