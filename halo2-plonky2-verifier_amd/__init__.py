@@ -136,6 +136,9 @@ SYMBOLS = {
     "h2w_ctx_footprint": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
     "h2w_ctx_reserve": (C.c_int, [_vp, C.c_uint64, C.c_uint64]),
     "h2w_trace_input": (C.c_int, [_vp, C.c_uint64, C.c_uint32]),
+    "h2w_trace_site": (C.c_int, [_vp, C.c_uint32]),
+    "h2w_plan_trace_verdict_info": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
+    "h2w_trace_verdict_batch": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, _vp]),
     "h2w_plan_from_trace": (_vp, [_vp, C.c_uint64, C.POINTER(C.c_char_p), C.c_size_t, C.c_int]),
     "h2w_plan_from_trace_ex": (_vp, [_vp, C.c_uint64, C.POINTER(C.c_char_p), C.c_size_t, C.c_int, C.POINTER(PoseidonConsts), C.c_uint32]),
     "h2w_plan_trace_info": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),

@@ -45,6 +45,11 @@ class Context:
         """Record the op tape of this context's run (h2w_ctx_trace_begin; Plan.from_trace turns it into a replayable plan)."""
         _ck(self.L.h2w_ctx_trace_begin(self.p), "h2w_ctx_trace_begin")
 
+    def trace_site(self, flag_bits):
+        """h2w_trace_site: the word that goes with every equality and range check recorded from here on (what a failing one raises in
+        Plan.trace_verdict's flags); nothing on a context that is not tracing."""
+        _ck(self.L.h2w_trace_site(self.p, flag_bits), "h2w_trace_site")
+
     def close(self):
         if getattr(self, "p", None):
             self.L.h2w_ctx_free(self.p)
@@ -398,6 +403,34 @@ class Plan:
             call = lambda np_, out: _ck(self.L.h2w_fri_verdict_batch(self.p, proofs_ptr, np_, out, stream), "h2w_fri_verdict_batch")
         else:
             call = lambda np_, out: _ck(self.L.h2w_fri_verdict_batch_ex(self.p, proofs_ptr, np_, out, stream, flags), "h2w_fri_verdict_batch_ex")
+        if verdict_ptr is not None:
+            call(n, verdict_ptr)
+            return None
+        if n == 0:
+            call(0, None)
+            return []
+        import torch
+        dev = f"cuda:{self.device_id}"
+        buf = torch.empty(4 * n, dtype=torch.int32, device=dev) if torch.cuda.is_available() else None      # (no device: the library says so)
+        call(n, buf.data_ptr() if buf is not None else None)
+        torch.cuda.synchronize(dev)
+        w = [int(x) & 0xFFFFFFFF for x in buf.cpu().tolist()]
+        return [tuple(w[4 * i:4 * i + 4]) for i in range(n)]
+
+    def trace_verdict_info(self):
+        """h2w_plan_trace_verdict_info of a traced plan: the equalities the trace recorded, those in the device tables (summed over instances), the
+        range sites, whether trace_verdict is available ("why": the lowering's reason when it is not), the templates with a table."""
+        out = (C.c_uint64 * 6)()
+        _ck(self.L.h2w_plan_trace_verdict_info(self.p, out), "h2w_plan_trace_verdict_info")
+        d = dict(zip(("recorded", "equalities", "range_sites", "available", "templates"), (int(x) for x in out)))
+        d["why"] = "" if d["available"] else last_error()
+        return d
+
+    def trace_verdict(self, proofs_ptr, n, workspace_ptr, stream=0, verdict_ptr=None):
+        """h2w_trace_verdict_batch on a traced plan: per proof (flags, n_failed, first_query, status), from the equalities the trace recorded; a proof
+        is accepted iff flags == 0 and n_failed == 0 and status == 0.  workspace_ptr: workspace_bytes(n) bytes, the witness call's.  verdict_ptr as in
+        verdict(): with it the call is enqueued and nothing returned; without it the device is synchronised and the tuples come back."""
+        call = lambda np_, out: _ck(self.L.h2w_trace_verdict_batch(self.p, proofs_ptr, np_, out, workspace_ptr, stream), "h2w_trace_verdict_batch")
         if verdict_ptr is not None:
             call(n, verdict_ptr)
             return None

@@ -54,7 +54,16 @@ struct AbiBackend {
     Gl gl_reduce(const Big &v) { Gl o; ck(h2w_gl_reduce(ctx, &v, &o)); return o; }
     void assert_equal(const Gl &a, const Gl &b) { ck(h2w_constrain_equal(ctx, &a, &b)); }
     void assert_equal_fr(const Fr &a, const Fr &b) { ck(h2w_constrain_equal(ctx, &a, &b)); }
-    void site(int) {}      // (which protocol check the next copy constraints belong to: the values sinks' business, valbackend.h)
+    // which protocol check the next copy constraints belong to: while the context records a trace, the H2W_VERDICT_* bit of the site goes with every
+    // equality recorded after it (h2w_trace_site; verdict.hip VerdictAcc::flag is the same mapping on the values sinks)
+    int n_perm_z = 0;
+    void site(int s) {
+        uint32_t f = 0;
+        if (s >= SITE_FINAL) f = H2W_VERDICT_FINAL;
+        else if (s >= SITE_FOLD) f = H2W_VERDICT_FOLD;
+        else if (s >= SITE_MERKLE) { const int kind = s - SITE_MERKLE; f = kind >= 3 ? H2W_VERDICT_MERKLE_STEP : kind == 0 ? H2W_VERDICT_MERKLE_TRACE : (kind == 1 && n_perm_z > 0) ? H2W_VERDICT_MERKLE_PERM_Z : H2W_VERDICT_MERKLE_QUOTIENT; }
+        ck(h2w_trace_site(ctx, f));
+    }
     // ---- NativeChip level
     Gl select(const Gl &a, const Gl &b, const Bool &sel) { Gl o; ck(h2w_select(ctx, &a, &b, &sel, &o)); return o; }
     void idx_to_indicator(const Gl &idx, int len, Bool *out) { ck(h2w_idx_to_indicator(ctx, &idx, (size_t)len, out)); }
@@ -98,7 +107,7 @@ struct AbiBackend {
     // the scopes the reference's #[count] macro opens around these functions (macro/src/lib.rs:9-61; fri/mod.rs:337, merkle/mod.rs:56)
     void merkle_begin(int, int) { ck(h2w_push_context(ctx, "verify_proof_to_cap_with_cap_index")); }
     void merkle_end(int, int) { ck(h2w_pop_context(ctx)); }
-    void query_begin(int) { ck(h2w_push_context(ctx, "verify_query_round")); }
+    void query_begin(int) { ck(h2w_push_context(ctx, "verify_query_round")); ck(h2w_trace_site(ctx, 0)); }      // (a query round starts at no site, as a values sink's lane does)
     void query_end(int) { ck(h2w_pop_context(ctx)); }
     bool bn_perm_unit(Fr *, const h2w_poseidon_consts_t *) { return false; }
     void bn_perm_begin() {}
@@ -182,7 +191,7 @@ int h2w_chip_verify_stark(h2w_ctx *ctx, const h2w_shape_t *shape, const h2w_pose
     if (!ctx || !shape || !k || !proof_words) { set_error("h2w_chip_verify_stark: null argument"); return -1; }
     if (const char *why = shape_check(*shape)) { set_error(std::string("h2w_chip_verify_stark: unsupported shape: ") + why); return -1; }
     Derived d = derive_shape(*shape); ProofLayout pl = proof_layout(*shape, d);
-    AbiBackend be(ctx, shape->hash_mode, proof_words, pl.total);
+    AbiBackend be(ctx, shape->hash_mode, proof_words, pl.total); be.n_perm_z = shape->n_perm_z;
     Verifier<AbiBackend> V(be, *shape, k);
     ChallengeBlock<AbiBackend> *cb = new ChallengeBlock<AbiBackend>();
     V.run_all(*cb);

@@ -196,7 +196,19 @@ TrRec::TrRec(h2w_ctx *c_, uint16_t code, uint16_t sub, uint64_t imm) : c(c_), t(
 }
 uint32_t TrRec::ctx_id() const { return c->id; }
 void TrRec::tag_required(const char *fn) { if (t && op.tag.kind == 0) t->fail(std::string(fn) + ": a witness whose value the library cannot recompute on another proof (tag it with h2w_trace_input, or use the level-2 hint ops)"); }
-void TrRec::done() { if (!t) return; op.ncells = (uint32_t)(c->ncells - op.cell0); t->ops.push_back(op); }
+void TrRec::done() {
+    if (!t) return;
+    op.ncells = (uint32_t)(c->ncells - op.cell0);
+    if (op.code == TR_RANGE_CHECK || op.code == TR_CLT_SAFE) t->range_sites.push_back(TraceRangeSite{(uint64_t)t->ops.size(), t->site});      // (beside the op, not in it: the tape is what it was)
+    t->ops.push_back(op);
+}
+// an assert_equal of the traced run: no op, no cell - the side list the plan's verdict is lowered from (trace.h)
+inline void tr_assert(h2w_ctx *c, const h2w_assigned_t *a, const h2w_assigned_t *b) {
+    Trace *t = c->trace; if (!t) return;
+    TraceAssert e; e.a = a ? a->offset : 0; e.b = b ? b->offset : 0; e.at = (uint64_t)t->ops.size(); e.site = t->site;
+    e.a_cell = a && a->has_cell && a->ctx_id == c->id ? 1 : 0; e.b_cell = b && b->has_cell && b->ctx_id == c->id ? 1 : 0;
+    t->asserts.push_back(e);
+}
 
 }  // namespace
 
@@ -380,7 +392,7 @@ int h2w_limbs_to_num(h2w_ctx *c, const h2w_assigned_t *limbs, size_t n, size_t l
 }
 int h2w_check_less_than_safe(h2w_ctx *c, const h2w_assigned_t *a, uint64_t b) { if (!check(c, "h2w_check_less_than_safe")) return -1; TrRec tr(c, TR_CLT_SAFE, 0, b); tr.in(a); if (c->keygen) c->mr.check_less_than_safe(off(a), b); t_check_less_than_safe(c, *a, b); tr.done(); return kg_done(c, "h2w_check_less_than_safe"); }
 int h2w_range_check(h2w_ctx *c, const h2w_assigned_t *a, size_t range_bits) { if (!check(c, "h2w_range_check")) return -1; TrRec tr(c, TR_RANGE_CHECK, 0, range_bits); tr.in(a); if (c->keygen) c->mr.range_check(off(a), range_bits); t_range_check(c, *a, range_bits); tr.done(); return kg_done(c, "h2w_range_check"); }
-int h2w_constrain_equal(h2w_ctx *c, const h2w_assigned_t *a, const h2w_assigned_t *b) { if (!check(c, "h2w_constrain_equal")) return -1; if (c->keygen) c->mr.equal(off(a), off(b)); return 0; }
+int h2w_constrain_equal(h2w_ctx *c, const h2w_assigned_t *a, const h2w_assigned_t *b) { if (!check(c, "h2w_constrain_equal")) return -1; if (c->keygen) c->mr.equal(off(a), off(b)); tr_assert(c, a, b); return 0; }
 
 // ---------------------------------------------------------------- ContextWrapper::{push_context, pop_context} (util/context_wrapper.rs:28-34)
 int h2w_push_context(h2w_ctx *c, const char *name) {
@@ -464,6 +476,7 @@ int h2w_gl_div(h2w_ctx *c, const h2w_assigned_t *a, const h2w_assigned_t *b, h2w
     TrRec tr(c, TR_GLOP, T_GLOP); tr.in(b); tr.in(&rw); tr.lit(0);
     if (c->keygen) { const int64_t pr = c->mr.gl_reduce(c->mr.mul(MR::EX(off(b)), MR::EX(off(&rw)))); c->mr.equal(off(a), pr); }      // gl.assert_equal(a, b * res)
     glop(c, T_GLOP, b->value.l[0], res, 0, &prod); tr.out(&prod); tr.done();
+    tr_assert(c, a, &prod);      // gl.assert_equal(a, b * res), base.rs:390: the hint's check, a chip-level assert_equal like the caller's
     *out = rw; return kg_done(c, "h2w_gl_div");
 }
 // GoldilocksChip::mul_sub (base.rs:332-343): mul_no_reduce, sub_no_reduce (= prod + c*(p-1) with a NEG_ONE constant cell), reduce: 70 cells
@@ -526,6 +539,11 @@ int h2w_trace_input(h2w_ctx *c, uint64_t word, uint32_t n_words) {
     if (!c->trace) return 0;                       // not tracing: nothing to tag
     if (n_words != 1 && n_words != 4) return fail(c, "h2w_trace_input: a proof value is 1 word (a Goldilocks element) or 4 (a BN254 hash)");
     c->trace->pending = TraceTag{1, word, n_words, 0, 0}; return 0;
+}
+int h2w_trace_site(h2w_ctx *c, uint32_t flag_bits) {
+    if (!check(c, "h2w_trace_site")) return -1;
+    if (!c->trace) return 0;                       // not tracing: nothing to attach the word to
+    c->trace->site = flag_bits; return 0;
 }
 
 // ---------------------------------------------------------------- keygen-side metadata of the eager context (witness_gen_only == 0)

@@ -33,6 +33,7 @@
 #include "glpval.h"
 #include "bnpval.h"
 #include "bnemit.h"
+#include "traceverdict.h"
 
 struct h2w_ctx;
 namespace h2w {
@@ -75,6 +76,11 @@ struct TracedPlan {
     // sharding: the depth-1 instances are the units (query q = the q-th in tape order); why_unshardable empty: they tile the stream behind the root's block
     std::string why_unshardable; std::vector<uint32_t> h_unit;      // h_unit: the unit of every instance (InstD order)
     std::vector<uint32_t> h_lanes, lane0; DevBuf<uint32_t> d_lanes; uint64_t lanes_n = 0; int lanes_rank = -1, lanes_world = 0;      // the lane table of the last (n, rank, world)
+    // the verdict (h2w_trace_verdict_batch): the lowered tables (tracelower.h verdict_tables; why_no_verdict non-empty: unavailable), their device copies,
+    // and the QUIET lane table of the last n - every (proof, instance) of every template with bit 31 set; members of its own, so that it neither passes
+    // for a sharded call's table nor evicts it
+    VerdictTables vt; std::string why_no_verdict; DevBuf<VEntD> d_vents; DevBuf<VInstD> d_vinst; DevBuf<VImpD> d_vimps; DevBuf<uint64_t> d_tinfo; DevBuf<uint32_t> d_vsites;
+    std::vector<uint32_t> qlane0; DevBuf<uint32_t> d_qlanes; uint64_t qlanes_n = 0;
 };
 
 // ------------------------------------------------------------------------------------------------------------------- device
@@ -400,6 +406,27 @@ static int lane_table(h2w_plan *p, uint64_t n, const ShardSpec &sh) {
     t->lanes_n = n; t->lanes_rank = sh.rank; t->lanes_world = sh.world;
     return 0;
 }
+// The k_replay launches of a call, depth by depth (a segment reads its ancestors' values; the templates of one depth share a launch).  lane0: the lane
+// table's template offsets when R.lanes is set (a sharded call's, the verdict call's quiet table), else null: every (proof, instance) in place.
+static void replay_launches(h2w_plan *p, ReplayArgs &R, const std::vector<uint32_t> *lane0, uint64_t n_proofs, uint64_t *blist, hipStream_t stream) {
+    TracedPlan *t = p->traced;
+    uint32_t maxd = 0; for (const TmplD &T : t->tmpls) if (T.depth > maxd) maxd = T.depth;
+    for (uint32_t d = 0; d <= maxd; d++) {
+        uint32_t nb = 0;
+        for (size_t i = 0; i < t->tmpls.size(); i++) {
+            R.blk0[i] = nb;
+            if (t->tmpls[i].depth == d) nb += (uint32_t)(((lane0 ? (*lane0)[i + 1] - (*lane0)[i] : n_proofs * t->tmpls[i].ninst) + 63) / 64);
+        }
+        R.blk0[t->tmpls.size()] = nb; R.depth = d;
+        if (t->timing && t->tev_used < 12) (void)hipEventRecord(t->tev[t->tev_used++], stream);
+        if (nb && t->nbnp) {
+            ReplayArgsT<true> RB; static_cast<ReplayArgs &>(RB) = R; RB.bnk = p->d_bn_tab.get() + BK_T; RB.blist = blist; RB.bnp0 = t->d_bnp0.get(); RB.nbnp = t->nbnp;
+            hipLaunchKernelGGL(k_replay<true>, dim3(nb), dim3(64), 0, stream, RB);
+        } else if (nb) hipLaunchKernelGGL(k_replay<false>, dim3(nb), dim3(64), 0, stream, R);
+    }
+}
+// the plan's part of k_replay's arguments; what belongs to the call - recs, out, the lane table, the sharding - is zero and the caller's to set
+static ReplayArgs replay_args(const h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, char *ws, const struct TracedWs &wl);
 int traced_run(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void *advice_dev, void *workspace_dev, void *stream_, ColMap cm, uint64_t cell_stride, const ShardSpec &sh) {
     TracedPlan *t = p->traced;
     if (n_proofs > 65535) { set_error("h2w_fri_witness_batch: more than 65535 proofs per call"); return -1; }
@@ -410,13 +437,8 @@ int traced_run(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void 
     if (sharded && lane_table(p, n_proofs, sh) != 0) return -1;
     hipStream_t stream = (hipStream_t)stream_;
     const TracedWs wl = traced_ws(p, n_proofs); char *ws = (char *)workspace_dev;
-    ReplayArgs R; memset(&R, 0, sizeof(R));
-    R.tape = t->d_tape.get(); R.insts = t->d_insts.get(); R.imps = t->d_imps.get(); R.inputs = t->d_inputs.get(); R.pool64 = t->d_pool64.get(); R.poolfr = t->d_poolfr.get();
-    R.proofs = proofs_dev; R.proof_words = p->pl.total; R.recs = (rec_t *)(ws + wl.recs); R.rec_stride = p->nrec; R.out = (fr_t *)advice_dev; R.cell_stride = cell_stride; R.cm = cm;      // (cm.starts: the FlexGate columns of every proof, cell_stride = ncols << k; else the flat stream)
-    R.vals = (uint64_t *)(ws + wl.vals); R.status = (uint32_t *)(ws + wl.status); R.ncells = p->d_ncells.get(); R.inv_pos = p->d_inv.get(); R.inv_neg = p->d_inv.get() + INV_TAB; R.P = p->P; R.L = p->shape.lookup_bits;
-    R.nproofs = (uint32_t)n_proofs; R.lflag = (uint32_t *)(ws + wl.lflag);
-    R.glk = reinterpret_cast<const uint64_t *>(p->d_consts.get()); R.glist = (uint64_t *)(ws + wl.glist); R.nglp = t->nglp;
-    R.ntmpl = (uint32_t)t->tmpls.size(); R.tm = t->d_tm.get(); R.prefix = t->d_prefix.get(); R.npool64 = t->npool64; R.npoolfr = t->npoolfr;
+    ReplayArgs R = replay_args(p, proofs_dev, n_proofs, ws, wl);
+    R.out = (fr_t *)advice_dev; R.cell_stride = cell_stride; R.cm = cm;      // (cm.starts: the FlexGate columns of every proof, cell_stride = ncols << k; else the flat stream)
     if (sharded) {
         R.lanes = t->d_lanes.get(); for (size_t i = 0; i < t->lane0.size(); i++) R.lane0[i] = t->lane0[i];
         R.sh_world = (uint32_t)sh.world; R.sh_rank = (uint32_t)sh.rank; R.sh_compact = (uint32_t)sh.compact; R.nq = (uint32_t)p->shape.num_queries;
@@ -424,24 +446,11 @@ int traced_run(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void 
     }
     H2W_HIP(hipMemsetAsync(ws + wl.status, 0, n_proofs * 4, stream));
     H2W_HIP(hipMemsetAsync(ws + wl.lflag, 0, n_proofs * 4, stream));
-    uint32_t maxd = 0; for (const TmplD &T : t->tmpls) if (T.depth > maxd) maxd = T.depth;
     uint64_t *const blist = (uint64_t *)(ws + wl.blist);
     // Montgomery form: the fused PoseidonBN254 permutations' cells leave their emission kernel converted; the ranged kernel takes the other direct cells
     const bool mont = p->output_form == H2W_FORM_MONTGOMERY, emit_mont = mont && t->nbnp && !p->trace_bn_ranged;
     t->tev_used = 0;
-    for (uint32_t d = 0; d <= maxd; d++) {      // a segment reads its ancestors' values: depth by depth; the templates of one depth in one launch
-        uint32_t nb = 0;
-        for (size_t i = 0; i < t->tmpls.size(); i++) {
-            R.blk0[i] = nb;
-            if (t->tmpls[i].depth == d) nb += (uint32_t)(((sharded ? t->lane0[i + 1] - t->lane0[i] : n_proofs * t->tmpls[i].ninst) + 63) / 64);
-        }
-        R.blk0[t->tmpls.size()] = nb; R.depth = d;
-        if (t->timing && t->tev_used < 12) H2W_HIP(hipEventRecord(t->tev[t->tev_used++], stream));
-        if (nb && t->nbnp) {
-            ReplayArgsT<true> RB; static_cast<ReplayArgs &>(RB) = R; RB.bnk = p->d_bn_tab.get() + BK_T; RB.blist = blist; RB.bnp0 = t->d_bnp0.get(); RB.nbnp = t->nbnp;
-            hipLaunchKernelGGL(k_replay<true>, dim3(nb), dim3(64), 0, stream, RB);
-        } else if (nb) hipLaunchKernelGGL(k_replay<false>, dim3(nb), dim3(64), 0, stream, R);
-    }
+    replay_launches(p, R, sharded ? &t->lane0 : nullptr, n_proofs, blist, stream);
     if (t->timing) H2W_HIP(hipEventRecord(t->tev[t->tev_used++], stream));
     if (t->nglp) {      // the records of the listed permutations, side by side
         GlpEmitArgs E; E.consts = p->d_consts.get(); E.list = R.glist; E.recs = R.recs; E.rec_stride = R.rec_stride; E.ncells = p->d_ncells.get(); E.unit = t->d_glp_unit.get();
@@ -475,6 +484,66 @@ int traced_run(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void 
     H2W_HIP(hipGetLastError());
     return 0;
 }
+static ReplayArgs replay_args(const h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, char *ws, const TracedWs &wl) {
+    const TracedPlan *t = p->traced;
+    ReplayArgs R; memset(&R, 0, sizeof(R));
+    R.tape = t->d_tape.get(); R.insts = t->d_insts.get(); R.imps = t->d_imps.get(); R.inputs = t->d_inputs.get(); R.pool64 = t->d_pool64.get(); R.poolfr = t->d_poolfr.get();
+    R.proofs = proofs_dev; R.proof_words = p->pl.total; R.recs = (rec_t *)(ws + wl.recs); R.rec_stride = p->nrec;
+    R.vals = (uint64_t *)(ws + wl.vals); R.status = (uint32_t *)(ws + wl.status); R.ncells = p->d_ncells.get(); R.inv_pos = p->d_inv.get(); R.inv_neg = p->d_inv.get() + INV_TAB; R.P = p->P; R.L = p->shape.lookup_bits;
+    R.nproofs = (uint32_t)n_proofs; R.lflag = (uint32_t *)(ws + wl.lflag);
+    R.glk = reinterpret_cast<const uint64_t *>(p->d_consts.get()); R.glist = (uint64_t *)(ws + wl.glist); R.nglp = t->nglp;
+    R.ntmpl = (uint32_t)t->tmpls.size(); R.tm = t->d_tm.get(); R.prefix = t->d_prefix.get(); R.npool64 = t->npool64; R.npoolfr = t->npoolfr;
+    return R;
+}
+// The quiet lane table of n proofs: template by template every (proof, instance) place with bit 31 set - the sharded call's format (lane_table) for a
+// world in which this rank owns nothing: the interpreter computes the values and stores nothing else
+static int quiet_lane_table(h2w_plan *p, uint64_t n) {
+    TracedPlan *t = p->traced;
+    if (t->d_qlanes.get() && t->qlanes_n == n) return 0;
+    std::vector<uint32_t> L; t->qlane0.assign(t->tmpls.size() + 1, 0);
+    for (size_t i = 0; i < t->tmpls.size(); i++) {
+        const TmplD &T = t->tmpls[i]; t->qlane0[i] = (uint32_t)L.size();
+        if (n * T.ninst >= 0x80000000ull || L.size() + n * T.ninst >= 0x80000000ull) { set_error("h2w_trace_verdict_batch: too many (proof, instance) lanes in one call; split the batch"); return -1; }
+        for (uint64_t g = 0; g < n * T.ninst; g++) L.push_back((uint32_t)g | 0x80000000u);
+    }
+    t->qlane0[t->tmpls.size()] = (uint32_t)L.size();
+    H2W_HIP(hipDeviceSynchronize());      // a previous call may still read the old table (plans are single-threaded handles, include/h2w.h)
+    t->d_qlanes.reset(); t->qlanes_n = 0;
+    if (t->d_qlanes.upload(L) != 0) return -1;
+    t->qlanes_n = n;
+    return 0;
+}
+static int trace_verdict_run(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, h2w_verdict_t *verdict_dev, void *workspace_dev, void *stream_) {
+    TracedPlan *t = p->traced; const VerdictTables &V = t->vt;
+    for (size_t i = 0; i < t->tmpls.size(); i++)
+        if ((uint64_t)n_proofs * t->tmpls[i].ninst * (V.ent0[i + 1] - V.ent0[i]) >= 0x80000000ull) { set_error("h2w_trace_verdict_batch: 2^31 or more (proof, instance, check) lanes in one call; split the batch"); return -1; }
+    DeviceGuard dg(p->device);
+    if (quiet_lane_table(p, n_proofs) != 0) return -1;
+    hipStream_t stream = (hipStream_t)stream_;
+    const TracedWs wl = traced_ws(p, n_proofs); char *ws = (char *)workspace_dev;
+    // 1. the values: k_replay as traced_run launches it, every lane quiet (no advice buffer: R.out stays null, nothing is stored through it)
+    ReplayArgs R = replay_args(p, proofs_dev, n_proofs, ws, wl);
+    R.cm = flat_cols(); R.cell_stride = p->ncells;
+    R.lanes = t->d_qlanes.get(); for (size_t i = 0; i < t->qlane0.size(); i++) R.lane0[i] = t->qlane0[i];
+    R.sh_world = 1; R.sh_rank = 0; R.sh_compact = 0; R.nq = (uint32_t)p->shape.num_queries;
+    H2W_HIP(hipMemsetAsync(ws + wl.status, 0, n_proofs * 4, stream));
+    H2W_HIP(hipMemsetAsync(ws + wl.lflag, 0, n_proofs * 4, stream));
+    TraceVerdictArgs A; memset(&A, 0, sizeof(A));
+    A.ents = t->d_vents.get(); A.vinst = t->d_vinst.get(); A.vimps = t->d_vimps.get(); A.sites = t->d_vsites.get(); A.tinfo = t->d_tinfo.get(); A.inputs = t->d_inputs.get(); A.pool64 = t->d_pool64.get(); A.poolfr = t->d_poolfr.get();
+    A.vals = R.vals; A.proofs = proofs_dev; A.proof_words = p->pl.total; A.verdict = verdict_dev; A.status = R.status; A.lflag = R.lflag; A.nproofs = (uint32_t)n_proofs; A.L = p->shape.lookup_bits;
+    launch_trace_verdict_init(A, stream);
+    const bool timing = t->timing; t->timing = false;      // (h2w_plan_trace_timing reports witness calls: this call records no events and leaves the last call's alone)
+    replay_launches(p, R, &t->qlane0, n_proofs, (uint64_t *)(ws + wl.blist), stream);
+    t->timing = timing;
+    // 2. the checks, template by template, behind the deepest depth
+    for (size_t i = 0; i < t->tmpls.size(); i++) {
+        A.tmpl = (uint32_t)i; A.inst0 = t->tmpls[i].inst0; A.ninst = t->tmpls[i].ninst; A.ent0 = V.ent0[i]; A.nent = V.ent0[i + 1] - V.ent0[i];
+        launch_trace_verdict(A, stream);
+    }
+    launch_trace_verdict_finish(A, stream);
+    H2W_HIP(hipGetLastError());
+    return 0;
+}
 }  // namespace h2w
 
 // h2w_plan_from_trace: the lowering stage by stage (tracelower.h), every tape checked (tapefmt.h), the plan handle, the upload.
@@ -504,6 +573,15 @@ static h2w_plan *plan_from_trace(h2w_ctx *ctx, uint64_t proof_words, const char 
         err = tape_check(LP.tape.data() + t0, t1 - t0, M);
         if (!err.empty()) { set_error("h2w_plan_from_trace: " + err); return nullptr; }
     }
+    // the verdict stage, behind the final tapes (it reads the lowering's maps and changes nothing); its table checked like a tape before it is uploaded
+    VerdictTables VT = verdict_tables(tr, LW, F, LP);
+    for (size_t t = 0; VT.why.empty() && t < LP.tmpls.size(); t++) {
+        TapeLimits M = LP.limits[t]; M.inputs = LP.inputs.data() + LP.insts[LP.tmpls[t].inst0].in0; M.npool64 = LP.pool64.size(); M.npoolfr = LP.poolfr.size(); M.proof_words = proof_words;
+        M.nimps = VT.nvimp[t];
+        err = verdict_table_check(VT.ents.data() + VT.ent0[t], VT.ent0[t + 1] - VT.ent0[t], M);
+        if (!err.empty()) { VT = VerdictTables(); VT.n_asserts = tr->asserts.size(); VT.why = "the traced plan has no verdict: " + err; }      // (the witness plan is not the verdict's to refuse)
+    }
+    err.clear();
     std::vector<uint64_t> op_counts(TAPE_COUNTS, 0);      // h2w_plan_trace_op_counts: over every template's final tape
     for (size_t t = 0; t < LP.tmpls.size(); t++) { const size_t t0 = LP.tmpls[t].tape0, t1 = t + 1 < LP.tmpls.size() ? LP.tmpls[t + 1].tape0 : LP.tape.size(); tape_op_counts(LP.tape.data() + t0, t1 - t0, op_counts.data()); }
     for (uint32_t w : LP.inputs) if (w >= proof_words) { set_error("h2w_plan_from_trace: an input tag beyond proof_words"); return nullptr; }
@@ -513,6 +591,7 @@ static h2w_plan *plan_from_trace(h2w_ctx *ctx, uint64_t proof_words, const char 
     tp->n_ops = tr->ops.size(); tp->n_segments = LP.n_segments; tp->why_unshardable = U.why_unshardable; tp->n_candidates = F.n_candidates;
     tp->bn_flag = fusing_bn; tp->n_bn_left = F.n_bn_left;
     tp->op_counts.swap(op_counts);
+    tp->why_no_verdict = VT.why; tp->vt = VT;
 
     // ---- the plan handle
     int ndev = 0; const bool on_device = hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0;      // (none: layout queries only)
@@ -562,6 +641,13 @@ static h2w_plan *plan_from_trace(h2w_ctx *ctx, uint64_t proof_words, const char 
     // the tables the fused permutations were verified on (handletabs.h); which shard unit a listed permutation belongs to / where it lies
     if (ok && tp->nglp) ok = upload_glp_consts(pl->d_consts, *consts) == 0 && tp->d_glp_unit.upload(tp->h_glp_unit) == 0;
     if (ok && tp->nbnp) ok = upload_bn_tab(pl->d_bn_tab, *consts, pl->P) == 0 && tp->d_bnp.upload(tp->h_bnp) == 0 && tp->d_bnp0.upload(tp->h_bnp0) == 0;
+    if (ok && VT.why.empty()) {      // the verdict's tables: the entries, per instance {first verdict import, first input, unit}, the imports, per template {prefix, instances}
+        std::vector<VInstD> vi(LP.insts.size()); std::vector<VImpD> vm(VT.vimps.size()); std::vector<uint64_t> ti(2 * tp->tmpls.size());
+        for (size_t i = 0; i < vi.size(); i++) vi[i] = VInstD{VT.vimp0[i], LP.insts[i].in0, LP.insts[i].unit, VT.site0[i]};
+        for (size_t i = 0; i < vm.size(); i++) vm[i] = VImpD{VT.vimps[i].tmpl, VT.vimps[i].inst, VT.vimps[i].slot, 0};
+        for (size_t i = 0; i < tp->tmpls.size(); i++) { ti[2 * i] = prefix[i]; ti[2 * i + 1] = tp->tmpls[i].ninst; }
+        ok = tp->d_vinst.upload(vi) == 0 && tp->d_tinfo.upload(ti) == 0 && (VT.ents.empty() || (tp->d_vents.upload(VT.ents) == 0 && tp->d_vsites.upload(VT.sites) == 0)) && (vm.empty() || tp->d_vimps.upload(vm) == 0);
+    }
     if (!ok) { h2w_plan_free(pl); return nullptr; }
     return pl;
 }
@@ -578,6 +664,24 @@ extern "C" int h2w_plan_trace_info(const h2w_plan *p, uint64_t out[6]) {
     const TracedPlan *t = p->traced;
     out[0] = t->n_ops; out[1] = t->n_segments; out[2] = t->tmpls.size(); out[3] = t->nglp; out[4] = t->n_candidates; out[5] = t->nglp;
     return 0;
+}
+extern "C" int h2w_plan_trace_verdict_info(const h2w_plan *p, uint64_t out[6]) {
+    if (!p || !out) { set_error("h2w_plan_trace_verdict_info: null argument"); return -1; }
+    if (!p->traced) { set_error("h2w_plan_trace_verdict_info: not a traced plan (h2w_plan_from_trace); a plan of h2w_plan_compile has h2w_fri_verdict_batch"); return -1; }
+    const TracedPlan *t = p->traced; const VerdictTables &V = t->vt;
+    out[0] = V.n_asserts; out[1] = V.n_eq_lanes; out[2] = V.n_range; out[3] = t->why_no_verdict.empty() ? 1 : 0; out[4] = V.n_tmpl; out[5] = 0;
+    if (!t->why_no_verdict.empty()) set_error("h2w_plan_trace_verdict_info: " + t->why_no_verdict);
+    return 0;
+}
+extern "C" int h2w_trace_verdict_batch(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, h2w_verdict_t *verdict_dev, void *workspace_dev, void *stream) {
+    if (!p) { set_error("h2w_trace_verdict_batch: null plan"); return -1; }
+    if (!p->traced) { set_error("h2w_trace_verdict_batch: a plan of h2w_plan_compile: use h2w_fri_verdict_batch"); return -1; }
+    if (!p->traced->why_no_verdict.empty()) { set_error("h2w_trace_verdict_batch: " + p->traced->why_no_verdict); return -1; }
+    if (p->device < 0) { set_error("h2w_trace_verdict_batch: no HIP device — the replay only runs on the GPU (no CPU fallback)"); return -1; }
+    if (n_proofs == 0) return 0;
+    if (!proofs_dev || !verdict_dev || !workspace_dev) { set_error("h2w_trace_verdict_batch: null buffer"); return -1; }
+    if (n_proofs > 65535) { set_error("h2w_trace_verdict_batch: more than 65535 proofs per call"); return -1; }
+    return trace_verdict_run(p, proofs_dev, n_proofs, verdict_dev, workspace_dev, stream);
 }
 extern "C" int h2w_plan_trace_op_counts(const h2w_plan *p, uint64_t *out, size_t n_out) {
     if (!p || (!out && n_out)) { set_error("h2w_plan_trace_op_counts: null argument"); return -1; }

@@ -32,8 +32,14 @@ struct TraceOp {
     uint64_t cell0; uint32_t ncells; // the cells the call appended: [cell0, cell0 + ncells)
     TraceTag tag;
 };
+// A chip-level assert_equal of the run (h2w_constrain_equal; the one inside h2w_gl_div): no cells, so not an op - a side list the traced plan's verdict
+// is lowered from (tracelower.h verdict_tables).  a, b: the cell offsets of the two handles (a_cell / b_cell 0: the handle has no cell of this
+// context); site: the word of h2w_trace_site in force; at: trace ops recorded before it (its place on the tape)
+struct TraceAssert { uint64_t a, b, at; uint32_t site; uint8_t a_cell, b_cell; };
+struct TraceRangeSite { uint64_t op; uint32_t site; };      // the site word in force at a TR_RANGE_CHECK / TR_CLT_SAFE op, by op index
 struct Trace {
     std::vector<TraceOp> ops; std::vector<TraceIn> ins; std::vector<uint64_t> outs; std::vector<fr_t> consts; std::vector<std::string> names;
+    std::vector<TraceAssert> asserts; std::vector<TraceRangeSite> range_sites; uint32_t site = 0;      // site: h2w_trace_site's current word
     TraceTag pending; std::string err;
     void fail(const std::string &m) { if (err.empty()) err = m; }
 };

@@ -94,7 +94,7 @@ static void lower_pass(const Trace *tr, int L, TemplateTable &tt, const char *co
     auto bad = [&](const std::string &m) { if (err.empty()) err = m; };
     // ---- pass 1: segments
     std::vector<SegInfo> &segs = LW.segs; segs.assign(1, SegInfo());
-    std::vector<int> op_seg(tr->ops.size(), 0);
+    std::vector<int> &op_seg = LW.op_seg; op_seg.assign(tr->ops.size(), 0);      // (kept: the verdict stage places the recorded equalities by it)
     {
         std::vector<int> stack;      // per open scope: the segment it opened, or -1 (an ordinary scope)
         int cur = 0;
@@ -537,6 +537,85 @@ bool group_templates(Lowered &LW, const ShardUnits &U, LoweredPlan &P, std::stri
     }
     P.pool64.swap(LW.pool64); P.poolfr.swap(LW.poolfr); P.meta.swap(LW.meta); P.nrec = LW.nrec; P.n_segments = segs.size();
     return true;
+}
+
+VerdictTables verdict_tables(const Trace *tr, const Lowered &LW, const Fusable &F, const LoweredPlan &P) {
+    VerdictTables V; V.n_asserts = tr->asserts.size();
+    const std::vector<SegInfo> &segs = LW.segs;
+    struct SegV { std::vector<VEntD> ents; std::vector<ImpD> imps; std::map<std::pair<uint32_t, uint32_t>, uint32_t> imp_of; };
+    std::vector<SegV> sv(segs.size());
+    auto unavailable = [&](const std::string &m) { if (V.why.empty()) V.why = "the traced plan has no verdict: " + m; };
+    auto is_ancestor = [&](int a, int s) { for (int x = s; x >= 0; x = segs[(size_t)x].parent) if (x == a) return true; return false; };
+    // a handle's cell as an operand of a check in segment s (lower_pass ref_of, on the finished maps and with the verdict's own imports)
+    auto vref = [&](int s, uint64_t cell, bool has_cell, const char *what, uint32_t &r) -> bool {
+        r = 0;
+        if (!has_cell) { unavailable(std::string(what) + " compares a handle that is no cell of the traced context"); return false; }
+        auto it = LW.val_of.find(cell);
+        if (it == LW.val_of.end()) {
+            for (const auto &kv : F.fuse) if (cell >= kv.second.cell0 && cell < kv.second.cell1) { unavailable(std::string(what) + " reads a value interior to a fused permutation, which the value store no longer has (cell " + std::to_string(cell) + "): lower the trace without the fuse flag for a verdict"); return false; }
+            unavailable(std::string(what) + " reads a cell that is no traced call's result handle (cell " + std::to_string(cell) + ")"); return false;
+        }
+        const ValInfo &v = LW.vals[it->second];
+        if (v.is_static) { r = v.width == WFR ? mkref(RK_LITFR, WFR, v.lit) : mkref(RK_LIT64, W64, v.lit); return true; }
+        if ((int)v.seg == s) { r = mkref(RK_LOCAL, v.width, v.slot); return true; }
+        if (!is_ancestor((int)v.seg, s)) { unavailable(std::string(what) + " reads a value computed in a scope that does not enclose it (cell " + std::to_string(cell) + ")"); return false; }
+        SegV &S = sv[(size_t)s]; const auto key = std::make_pair(v.seg, v.slot);
+        auto im = S.imp_of.find(key);
+        if (im == S.imp_of.end()) { S.imps.push_back(ImpD{v.seg, 0, v.slot}); im = S.imp_of.emplace(key, (uint32_t)S.imps.size() - 1).first; }
+        r = mkref(RK_IMPORT, v.width, im->second); return true;
+    };
+    for (const TraceAssert &e : tr->asserts) {
+        if (e.at > LW.op_seg.size()) { unavailable("internal: an equality beyond the tape"); break; }
+        const int s = e.at == 0 ? 0 : LW.op_seg[(size_t)e.at - 1];
+        VEntD d; d.kind = VK_EQUAL; d.site = e.site; d.aux = 0;
+        if (!vref(s, e.a, e.a_cell != 0, "an equality", d.a) || !vref(s, e.b, e.b_cell != 0, "an equality", d.b)) break;
+        sv[(size_t)s].ents.push_back(d);
+    }
+    for (const TraceRangeSite &rs : tr->range_sites) {
+        if (!V.why.empty()) break;
+        if (rs.op >= tr->ops.size()) { unavailable("internal: a range site beyond the tape"); break; }
+        const TraceOp &o = tr->ops[(size_t)rs.op]; const int s = LW.op_seg[(size_t)rs.op];
+        if (o.n_in != 1 || tr->ins[o.first_in].lit) { unavailable("internal: a range check without its operand"); break; }
+        VEntD d; d.kind = o.code == TR_CLT_SAFE ? VK_CLT : VK_RANGE; d.site = rs.site; d.aux = o.imm; d.b = 0;
+        if (!vref(s, tr->ins[o.first_in].v, true, "a range check", d.a)) break;
+        if (vref_words(d.a) != 1) { unavailable("internal: a range check of a wide value"); break; }
+        sv[(size_t)s].ents.push_back(d);
+    }
+    // the instances of a template share one table (their import tables, one per instance, make it concrete): InstD order
+    std::vector<std::vector<int>> members(P.tmpls.size());
+    for (size_t si = 0; si < segs.size(); si++) {
+        const SegInfo &S = segs[si];
+        if (S.tmpl < 0 || (size_t)S.tmpl >= members.size()) { unavailable("internal: a segment without a template"); break; }
+        std::vector<int> &m = members[(size_t)S.tmpl]; if (m.size() <= S.inst) m.resize(S.inst + 1, -1); m[S.inst] = (int)si;
+    }
+    auto same = [](const VEntD &x, const VEntD &y) { return x.a == y.a && x.b == y.b && x.kind == y.kind && x.aux == y.aux; };      // (the site words are per instance)
+    for (size_t t = 0; t < P.tmpls.size() && V.why.empty(); t++) {
+        V.ent0.push_back((uint32_t)V.ents.size());
+        if (members[t].size() != P.tmpls[t].ninst || members[t].empty() || members[t][0] < 0) { unavailable("internal: the instances of a template"); break; }
+        const SegV &M = sv[(size_t)members[t][0]];
+        for (int si : members[t]) {
+            if (si < 0) { unavailable("internal: the instances of a template"); break; }
+            const SegV &S = sv[(size_t)si]; bool eq = S.ents.size() == M.ents.size() && S.imps.size() == M.imps.size();
+            for (size_t k = 0; eq && k < S.ents.size(); k++) eq = same(S.ents[k], M.ents[k]);
+            if (!eq) { unavailable("the instances of one template (isomorphic scope instances) differ in the equalities recorded in them (template " + std::to_string(t) + ")"); break; }
+            V.vimp0.push_back((uint32_t)V.vimps.size()); V.site0.push_back((uint32_t)V.sites.size());
+            for (const VEntD &d : S.ents) V.sites.push_back(d.site);
+            for (const ImpD &m : S.imps) { const SegInfo &Pn = segs[(size_t)m.tmpl]; V.vimps.push_back(ImpD{(uint32_t)Pn.tmpl, Pn.inst, m.slot}); }
+            for (const VEntD &d : S.ents) {
+                (d.kind == VK_EQUAL ? V.n_eq_lanes : V.n_range)++;
+                // an imported value lies within its producer's slots, by the width the entry reads it with
+                for (uint32_t r : {d.a, d.kind == VK_EQUAL ? d.b : d.a}) if (ref_kind(r) == RK_IMPORT) {
+                    const ImpD &m = S.imps[ref_idx(r)]; const SegInfo &Pn = segs[(size_t)m.tmpl];
+                    if ((uint64_t)m.slot + vref_words(r) > P.tmpls[(size_t)Pn.tmpl].nslots) unavailable("internal: an imported value beyond its producer's slots");
+                }
+            }
+        }
+        V.ents.insert(V.ents.end(), M.ents.begin(), M.ents.end()); V.nvimp.push_back((uint32_t)M.imps.size());
+        if (!M.ents.empty()) V.n_tmpl++;
+    }
+    V.ent0.push_back((uint32_t)V.ents.size());
+    if (!V.why.empty()) { V.ents.clear(); V.ent0.clear(); V.vimps.clear(); V.vimp0.clear(); V.nvimp.clear(); V.sites.clear(); V.site0.clear(); V.n_eq_lanes = V.n_range = V.n_tmpl = 0; }
+    return V;
 }
 
 bool direct_cell_map(const LoweredPlan &P, const TemplateTable &tt, uint64_t ncells, std::vector<uint64_t> &direct, uint64_t &n_direct, std::string &err) {

@@ -7,6 +7,7 @@
 #include <unordered_map>
 #include <vector>
 #include "tapefmt.h"
+#include "verdictfmt.h"
 #include "trace.h"
 
 namespace h2w {
@@ -40,6 +41,7 @@ struct Lowered {
     std::vector<SegInfo> segs; std::vector<ValInfo> vals; std::unordered_map<uint64_t, uint32_t> val_of;      // val_of: cell offset of a handle -> value
     std::vector<uint64_t> pool64; std::map<uint64_t, uint32_t> pool64_of; std::vector<fr_t> poolfr;
     std::vector<uint64_t> meta; uint64_t nrec = 0; std::string err;
+    std::vector<int> op_seg;      // the segment every trace op lies in (a scope op: the segment current behind it)
 };
 constexpr int MAX_PERM_IO = GLPERM_IO;
 enum { CANON_GL = 0, CANON_BN = 1, CANON_BN_ZERO = 2 };      // CANON_BN_ZERO: the PoseidonBN254 tape recorded on a fresh context (the load_zero cell inside its first mix)
@@ -85,5 +87,20 @@ bool direct_cell_map(const LoweredPlan &P, const TemplateTable &tt, uint64_t nce
 // ... and the map the ranged kernel works from when the fused PoseidonBN254 permutations' cells leave their own kernel converted: `direct` without
 // [BnpD::cell0, + perm_cells) of every listed permutation.  false: err - one of those cells is not a direct cell.
 bool ranged_cell_map(const LoweredPlan &P, uint64_t perm_cells, const std::vector<uint64_t> &direct, std::vector<uint64_t> &ranged, std::string &err);
+
+// ---- the verdict stage (h2w_trace_verdict_batch): runs behind group_templates, reads what the stages above left and changes none of it.
+// The recorded assert_equal calls (Trace::asserts) and the level-1 range checks of the tape as a per-template table of VEntD (verdictfmt.h); every
+// side of an equality becomes an old-style ref through the lowering's own map from a handle's cell to (segment, slot, width) or a literal.  A value
+// of an enclosing segment goes through the verdict's OWN import table (vimps: per instance, nvimp[template] entries from vimp0[instance]) - the
+// witness plan's import tables stay what they are.  why non-empty: the plan has no verdict (an operand that is no op's result handle, an operand
+// interior to a fused stretch, instances of a template whose tables differ in more than the site words) - the plan itself is built as before.
+struct VerdictTables {
+    std::string why;
+    std::vector<VEntD> ents; std::vector<uint32_t> ent0;                                   // template t's entries: [ent0[t], ent0[t + 1])
+    std::vector<ImpD> vimps; std::vector<uint32_t> vimp0, nvimp;                           // vimp0: per instance (InstD order); nvimp: per template
+    std::vector<uint32_t> sites, site0;                                                    // the site word of every (instance, entry): instance i's from site0[i]
+    uint64_t n_asserts = 0, n_eq_lanes = 0, n_range = 0, n_tmpl = 0;                       // recorded equalities; equalities over all instances; range sites over all instances; templates with entries
+};
+VerdictTables verdict_tables(const Trace *tr, const Lowered &LW, const Fusable &F, const LoweredPlan &P);
 
 }  // namespace h2w

@@ -252,6 +252,36 @@ int h2w_plan_trace_info(const h2w_plan *, uint64_t out[6]);
 int h2w_plan_trace_info_bn(const h2w_plan *, uint64_t out[3]);
 int h2w_plan_trace_op_counts(const h2w_plan *, uint64_t *out, size_t n_out);
 int h2w_plan_trace_timing(h2w_plan *, float *ms, uint32_t cap);
+/* ---- per-proof verdicts of a TRACED plan (3b below is the compiled plan's call; h2w_fri_verdict_batch refuses a traced plan).
+ * While a context records a trace, every h2w_constrain_equal(a, b) - and the assert_equal inside h2w_gl_div - is kept beside the tape: its two handles'
+ * cells, its place, and the SITE WORD in force.  h2w_trace_site(ctx, flag_bits) sets that word (0 at h2w_ctx_trace_begin; a no-op returning 0 on a
+ * context that is not tracing): call it where a protocol check begins, with the bits its failing equalities shall raise - h2w_chip_verify_stark calls it
+ * with the H2W_VERDICT_* bit of every Merkle / fold / final-polynomial site and with 0 where a query round begins.  The word also goes with every
+ * h2w_range_check / h2w_check_less_than_safe recorded after it (a range site).  Recording changes nothing of the tape or of the plan lowered from it.
+ * h2w_plan_from_trace lowers the recorded checks to a per-template table once the witness plan is final; where it cannot - a handle that is no traced
+ * call's result, a value interior to a fused permutation (no longer in the value store), instances of one template whose checks differ - the plan is
+ * built as before and only its verdict is unavailable; the reason is h2w_last_error() after the two calls below.
+ * h2w_trace_verdict_batch runs the replay's interpreter on quiet lanes (values into the workspace's value store; no record, no cell, no list entry; no
+ * emission kernel, no expansion) and one kernel that compares both sides of every recorded equality, as 256-bit values zero-extended from their widths:
+ *   flags        OR of the site words of the failing equalities and range sites, | H2W_TRACE_VERDICT_RANGE for a failing range site (a value beyond its
+ *                range_bits; for check_less_than_safe a value >= the bound)
+ *   n_failed     failing equalities, + 1 for a range site whose value does not fit the ceil(bits / lookup_bits) limbs RangeChip::range_check decomposes
+ *                it into (more than one limb: the copy constraint on the limb sum, as 3b counts it for the PoW response); check_less_than_safe(a, b) is
+ *                range_check(a, n limbs) and range_check(a + 2^(n lookup_bits) - b, n limbs): a >= b breaks the second limb sum (+ 1 with n > 1)
+ *   first_query  the lowest shard unit (the depth-1 parallel instance an equality's scope is or lies in) that owns a failing equality; 0xFFFFFFFF: none
+ *                fails, or only the root's, or the plan has no units.  Range sites do not count here
+ *   status       the word h2w_plan_status reports after a witness call of the plan on the same proofs (1, 2: the hint ops; 4: a proof word outside its field)
+ * A proof is accepted iff flags == 0 && n_failed == 0 && status == 0.  On a trace of h2w_chip_verify_stark the first three words are those of 3b's call
+ * on the compiled plan of the shape (the hint checks in the prologue, which 3b's kernels do not judge, can only fail beside status 1 / 2).
+ * workspace_dev: h2w_plan_workspace_bytes(n_proofs) bytes, the witness call's (the value store and the status words live there; whoever runs next on it
+ * re-zeroes its status words).  Stream-ordered; the first call of a batch size uploads a lane table (one device synchronisation, as the first sharded
+ * call); the plan's device is current for the call only; n_proofs == 0: 0; whole proofs only; nothing but the workspace and verdict_dev is written.
+ * -1 before any device work, the reason in h2w_last_error(): a null plan or buffer, a plan of h2w_plan_compile, a plan whose verdict is unavailable,
+ * no device, more than 65,535 proofs or 2^31 lanes.
+ * h2w_plan_trace_verdict_info: out = {equalities recorded, equalities in the device tables summed over instances, range sites, 1 if the verdict call
+ * is available (else 0, the reason in h2w_last_error()), templates with a table, 0}.  No device needed.  -1 for a plan of h2w_plan_compile. */
+int h2w_trace_site(h2w_ctx *, uint32_t flag_bits);
+int h2w_plan_trace_verdict_info(const h2w_plan *, uint64_t out[6]);
 
 /* ------------------------------------------------------------------ advice hand-off (eager contexts) */
 /* Expands all pending records on the GPU; *dev_ptr receives a device pointer to num_cells*32 bytes
@@ -492,7 +522,7 @@ uint64_t h2w_plan_num_chain_cells(const h2w_plan *);
  * A proof is accepted iff flags == 0 && status == 0.  Without permutation Zs (n_perm_z == 0) initial oracle 1 is the quotient tree.
  * Stream-ordered, no synchronisation; whole proofs only (no sharded form); the call's workspace (challenge blocks) is a stream-ordered allocation
  * inside it; the result depends on no h2w_plan_configure option; the plan's device is current for the duration of the call only.
- * verdict_dev: [n_proofs], device.  n_proofs == 0: 0.  A plan of h2w_plan_from_trace: -1.  Without a device: -1 ("no HIP device"). */
+ * verdict_dev: [n_proofs], device.  n_proofs == 0: 0.  A plan of h2w_plan_from_trace: -1 (its call is h2w_trace_verdict_batch, 2d).  Without a device: -1 ("no HIP device"). */
 typedef struct { uint32_t flags, n_failed, first_query, status; } h2w_verdict_t;
 #define H2W_VERDICT_POW              1   /* pow_response does not fit 64 - pow_bits bits (fri/mod.rs:130-145) */
 #define H2W_VERDICT_MERKLE_TRACE     2   /* a root != cap entry, per tree (merkle/mod.rs:57-78) */
@@ -502,6 +532,9 @@ typedef struct { uint32_t flags, n_failed, first_query, status; } h2w_verdict_t;
 #define H2W_VERDICT_FOLD            32   /* fri/mod.rs:403-438, the consistency check of a fold step */
 #define H2W_VERDICT_FINAL           64   /* final-polynomial evaluation */
 int h2w_fri_verdict_batch(h2w_plan *, const uint64_t *proofs_dev, uint64_t n_proofs, h2w_verdict_t *verdict_dev, void *stream);
+#define H2W_TRACE_VERDICT_RANGE 1u   /* = H2W_VERDICT_POW: set by a failing range site, beside the site word in force at it (2d) */
+int h2w_trace_verdict_batch(h2w_plan *, const uint64_t *proofs_dev, uint64_t n_proofs,
+                            h2w_verdict_t *verdict_dev, void *workspace_dev, void *stream);      /* 2d: the verdict call of a traced plan */
 /* The same verdict words from other kernels and streams: `flags` = one H2W_VERDICT_FORM_*, optionally | H2W_VERDICT_FORK.  Every accepted value gives the
  * words h2w_fri_verdict_batch gives; flags == H2W_VERDICT_FORM_QUAD enqueues exactly what it enqueues.
  *   FORM_ROW   PoseidonBN254 caps only: one wavefront per Merkle path (the four rows of the wavefront hold the four state elements) instead of four lanes -
