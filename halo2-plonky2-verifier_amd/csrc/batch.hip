@@ -20,6 +20,7 @@
 #include <string>
 #include <cstring>
 #include "plan.h"
+#include "traceplan.h"
 
 namespace h2w {
 
@@ -177,12 +178,6 @@ extern "C" __global__ void k_columns_fixup(ulonglong2 *cols, const uint64_t *len
 }
 
 namespace h2w {
-// a traced plan (replay.hip)
-uint64_t traced_workspace_bytes(const h2w_plan *p, uint64_t n);
-uint64_t traced_status_offset(const h2w_plan *p, uint64_t n, bool flags);
-int traced_run(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void *advice_dev, void *workspace_dev, void *stream_, ColMap cm, uint64_t cell_stride, const ShardSpec &sh);
-const char *traced_shard_refusal(const h2w_plan *p);      // null: the traced plan shards by its depth-1 parallel instances
-
 static uint64_t own_count(uint64_t total, int rank, int world) { return total > (uint64_t)rank ? (total - (uint64_t)rank + (uint64_t)world - 1) / (uint64_t)world : 0; }
 static uint32_t unit_slot_of(const h2w_plan *p) { return (uint32_t)(p->st.q_nunit[0] > p->st.q_nunit[1] ? p->st.q_nunit[0] : p->st.q_nunit[1]); }
 static uint64_t shard_q_slot(const h2w_plan *p) { return p->st.q_ncell[0] > p->st.q_ncell[1] ? p->st.q_ncell[0] : p->st.q_ncell[1]; }      // a query block's slot in the packed layout (ShardMap)
@@ -240,7 +235,7 @@ static int run_batch(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs,
     if (p->device < 0) { set_error("h2w_fri_witness_batch: no HIP device — the hot path only runs on the GPU (no CPU fallback)"); return -1; }
     if (!proofs_dev || !advice_dev || !workspace_dev) { set_error("h2w_fri_witness_batch: null buffer"); return -1; }
     if (n_proofs == 0) return 0;
-    if (p->traced) {      // a recorded run (replay.hip): the flat stream, the FlexGate columns, or this rank's (proof, query) units
+    if (p->traced) {      // a recorded run (traceplan.h; replay.hip traced_run): the flat stream, the FlexGate columns, or this rank's (proof, query) units
         if (emit_stream_ != stream_) { set_error("h2w_fri_witness_batch: a traced plan runs on one stream"); return -1; }
         return traced_run(p, proofs_dev, n_proofs, advice_dev, workspace_dev, stream_, cm, cell_stride, sh);
     }
@@ -447,9 +442,8 @@ uint64_t h2w_plan_shard_cells(const h2w_plan *p, uint64_t n_proofs, int rank, in
 int h2w_plan_shard_block(const h2w_plan *p, int rank, int world, uint64_t proof, int query, uint64_t *local_cell, uint64_t *n_cells, uint64_t *global_cell) {
     if (!p || world < 1 || rank < 0 || rank >= world || query >= p->shape.num_queries) { set_error("h2w_plan_shard_block: bad argument"); return -1; }
     if (const char *why = traced_shard_refusal(p)) { set_error(std::string("h2w_plan_shard_block: ") + why); return -1; }
-    const uint64_t W = (uint64_t)world, r = (uint64_t)rank, nq = (uint64_t)p->shape.num_queries, u0 = proof * nq;
-    const bool owned = query < 0 ? proof % W == r : (u0 + (uint64_t)query) % W == r;
-    if (!owned) return 1;
+    const uint64_t W = (uint64_t)world, r = (uint64_t)rank, nq = (uint64_t)p->shape.num_queries;
+    if (!shard_owns(W, r, nq, proof, query)) return 1;
     const uint64_t local = packed_block_start(W, r, nq, p->st.pro_ncell, shard_q_slot(p), proof, query);
     uint64_t n = p->st.pro_ncell, g = 0;
     if (query >= 0) { n = p->st.q_ncell[query == 0 ? 0 : 1]; g = strand_q_cell(p->st, query); }
@@ -546,11 +540,7 @@ int h2w_plan_configure(h2w_plan *p, int option, int value) {
             MontForm K; montform_init(K, p->tt.rb);
             DevBuf<uint64_t> bits, ranged; DevBuf<MontForm> d; DevBuf<fr_t> tabm;
             if (bits.upload(p->direct_bits) != 0 || d.upload(&K, 1) != 0) return -1;      // (nothing kept: the next call starts over)
-            if (p->traced && p->d_bn_tab.get()) {      // a traced plan with fused PoseidonBN254 permutations: the emitter's Montgomery cell table, the ranged kernel's map
-                std::vector<fr_t> tab(BK_ALL); bn_table_build(p->h_consts, p->P, tab.data());
-                for (int i = 0; i < BK_T; i++) tab[(size_t)i] = fr_mont_mul(tab[(size_t)i], mont_k(), p->P.ninv);
-                if (tabm.upload(tab) != 0 || ranged.upload(p->ranged_bits) != 0) return -1;
-            }
+            if (traced_mont_tables(p, tabm, ranged) != 0) return -1;      // (a traced plan with fused PoseidonBN254 permutations: the emitter's Montgomery cell table, the ranged kernel's map)
             p->d_direct_bits = std::move(bits); p->d_mont = std::move(d); p->d_bn_tab_mont = std::move(tabm); p->d_ranged_bits = std::move(ranged);
         }
         p->output_form = value; return 0;

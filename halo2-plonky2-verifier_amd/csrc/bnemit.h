@@ -5,7 +5,7 @@
 // works from a dense list of items: every (proof, entry) pair, or - sharded - `items`, the pairs of this rank's blocks (the others' entries were never
 // written).  The quads of a wavefront cooperate (cross-lane moves over the whole wavefront): none leaves early, tail quads redo the last item and write
 // identical bytes.  WHERE a permutation's cells go is static (BnpD, checked against the entry: status 97 if the interpreter listed another cell); only
-// the state comes from the list.  LDS: the tables (34.7 KB) + 10 KB of value slots per wavefront, as k_merkle_bn_fused: two blocks per CU.
+// the state comes from the list.  Both are launched by replay.hip traced_run; the plan's tables they read are traceplan.cpp's uploads.  LDS: the tables (34.7 KB) + 10 KB of value slots per wavefront, as k_merkle_bn_fused: two blocks per CU.
 #pragma once
 #include "plan.h"
 #include "tracelower.h"

@@ -2,7 +2,7 @@
 // launches it when the plan's output form is H2W_FORM_MONTGOMERY).  Each fused permutation's 4,032 cells are stored once, already as v * 2^256 mod r:
 // the emitter is coop.h's one-pass form in its QUAD_FUSED_MONT mode - the flush code, the addresses (flat, columns, sharded, packed), the store
 // pattern (64 contiguous bytes per quad and store) and the status-97 check are the canonical kernel's.  What differs is what the flushes read: the
-// canonical half of the LDS table holds the plan's cell table in Montgomery form (host-built, uploaded when the form is first selected), and every value
+// canonical half of the LDS table holds the plan's cell table in Montgomery form (host-built, uploaded when the form is first selected: traceplan.cpp traced_mont_tables), and every value
 // slot is filled with fr_mont_mul(v, mont_k, ninv) - the product h2w_advice_to_montgomery and k_direct_to_montgomery apply, hence the same bytes.
 // LDS: the tables (34.7 KB) + the canonical round constants the adds take (2.8 KB) + 10 KB of value slots per wavefront = 76.6 KB: two blocks per CU.
 // A unit of its own: the LDS variables of a unit are laid out together, and replay.hip's interpreter keeps the layout - and the code - it has.

@@ -1,5 +1,5 @@
 // handletabs.h — the derived tables every handle of the value backend needs, built and uploaded in ONE place (host code): the constructors of
-// a compiled plan (plancompile.cpp), a traced plan (replay.hip) and the batched chip ops (chipbatch.hip, chiphash.hip) call these.
+// a compiled plan (plancompile.cpp), a traced plan (traceplan.cpp) and the batched chip ops (chipbatch.hip, chiphash.hip) call these.
 #pragma once
 #include "common.h"
 #include "valbackend.h"

@@ -1,4 +1,4 @@
-// plan.h — the plan handle of API level 3 (include/h2w.h): a compiled shape (plancompile.cpp h2w_plan_compile) or a traced run (replay.hip h2w_plan_from_trace).
+// plan.h — the plan handle of API level 3 (include/h2w.h): a compiled shape (plancompile.cpp h2w_plan_compile) or a traced run (traceplan.cpp h2w_plan_from_trace).
 // Every device table, event and side stream of the handle is an owner of devbuf.h: h2w_plan_free sets the device and deletes the handle.
 #pragma once
 #include "common.h"
@@ -10,7 +10,7 @@ namespace h2w {
 struct TracedPlan;
 struct ShardSpec { int rank = 0, world = 1, compact = 0; };
 }
-using namespace h2w;      // (included by the plan's units only - plancompile.cpp, batch.hip, advicetools.hip, replay.hip -, which live in that namespace's vocabulary)
+using namespace h2w;      // (included by the plan's units only - plancompile.cpp, batch.hip, advicetools.hip, traceplan.cpp, replay.hip -, which live in that namespace's vocabulary)
 struct h2w_plan {
     h2w_shape_t shape; int device;
     TemplateTable tt; DeviceTables dt; StrandTable st; FrParams P;
@@ -47,7 +47,7 @@ struct h2w_plan {
     std::vector<uint64_t> ranged_bits; DevBuf<uint64_t> d_ranged_bits; DevBuf<fr_t> d_bn_tab_mont; bool trace_bn_ranged = false;
     bool fork_chains = true;         // of their own batch (they share only the prologue): one side stream per caller stream seen (created on demand)
     uint64_t n_batches = 0; bool ev_recorded = false;
-    h2w::TracedPlan *traced = nullptr;      // set: the plan replays a recorded tape (replay.hip); the strand tables above are unused
+    h2w::TracedPlan *traced = nullptr;      // set: the plan replays a recorded tape (traceplan.h); the strand tables above are unused
     explicit h2w_plan(int L) : tt(L) {}
 };
 extern "C" int h2w_plan_metadata(h2w_plan *pl);      // plancompile.cpp: the keygen-metadata replay, once per plan (the selector / lookup queries and advicetools.hip call it)

@@ -11,6 +11,7 @@
 #include <string>
 #include <cstring>
 #include "plan.h"
+#include "traceplan.h"
 
 namespace h2w {
 
@@ -66,7 +67,6 @@ static ValCfg host_replay_cfg(const h2w_shape_t &s, const FrParams &P, const std
     ValCfg cfg{}; cfg.proof = proof; cfg.mode = s.hash_mode; cfg.L = s.lookup_bits; cfg.P = P; cfg.inv_pos = inv.data(); cfg.inv_neg = inv.data() + INV_TAB;
     return cfg;
 }
-void traced_free(h2w_plan *p);      // replay.hip
 PlanEqualities &plan_equalities(h2w_plan *p) { return p->eqs; }
 bool plan_traced(const h2w_plan *p) { return p->traced != nullptr; }
 const h2w_shape_t &plan_shape(const h2w_plan *p) { return p->shape; }

@@ -15,29 +15,24 @@
 //              global memory alone an op cost 2-7 us.  The last RING_K value slots of a lane live in LDS as well (a different counter): the lowering
 //              knows the distance from every operand to its producer (99.8 % of the prologue's operands, 93 % of the glue's, all of a PoseidonBN254
 //              path's are within 256 slots) and addresses those through the ring; the global store stays (write-through: far operands, imports).
-// This file is the device side and what launches it: the interpreter k_replay, the two emission kernels of the fused permutations, the plan's device
-// tables and their upload, the entry points.  The tape format (ops, operand words, the checker every tape passes before it is uploaded) is tapefmt.h;
-// the lowering (segments, templates, fused stretches, shard units: host code) is tracelower.h / tracelower.cpp.
+// This file is the device side and what launches it, and nothing else: the interpreter k_replay, the two emission kernels of the fused permutations,
+// the witness call (traced_run) and the verdict call (h2w_trace_verdict_batch).  Every function here is a kernel or enqueues one: the unit's LDS
+// variables are laid out together and the interpreter's code is held to the instruction, so what need not be compiled with it is not.  The plan
+// itself - h2w_plan_from_trace, TracedPlan, the workspace layout, the lane tables, the information entry points - is traceplan.h / traceplan.cpp; the
+// tape format (ops, operand words, the checker every tape passes before it is uploaded) is tapefmt.h; the lowering (segments, templates, fused
+// stretches, shard units: host code) is tracelower.h / tracelower.cpp.
 #define H2W_FLATTEN_CHIPS 1      // the interpreter's ops are the value backend's, inlined: out of line every op is a function call, and a call waits for the stores in flight (glue.hip)
 #include <hip/hip_runtime.h>
-#include <unordered_map>
 #include <vector>
 #include <string>
 #include <cstring>
 #include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-#include "plan.h"
-#include "tracelower.h"
-#include "keygen.h"
+#include "traceplan.h"
 #include "glpval.h"
 #include "bnpval.h"
 #include "bnemit.h"
-#include "traceverdict.h"
 
-struct h2w_ctx;
 namespace h2w {
-Trace *ctx_trace(h2w_ctx *); int ctx_lookup_bits(const h2w_ctx *); uint64_t ctx_num_cells(const h2w_ctx *); const MetaRecorder *ctx_meta(const h2w_ctx *);      // eager.cpp
 static_assert(GLPERM_IO == (uint32_t)SPONGE_WIDTH && BNPERM_IO == (uint32_t)BN_WIDTH, "tapefmt.h states the permutations' widths on its own");
 
 struct ReplayArgs {
@@ -48,7 +43,7 @@ struct ReplayArgs {
     const TmplD *tm; const uint64_t *prefix;      // per template (device tables of the plan): its description; the u64 elements per proof of the value stores before it
     uint32_t blk0[MAX_TMPL + 1];                  // first block of each template among the blocks of this launch (templates of `depth` only)
     uint32_t *lflag;                              // per proof: 4 when a proof word is outside its field (h2w_plan_status)
-    // (proof, query) sharding (ShardSpec): lanes != null lists the lanes of this rank, template t's at [lane0[t], lane0[t + 1]) (lane_table)
+    // (proof, query) sharding (ShardSpec): lanes != null lists the lanes of this rank, template t's at [lane0[t], lane0[t + 1]) (lanetable.h)
     const uint32_t *lanes; uint32_t lane0[MAX_TMPL + 1];
     uint32_t sh_world, sh_rank, sh_compact, nq; uint64_t pro_ncell, q_slot;      // the packed layout (shardmap.h)
     // fused permutations (DOP_GLPERM): the Goldilocks block of the tables the lowering verified them on; the list [nproofs][nglp][GLP_LIST_WORDS]
@@ -61,27 +56,6 @@ template <bool BN> struct ReplayArgsSel { typedef ReplayArgs type; };
 struct ReplayArgsBN : ReplayArgs { const fr_t *bnk; uint64_t *blist; const uint32_t *bnp0; uint32_t nbnp; };
 template <> struct ReplayArgsSel<true> { typedef ReplayArgsBN type; };
 template <bool BN> using ReplayArgsT = typename ReplayArgsSel<BN>::type;
-
-struct TracedPlan {
-    std::vector<TmplD> tmpls; uint64_t total_slot_lanes = 0;      // sum over templates of nslots * ninst: u64 elements of the value store per proof
-    DevBuf<TmplD> d_tm; DevBuf<uint64_t> d_prefix; uint32_t npool64 = 0, npoolfr = 0;
-    DevBuf<uint32_t> d_tape; DevBuf<InstD> d_insts; DevBuf<ImpD> d_imps; DevBuf<uint32_t> d_inputs; DevBuf<uint64_t> d_pool64; DevBuf<fr_t> d_poolfr;
-    uint64_t n_ops = 0, n_segments = 0;
-    std::vector<uint64_t> op_counts;      // tape_op_counts over the templates' tapes (h2w_plan_trace_op_counts)
-    // fused Goldilocks-Poseidon permutations: per proof nglp list entries (entry e belongs to shard unit h_glp_unit[e], NO_SLOT: the root's block)
-    uint32_t nglp = 0; uint64_t n_candidates = 0; std::vector<uint32_t> h_glp_unit; DevBuf<uint32_t> d_glp_unit;
-    // fused PoseidonBN254 permutations: per proof nbnp list entries; items: the (proof, entry) pairs of this rank's blocks (sharded calls, beside the lane table)
-    bool bn_flag = false; uint32_t nbnp = 0; uint64_t n_bn_left = 0; std::vector<BnpD> h_bnp; DevBuf<BnpD> d_bnp; std::vector<uint32_t> h_bnp0; DevBuf<uint32_t> d_bnp0, d_bn_items; uint64_t n_bn_items = 0;
-    DevEvent tev[17]; int tev_used = 0; bool timing = false;      // h2w_plan_trace_timing: around every kernel of the last call (12 depths at most, three kernels, the expansion)
-    // sharding: the depth-1 instances are the units (query q = the q-th in tape order); why_unshardable empty: they tile the stream behind the root's block
-    std::string why_unshardable; std::vector<uint32_t> h_unit;      // h_unit: the unit of every instance (InstD order)
-    std::vector<uint32_t> h_lanes, lane0; DevBuf<uint32_t> d_lanes; uint64_t lanes_n = 0; int lanes_rank = -1, lanes_world = 0;      // the lane table of the last (n, rank, world)
-    // the verdict (h2w_trace_verdict_batch): the lowered tables (tracelower.h verdict_tables; why_no_verdict non-empty: unavailable), their device copies,
-    // and the QUIET lane table of the last n - every (proof, instance) of every template with bit 31 set; members of its own, so that it neither passes
-    // for a sharded call's table nor evicts it
-    VerdictTables vt; std::string why_no_verdict; DevBuf<VEntD> d_vents; DevBuf<VInstD> d_vinst; DevBuf<VImpD> d_vimps; DevBuf<uint64_t> d_tinfo; DevBuf<uint32_t> d_vsites;
-    std::vector<uint32_t> qlane0; DevBuf<uint32_t> d_qlanes; uint64_t qlanes_n = 0;
-};
 
 // ------------------------------------------------------------------------------------------------------------------- device
 // (its own sink type: the flattened value backend of this unit is instantiated nowhere else - field.h HNI)
@@ -346,76 +320,30 @@ template <bool COLS> __global__ __launch_bounds__(QUAD_BLOCK) H2W_QUAD_ATTR void
     sink.template bn_emit_cells<false>(st, cfg, zc);
 }
 
-}  // namespace h2w
-
-using namespace h2w;
-
-namespace h2w {
-uint64_t traced_workspace_bytes(const h2w_plan *p, uint64_t n);
-int traced_run(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void *advice_dev, void *workspace_dev, void *stream_, ColMap cm, uint64_t cell_stride, const ShardSpec &sh);
-void traced_free(h2w_plan *p);
-const char *traced_shard_refusal(const h2w_plan *p) { return p->traced && !p->traced->why_unshardable.empty() ? p->traced->why_unshardable.c_str() : nullptr; }
-struct TracedWs { size_t recs, status, lflag, ctr, vals, glist, blist, total; };
-static size_t al(size_t x) { return (x + 255) / 256 * 256; }
-static TracedWs traced_ws(const h2w_plan *p, uint64_t n) {
-    TracedWs w; size_t o = 0;
-    w.recs = o; o += al((size_t)n * p->nrec * sizeof(rec_t));
-    w.status = o; o += al((size_t)n * 4); w.lflag = o; o += al((size_t)n * 4); w.ctr = o; o += al((size_t)n * 4);
-    w.vals = o; o += al((size_t)n * p->traced->total_slot_lanes * 8);
-    w.glist = o; o += al((size_t)n * p->traced->nglp * GLP_LIST_WORDS * 8);      // the fused permutations' list (none: the layout of an unfused plan)
-    w.blist = o; o += al((size_t)n * p->traced->nbnp * BNP_LIST_WORDS * 8);      // the fused PoseidonBN254 permutations' list (none: nothing)
-    w.total = o; return w;
+// ------------------------------------------------------------------------------------------------------------------- launches
+// the plan's part of k_replay's arguments; what belongs to the call - recs, out, the lane table, the sharding - is zero and the caller's to set
+static ReplayArgs replay_args(const h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, char *ws, const TracedWs &wl) {
+    const TracedPlan *t = p->traced;
+    ReplayArgs R; memset(&R, 0, sizeof(R));
+    R.tape = t->d_tape.get(); R.insts = t->d_insts.get(); R.imps = t->d_imps.get(); R.inputs = t->d_inputs.get(); R.pool64 = t->d_pool64.get(); R.poolfr = t->d_poolfr.get();
+    R.proofs = proofs_dev; R.proof_words = p->pl.total; R.recs = (rec_t *)(ws + wl.recs); R.rec_stride = p->nrec;
+    R.vals = (uint64_t *)(ws + wl.vals); R.status = (uint32_t *)(ws + wl.status); R.ncells = p->d_ncells.get(); R.inv_pos = p->d_inv.get(); R.inv_neg = p->d_inv.get() + INV_TAB; R.P = p->P; R.L = p->shape.lookup_bits;
+    R.nproofs = (uint32_t)n_proofs; R.lflag = (uint32_t *)(ws + wl.lflag);
+    R.glk = reinterpret_cast<const uint64_t *>(p->d_consts.get()); R.glist = (uint64_t *)(ws + wl.glist); R.nglp = t->nglp;
+    R.ntmpl = (uint32_t)t->tmpls.size(); R.tm = t->d_tm.get(); R.prefix = t->d_prefix.get(); R.npool64 = t->npool64; R.npoolfr = t->npoolfr;
+    return R;
 }
-uint64_t traced_workspace_bytes(const h2w_plan *p, uint64_t n) { return traced_ws(p, n).total; }
-uint64_t traced_status_offset(const h2w_plan *p, uint64_t n, bool flags) { const TracedWs w = traced_ws(p, n); return flags ? w.lflag : w.status; }
-void traced_free(h2w_plan *p) { delete p->traced; p->traced = nullptr; }      // (its tables and events are owners: devbuf.h)
-// The lanes a rank launches (sharded calls), template by template: the root lane of every proof - those of the proofs the rank owns first, then, from
-// the next wavefront on, the others marked with bit 31 (they compute the values the units import, and store nothing else) -, and of every deeper
-// template only the (proof, instance) pairs whose unit (proof * nq + q) % world == rank (h2w_plan_shard_block, distributed.py unit_owner).
-static int lane_table(h2w_plan *p, uint64_t n, const ShardSpec &sh) {
-    TracedPlan *t = p->traced;
-    if (t->d_lanes.get() && t->lanes_n == n && t->lanes_rank == sh.rank && t->lanes_world == sh.world) return 0;
-    const uint64_t W = (uint64_t)sh.world, r = (uint64_t)sh.rank, nq = (uint64_t)p->shape.num_queries;
-    std::vector<uint32_t> &L = t->h_lanes; L.clear(); t->lane0.assign(t->tmpls.size() + 1, 0);
-    for (size_t i = 0; i < t->tmpls.size(); i++) {
-        const TmplD &T = t->tmpls[i]; t->lane0[i] = (uint32_t)L.size();
-        if (n * T.ninst >= 0x80000000ull) { set_error("h2w_fri_witness_batch_shard: too many (proof, instance) lanes in one call"); return -1; }
-        if (T.depth == 0) {
-            for (uint64_t pr = r; pr < n; pr += W) L.push_back((uint32_t)pr);
-            while ((L.size() - t->lane0[i]) % 64) L.push_back(NO_SLOT);
-            for (uint64_t pr = 0; pr < n; pr++) if (pr % W != r) L.push_back((uint32_t)pr | 0x80000000u);
-        } else
-            for (uint64_t pr = 0; pr < n; pr++)
-                for (uint32_t k = 0; k < T.ninst; k++) if ((pr * nq + t->h_unit[T.inst0 + k]) % W == r) L.push_back((uint32_t)(pr * T.ninst + k));
-    }
-    t->lane0[t->tmpls.size()] = (uint32_t)L.size();
-    // the listed PoseidonBN254 permutations of this rank's blocks, dense: (proof, entry) as proof * nbnp + entry - the root's of the proofs it owns, a
-    // unit's where it owns the unit (the lanes above that run with emit set: the entries that get written)
-    std::vector<uint32_t> items;
-    if (t->nbnp) {
-        if (n * t->nbnp >= 0xffffffffull) { set_error("h2w_fri_witness_batch_shard: too many fused permutations in one call"); return -1; }
-        for (uint64_t pr = 0; pr < n; pr++)
-            for (uint32_t e = 0; e < t->nbnp; e++) {
-                const uint32_t u = t->h_bnp[e].unit;
-                if ((u == NO_SLOT ? pr : pr * nq + u) % W == r) items.push_back((uint32_t)(pr * t->nbnp + e));
-            }
-    }
-    H2W_HIP(hipDeviceSynchronize());      // a previous call may still read the old table (plans are single-threaded handles, include/h2w.h)
-    t->d_lanes.reset(); t->d_bn_items.reset(); t->n_bn_items = items.size();      // (a failed upload leaves no lane table: the next call builds it again)
-    if ((t->nbnp && t->d_bn_items.upload(items) != 0) || t->d_lanes.upload(L) != 0) return -1;
-    t->lanes_n = n; t->lanes_rank = sh.rank; t->lanes_world = sh.world;
-    return 0;
-}
-// The k_replay launches of a call, depth by depth (a segment reads its ancestors' values; the templates of one depth share a launch).  lane0: the lane
-// table's template offsets when R.lanes is set (a sharded call's, the verdict call's quiet table), else null: every (proof, instance) in place.
-static void replay_launches(h2w_plan *p, ReplayArgs &R, const std::vector<uint32_t> *lane0, uint64_t n_proofs, uint64_t *blist, hipStream_t stream) {
+static void use_lanes(ReplayArgs &R, const LaneTable &T) { R.lanes = T.d_lanes.get(); for (size_t i = 0; i < T.lane0.size(); i++) R.lane0[i] = T.lane0[i]; }
+// The k_replay launches of a call, depth by depth (a segment reads its ancestors' values; the templates of one depth share a launch).  lanes: the
+// table R.lanes is of (a sharded call's, the verdict call's quiet one), else null: every (proof, instance) in place.
+static void replay_launches(h2w_plan *p, ReplayArgs &R, const LaneTable *lanes, uint64_t n_proofs, uint64_t *blist, hipStream_t stream) {
     TracedPlan *t = p->traced;
     uint32_t maxd = 0; for (const TmplD &T : t->tmpls) if (T.depth > maxd) maxd = T.depth;
     for (uint32_t d = 0; d <= maxd; d++) {
         uint32_t nb = 0;
         for (size_t i = 0; i < t->tmpls.size(); i++) {
             R.blk0[i] = nb;
-            if (t->tmpls[i].depth == d) nb += (uint32_t)(((lane0 ? (*lane0)[i + 1] - (*lane0)[i] : n_proofs * t->tmpls[i].ninst) + 63) / 64);
+            if (t->tmpls[i].depth == d) nb += (uint32_t)(((lanes ? lanes->lane0[i + 1] - lanes->lane0[i] : n_proofs * t->tmpls[i].ninst) + 63) / 64);
         }
         R.blk0[t->tmpls.size()] = nb; R.depth = d;
         if (t->timing && t->tev_used < 12) (void)hipEventRecord(t->tev[t->tev_used++], stream);
@@ -425,8 +353,6 @@ static void replay_launches(h2w_plan *p, ReplayArgs &R, const std::vector<uint32
         } else if (nb) hipLaunchKernelGGL(k_replay<false>, dim3(nb), dim3(64), 0, stream, R);
     }
 }
-// the plan's part of k_replay's arguments; what belongs to the call - recs, out, the lane table, the sharding - is zero and the caller's to set
-static ReplayArgs replay_args(const h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, char *ws, const struct TracedWs &wl);
 int traced_run(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void *advice_dev, void *workspace_dev, void *stream_, ColMap cm, uint64_t cell_stride, const ShardSpec &sh) {
     TracedPlan *t = p->traced;
     if (n_proofs > 65535) { set_error("h2w_fri_witness_batch: more than 65535 proofs per call"); return -1; }
@@ -434,13 +360,16 @@ int traced_run(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void 
     if ((sharded || sh.compact) && !t->why_unshardable.empty()) { set_error("h2w_fri_witness_batch_shard: " + t->why_unshardable); return -1; }
     if (sh.compact && !sharded) { set_error("h2w_fri_witness_batch_shard_compact: world 1 on a traced plan: use h2w_fri_witness_batch (the packed form of one rank is the flat stream)"); return -1; }
     DeviceGuard dg(p->device);
-    if (sharded && lane_table(p, n_proofs, sh) != 0) return -1;
+    if (sharded && traced_sharded_lanes(p, n_proofs, sh) != 0) return -1;
+    // the grids of the two emission kernels: a wavefront per listed Goldilocks-Poseidon permutation, a quad per PoseidonBN254 one of this rank's blocks
+    const uint64_t bn_items = !t->nbnp ? 0 : sharded ? t->lanes.n_bn_items : n_proofs * t->nbnp, bn_blocks = (bn_items * 4 + QUAD_BLOCK - 1) / QUAD_BLOCK;
+    if (n_proofs * t->nglp >= 0x7fffffffull || bn_blocks >= 0x7fffffffull) { set_error("h2w_fri_witness_batch: too many fused permutations in one call"); return -1; }
     hipStream_t stream = (hipStream_t)stream_;
     const TracedWs wl = traced_ws(p, n_proofs); char *ws = (char *)workspace_dev;
     ReplayArgs R = replay_args(p, proofs_dev, n_proofs, ws, wl);
     R.out = (fr_t *)advice_dev; R.cell_stride = cell_stride; R.cm = cm;      // (cm.starts: the FlexGate columns of every proof, cell_stride = ncols << k; else the flat stream)
     if (sharded) {
-        R.lanes = t->d_lanes.get(); for (size_t i = 0; i < t->lane0.size(); i++) R.lane0[i] = t->lane0[i];
+        use_lanes(R, t->lanes);
         R.sh_world = (uint32_t)sh.world; R.sh_rank = (uint32_t)sh.rank; R.sh_compact = (uint32_t)sh.compact; R.nq = (uint32_t)p->shape.num_queries;
         R.pro_ncell = p->st.pro_ncell; R.q_slot = std::max(p->st.q_ncell[0], p->st.q_ncell[1]);
     }
@@ -450,12 +379,11 @@ int traced_run(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void 
     // Montgomery form: the fused PoseidonBN254 permutations' cells leave their emission kernel converted; the ranged kernel takes the other direct cells
     const bool mont = p->output_form == H2W_FORM_MONTGOMERY, emit_mont = mont && t->nbnp && !p->trace_bn_ranged;
     t->tev_used = 0;
-    replay_launches(p, R, sharded ? &t->lane0 : nullptr, n_proofs, blist, stream);
+    replay_launches(p, R, sharded ? &t->lanes : nullptr, n_proofs, blist, stream);
     if (t->timing) H2W_HIP(hipEventRecord(t->tev[t->tev_used++], stream));
     if (t->nglp) {      // the records of the listed permutations, side by side
         GlpEmitArgs E; E.consts = p->d_consts.get(); E.list = R.glist; E.recs = R.recs; E.rec_stride = R.rec_stride; E.ncells = p->d_ncells.get(); E.unit = t->d_glp_unit.get();
         E.nglp = t->nglp; E.world = sharded ? (uint32_t)sh.world : 1u; E.rank = (uint32_t)sh.rank; E.nq = (uint32_t)p->shape.num_queries;
-        if ((uint64_t)n_proofs * t->nglp >= 0x7fffffffull) { set_error("h2w_fri_witness_batch: too many fused permutations in one call"); return -1; }
         hipLaunchKernelGGL(k_glp_emit_traced, dim3((uint32_t)(n_proofs * t->nglp)), dim3(64), 0, stream, E);
     }
     if (t->timing && t->bn_flag) H2W_HIP(hipEventRecord(t->tev[t->tev_used++], stream));
@@ -463,14 +391,10 @@ int traced_run(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void 
         BnEmitMontArgs EM; memset(&EM, 0, sizeof(EM)); BnEmitArgs &E = EM;
         EM.bn_tab_mont = p->d_bn_tab_mont.get(); EM.mont_k = mont_k();
         E.bn_tab = p->d_bn_tab.get(); E.list = blist; E.bnp = t->d_bnp.get(); E.nbnp = t->nbnp; E.out = R.out; E.cell_stride = cell_stride; E.cm = cm; E.P = p->P; E.status = R.status;
-        if (sharded) {
-            E.items = t->d_bn_items.get(); E.nitems = t->n_bn_items;
-            E.sh_world = R.sh_world; E.sh_rank = R.sh_rank; E.sh_compact = R.sh_compact; E.nq = R.nq; E.pro_ncell = R.pro_ncell; E.q_slot = R.q_slot;
-        } else { E.items = nullptr; E.nitems = (uint64_t)n_proofs * t->nbnp; }
-        const uint64_t nblk = (E.nitems * 4 + QUAD_BLOCK - 1) / QUAD_BLOCK;
-        if (nblk >= 0x7fffffffull) { set_error("h2w_fri_witness_batch: too many fused permutations in one call"); return -1; }
-        if (nblk && emit_mont) launch_bn_emit_traced_mont(EM, cm.starts != nullptr, (uint32_t)nblk, stream);
-        else if (nblk) launch_cols(cm.starts != nullptr, k_bn_emit_traced<true>, k_bn_emit_traced<false>, dim3((uint32_t)nblk), dim3(QUAD_BLOCK), 0, stream, E);
+        E.items = sharded ? t->lanes.d_bn_items.get() : nullptr; E.nitems = bn_items;
+        if (sharded) { E.sh_world = R.sh_world; E.sh_rank = R.sh_rank; E.sh_compact = R.sh_compact; E.nq = R.nq; E.pro_ncell = R.pro_ncell; E.q_slot = R.q_slot; }
+        if (bn_blocks && emit_mont) launch_bn_emit_traced_mont(EM, cm.starts != nullptr, (uint32_t)bn_blocks, stream);
+        else if (bn_blocks) launch_cols(cm.starts != nullptr, k_bn_emit_traced<true>, k_bn_emit_traced<false>, dim3((uint32_t)bn_blocks), dim3(QUAD_BLOCK), 0, stream, E);
     }
     if (t->timing) H2W_HIP(hipEventRecord(t->tev[t->tev_used++], stream));
     // Montgomery form (plans lowered with H2W_TRACE_OUTPUT_FORMS): the direct cells - the interpreter's; the emission kernel's above too where it wrote
@@ -484,47 +408,18 @@ int traced_run(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void 
     H2W_HIP(hipGetLastError());
     return 0;
 }
-static ReplayArgs replay_args(const h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, char *ws, const TracedWs &wl) {
-    const TracedPlan *t = p->traced;
-    ReplayArgs R; memset(&R, 0, sizeof(R));
-    R.tape = t->d_tape.get(); R.insts = t->d_insts.get(); R.imps = t->d_imps.get(); R.inputs = t->d_inputs.get(); R.pool64 = t->d_pool64.get(); R.poolfr = t->d_poolfr.get();
-    R.proofs = proofs_dev; R.proof_words = p->pl.total; R.recs = (rec_t *)(ws + wl.recs); R.rec_stride = p->nrec;
-    R.vals = (uint64_t *)(ws + wl.vals); R.status = (uint32_t *)(ws + wl.status); R.ncells = p->d_ncells.get(); R.inv_pos = p->d_inv.get(); R.inv_neg = p->d_inv.get() + INV_TAB; R.P = p->P; R.L = p->shape.lookup_bits;
-    R.nproofs = (uint32_t)n_proofs; R.lflag = (uint32_t *)(ws + wl.lflag);
-    R.glk = reinterpret_cast<const uint64_t *>(p->d_consts.get()); R.glist = (uint64_t *)(ws + wl.glist); R.nglp = t->nglp;
-    R.ntmpl = (uint32_t)t->tmpls.size(); R.tm = t->d_tm.get(); R.prefix = t->d_prefix.get(); R.npool64 = t->npool64; R.npoolfr = t->npoolfr;
-    return R;
-}
-// The quiet lane table of n proofs: template by template every (proof, instance) place with bit 31 set - the sharded call's format (lane_table) for a
-// world in which this rank owns nothing: the interpreter computes the values and stores nothing else
-static int quiet_lane_table(h2w_plan *p, uint64_t n) {
-    TracedPlan *t = p->traced;
-    if (t->d_qlanes.get() && t->qlanes_n == n) return 0;
-    std::vector<uint32_t> L; t->qlane0.assign(t->tmpls.size() + 1, 0);
-    for (size_t i = 0; i < t->tmpls.size(); i++) {
-        const TmplD &T = t->tmpls[i]; t->qlane0[i] = (uint32_t)L.size();
-        if (n * T.ninst >= 0x80000000ull || L.size() + n * T.ninst >= 0x80000000ull) { set_error("h2w_trace_verdict_batch: too many (proof, instance) lanes in one call; split the batch"); return -1; }
-        for (uint64_t g = 0; g < n * T.ninst; g++) L.push_back((uint32_t)g | 0x80000000u);
-    }
-    t->qlane0[t->tmpls.size()] = (uint32_t)L.size();
-    H2W_HIP(hipDeviceSynchronize());      // a previous call may still read the old table (plans are single-threaded handles, include/h2w.h)
-    t->d_qlanes.reset(); t->qlanes_n = 0;
-    if (t->d_qlanes.upload(L) != 0) return -1;
-    t->qlanes_n = n;
-    return 0;
-}
 static int trace_verdict_run(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, h2w_verdict_t *verdict_dev, void *workspace_dev, void *stream_) {
     TracedPlan *t = p->traced; const VerdictTables &V = t->vt;
     for (size_t i = 0; i < t->tmpls.size(); i++)
         if ((uint64_t)n_proofs * t->tmpls[i].ninst * (V.ent0[i + 1] - V.ent0[i]) >= 0x80000000ull) { set_error("h2w_trace_verdict_batch: 2^31 or more (proof, instance, check) lanes in one call; split the batch"); return -1; }
     DeviceGuard dg(p->device);
-    if (quiet_lane_table(p, n_proofs) != 0) return -1;
+    if (traced_quiet_lanes(p, n_proofs) != 0) return -1;
     hipStream_t stream = (hipStream_t)stream_;
     const TracedWs wl = traced_ws(p, n_proofs); char *ws = (char *)workspace_dev;
     // 1. the values: k_replay as traced_run launches it, every lane quiet (no advice buffer: R.out stays null, nothing is stored through it)
     ReplayArgs R = replay_args(p, proofs_dev, n_proofs, ws, wl);
     R.cm = flat_cols(); R.cell_stride = p->ncells;
-    R.lanes = t->d_qlanes.get(); for (size_t i = 0; i < t->qlane0.size(); i++) R.lane0[i] = t->qlane0[i];
+    use_lanes(R, t->qlanes);
     R.sh_world = 1; R.sh_rank = 0; R.sh_compact = 0; R.nq = (uint32_t)p->shape.num_queries;
     H2W_HIP(hipMemsetAsync(ws + wl.status, 0, n_proofs * 4, stream));
     H2W_HIP(hipMemsetAsync(ws + wl.lflag, 0, n_proofs * 4, stream));
@@ -533,7 +428,7 @@ static int trace_verdict_run(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n
     A.vals = R.vals; A.proofs = proofs_dev; A.proof_words = p->pl.total; A.verdict = verdict_dev; A.status = R.status; A.lflag = R.lflag; A.nproofs = (uint32_t)n_proofs; A.L = p->shape.lookup_bits;
     launch_trace_verdict_init(A, stream);
     const bool timing = t->timing; t->timing = false;      // (h2w_plan_trace_timing reports witness calls: this call records no events and leaves the last call's alone)
-    replay_launches(p, R, &t->qlane0, n_proofs, (uint64_t *)(ws + wl.blist), stream);
+    replay_launches(p, R, &t->qlanes, n_proofs, (uint64_t *)(ws + wl.blist), stream);
     t->timing = timing;
     // 2. the checks, template by template, behind the deepest depth
     for (size_t i = 0; i < t->tmpls.size(); i++) {
@@ -546,133 +441,6 @@ static int trace_verdict_run(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n
 }
 }  // namespace h2w
 
-// h2w_plan_from_trace: the lowering stage by stage (tracelower.h), every tape checked (tapefmt.h), the plan handle, the upload.
-static h2w_plan *plan_from_trace(h2w_ctx *ctx, uint64_t proof_words, const char *const *parallel_scopes, size_t n_scopes, int device_id, const h2w_poseidon_consts_t *consts, uint32_t flags) {
-    Trace *tr = ctx_trace(ctx);
-    if (!tr) { set_error("h2w_plan_from_trace: the context is not in trace mode (h2w_ctx_trace_begin)"); return nullptr; }
-    if (!tr->err.empty()) { set_error("h2w_plan_from_trace: " + tr->err); return nullptr; }
-    if (tr->pending.kind) { set_error("h2w_plan_from_trace: a h2w_trace_input tag was never consumed"); return nullptr; }
-    const bool fusing = (flags & H2W_TRACE_FUSE_GL_PERMUTE) != 0, fusing_bn = (flags & H2W_TRACE_FUSE_BN_PERMUTE) != 0;
-    if (flags & ~(uint32_t)(H2W_TRACE_FUSE_GL_PERMUTE | H2W_TRACE_FUSE_BN_PERMUTE | H2W_TRACE_OUTPUT_FORMS)) { set_error("h2w_plan_from_trace_ex: unknown flag"); return nullptr; }
-    if (fusing && !consts) { set_error("h2w_plan_from_trace_ex: H2W_TRACE_FUSE_GL_PERMUTE needs the Poseidon tables the permutations are claimed to use"); return nullptr; }
-    if (fusing_bn && !consts) { set_error("h2w_plan_from_trace_ex: H2W_TRACE_FUSE_BN_PERMUTE needs the Poseidon tables the permutations are claimed to use"); return nullptr; }
-    const int L = ctx_lookup_bits(ctx); const uint64_t ncells = ctx_num_cells(ctx);
-    TemplateTable tt(L);
-    std::string err; Fusable F; Lowered LW; LoweredPlan LP;
-    if (!find_fusable(tr, L, tt, parallel_scopes, n_scopes, consts, fusing, fusing_bn, F, err)) { set_error(err); return nullptr; }
-    lower_trace(tr, L, tt, parallel_scopes, n_scopes, F, LW);
-    if (!LW.err.empty()) { set_error("h2w_plan_from_trace: " + LW.err); return nullptr; }
-    const ShardUnits U = shard_units(LW, ncells);
-    pack_glop_runs(LW, tt);
-    if (!group_templates(LW, U, LP, err)) { set_error(err); return nullptr; }
-    for (size_t t = 0; t < LP.tmpls.size(); t++) {
-        TapeLimits M = LP.limits[t]; M.inputs = LP.inputs.data() + LP.insts[LP.tmpls[t].inst0].in0; M.npool64 = LP.pool64.size(); M.npoolfr = LP.poolfr.size();
-        M.proof_words = proof_words; M.fusing_gl = fusing; M.fusing_bn = fusing_bn;
-        M.glp_block_cells = F.glp_block_cells; M.glp_recs = F.glp_meta.size(); M.glp_recs_kernel = (size_t)GLP_RECS; M.bn_perm_cells = (uint64_t)BN_PERM_CELLS;
-        const size_t t0 = LP.tmpls[t].tape0, t1 = t + 1 < LP.tmpls.size() ? LP.tmpls[t + 1].tape0 : LP.tape.size();
-        err = tape_check(LP.tape.data() + t0, t1 - t0, M);
-        if (!err.empty()) { set_error("h2w_plan_from_trace: " + err); return nullptr; }
-    }
-    // the verdict stage, behind the final tapes (it reads the lowering's maps and changes nothing); its table checked like a tape before it is uploaded
-    VerdictTables VT = verdict_tables(tr, LW, F, LP);
-    for (size_t t = 0; VT.why.empty() && t < LP.tmpls.size(); t++) {
-        TapeLimits M = LP.limits[t]; M.inputs = LP.inputs.data() + LP.insts[LP.tmpls[t].inst0].in0; M.npool64 = LP.pool64.size(); M.npoolfr = LP.poolfr.size(); M.proof_words = proof_words;
-        M.nimps = VT.nvimp[t];
-        err = verdict_table_check(VT.ents.data() + VT.ent0[t], VT.ent0[t + 1] - VT.ent0[t], M);
-        if (!err.empty()) { VT = VerdictTables(); VT.n_asserts = tr->asserts.size(); VT.why = "the traced plan has no verdict: " + err; }      // (the witness plan is not the verdict's to refuse)
-    }
-    err.clear();
-    std::vector<uint64_t> op_counts(TAPE_COUNTS, 0);      // h2w_plan_trace_op_counts: over every template's final tape
-    for (size_t t = 0; t < LP.tmpls.size(); t++) { const size_t t0 = LP.tmpls[t].tape0, t1 = t + 1 < LP.tmpls.size() ? LP.tmpls[t + 1].tape0 : LP.tape.size(); tape_op_counts(LP.tape.data() + t0, t1 - t0, op_counts.data()); }
-    for (uint32_t w : LP.inputs) if (w >= proof_words) { set_error("h2w_plan_from_trace: an input tag beyond proof_words"); return nullptr; }
-    for (const BnpD &b : LP.bnp) if (b.cell0 + (uint64_t)BN_PERM_CELLS > ncells) { set_error("h2w_plan_from_trace_ex: internal: a fused permutation's cells lie beyond the stream"); return nullptr; }
-    TracedPlan *tp = new TracedPlan();
-    tp->tmpls = LP.tmpls; tp->total_slot_lanes = LP.total_slot_lanes; tp->h_unit = LP.unit; tp->nglp = LP.nglp; tp->h_glp_unit = LP.glp_unit; tp->nbnp = LP.nbnp; tp->h_bnp = LP.bnp; tp->h_bnp0 = LP.bnp0;
-    tp->n_ops = tr->ops.size(); tp->n_segments = LP.n_segments; tp->why_unshardable = U.why_unshardable; tp->n_candidates = F.n_candidates;
-    tp->bn_flag = fusing_bn; tp->n_bn_left = F.n_bn_left;
-    tp->op_counts.swap(op_counts);
-    tp->why_no_verdict = VT.why; tp->vt = VT;
-
-    // ---- the plan handle
-    int ndev = 0; const bool on_device = hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0;      // (none: layout queries only)
-    if (on_device && (device_id < 0 || device_id >= ndev)) { set_error("h2w_plan_from_trace: device_id out of range"); delete tp; return nullptr; }
-    h2w_plan *pl = new h2w_plan(L);
-    memset(&pl->shape, 0, sizeof(pl->shape)); pl->shape.lookup_bits = L; pl->shape.num_queries = U.num_queries; pl->shape.hash_mode = 1;
-    pl->device = on_device ? device_id : -1; pl->P = fr_params_init(); memset(&pl->st, 0, sizeof(pl->st)); memset(&pl->pl, 0, sizeof(pl->pl)); memset(&pl->d, 0, sizeof(pl->d));
-    pl->pl.total = proof_words; pl->nrec = LP.nrec; pl->ncells = ncells; pl->traced = tp;
-    if (flags & H2W_TRACE_OUTPUT_FORMS) {      // the direct-cell map of H2W_OPT_OUTPUT_FORM (the plan does not keep the tape: now)
-        if (!direct_cell_map(LP, pl->tt, ncells, pl->direct_bits, pl->n_direct, err) || !ranged_cell_map(LP, (uint64_t)BN_PERM_CELLS, pl->direct_bits, pl->ranged_bits, err)) { set_error(err); h2w_plan_free(pl); return nullptr; }
-        pl->trace_forms = true; pl->trace_bn_ranged = getenv("H2W_TRACE_BN_RANGED") != nullptr;
-    }
-    if (consts) pl->h_consts = *consts;
-    for (uint64_t m : LP.meta) pl->rec_cells += (uint64_t)pl->tt.ncells((int)meta_tmpl(m));
-    // the block structure (StrandTable: what h2w_plan_strand_layout / _shard_cells / _shard_block and the sharded expansion read): unshardable, one block
-    StrandTable &st = pl->st; st.first_zero_kind = -1; st.first_zero_unit = -1; st.total_rec = LP.nrec; st.total_cell = ncells;
-    st.pro_ncell = U.pro_ncell; st.pro_nrec = U.pro_nrec;
-    for (int k = 0; k < 2; k++) { st.q_cell0[k] = U.q_cell0[k]; st.q_rec0[k] = U.q_rec0[k]; st.q_ncell[k] = U.q_ncell[k]; st.q_nrec[k] = U.q_nrec[k]; }
-    // keygen metadata (witness_gen_only = 0): the tracing context's own lists (keygen.h), as h2w_plan_metadata / h2w_plan_equalities hand them out
-    if (const MetaRecorder *mr = ctx_meta(ctx)) {
-        pl->sel_bits.assign((size_t)(pl->ncells + 7) / 8, 0); pl->lk_bits.assign(pl->sel_bits.size(), 0);
-        for (uint64_t c : mr->sel) if (c < pl->ncells) pl->sel_bits[c / 8] |= (uint8_t)(1u << (c & 7));
-        for (uint64_t c : mr->lookups) if (c < pl->ncells) pl->lk_bits[c / 8] |= (uint8_t)(1u << (c & 7));
-        for (uint8_t b : pl->sel_bits) pl->n_gates += (uint64_t)__builtin_popcount(b);
-        for (uint8_t b : pl->lk_bits) pl->n_lookups += (uint64_t)__builtin_popcount(b);
-        pl->meta_ready = true;
-        PlanEqualities &E = pl->eqs; E.pairs = mr->eq; E.const_cells = mr->ceq_cell; E.const_values = mr->ceq_val; E.const_word.assign(E.const_cells.size(), -1);
-        // proof words loaded as constants (Goldilocks-Poseidon hash wires, hash/poseidon/hash.rs:86-96): their constant equality takes the given proof's word
-        std::unordered_map<uint64_t, const TraceOp *> word_const;
-        for (const TraceOp &o : tr->ops) if (o.code == TR_LOAD_CONSTANT && o.tag.kind == 1) word_const[o.cell0] = &o;
-        for (size_t i = 0; i < E.const_cells.size(); i++) {
-            auto it = word_const.find(E.const_cells[i]);
-            if (it != word_const.end() && fr_eq(E.const_values[i], tr->consts[(size_t)it->second->imm])) E.const_word[i] = (int64_t)it->second->tag.word;
-        }
-        E.ready = true;
-    }
-    if (!on_device) { if (pl->trace_forms) pl->h_meta = LP.meta; return pl; }      // (h2w_plan_record_ranges: with a device it reads d_meta back)
-    DeviceGuard dg(device_id);
-    for (int k2 = 0; k2 < 16; k2++) LP.tape.push_back(DOP_END | (1u << 24));      // the interpreter reads a window ahead
-    std::vector<uint64_t> prefix(tp->tmpls.size()); uint64_t acc = 0;
-    for (size_t i = 0; i < tp->tmpls.size(); i++) { prefix[i] = acc; acc += (uint64_t)tp->tmpls[i].nslots * tp->tmpls[i].ninst; }
-    tp->npool64 = (uint32_t)LP.pool64.size(); tp->npoolfr = (uint32_t)LP.poolfr.size();
-    bool ok = pl->dt.upload(pl->tt) == 0 && pl->d_meta.upload(LP.meta) == 0 && tp->d_tape.upload(LP.tape) == 0 && tp->d_tm.upload(tp->tmpls) == 0 &&
-              tp->d_prefix.upload(prefix) == 0 && tp->d_insts.upload(LP.insts) == 0 && tp->d_imps.upload(LP.imps) == 0 && tp->d_inputs.upload(LP.inputs) == 0 &&
-              tp->d_pool64.upload(LP.pool64) == 0 && tp->d_poolfr.upload(LP.poolfr) == 0 && upload_tmpl_cells(pl->d_ncells, pl->tt) == 0 &&
-              pl->d_inv.upload(inverse_table(pl->P)) == 0;
-    // the tables the fused permutations were verified on (handletabs.h); which shard unit a listed permutation belongs to / where it lies
-    if (ok && tp->nglp) ok = upload_glp_consts(pl->d_consts, *consts) == 0 && tp->d_glp_unit.upload(tp->h_glp_unit) == 0;
-    if (ok && tp->nbnp) ok = upload_bn_tab(pl->d_bn_tab, *consts, pl->P) == 0 && tp->d_bnp.upload(tp->h_bnp) == 0 && tp->d_bnp0.upload(tp->h_bnp0) == 0;
-    if (ok && VT.why.empty()) {      // the verdict's tables: the entries, per instance {first verdict import, first input, unit}, the imports, per template {prefix, instances}
-        std::vector<VInstD> vi(LP.insts.size()); std::vector<VImpD> vm(VT.vimps.size()); std::vector<uint64_t> ti(2 * tp->tmpls.size());
-        for (size_t i = 0; i < vi.size(); i++) vi[i] = VInstD{VT.vimp0[i], LP.insts[i].in0, LP.insts[i].unit, VT.site0[i]};
-        for (size_t i = 0; i < vm.size(); i++) vm[i] = VImpD{VT.vimps[i].tmpl, VT.vimps[i].inst, VT.vimps[i].slot, 0};
-        for (size_t i = 0; i < tp->tmpls.size(); i++) { ti[2 * i] = prefix[i]; ti[2 * i + 1] = tp->tmpls[i].ninst; }
-        ok = tp->d_vinst.upload(vi) == 0 && tp->d_tinfo.upload(ti) == 0 && (VT.ents.empty() || (tp->d_vents.upload(VT.ents) == 0 && tp->d_vsites.upload(VT.sites) == 0)) && (vm.empty() || tp->d_vimps.upload(vm) == 0);
-    }
-    if (!ok) { h2w_plan_free(pl); return nullptr; }
-    return pl;
-}
-
-extern "C" h2w_plan *h2w_plan_from_trace(h2w_ctx *ctx, uint64_t proof_words, const char *const *parallel_scopes, size_t n_scopes, int device_id) {
-    return plan_from_trace(ctx, proof_words, parallel_scopes, n_scopes, device_id, nullptr, 0);
-}
-extern "C" h2w_plan *h2w_plan_from_trace_ex(h2w_ctx *ctx, uint64_t proof_words, const char *const *parallel_scopes, size_t n_scopes, int device_id, const h2w_poseidon_consts_t *consts, uint32_t flags) {
-    return plan_from_trace(ctx, proof_words, parallel_scopes, n_scopes, device_id, consts, flags);
-}
-extern "C" int h2w_plan_trace_info(const h2w_plan *p, uint64_t out[6]) {
-    if (!p || !out) { set_error("h2w_plan_trace_info: null argument"); return -1; }
-    if (!p->traced) { set_error("h2w_plan_trace_info: not a traced plan (h2w_plan_from_trace)"); return -1; }
-    const TracedPlan *t = p->traced;
-    out[0] = t->n_ops; out[1] = t->n_segments; out[2] = t->tmpls.size(); out[3] = t->nglp; out[4] = t->n_candidates; out[5] = t->nglp;
-    return 0;
-}
-extern "C" int h2w_plan_trace_verdict_info(const h2w_plan *p, uint64_t out[6]) {
-    if (!p || !out) { set_error("h2w_plan_trace_verdict_info: null argument"); return -1; }
-    if (!p->traced) { set_error("h2w_plan_trace_verdict_info: not a traced plan (h2w_plan_from_trace); a plan of h2w_plan_compile has h2w_fri_verdict_batch"); return -1; }
-    const TracedPlan *t = p->traced; const VerdictTables &V = t->vt;
-    out[0] = V.n_asserts; out[1] = V.n_eq_lanes; out[2] = V.n_range; out[3] = t->why_no_verdict.empty() ? 1 : 0; out[4] = V.n_tmpl; out[5] = 0;
-    if (!t->why_no_verdict.empty()) set_error("h2w_plan_trace_verdict_info: " + t->why_no_verdict);
-    return 0;
-}
 extern "C" int h2w_trace_verdict_batch(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, h2w_verdict_t *verdict_dev, void *workspace_dev, void *stream) {
     if (!p) { set_error("h2w_trace_verdict_batch: null plan"); return -1; }
     if (!p->traced) { set_error("h2w_trace_verdict_batch: a plan of h2w_plan_compile: use h2w_fri_verdict_batch"); return -1; }
@@ -682,32 +450,4 @@ extern "C" int h2w_trace_verdict_batch(h2w_plan *p, const uint64_t *proofs_dev, 
     if (!proofs_dev || !verdict_dev || !workspace_dev) { set_error("h2w_trace_verdict_batch: null buffer"); return -1; }
     if (n_proofs > 65535) { set_error("h2w_trace_verdict_batch: more than 65535 proofs per call"); return -1; }
     return trace_verdict_run(p, proofs_dev, n_proofs, verdict_dev, workspace_dev, stream);
-}
-extern "C" int h2w_plan_trace_op_counts(const h2w_plan *p, uint64_t *out, size_t n_out) {
-    if (!p || (!out && n_out)) { set_error("h2w_plan_trace_op_counts: null argument"); return -1; }
-    if (!p->traced) { set_error("h2w_plan_trace_op_counts: not a traced plan (h2w_plan_from_trace)"); return -1; }
-    const std::vector<uint64_t> &c = p->traced->op_counts;
-    for (size_t i = 0; i < n_out; i++) out[i] = i < c.size() ? c[i] : 0;
-    return (int)c.size();
-}
-extern "C" int h2w_plan_trace_info_bn(const h2w_plan *p, uint64_t out[3]) {
-    if (!p || !out) { set_error("h2w_plan_trace_info_bn: null argument"); return -1; }
-    if (!p->traced) { set_error("h2w_plan_trace_info_bn: not a traced plan (h2w_plan_from_trace)"); return -1; }
-    const TracedPlan *t = p->traced;
-    out[0] = t->nbnp; out[1] = t->n_bn_left; out[2] = t->nbnp;
-    return 0;
-}
-// ms of the kernels of the last call: the k_replay launch of every depth, k_glp_emit_traced, (plans built with H2W_TRACE_FUSE_BN_PERMUTE) k_bn_emit_traced,
-// (plans built with H2W_TRACE_OUTPUT_FORMS) the direct cells' conversion - nothing in canonical form -, the expansion.  The first call switches the events on
-// (0 entries); later ones wait for the last call and report it.
-extern "C" int h2w_plan_trace_timing(h2w_plan *p, float *ms, uint32_t cap) {
-    if (!p || !ms) { set_error("h2w_plan_trace_timing: null argument"); return -1; }
-    if (!p->traced || p->device < 0) { set_error("h2w_plan_trace_timing: not a traced plan on a device"); return -1; }
-    TracedPlan *t = p->traced; DeviceGuard dg(p->device);
-    if (!t->timing) { for (DevEvent &e : t->tev) if (e.create() != 0) return -1; t->timing = true; return 0; }
-    if (t->tev_used < 2) return 0;
-    H2W_HIP(hipEventSynchronize(t->tev[t->tev_used - 1]));
-    int n = 0;
-    for (int i = 0; i + 1 < t->tev_used && (uint32_t)n < cap; i++, n++) H2W_HIP(hipEventElapsedTime(&ms[n], t->tev[i], t->tev[i + 1]));
-    return n;
 }

@@ -9,6 +9,8 @@
 
 namespace h2w {
 
+// Does rank r of W own block (proof, q)?  q < 0: the prologue block.  (Host code's one statement of the rule; a kernel writes it out.)
+HD bool shard_owns(uint64_t W, uint64_t r, uint64_t nq, uint64_t proof, int64_t q) { return (q < 0 ? proof : proof * nq + (uint64_t)q) % W == r; }
 // The local start cell of block (proof, q) in rank r's packed buffer; q < 0: the prologue block.  (The caller owns the block; the pointer a
 // kernel adds the block's GLOBAL in-proof cell offsets to is out + this - the block's global start.)
 HD uint64_t packed_block_start(uint64_t W, uint64_t r, uint64_t nq, uint64_t pro_ncell, uint64_t q_slot, uint64_t proof, int64_t q) {

@@ -43,6 +43,14 @@ constexpr uint32_t GLPERM_IO = 12, BNPERM_IO = 4;      // the states of the two 
 // a list entry of a fused PoseidonBN254 permutation: {first cell of its block in the proof's stream, zero-cell flag (1: the Context's load_zero cell is
 // cached, the block is the 4,032 cells), the 4 x 32-byte input state}
 constexpr uint32_t BNP_LIST_WORDS = 18;
+// ---- the plan's tables as the device reads them (here, not in tracelower.h: the lane tables, lanetable.h, are plain C++ too)
+// unit: the depth-1 parallel instance (shard unit) the instance is or lies in, NO_SLOT for the root; ucell0: that unit's first cell (root: 0)
+// glp0: the instance's first entry in the proof's list of fused permutations
+struct InstD { uint64_t cell0, rec0, ucell0; uint32_t imp0, in0, unit, glp0; };
+struct ImpD { uint32_t tmpl, inst, slot; };
+struct TmplD { uint32_t tape0, nslots, ninst, inst0, depth; };
+// a listed PoseidonBN254 permutation, static per plan: its first cell in the proof's stream, its shard unit (NO_SLOT: the root's block), that unit's first cell
+struct BnpD { uint64_t cell0, ucell0; uint32_t unit, pad; };
 
 // ---- the shape of every op
 // How many words of an operand the interpreter reads is the ref's own width field (get64(r, 0) for a one-word operand, getfr(r) by width for a

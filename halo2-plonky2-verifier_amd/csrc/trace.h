@@ -1,6 +1,6 @@
 // trace.h — the op tape an eager context records in trace mode (h2w_ctx_trace_begin): one entry per level-1 / level-2 call of include/h2w.h,
 // operands and results named by the CELL OFFSETS their h2w_assigned_t handles carry (every wire of the reference is a cell of Context::advice:
-// field/native.rs:28-193 returns AssignedValue handles).  h2w_plan_from_trace (replay.hip) lowers the tape to a device program that
+// field/native.rs:28-193 returns AssignedValue handles).  h2w_plan_from_trace (traceplan.cpp) lowers the tape to a device program that
 // h2w_fri_witness_batch replays on other proofs of the same shape: the reference's circuit driven ONCE through the operator API, then served at
 // GPU speed - no hand restatement of the gadget in between (VERDICT r03 task 4).
 // What makes a run replayable: control flow is data-independent, every value that depends on the proof enters as a TAGGED proof word
@@ -43,5 +43,7 @@ struct Trace {
     TraceTag pending; std::string err;
     void fail(const std::string &m) { if (err.empty()) err = m; }
 };
+// what a context hands the lowering (eager.cpp): its tape (null: not in trace mode), its lookup bits, the cells of the run, its keygen lists (keygen.h; null: witness_gen_only != 0)
+Trace *ctx_trace(h2w_ctx *); int ctx_lookup_bits(const h2w_ctx *); uint64_t ctx_num_cells(const h2w_ctx *); const struct MetaRecorder *ctx_meta(const h2w_ctx *);
 
 }  // namespace h2w

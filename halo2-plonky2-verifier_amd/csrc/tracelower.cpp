@@ -13,9 +13,7 @@
 #include "valbackend.h"
 #include "coop.h"
 
-struct h2w_ctx;
 namespace h2w {
-Trace *ctx_trace(h2w_ctx *);      // eager.cpp
 static_assert(GLPERM_IO == (uint32_t)SPONGE_WIDTH && BNPERM_IO == (uint32_t)BN_WIDTH, "tapefmt.h states the permutations' widths on its own");
 
 // ---- stretches of a tape that ARE a permutation (H2W_TRACE_FUSE_GL_PERMUTE, H2W_TRACE_FUSE_BN_PERMUTE).  A lowered op, before its operands become fast refs:

@@ -1,5 +1,5 @@
 // tracelower.h — the lowering of a recorded tape (trace.h) to the device program of a traced plan: host code only, no kernel, no HIP call.
-// h2w_plan_from_trace (replay.hip) runs its stages in order - find_fusable, lower_trace, shard_units, pack_glop_runs, group_templates -, checks
+// h2w_plan_from_trace (traceplan.cpp) runs its stages in order - find_fusable, lower_trace, shard_units, pack_glop_runs, group_templates -, checks
 // every template's tape (tapefmt.h tape_check) and uploads the result, a LoweredPlan of plain host vectors.
 #pragma once
 #include <map>
@@ -12,15 +12,7 @@
 
 namespace h2w {
 
-constexpr int MAX_TMPL = 48;
-// ---- the plan's tables as the device reads them
-// unit: the depth-1 parallel instance (shard unit) the instance is or lies in, NO_SLOT for the root; ucell0: that unit's first cell (root: 0)
-// glp0: the instance's first entry in the proof's list of fused permutations
-struct InstD { uint64_t cell0, rec0, ucell0; uint32_t imp0, in0, unit, glp0; };
-struct ImpD { uint32_t tmpl, inst, slot; };
-struct TmplD { uint32_t tape0, nslots, ninst, inst0, depth; };
-// a listed PoseidonBN254 permutation, static per plan: its first cell in the proof's stream, its shard unit (NO_SLOT: the root's block), that unit's first cell
-struct BnpD { uint64_t cell0, ucell0; uint32_t unit, pad; };
+constexpr int MAX_TMPL = 48;      // (the plan's tables as the device reads them - InstD, ImpD, TmplD, BnpD - are tapefmt.h's)
 
 // ---- the lowering's own state
 struct ValInfo { uint32_t seg, slot; uint8_t width, is_static; uint32_t lit; };
@@ -67,7 +59,7 @@ struct ShardUnits {
 ShardUnits shard_units(Lowered &LW, uint64_t total_cells);
 // consecutive Goldilocks-level ops -> runs (DOP_GLOPRUN)
 void pack_glop_runs(Lowered &LW, const TemplateTable &tt);
-// What replay.hip uploads.  Isomorphic instances (equal tapes, slot counts, table sizes) share one template; tapes back to back in `tape`.
+// What traceplan.cpp uploads.  Isomorphic instances (equal tapes, slot counts, table sizes) share one template; tapes back to back in `tape`.
 struct LoweredPlan {
     std::vector<uint32_t> tape; std::vector<TmplD> tmpls; std::vector<InstD> insts; std::vector<ImpD> imps; std::vector<uint32_t> inputs;
     std::vector<uint64_t> pool64; std::vector<fr_t> poolfr; std::vector<uint64_t> meta; uint64_t nrec = 0;
@@ -77,6 +69,8 @@ struct LoweredPlan {
     uint32_t nglp = 0; std::vector<uint32_t> glp_unit;      // fused Goldilocks-Poseidon permutations per proof; the shard unit of every list entry
     uint32_t nbnp = 0; std::vector<BnpD> bnp; std::vector<uint32_t> bnp0;      // fused PoseidonBN254 permutations per proof; the entries; per instance its first entry
     uint64_t total_slot_lanes = 0, n_segments = 0;
+    const uint32_t *tmpl_tape(size_t t) const { return tape.data() + tmpls[t].tape0; }      // template t's tape and its words: up to the next template's
+    size_t tmpl_tape_words(size_t t) const { return (t + 1 < tmpls.size() ? tmpls[t + 1].tape0 : tape.size()) - tmpls[t].tape0; }
 };
 // false: err ("more than MAX_TMPL distinct scope shapes").  Takes the pools and the record meta list out of LW.
 bool group_templates(Lowered &LW, const ShardUnits &U, LoweredPlan &P, std::string &err);
