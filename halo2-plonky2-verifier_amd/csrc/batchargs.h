@@ -1,7 +1,8 @@
 // batchargs.h - kernel arguments of the batched hot path, shared by its translation units (batch.hip, glue.hip; the plan handle, plan.h, rests on it).
 #pragma once
 #include "valbackend.h"
-#include "coop.h"
+#include "glcoop.h"
+#include "bnquad.h"
 #include "rowfr.h"
 #include "shardmap.h"
 
@@ -30,9 +31,9 @@ struct BatchArgs {
     const uint16_t *ncells; const fr_t *inv_pos, *inv_neg;
     const StrandTable *st; FrParams P;      // the shape's strand table, in device memory (a by-value copy in the kernel arguments is copied to every lane's stack as soon as it is indexed)
     int nproofs;
-    const fr_t *bn_tab;             // PoseidonBN254 tables of this plan: [2][BK_T] canonical / times R (coop.h bn_table_build)
+    const fr_t *bn_tab;             // PoseidonBN254 tables of this plan: [2][BK_T] canonical / times R (bntab.h bn_table_build)
     const FriTab *fri;              // the shape's FRI-gadget constants (valbackend.h FriTab)
-    const uint32_t *bn_tab9;        // the times-R entries and the BK_X block in limb form (coop.h bn_table9_build): the values pass
+    const uint32_t *bn_tab9;        // the times-R entries and the BK_X block in limb form (bntab.h bn_table9_build): the values pass
     fr_t *unit_state;               // [own units][unit_slot][4]: output state of every PoseidonBN254 permutation unit of this rank's (proof, query) units (values phase -> emission)
     fr_t *unit_sbox;                // [own units][unit_slot][56][3]: canonical x^2, x^4, x^5 of its partial rounds' S-boxes
     uint32_t *unit_sbox9;           // the same values as the row-cooperative values pass leaves them: times R, lazy, 12 dwords of 29-bit limbs each (rowperm.h; k_sbox_canon9 -> unit_sbox)

@@ -1,7 +1,7 @@
 // bnemit.h — the emission of a traced plan's fused PoseidonBN254 permutations (H2W_TRACE_FUSE_BN_PERMUTE): the arguments of replay.hip's
 // k_bn_emit_traced (canonical cells) and of bnemit_mont.hip's k_bn_emit_traced_mont (H2W_FORM_MONTGOMERY), its twin line for line.
 // One QUAD per listed PoseidonBN254 permutation of the launch: its 4,032 cells from the entry's input state, by the one-pass emitter the compiled plan's
-// k_merkle_bn_fused runs (coop.h QuadSinkT::bn_emit_cells<false>: it walks the S-box chain itself; 64 contiguous bytes per quad and store).  The launch
+// k_merkle_bn_fused runs (bnquad.h QuadSinkT::bn_emit_cells<false>: it walks the S-box chain itself; 64 contiguous bytes per quad and store).  The launch
 // works from a dense list of items: every (proof, entry) pair, or - sharded - `items`, the pairs of this rank's blocks (the others' entries were never
 // written).  The quads of a wavefront cooperate (cross-lane moves over the whole wavefront): none leaves early, tail quads redo the last item and write
 // identical bytes.  WHERE a permutation's cells go is static (BnpD, checked against the entry: status 97 if the interpreter listed another cell); only
@@ -9,7 +9,7 @@
 #pragma once
 #include "plan.h"
 #include "tracelower.h"
-#include "coop.h"
+#include "bnquad.h"
 
 namespace h2w {
 

@@ -1,6 +1,6 @@
 // bnemit_mont.hip — k_bn_emit_traced_mont: the Montgomery instantiation of a traced plan's PoseidonBN254 emission (bnemit.h; replay.hip traced_run
 // launches it when the plan's output form is H2W_FORM_MONTGOMERY).  Each fused permutation's 4,032 cells are stored once, already as v * 2^256 mod r:
-// the emitter is coop.h's one-pass form in its QUAD_FUSED_MONT mode - the flush code, the addresses (flat, columns, sharded, packed), the store
+// the emitter is bnquad.h's one-pass form in its QUAD_FUSED_MONT mode - the flush code, the addresses (flat, columns, sharded, packed), the store
 // pattern (64 contiguous bytes per quad and store) and the status-97 check are the canonical kernel's.  What differs is what the flushes read: the
 // canonical half of the LDS table holds the plan's cell table in Montgomery form (host-built, uploaded when the form is first selected: traceplan.cpp traced_mont_tables), and every value
 // slot is filled with fr_mont_mul(v, mont_k, ninv) - the product h2w_advice_to_montgomery and k_direct_to_montgomery apply, hence the same bytes.

@@ -43,8 +43,8 @@ template <class K> HF void bn_permute_values(fr_t (&s)[BN_WIDTH], const FrParams
             // ---- the partial rounds (:83-110): x^5 and the round constant on s0, the sparse row into s0, the sparse column into s1..s3
             BV_LOOP
             for (int r = 0; r < BN_PARTIAL_ROUNDS; r++) {
-                const int ix = BK_S + (BN_WIDTH * 2 - 1) * r;
-                const fr_t s0 = fr_add(bnv_exp5(s[0], ninv), k(BK_C + (BN_FULL_ROUNDS / 2 + 1) * BN_WIDTH + r));
+                const int ix = BK_S + bn_s_row(r);
+                const fr_t s0 = fr_add(bnv_exp5(s[0], ninv), k(BK_C + bn_c_partial(r)));
                 fr_t row = fr_mont_mul(k(ix), s0, ninv);
                 row = fr_add(fr_mont_mul(k(ix + 1), s[1], ninv), row);
                 row = fr_add(fr_mont_mul(k(ix + 2), s[2], ninv), row);
@@ -60,7 +60,7 @@ template <class K> HF void bn_permute_values(fr_t (&s)[BN_WIDTH], const FrParams
         for (int r = 0; r < BN_FULL_ROUNDS / 2; r++) {
             const bool last = r == BN_FULL_ROUNDS / 2 - 1;
             const bool ark = !(half == 1 && last);
-            const int it = BK_C + (half == 0 ? (r + 1) * BN_WIDTH : (BN_FULL_ROUNDS / 2 + 1) * BN_WIDTH + BN_PARTIAL_ROUNDS + r * BN_WIDTH);
+            const int it = BK_C + bn_c_full(half, r);
             BV_LOOP
             for (int i = 0; i < BN_WIDTH; i++) {
                 fr_t x = bnv_exp5(s[0], ninv);

@@ -1,6 +1,6 @@
 // bntab.h — layout and host-side construction of the PoseidonBN254 tables a plan uploads (hash/poseidon_bn254/permutation.rs:86-109,138-159,163-170:
-// C_CONSTANTS, S_CONSTANTS, M_MATRIX, P_MATRIX): canonical and times-R forms for the emitting kernels (coop.h), the limb form of the times-R entries
-// for the values passes (coop.h bn_values, rowperm.h).  Plain C++: the host checks of the values passes build the same tables.
+// C_CONSTANTS, S_CONSTANTS, M_MATRIX, P_MATRIX): canonical and times-R forms for the emitting kernels (bnquad.h), the limb form of the times-R entries
+// for the values passes (bnquad.h bn_values, rowperm.h).  Plain C++: the host checks of the values passes build the same tables.
 #pragma once
 #include "chips.h"
 
@@ -21,7 +21,7 @@ inline void bn_table_build(const h2w_poseidon_consts_t &k, const FrParams &P, fr
     tab[BK_ZERO] = fr_zero(); tab[BK_ONE] = fr_from_u64(1);
     for (int i = 0; i < BK_T; i++) tab[BK_T + i] = fr_mont_mul(tab[i], P.r2, P.ninv);
     for (int r = 0; r < 56; r++) {
-        tab[BK_X + r] = fr_mont_mul(tab[BK_T + BK_S + 7 * r], tab[BK_T + BK_C + 20 + r], P.ninv);
+        tab[BK_X + r] = fr_mont_mul(tab[BK_T + BK_S + bn_s_row(r)], tab[BK_T + BK_C + bn_c_partial(r)], P.ninv);
         tab[BK_XC + r] = fr_mont_mul(tab[BK_X + r], fr_from_u64(1), P.ninv);
     }
 }

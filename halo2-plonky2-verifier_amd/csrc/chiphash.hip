@@ -6,11 +6,11 @@
 // tests (permutation.rs:325-347, poseidon_bn254/permutation.rs:266-301, hash.rs test_hash_no_pad / test_hash_two_to_one, merkle/mod.rs:136-265).
 // The single-source chips (chips.h) on the device sinks the batched verifier runs them on, behind a front end that knows no proof shape:
 //   Goldilocks-Poseidon (hash_mode 0, GL_PERMUTE)   k_chiphash_gl: one wavefront per instance walks the op wave-uniformly on the values-phase sink
-//       (coop.h CoopSinkT<false, true, 0>): lane 0 stores the load / select records and direct cells, every permutation runs on values with
+//       (glcoop.h CoopSinkT<false, true, 0>): lane 0 stores the load / select records and direct cells, every permutation runs on values with
 //       glp_permute_lanes and is listed {first record, input state}; k_chiphash_glp_emit: one wavefront per listed permutation writes its 2,604 records
 //       (CoopSinkT::coop_poseidon_permute, as k_glp_emit_traced); the expansion kernel turns the records into cells.
 //   PoseidonBN254 (hash_mode 1, BN_PERMUTE)         k_chiphash_bn: one quad per instance walks the op and emits every permutation's 4,032 cells itself
-//       (coop.h QuadSinkT<false, QUAD_FUSED>::bn_emit_cells<false>, as k_merkle_bn_fused); lane 0 of the quad stores the Goldilocks-level records (leaf
+//       (bnquad.h QuadSinkT<false, QUAD_FUSED>::bn_emit_cells<false>, as k_merkle_bn_fused); lane 0 of the quad stores the Goldilocks-level records (leaf
 //       loads) and the other direct cells.  The quads of a wavefront run the same program in lockstep; tail quads redo the last instance.
 //   k_chiphash_check                                one lane per (instance, operand item): status 4 for a word outside its field / an index >= 2^depth.
 // The layout of an instance (record metas, cells, listed permutations) is one host replay of the same program on the sequential gadgets.

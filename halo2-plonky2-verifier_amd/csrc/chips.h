@@ -15,6 +15,11 @@ namespace h2w {
 
 constexpr int SPONGE_WIDTH = 12, SPONGE_RATE = 8, HALF_N_FULL_ROUNDS = 4, N_PARTIAL_ROUNDS = 22, NUM_HASH_OUT_ELTS = 4;
 constexpr int BN_WIDTH = 4, BN_RATE = 3, BN_FULL_ROUNDS = 8, BN_PARTIAL_ROUNDS = 56;
+// Where a round's constants sit in bn_c (C_CONSTANTS) and bn_s (S_CONSTANTS), and so in every table that copies the two (bntab.h BK_C, BK_S): bn_s is one sparse row per partial
+// round, BN_WIDTH row entries and then BN_WIDTH - 1 column entries; bn_c the first ark's constants and those behind each S-box layer of the first half (BN_WIDTH each), one per partial round, the second half's.
+constexpr int bn_s_row(int r) { return (BN_WIDTH * 2 - 1) * r; }
+constexpr int bn_c_partial(int r) { return (BN_FULL_ROUNDS / 2 + 1) * BN_WIDTH + r; }
+constexpr int bn_c_full(int half, int r) { return half == 0 ? (r + 1) * BN_WIDTH : bn_c_partial(BN_PARTIAL_ROUNDS) + r * BN_WIDTH; }      // behind the S-box layer of full round r of a half
 constexpr int MAX_STEPS = 8, MAX_ARITY = 16, MAX_CAP = 64, MAX_BATCH_POLYS = 16, MAX_FINAL_POLY = 128;      // MAX_CAP: cap_height <= 6 (sizes only the host-side / Goldilocks-caps indicator arrays)
 // Constants of the FRI gadgets that depend on the shape only (fri/mod.rs:222-322 recomputes them at every call: the two-adic subgroup of each
 // arity, its barycentric weights - an inversion each -, the inverse generator, the generator of the LDE domain).  Built once per plan on the host
@@ -287,7 +292,7 @@ template <class B> struct PoseidonPermutationChip {
     HF void load_zero(Gl *st) { gl.load_zero_array(SPONGE_WIDTH, st); }               // :264-268
     HNI void permute(Gl *st) {                                                        // :270-284
         be.glp_note();
-        if constexpr (B::kCoopPoseidon) be.coop_poseidon_permute(st, k);              // one wavefront cooperates on the 12-wide state (coop.h)
+        if constexpr (B::kCoopPoseidon) be.coop_poseidon_permute(st, k);              // one wavefront cooperates on the 12-wide state (glcoop.h)
         else { int rc = 0; full_rounds(st, rc); partial_rounds(st, rc); full_rounds(st, rc); }
     }
     template <class In> HF void absorb_goldilocks(Gl *st, const In &in, int n) {      // :286-301 (overwrite mode); `in`: anything indexable
@@ -317,11 +322,11 @@ template <class B> struct PoseidonBN254PermutationChip {
     HNI void partial_rounds(Fr *st) {                                                                  // :83-110
         for (int i = 0; i < BN_PARTIAL_ROUNDS; i++) {
             st[0] = exp5(st[0]);
-            Fr c = be.fr_const(k->bn_c[(BN_FULL_ROUNDS / 2 + 1) * BN_WIDTH + i]);
+            Fr c = be.fr_const(k->bn_c[bn_c_partial(i)]);
             st[0] = be.fr_add(st[0], c);
             Fr ns0 = be.fr_load_zero();
-            for (int j = 0; j < BN_WIDTH; j++) { Fr s = be.fr_const(k->bn_s[(BN_WIDTH * 2 - 1) * i + j]); ns0 = be.fr_mul_add(s, st[j], ns0); }
-            for (int kk = 1; kk < BN_WIDTH; kk++) { Fr s = be.fr_const(k->bn_s[(BN_WIDTH * 2 - 1) * i + BN_WIDTH + kk - 1]); st[kk] = be.fr_mul_add(s, st[0], st[kk]); }
+            for (int j = 0; j < BN_WIDTH; j++) { Fr s = be.fr_const(k->bn_s[bn_s_row(i) + j]); ns0 = be.fr_mul_add(s, st[j], ns0); }
+            for (int kk = 1; kk < BN_WIDTH; kk++) { Fr s = be.fr_const(k->bn_s[bn_s_row(i) + BN_WIDTH + kk - 1]); st[kk] = be.fr_mul_add(s, st[0], st[kk]); }
             st[0] = ns0;
         }
     }
@@ -331,15 +336,14 @@ template <class B> struct PoseidonBN254PermutationChip {
         for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) p[i * 4 + j] = be.fr_const(k->bn_p[i][j]);
         for (int i = 0; i < BN_FULL_ROUNDS / 2 - 1; i++) {
             exp5_state(st);
-            if (is_first) ark(st, (i + 1) * BN_WIDTH);
-            else ark(st, (BN_FULL_ROUNDS / 2 + 1) * BN_WIDTH + BN_PARTIAL_ROUNDS + i * BN_WIDTH);
+            ark(st, bn_c_full(is_first ? 0 : 1, i));
             mix(st, m);
         }
         exp5_state(st);
-        if (is_first) { ark(st, (BN_FULL_ROUNDS / 2) * BN_WIDTH); mix(st, p); } else mix(st, m);
+        if (is_first) { ark(st, bn_c_full(0, BN_FULL_ROUNDS / 2 - 1)); mix(st, p); } else mix(st, m);
     }
     HF void permute(Fr *st) {                                                                         // :190-203
-        if constexpr (B::kBnUnits) { be.bn_perm_unit(st, k); return; }      // device chain strands: the quad's sink computes / emits the permutation unit (coop.h)
+        if constexpr (B::kBnUnits) { be.bn_perm_unit(st, k); return; }      // device chain strands: the quad's sink computes / emits the permutation unit (bnquad.h)
         else if (be.bn_perm_unit(st, k)) return;
         be.bn_perm_begin();
         ark(st, 0); full_rounds(st, true); partial_rounds(st); full_rounds(st, false);

@@ -223,7 +223,7 @@ HD fr_t fr_mont_mul(const fr_t &A, const fr_t &B, uint64_t ninv) {
     return r;
 }
 // The same product on values that STAY in nine 29-bit limbs and are never reduced below r ("lazy" form; the values pass of the PoseidonBN254
-// Merkle paths, coop.h bn_values): no unpacking, no packing, no conditional subtraction.  R = 2^261 leaves 7 bits above r (2^253.6):
+// Merkle paths, bnquad.h bn_values): no unpacking, no packing, no conditional subtraction.  R = 2^261 leaves 7 bits above r (2^253.6):
 //   fr9_mont(a, b) = (a b + m r) / R < a b / R + r,
 // so the product of a value below 62 r (the worst the values pass forms: a state element after 56 lazy column updates) with a table constant
 // (< r) is below 1.4 r, and squares of anything below 6.2 r are below 1.3 r: every value stays below 2^261 without a single reduction

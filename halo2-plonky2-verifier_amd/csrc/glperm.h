@@ -1,4 +1,4 @@
-// glperm.h — the Goldilocks Poseidon permutation on VALUES, the lanes of one wavefront cooperating (device only; included by coop.h).
+// glperm.h — the Goldilocks Poseidon permutation on VALUES, the lanes of one wavefront cooperating (device only; included by glcoop.h).
 //
 // A wavefront that has its SIMD to itself issues one instruction every ~4 cycles, a wait state (s_nop) costs the same 4 cycles, and a DEPENDENT
 // instruction waits ~9 (tools/ubench/ubench_wave1.hip, profiles/r04_ubench_wave1.txt): a permutation that is one dependent chain is priced by its
@@ -142,10 +142,10 @@ __device__ __forceinline__ void glq_dense12(uint32_t limb, const uint32_t (&wl)[
 }
 
 // Goldilocks Poseidon (plonky2's fast form, hash/poseidon/permutation.rs:216-284) on VALUES.  Lane l of EVERY 16-lane row holds state element l & 15
-// (l & 15 < 12; the callers keep the four rows alike: coop.h sponge_challenge, coop_poseidon_permute) and returns its element of the output on every row
+// (l & 15 < 12; the callers keep the four rows alike: glcoop.h sponge_challenge, coop_poseidon_permute) and returns its element of the output on every row
 // (lanes 12..15 of a row compute along on element 11 and are ignored).
 // K: the constant block in LDS, M: the dense MDS rows, X: the derived tables of the partial rounds (stage_glp_consts<true>).
-// list_at / list_word: a word this lane leaves in memory on the way in (the strand's permutation list, coop.h sponge_permute; null: none) - issued here, it
+// list_at / list_word: a word this lane leaves in memory on the way in (the strand's permutation list, glcoop.h sponge_permute; null: none) - issued here, it
 // has the whole permutation to complete in; issued by the caller, the entry of this function would wait for it.
 __device__ __noinline__ uint64_t glp_permute_lanes(uint64_t x, lds64_t *K, lds64_t *M, lds64_t *X, int l, bool small, uint64_t *list_at = nullptr, uint64_t list_word = 0) {
     if (list_at) H2W_GSTORE64(reinterpret_cast<unsigned long long *>(list_at), list_word);

@@ -20,7 +20,7 @@ inline int upload_tmpl_cells(DevBuf<uint16_t> &d, const TemplateTable &tt) {
     for (size_t i = 0; i < tt.info.size(); i++) nc[i] = tt.info[i].ncells;
     return d.upload(nc);
 }
-// the Goldilocks-Poseidon constants, and behind them the derived tables of the values phase (glptab.h glp_aux_tables; coop.h stage_glp_consts reads them there)
+// the Goldilocks-Poseidon constants, and behind them the derived tables of the values phase (glptab.h glp_aux_tables; glcoop.h stage_glp_consts reads them there)
 struct GlpConsts : h2w_poseidon_consts_t { uint64_t aux[GLP_AUX_WORDS]; };
 static_assert(sizeof(GlpConsts) == sizeof(h2w_poseidon_consts_t) + GLP_AUX_WORDS * sizeof(uint64_t), "the derived tables start where the constants end");
 inline int upload_glp_consts(DevBuf<GlpConsts> &d, const h2w_poseidon_consts_t &k) {

@@ -23,7 +23,7 @@ struct h2w_plan {
     PlanEqualities eqs;
     DevBuf<fr_t> d_bn_tab; DevBuf<uint32_t> d_bn_tab9; DevBuf<FriTab> d_fri; uint64_t nunit = 0; DevBuf<rf::RowConst> d_rowk;     // PoseidonBN254 tables of this plan (handletabs.h upload_bn_tab)
     DevBuf<StrandTable> d_st;                         // device copy of st
-    bool small_mds = false;                           // Goldilocks-Poseidon MDS entries are tiny (coop.h glp_small_mds)
+    bool small_mds = false;                           // Goldilocks-Poseidon MDS entries are tiny (glcoop.h glp_small_mds)
     DevBuf<uint64_t> d_meta; DevBuf<GlpConsts> d_consts; DevBuf<uint16_t> d_ncells; DevBuf<fr_t> d_inv;
     static constexpr int EV_RING = 64, N_SIDE = 16;
     // event slots of a call: slot i < H2W_EV_COUNT is the public H2W_EV_* i (include/h2w.h: call start / end, prologue block complete, glue (+ Goldilocks

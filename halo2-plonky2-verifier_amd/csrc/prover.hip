@@ -138,18 +138,18 @@ HDN inline void bn_permute_m(const ProverConsts *K, fr_t *st) {
         if (half == 1) {
 #pragma unroll 1
             for (int r = 0; r < BN_PARTIAL_ROUNDS; r++) {
-                st[0] = fr_add(bn_pow5(st[0], ni), B.c[(BN_FULL_ROUNDS / 2 + 1) * BN_WIDTH + r]);
-                fr_t ns0 = mmul(B.s[7 * r], st[0], ni);
+                st[0] = fr_add(bn_pow5(st[0], ni), B.c[bn_c_partial(r)]);
+                fr_t ns0 = mmul(B.s[bn_s_row(r)], st[0], ni);
 #pragma unroll
-                for (int j = 1; j < 4; j++) ns0 = fr_add(ns0, mmul(B.s[7 * r + j], st[j], ni));
+                for (int j = 1; j < 4; j++) ns0 = fr_add(ns0, mmul(B.s[bn_s_row(r) + j], st[j], ni));
 #pragma unroll
-                for (int kk = 1; kk < 4; kk++) st[kk] = fr_add(st[kk], mmul(B.s[7 * r + 4 + kk - 1], st[0], ni));
+                for (int kk = 1; kk < 4; kk++) st[kk] = fr_add(st[kk], mmul(B.s[bn_s_row(r) + BN_WIDTH + kk - 1], st[0], ni));
                 st[0] = ns0;
             }
         }
 #pragma unroll 1
         for (int i = 0; i < BN_FULL_ROUNDS / 2 - 1; i++) {
-            const int it = half == 0 ? (i + 1) * BN_WIDTH : (BN_FULL_ROUNDS / 2 + 1) * BN_WIDTH + BN_PARTIAL_ROUNDS + i * BN_WIDTH;
+            const int it = bn_c_full(half, i);
 #pragma unroll
             for (int j = 0; j < 4; j++) st[j] = fr_add(bn_pow5(st[j], ni), B.c[it + j]);
             bn_mix(st, B.m, ni);

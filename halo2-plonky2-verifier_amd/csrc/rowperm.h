@@ -1,7 +1,7 @@
 // rowperm.h — one PoseidonBN254 permutation (hash/poseidon_bn254/permutation.rs:83-203; circomlib's optimised t = 4 form) ON VALUES, by one
 // wavefront: the four 16-lane rows hold the four state elements, one 29-bit limb per lane (rowfr.h).  The values pass of the two-pass Merkle
 // paths (k_merkle_bn_values_row): one wavefront per (proof, query, tree) walks the path; every permutation is ~31 k wavefront instructions
-// instead of the 78 k of the four-lanes-per-path form (coop.h bn_values), and a path is as deep as before: 18 permutations.
+// instead of the 78 k of the four-lanes-per-path form (bnquad.h bn_values), and a path is as deep as before: 18 permutations.
 //
 // Schedule of a partial round (three product slots; every row runs one product per slot, rowfr.h mont):
 //   slot 1   row 0  X2 = s0 s0        | rows k  U_k = S'_k s0' of round r - 1   (its column update: s_k += U_k)
@@ -10,7 +10,7 @@
 //   s0' = X5 + c;   new s0 = T0 + S_0 c + W_1 + W_2 + W_3   (S_0 s0' = X4 (s0 S_0) + S_0 c: the row product does not wait for X5; S_0 c from the table)
 // The operand a slot replicates (rowfr.h A9) is a table constant (nine LDS dwords per lane, the same on the 16 lanes of a row) except on the
 // rows that multiply two values: there it is the nine limbs of ONE value of the wavefront (s0, X2, X4: nine v_readlane).
-// Sizes of the values: as at coop.h bn_values (the algebra is the same); limbs: a product comes out below 2^29 + 8, a sum of two is a valid
+// Sizes of the values: as at bnquad.h bn_values (the algebra is the same); limbs: a product comes out below 2^29 + 8, a sum of two is a valid
 // operand, a sum of more goes through rowfr.h tighten.
 //
 // What it leaves for the emission pass: the unit's output state (canonical, as before) and the S-box values x^2, x^4, x^5 of the 56 partial
@@ -96,9 +96,9 @@ RF_FN void bn_permute_rows_as(fr_t st[4], const RowConst &K, const LaneK &L, uin
             V s0p_all = V(0u);                                                                 // s0' = s0^5 + c of the previous round (rows 1..3); nothing is pending before round 0
             struct RoundK { A9 kp, k2, k1; V kc, kx; };                                        // the table entries of a round, read a round ahead
             auto round_k = [&](int r) {
-                const uint32_t ix = (uint32_t)(BK_S + (BN_WIDTH * 2 - 1) * r), ic = (uint32_t)(BK_C + (BN_FULL_ROUNDS / 2 + 1) * BN_WIDTH + r);
+                const uint32_t ix = (uint32_t)(BK_S + bn_s_row(r)), ic = (uint32_t)(BK_C + bn_c_partial(r));
                 RoundK k;
-                k.kp = ld_rep(V(ix - (BN_WIDTH * 2 - 1) + BN_WIDTH) + km1);                    // S'_k of round r - 1 (round 0: s0' = 0, the entry read is in the table)
+                k.kp = ld_rep(V(ix - bn_s_row(1) + BN_WIDTH) + km1);                    // S'_k of round r - 1 (round 0: s0' = 0, the entry read is in the table)
                 k.k2 = ld_rep(V(ix) + sel(L.row1, V(0u), row));                                // row 1: S_0, rows 2, 3: S_2, S_3
                 k.k1 = ld_rep(V(ix + 1));                                                      // row 1: S_1
                 k.kc = ld_dist(V(ic), L); k.kx = ld_dist(V((uint32_t)(BK9_X + r)), L);
@@ -140,7 +140,7 @@ RF_FN void bn_permute_rows_as(fr_t st[4], const RowConst &K, const LaneK &L, uin
                 kr = kn;
             }
             {   // the last round's column update
-                const A9 A = ld_rep(V((uint32_t)(BK_S + (BN_WIDTH * 2 - 1) * (BN_PARTIAL_ROUNDS - 1) + BN_WIDTH)) + km1);
+                const A9 A = ld_rep(V((uint32_t)(BK_S + bn_s_row(BN_PARTIAL_ROUNDS - 1) + BN_WIDTH)) + km1);
                 const V U = mont(A, s0p_all, K, L);
                 S = sel(L.row0, S, tighten(S + U));
             }
@@ -151,7 +151,7 @@ RF_FN void bn_permute_rows_as(fr_t st[4], const RowConst &K, const LaneK &L, uin
         for (int r = 0; r < BN_FULL_ROUNDS / 2; r++) {
             const bool last = r == BN_FULL_ROUNDS / 2 - 1;
             const MixK mk = mix_k(half == 0 && last ? BK_P : BK_M);
-            const V ck = ld_dist(V((uint32_t)(BK_C + (half == 0 ? (r + 1) * BN_WIDTH : (BN_FULL_ROUNDS / 2 + 1) * BN_WIDTH + BN_PARTIAL_ROUNDS + r * BN_WIDTH))) + row, L);
+            const V ck = ld_dist(V((uint32_t)(BK_C + bn_c_full(half, r))) + row, L);
             sbox();
             if (!(half == 1 && last)) S = S + ck;
             mix(mk);

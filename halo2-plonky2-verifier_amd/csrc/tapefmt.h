@@ -118,7 +118,7 @@ struct TapeLimits {
     uint32_t nglp = 0, nbnp = 0;                         // fused permutations of the segment (its list slots)
     bool fusing_gl = false, fusing_bn = false;           // the plan's flags
     uint64_t glp_block_cells = 0;                        // cells of a Goldilocks permutation's record block
-    size_t glp_recs = 0, glp_recs_kernel = 0;            // its records as the lowering laid them out; as the emission kernel writes them (coop.h GLP_RECS)
+    size_t glp_recs = 0, glp_recs_kernel = 0;            // its records as the lowering laid them out; as the emission kernel writes them (glcoop.h GLP_RECS)
     uint64_t bn_perm_cells = 0;                          // cells of a PoseidonBN254 permutation (bntab.h BN_PERM_CELLS)
 };
 // empty: the tape is well formed; else "internal: malformed device tape (template t, word w, op o)" (w: the first word of the op) or "... does not end"

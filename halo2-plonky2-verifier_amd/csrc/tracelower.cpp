@@ -5,13 +5,14 @@
 // one-word input ... produced it), never on the traced values: the layout of the records must not depend on the proof.
 // What brings HIP into a file without a kernel: field.h marks its functions __host__ __device__ once the unit is compiled as HIP (build.sh compiles
 // every unit that way, and the annotations need the runtime header in front), and glp_block_layout instantiates ValBackend<LayoutSink> and the
-// permutation chip over it (valbackend.h; coop.h for GLP_RECS), templates shared with the device sinks.  No function of the runtime is called.
+// permutation chip over it (valbackend.h; glcoop.h for GLP_RECS, bntab.h for BN_PERM_CELLS), templates shared with the device sinks.  No function of the runtime is called.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstring>
 #include "tracelower.h"
 #include "valbackend.h"
-#include "coop.h"
+#include "glcoop.h"
+#include "bntab.h"
 
 namespace h2w {
 static_assert(GLPERM_IO == (uint32_t)SPONGE_WIDTH && BNPERM_IO == (uint32_t)BN_WIDTH, "tapefmt.h states the permutations' widths on its own");

@@ -264,7 +264,7 @@ template <class Sink> struct ValBackend {
     }
     HF void bn_perm_begin() { sink.bn_perm_begin(zero_cached); }
     HF void bn_perm_end() { sink.bn_perm_end(zero_cached); unit_idx++; }
-    // ---------------------------------------------------------------- the sponge of a device prologue wavefront (kDevSponge; coop.h)
+    // ---------------------------------------------------------------- the sponge of a device prologue wavefront (kDevSponge; glcoop.h)
     HF void note_cap_hash(uint64_t w) { sink.note_cap_hash(w); }      // a cap hash is about to be decomposed into limbs (the shape compiler lists it for the load kernel)
     HF void sponge_init() { sink.sponge_init(); }
     HF void sponge_observe(Gl t) { if (!sink.sponge_observe(t)) fail(3); }

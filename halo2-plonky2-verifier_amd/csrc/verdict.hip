@@ -11,7 +11,7 @@
 //   k_verdict_glue          one lane per (proof, query): Verifier::query_round on a sink without cells - the fold steps' consistency checks and the
 //                           final polynomial's evaluation
 //   k_verdict_merkle_gl     Goldilocks caps: one wavefront per (proof, query, tree), permutations on glp_permute_lanes (k_merkle_gl_values without list or records)
-//   k_verdict_merkle_bn     PoseidonBN254 caps: four lanes per (proof, query, tree) on the lazy nine-limb values walk (coop.h QuadSinkT bn_values, QUAD_VERDICT:
+//   k_verdict_merkle_bn     PoseidonBN254 caps: four lanes per (proof, query, tree) on the lazy nine-limb values walk (bnquad.h QuadSinkT bn_values, QUAD_VERDICT:
 //                           no unit states, no S-box values; the cap lookup's value is taken)
 //   k_verdict_merkle_row    PoseidonBN254 caps, few paths (h2w_fri_verdict_batch_ex, H2W_VERDICT_FORM_ROW): one wavefront per (proof, query, tree), the four rows
 //                           of the wavefront = the four state elements (rowfr.h; rowperm.h bn_permute_rows<false>: the permutation of k_merkle_bn_values_row

@@ -1,5 +1,5 @@
 // Host check of the lazy nine-limb Montgomery arithmetic (csrc/field.h fr9_t) that the values pass of the PoseidonBN254 Merkle paths runs on:
-// products of un-reduced representatives (a + k r, up to the bounds written at coop.h bn_values) agree with the canonical product, stay below
+// products of un-reduced representatives (a + k r, up to the bounds written at bnquad.h bn_values) agree with the canonical product, stay below
 // a b / R + r < 2^261, and come out with normalised limbs; a sum of two normalised values is a valid operand against a normalised one.
 // Built and run by tests/test_field_lazy.py (g++; field.h compiles as plain C++ on the host).
 #include <cstdio>
@@ -43,7 +43,7 @@ int main() {
     int fails = 0; int max_bits = 0;
     // pack / unpack
     for (int it = 0; it < 1000; it++) { const fr_t a = rnd_fr(); if (!eq(fr9_pack(fr9_from(a)), a)) { printf("pack(from(a)) != a\n"); fails++; } }
-    // products of un-reduced representatives: (multiple of r on a, on b) as far as the values pass goes (coop.h bn_values) and beyond
+    // products of un-reduced representatives: (multiple of r on a, on b) as far as the values pass goes (bnquad.h bn_values) and beyond
     const unsigned ks[][2] = {{0, 0}, {1, 1}, {6, 6}, {7, 0}, {63, 0}, {63, 1}, {25, 5}, {63, 63}, {100, 1}};
     for (auto &k : ks)
         for (int it = 0; it < 300; it++) {

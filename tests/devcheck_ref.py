@@ -233,8 +233,8 @@ def glq_check(cases, out):
 # ------------------------------------------------------------------------------------------------ (b) glq_mds_small, glq_dense12
 @functools.lru_cache(None)
 def small_mds_bits():
-    """The bound glp_small_mds (coop.h) admits: circulant and diagonal entries below 2^bits each."""
-    src = open(os.path.join(CSRC, "coop.h")).read()
+    """The bound glp_small_mds (glcoop.h) admits: circulant and diagonal entries below 2^bits each."""
+    src = open(os.path.join(CSRC, "glcoop.h")).read()
     m = re.search(r"inline bool glp_small_mds\(.*?\{(.*?)\n\}", src, flags=re.S)
     sh = set(re.findall(r">= \(1ull << (\d+)\)", m.group(1)))
     assert len(sh) == 1, sh
@@ -316,7 +316,7 @@ def mds_check(cases, out):
 
 
 # ------------------------------------------------------------------------------------------------ the constant block (include/h2w.h h2w_poseidon_consts_t) as words
-KO = dict(arc=0, circ=360, diag=372, first=384, prc=396, init=418, what=539, vs=781)      # coop.h KO_*
+KO = dict(arc=0, circ=360, diag=372, first=384, prc=396, init=418, what=539, vs=781)      # glcoop.h KO_*
 GL_WORDS = 1023
 BO = dict(c=GL_WORDS, s=GL_WORDS + 88 * 4, m=GL_WORDS + 480 * 4, p=GL_WORDS + 496 * 4)
 KW = GL_WORDS + 512 * 4

@@ -118,7 +118,7 @@ static int run_mds(const std::vector<uint64_t> &in, const uint64_t *din, std::ve
 
 // ---------------------------------------------------------------------------------------------- (c) glp_permute_lanes, one wavefront per case
 // case (16 words): table, small, n, list, state[12]  ->  80 words: every lane's output of the n-th permutation, then the 13 words the first permutation lists
-// (lane 0: a tag, lanes 1..12: the input state, as coop.h coop_poseidon_permute lists them; untouched when `list` is 0)
+// (lane 0: a tag, lanes 1..12: the input state, as glcoop.h coop_poseidon_permute lists them; untouched when `list` is 0)
 __global__ __launch_bounds__(64) void k_perm(const uint64_t *tabs, const uint64_t *cases, uint64_t *out) {
     const uint64_t *cs = cases + (size_t)blockIdx.x * 16;
     const int tab = __builtin_amdgcn_readfirstlane((int)cs[0]), small = __builtin_amdgcn_readfirstlane((int)cs[1]), n = __builtin_amdgcn_readfirstlane((int)cs[2]),

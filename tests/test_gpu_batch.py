@@ -82,7 +82,7 @@ def test_values_pass_forms_on_the_published_tables_and_on_valid_proofs(h2w, h2w_
 @pytest.mark.parametrize("table", ["full_width", "largest_small", "just_beyond_small"])
 def test_goldilocks_mds_tables_of_every_width(h2w, h2w_api, oracle, consts, mode, table):
     """The values phase walks a small-entry Goldilocks MDS matrix as two 64-bit sums and one reduction (csrc/glperm.h glq_mds_small: entries below 2^26,
-    coop.h glp_small_mds) and any other with one multiply-add per entry: both paths, and the bound between them, against the oracle - the synthetic and
+    glcoop.h glp_small_mds) and any other with one multiply-add per entry: both paths, and the bound between them, against the oracle - the synthetic and
     the published tables are all tiny-entry ones.  Challenger permutations in both hash modes, Merkle permutations too with Goldilocks caps."""
     ko0, _ = consts
     ko = oracle.Consts.from_buffer_copy(bytes(ko0))

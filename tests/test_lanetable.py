@@ -49,7 +49,7 @@ def test_the_ownership_helper_agrees_with_shard_block(check_output):
 
 def test_the_lane_table_header_needs_no_hip():
     """lanetable.h and the header of the ownership rule are plain C++ (the check above is compiled by g++): the format and field headers, nothing
-    of the runtime, no coop.h."""
+    of the runtime, no device sink (glcoop.h, bnquad.h)."""
     allowed = {"lanetable.h": {"cstdint", "vector", "tapefmt.h", "shardmap.h"}, "shardmap.h": {"stdint.h", "field.h"}}
     for name, ok in allowed.items():
         src = open(os.path.join(CSRC, name)).read()

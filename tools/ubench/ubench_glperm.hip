@@ -53,7 +53,7 @@ int main() {
     h2w_poseidon_consts_t *dk; uint64_t *io; long long *cyc;
     CK(hipMalloc(&dk, sizeof(h2w_poseidon_consts_t) + GLP_AUX_WORDS * 8)); CK(hipMalloc(&io, 24 * 8)); CK(hipMalloc(&cyc, 8));
     int bad_total = 0;
-    for (int cfg = 0; cfg < 12; cfg++) {      // 4..11: full-width entries on the diagonal too | 0: tiny MDS entries (plonky2's are <= 41) | 1: entries up to 2^26 - 1 (the small path's bound, coop.h glp_small_mds) | 2: 64-bit entries (the dense path) | 3: extreme words
+    for (int cfg = 0; cfg < 12; cfg++) {      // 4..11: full-width entries on the diagonal too | 0: tiny MDS entries (plonky2's are <= 41) | 1: entries up to 2^26 - 1 (the small path's bound, glcoop.h glp_small_mds) | 2: 64-bit entries (the dense path) | 3: extreme words
         std::vector<uint64_t> K(sizeof(h2w_poseidon_consts_t) / 8, 0);
         for (int i = 0; i < GLP_CONST_WORDS; i++) K[i] = cfg == 3 ? (i % 3 == 0 ? GL_P - 1 : i % 3 == 1 ? GL_P - 1 - (rnd() & 0xFFFF) : rnd() % GL_P) : rnd() % GL_P;
         for (int i = 0; i < 12; i++) {
