@@ -77,6 +77,7 @@ _fr = C.POINTER(Fr)
 H2W_TRACE_FUSE_GL_PERMUTE = 1      # flags of h2w_plan_from_trace_ex (include/h2w.h)
 H2W_TRACE_FUSE_BN_PERMUTE = 2
 H2W_TRACE_OUTPUT_FORMS = 8         # (4 is unassigned)
+H2W_TRACE_SPLIT_SELECTS = 32       # (16 is unassigned)
 # batched chip ops (include/h2w.h 2c): the hash and Merkle ops of h2w_chipbatch_new_hash, and the option of h2w_chipbatch_configure
 H2W_OP_GL_PERMUTE, H2W_OP_BN_PERMUTE, H2W_OP_HASH_NO_PAD, H2W_OP_TWO_TO_ONE, H2W_OP_MERKLE_VERIFY = 9, 10, 11, 12, 13
 H2W_CHIPBATCH_MAX_N_IN = 4096

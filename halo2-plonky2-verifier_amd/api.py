@@ -7,7 +7,7 @@ argument meaning and error behaviour (a non-zero status raises H2WError where th
 """
 import ctypes as C
 
-from . import (Assigned, Fr, H2W_CHIPBATCH_OPT_CHUNK, H2W_TRACE_FUSE_BN_PERMUTE, H2W_TRACE_FUSE_GL_PERMUTE, H2W_TRACE_OUTPUT_FORMS, H2WError, PoseidonConsts, Shape, _ck, last_error, lib)
+from . import (Assigned, Fr, H2W_CHIPBATCH_OPT_CHUNK, H2W_TRACE_FUSE_BN_PERMUTE, H2W_TRACE_FUSE_GL_PERMUTE, H2W_TRACE_OUTPUT_FORMS, H2W_TRACE_SPLIT_SELECTS, H2WError, PoseidonConsts, Shape, _ck, last_error, lib)
 
 GL_P = 0xFFFFFFFF00000001
 FR_MODULUS = 21888242871839275222246405745257275088548364400416034343698204186575808495617
@@ -257,7 +257,7 @@ class Plan:
         self.num_chain_cells = int(self.L.h2w_plan_num_chain_cells(self.p))
 
     @classmethod
-    def from_trace(cls, ctx, proof_words, parallel_scopes=("verify_query_round", "verify_proof_to_cap_with_cap_index"), device_id=0, fuse_consts=None, fuse_bn=False, fuse_gl=True, output_forms=False):
+    def from_trace(cls, ctx, proof_words, parallel_scopes=("verify_query_round", "verify_proof_to_cap_with_cap_index"), device_id=0, fuse_consts=None, fuse_bn=False, fuse_gl=True, output_forms=False, split_selects=False):
         """h2w_plan_from_trace: the tape `ctx` recorded (Context.trace_begin, then ONE run through the level-1 / level-2 calls) as a plan that
         h2w_fri_witness_batch replays on other proofs of the shape.  parallel_scopes: the #[count] scopes whose instances are independent
         (fri/mod.rs:488-501, merkle/mod.rs:57-78); the library checks the claim on the tape.  The depth-1 instances (the query rounds) are the
@@ -268,12 +268,14 @@ class Plan:
         fuse_bn (with fuse_consts): H2W_TRACE_FUSE_BN_PERMUTE as well - the PoseidonBN254 permutations on these tables run as one op each, their cells
         written by a kernel of their own; trace_info_bn() says how many did.  fuse_gl=False with fuse_bn: the PoseidonBN254 flag alone.
         output_forms: H2W_TRACE_OUTPUT_FORMS (with or without fuse_consts) - the lowering also maps the plan's direct cells, and set_output_form,
-        direct_cells and record_ranges work as on a compiled plan."""
+        direct_cells and record_ranges work as on a compiled plan.
+        split_selects: H2W_TRACE_SPLIT_SELECTS (with or without fuse_consts) - a select_array_by_indicator / select_from_idx on 52 to 64 wide entries
+        (a PoseidonBN254 verifier with cap_height 6), refused otherwise, is lowered as consecutive parts; the stream is that of the one op."""
         L = lib()
         names = (C.c_char_p * len(parallel_scopes))(*[s.encode() for s in parallel_scopes])
         if fuse_bn and fuse_consts is None:
             raise H2WError("Plan.from_trace: fuse_bn needs fuse_consts")
-        forms = H2W_TRACE_OUTPUT_FORMS if output_forms else 0
+        forms = (H2W_TRACE_OUTPUT_FORMS if output_forms else 0) | (H2W_TRACE_SPLIT_SELECTS if split_selects else 0)
         if fuse_consts is not None:
             flags = (H2W_TRACE_FUSE_GL_PERMUTE if fuse_gl else 0) | (H2W_TRACE_FUSE_BN_PERMUTE if fuse_bn else 0) | forms
             h = L.h2w_plan_from_trace_ex(ctx.p, proof_words, names, len(parallel_scopes), device_id, C.byref(fuse_consts), flags)

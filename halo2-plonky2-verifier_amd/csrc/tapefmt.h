@@ -3,7 +3,7 @@
 //
 // A tape is a sequence of ops, word 0 of each = op | n << 8 | aux << 16 | (words of the op) << 24, then its operand refs, then (ops with results)
 // the first output slot, then (some ops) trailing words; it ends in DOP_END.  OP_DESC below gives that shape per op; the ops it cannot express
-// (DOP_FETCH, DOP_GLOPRUN, the trailing words of the fused permutations) have their few lines in tape_check next to it.  The interpreter keeps its
+// (DOP_FETCH, DOP_GLOPRUN, the trailing words of the fused permutations, the chain of a split select's parts) have their few lines in tape_check next to it.  The interpreter keeps its
 // own hand-written decode (its scalar-register window depends on it) and takes only the names from here.
 #pragma once
 #include <cstdint>
@@ -38,6 +38,11 @@ enum { DOP_END = 0, DOP_SKIP, DOP_CONST1, DOP_FRCELL, DOP_LOADW, DOP_LOADW_DIV, 
        DOP_GLPERM,         // a verified Goldilocks-Poseidon permutation as one op (H2W_TRACE_FUSE_GL_PERMUTE): [hdr][12 operands][first output slot][list slot][cells of its record block]
        DOP_BNPERM,         // a verified PoseidonBN254 permutation as one op (H2W_TRACE_FUSE_BN_PERMUTE): [hdr][4 operands][first output slot (4 x 4 slots)][list slot][its cells]
        DOP_COUNT };
+// A wide select_by_indicator whose fetched operands do not fit the ring is cut at entry boundaries into PARTS (H2W_TRACE_SPLIT_SELECTS): consecutive
+// DOP_FR_SELIND ops, each over a contiguous run of the entries and their indicators, its own DOP_FETCH ops in front of it.  The aux byte of a part
+// (0: a whole select) says where it stands in the chain; the running sum passes from a part to the next in the lane's registers, it has no value slot.
+constexpr uint32_t SELIND_CONTINUES = 1;      // not the first part: no leading zero cell, the sum starts from the previous part's
+constexpr uint32_t SELIND_CONTINUED = 2;      // not the last part: another follows (nothing but its DOP_FETCH ops in between); its result is NO_SLOT
 constexpr uint32_t GLPERM_WORDS = 16, BNPERM_WORDS = 8;
 constexpr uint32_t GLPERM_IO = 12, BNPERM_IO = 4;      // the states of the two permutations (chips.h SPONGE_WIDTH, BN_WIDTH: asserted where both are seen)
 // a list entry of a fused PoseidonBN254 permutation: {first cell of its block in the proof's stream, zero-cell flag (1: the Context's load_zero cell is
@@ -90,7 +95,7 @@ constexpr OpDesc OP_DESC[DOP_COUNT] = {
     /* DOP_FR_SELECT    */ op_fixed(3, RS_FIXED, 4),                       // reads 4, 4, 1
     /* DOP_IDX2IND      */ op_array(1),                                    // reads 1  (NO_SLOT passes for its n results although the interpreter stores them unconditionally: the lowering never emits it)
     /* DOP_SELIND       */ op_list(2, 1, 1),                               // reads 1 x n, 1 x n
-    /* DOP_FR_SELIND    */ op_list(2, 4, 1),                               // reads 4 x n, 1 x n
+    /* DOP_FR_SELIND    */ op_list(2, 4, 1),                               // reads 4 x n, 1 x n; aux: SELIND_* bits (a part of a split select: tape_check holds the chain)
     /* DOP_NUM2BITS     */ op_array(1),                                    // reads 1  (NO_SLOT: as DOP_IDX2IND)
     /* DOP_BITS2NUM     */ op_list(1, 1, 0),                               // reads 1 x n
     /* DOP_DECOMP565    */ op_fixed(1, RS_FIXED, 5),                       // reads 4  (NO_SLOT: as DOP_IDX2IND)
@@ -147,8 +152,19 @@ inline std::string tape_check(const uint32_t *T, size_t nwords, const TapeLimits
     auto okout = [&](uint32_t slot, uint32_t nsl, bool no_slot_ok) { return slot == NO_SLOT ? no_slot_ok : (uint64_t)slot + nsl <= M.nslots; };
     size_t pc = 0; bool ended = false;
     uint32_t fetched = 0;      // slots the DOP_FETCH ops in front of one op have written: beyond RING_K the later ones overwrite the earlier ones (slot mod RING_K) before the op reads them
+    // the parts of a split select: a "continued" part is open until the next op that is no DOP_FETCH, which must be a "continues" part (the
+    // interpreter carries the sum between exactly those two); a broken chain is reported at the part that is left without its neighbour
+    const std::string selind = ", op " + std::to_string((int)DOP_FR_SELIND) + ")";
+    bool open = false; size_t open_at = 0;
+    auto broken = [&](size_t at) { return "internal: malformed device tape (template " + std::to_string(M.tmpl) + ", word " + std::to_string(at) + selind; };
     while (pc < nwords) {
         const uint32_t h = T[pc], op = h & 0xff, n = (h >> 8) & 0xff, len = op == DOP_GLOPRUN ? 2 + 4 * n : h >> 24; bool ok = len >= 1 && pc + len <= nwords;
+        if (op != DOP_FETCH) {
+            const bool continues = op == DOP_FR_SELIND && (((h >> 16) & 0xff) & SELIND_CONTINUES) != 0;
+            if (open && !continues) return broken(open_at);
+            if (!open && continues) return broken(pc);
+            open = false;
+        }
         if (op == DOP_END) { ended = ok && pc + 1 == nwords; break; }
         const uint32_t *R = T + pc;
         fetched = op == DOP_FETCH ? fetched + n : 0;
@@ -163,6 +179,12 @@ inline std::string tape_check(const uint32_t *T, size_t nwords, const TapeLimits
             const uint32_t nops = D.nops + D.nops_per_n * n;
             for (uint32_t k = 0; ok && k < nops; k++) { const uint32_t w = (R[1 + k] >> 27) & 3u; ok = okref(R[1 + k]) && (D.wcons == WC_ANY || (D.wcons == WC_IS64) == (w == W64)); }
             if (ok && D.res != RS_NONE) ok = okout(R[1 + nops], D.res == RS_N ? n : D.res_slots, D.no_slot_ok);
+            // aux of the two selects: the narrow one is never split; a part that is continued stores no result (the last part does)
+            if (ok && op == DOP_SELIND) ok = ((h >> 16) & 0xff) == 0;
+            if (ok && op == DOP_FR_SELIND) {
+                const uint32_t aux = (h >> 16) & 0xff; ok = aux <= (SELIND_CONTINUES | SELIND_CONTINUED);
+                if (ok && (aux & SELIND_CONTINUED)) { ok = R[1 + nops] == NO_SLOT; open = true; open_at = pc; }
+            }
             // the trailing words of the fused permutations: the plan was built with the flag; the op's slot in the segment's list; its cells
             if (ok && op == DOP_GLPERM) ok = M.fusing_gl && M.glp_recs == M.glp_recs_kernel && R[14] < M.nglp && R[15] == (uint32_t)M.glp_block_cells;
             if (ok && op == DOP_BNPERM) ok = M.fusing_bn && R[6] < M.nbnp && R[7] == (uint32_t)M.bn_perm_cells;

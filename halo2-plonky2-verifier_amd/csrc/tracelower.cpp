@@ -87,7 +87,8 @@ static uint64_t glp_block_layout(const TemplateTable &tt, int L, const h2w_posei
 }
 // fuse: the stretches to lower as ONE op (by their first trace op), glp_meta their record block; cn: look for stretches instead (-> found);
 // capture: the lowered ops of the root segment as they are (the canonical tape is made from them)
-static void lower_pass(const Trace *tr, int L, TemplateTable &tt, const char *const *parallel_scopes, size_t n_scopes, Lowered &LW,
+// split_selects: a wide select whose fetched operands do not fit the ring is emitted as parts (tapefmt.h SELIND_*) instead of refused
+static void lower_pass(const Trace *tr, int L, TemplateTable &tt, const char *const *parallel_scopes, size_t n_scopes, Lowered &LW, bool split_selects,
                         const std::map<size_t, Stretch> *fuse, const std::vector<uint64_t> *glp_meta, const std::vector<const Canon *> *cns, std::vector<Stretch> *found, std::vector<NormOp> *capture) {
     std::string &err = LW.err;
     auto bad = [&](const std::string &m) { if (err.empty()) err = m; };
@@ -320,28 +321,56 @@ static void lower_pass(const Trace *tr, int L, TemplateTable &tt, const char *co
                 return false;
             };
             auto words_of = [&](uint32_t r) { const int k = ref_kind(r); return (uint32_t)(k == RK_LITFR ? 4 : k == RK_INPUT ? (ref_width(r) == WFR ? 4 : 1) : SLOTS_OF[ref_width(r)]); };
-            uint32_t temps = 0;
-            for (;;) { uint32_t need = 0; for (uint32_t k2 = 0; k2 < count; k2++) { const uint32_t r = T[op_at + first + k2]; if (!in_lds(r, S.nslots + temps)) need += words_of(r); } if (need == temps) break; temps = need; }
+            // the slots to fetch for the operand words R[0, m): a fixed point (the temporaries push the oldest ring slots out, which may be operands too)
+            auto fetched_slots = [&](const uint32_t *R, uint32_t m) { uint32_t t = 0; for (;;) { uint32_t need = 0; for (uint32_t k2 = 0; k2 < m; k2++) if (!in_lds(R[k2], S.nslots + t)) need += words_of(R[k2]); if (need == t) return t; t = need; } };
+            // R[0, m) become fast refs in place, the DOP_FETCH ops of those not at hand go to `fetches`; the segment's slots move behind the temporaries
+            auto to_fast_refs = [&](uint32_t *R, uint32_t m, uint32_t temps, std::vector<uint32_t> &fetches) {
+                const uint32_t nf = S.nslots + temps; uint32_t tslot = S.nslots;
+                for (uint32_t k2 = 0; k2 < m; k2++) {
+                    const uint32_t r = R[k2]; const int k = ref_kind(r), w = ref_width(r); uint32_t fr2;
+                    if (in_lds(r, nf)) fr2 = k == RK_LOCAL ? fastref_ring(w, ref_idx(r)) : k == RK_LIT64 ? fastref_pool(W64, LDS_POOL64 + ref_idx(r) * 8) : fastref_pool(WFR, LDS_POOLFR + ref_idx(r) * 32);
+                    else {
+                        const uint32_t nw = words_of(r);
+                        fetches.push_back(DOP_FETCH | (nw << 8) | (3u << 24)); fetches.push_back(r); fetches.push_back(tslot);
+                        fr2 = fastref_ring(nw == 4 ? WFR : nw == 2 ? W128 : W64, tslot); tslot += nw;
+                    }
+                    R[k2] = fr2;
+                }
+                S.nslots = nf;
+            };
+            const uint32_t temps = fetched_slots(T.data() + op_at + first, count);
             // the ring is RING_K slots (slot mod RING_K): with more temporaries than that the later fetches overwrite the earlier ones before the op reads
             // them.  (The op's own result slots may alias them: every op reads all its operands before it stores a result.)
-            if (temps > RING_K) {
+            if (temps > RING_K && split_selects && (T[op_at] & 0xff) == DOP_FR_SELIND) {
+                // The wide select walks its entries in order and carries one sum: cut at an entry boundary it is two ops that share nothing else.  Parts
+                // [e0, e1) in order, each the longest run whose own fetches fit (a shorter run never needs more: the fewest parts), each behind the slots
+                // the parts before it took - so a part fetches what their temporaries pushed out of the ring, its indicators included.  The result slot
+                // is the unsplit op's (taken above) and goes with the last part; the sum in between has no slot.
+                const uint32_t n = count / 2, res = T[op_at + first + count];
+                const std::vector<uint32_t> ops(T.begin() + (long)(op_at + first), T.begin() + (long)(op_at + first + count));
+                T.resize(op_at);
+                for (uint32_t e0 = 0; e0 < n && err.empty();) {
+                    std::vector<uint32_t> part, fetches; uint32_t e1 = n, pt = 0;
+                    for (;; e1--) {
+                        part.assign(ops.begin() + e0, ops.begin() + e1); part.insert(part.end(), ops.begin() + n + e0, ops.begin() + n + e1);
+                        pt = fetched_slots(part.data(), (uint32_t)part.size());
+                        if (pt <= RING_K || e1 == e0 + 1) break;
+                    }
+                    if (pt > RING_K) { bad("internal: one entry of a split select_by_indicator does not fit the value slots a lane keeps at hand"); break; }
+                    to_fast_refs(part.data(), (uint32_t)part.size(), pt, fetches);
+                    const uint32_t m = e1 - e0, aux = (e0 ? SELIND_CONTINUES : 0u) | (e1 < n ? SELIND_CONTINUED : 0u);
+                    T.insert(T.end(), fetches.begin(), fetches.end());
+                    T.push_back(DOP_FR_SELIND | (m << 8) | (aux << 16) | ((2 * m + 2) << 24)); T.insert(T.end(), part.begin(), part.end()); T.push_back(e1 < n ? NO_SLOT : res);
+                    LW.n_select_parts++; e0 = e1;
+                }
+            } else if (temps > RING_K) {
                 bad((o.code == TR_SELECT_BY_INDICATOR ? std::string("select_by_indicator") : "trace op " + std::to_string((int)o.code) + " (device op " + std::to_string(T[op_at] & 0xff) + ")") + " with " + std::to_string(count) + " operands: " + std::to_string(temps) + " slots of them have to be fetched (values of an enclosing scope, values computed more than " +
                     std::to_string(RING_K) + " slots earlier, proof words, far constants), more than the " + std::to_string(RING_K) + " value slots a lane keeps at hand");
                 break;
+            } else {
+                std::vector<uint32_t> fetches; to_fast_refs(T.data() + op_at + first, count, temps, fetches);
+                if (!fetches.empty()) { T.insert(T.begin() + (long)op_at, fetches.begin(), fetches.end()); if (S.last_const_at == (long)op_at) S.last_const_at += (long)fetches.size(); }
             }
-            std::vector<uint32_t> fetches; const uint32_t nf = S.nslots + temps; uint32_t tslot = S.nslots;
-            for (uint32_t k2 = 0; k2 < count; k2++) {
-                const uint32_t r = T[op_at + first + k2]; const int k = ref_kind(r), w = ref_width(r); uint32_t fr2;
-                if (in_lds(r, nf)) fr2 = k == RK_LOCAL ? fastref_ring(w, ref_idx(r)) : k == RK_LIT64 ? fastref_pool(W64, LDS_POOL64 + ref_idx(r) * 8) : fastref_pool(WFR, LDS_POOLFR + ref_idx(r) * 32);
-                else {
-                    const uint32_t nw = words_of(r);
-                    fetches.push_back(DOP_FETCH | (nw << 8) | (3u << 24)); fetches.push_back(r); fetches.push_back(tslot);
-                    fr2 = fastref_ring(nw == 4 ? WFR : nw == 2 ? W128 : W64, tslot); tslot += nw;
-                }
-                T[op_at + first + k2] = fr2;
-            }
-            S.nslots = nf;
-            if (!fetches.empty()) { T.insert(T.begin() + (long)op_at, fetches.begin(), fetches.end()); if (S.last_const_at == (long)op_at) S.last_const_at += (long)fetches.size(); }
         }
         if (err.empty() && want_cells != o.ncells) bad("internal: op " + std::to_string(o.code) + " appended " + std::to_string(o.ncells) + " cells on the host, the device template has " + std::to_string(want_cells));
     }
@@ -371,7 +400,7 @@ static bool canonical_tape(int id, int L, TemplateTable &tt, const h2w_poseidon_
     const Trace *tr = ctx_trace(c);
     if (rc != 0 || !tr || !tr->err.empty()) { err = "cannot record the canonical permutation"; h2w_ctx_free(c); return false; }
     Lowered LW; std::vector<NormOp> ops;
-    lower_pass(tr, L, tt, nullptr, 0, LW, nullptr, nullptr, nullptr, nullptr, &ops);
+    lower_pass(tr, L, tt, nullptr, 0, LW, false, nullptr, nullptr, nullptr, nullptr, &ops);
     const size_t first = lead + (size_t)nio;
     bool ok = LW.err.empty() && ops.size() > first;
     if (!ok) err = "the canonical permutation does not lower: " + LW.err;
@@ -406,12 +435,12 @@ static bool canonical_tape(int id, int L, TemplateTable &tt, const h2w_poseidon_
     return ok;
 }
 
-void lower_trace(const Trace *tr, int L, TemplateTable &tt, const char *const *parallel_scopes, size_t n_scopes, const Fusable &F, Lowered &LW) {
-    lower_pass(tr, L, tt, parallel_scopes, n_scopes, LW, F.fuse.empty() ? nullptr : &F.fuse, &F.glp_meta, nullptr, nullptr, nullptr);
+void lower_trace(const Trace *tr, int L, TemplateTable &tt, const char *const *parallel_scopes, size_t n_scopes, const Fusable &F, bool split_selects, Lowered &LW) {
+    lower_pass(tr, L, tt, parallel_scopes, n_scopes, LW, split_selects, F.fuse.empty() ? nullptr : &F.fuse, &F.glp_meta, nullptr, nullptr, nullptr);
 }
 
 // The stretches that equal a canonical tape word for word, found on a first lowering; those nothing outside reads into are lowered as one op
-bool find_fusable(const Trace *tr, int L, TemplateTable &tt, const char *const *parallel_scopes, size_t n_scopes, const h2w_poseidon_consts_t *consts, bool gl, bool bn, Fusable &F, std::string &err) {
+bool find_fusable(const Trace *tr, int L, TemplateTable &tt, const char *const *parallel_scopes, size_t n_scopes, const h2w_poseidon_consts_t *consts, bool gl, bool bn, bool split_selects, Fusable &F, std::string &err) {
     if (!gl && !bn) return true;
     const std::string ex = "h2w_plan_from_trace_ex: ";
     Canon cn, cnb, cnz; std::string cerr; std::vector<Stretch> found; std::vector<const Canon *> cns;
@@ -426,7 +455,7 @@ bool find_fusable(const Trace *tr, int L, TemplateTable &tt, const char *const *
         if (cnb.ncells != (uint64_t)BN_PERM_CELLS || cnz.ncells != (uint64_t)BN_PERM_CELLS + 1) { err = ex + "a PoseidonBN254 permutation has " + std::to_string(cnb.ncells) + " traced cells, the emission kernel writes " + std::to_string(BN_PERM_CELLS); return false; }
         cns.push_back(&cnb); cns.push_back(&cnz);
     }
-    { Lowered first; lower_pass(tr, L, tt, parallel_scopes, n_scopes, first, nullptr, nullptr, &cns, &found, nullptr); if (!first.err.empty()) { err = "h2w_plan_from_trace: " + first.err; return false; } }
+    { Lowered first; lower_pass(tr, L, tt, parallel_scopes, n_scopes, first, split_selects, nullptr, nullptr, &cns, &found, nullptr); if (!first.err.empty()) { err = "h2w_plan_from_trace: " + first.err; return false; } }
     std::sort(found.begin(), found.end(), [](const Stretch &a, const Stretch &b) { return a.cell0 < b.cell0; });
     // an interior value read outside its stretch: every operand handle of the trace (the hints' operands too) against the stretches' cell ranges
     auto reads = [&](size_t op, uint64_t cell) {
@@ -534,7 +563,7 @@ bool group_templates(Lowered &LW, const ShardUnits &U, LoweredPlan &P, std::stri
         }
         P.tmpls.push_back(T); P.total_slot_lanes += (uint64_t)T.nslots * T.ninst;
     }
-    P.pool64.swap(LW.pool64); P.poolfr.swap(LW.poolfr); P.meta.swap(LW.meta); P.nrec = LW.nrec; P.n_segments = segs.size();
+    P.pool64.swap(LW.pool64); P.poolfr.swap(LW.poolfr); P.meta.swap(LW.meta); P.nrec = LW.nrec; P.n_segments = segs.size(); P.n_select_parts = LW.n_select_parts;
     return true;
 }
 

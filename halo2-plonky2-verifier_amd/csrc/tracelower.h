@@ -34,6 +34,7 @@ struct Lowered {
     std::vector<uint64_t> pool64; std::map<uint64_t, uint32_t> pool64_of; std::vector<fr_t> poolfr;
     std::vector<uint64_t> meta; uint64_t nrec = 0; std::string err;
     std::vector<int> op_seg;      // the segment every trace op lies in (a scope op: the segment current behind it)
+    uint64_t n_select_parts = 0;  // parts of split selects (H2W_TRACE_SPLIT_SELECTS: tapefmt.h SELIND_*) over all segments; 0: nothing was split
 };
 constexpr int MAX_PERM_IO = GLPERM_IO;
 enum { CANON_GL = 0, CANON_BN = 1, CANON_BN_ZERO = 2 };      // CANON_BN_ZERO: the PoseidonBN254 tape recorded on a fresh context (the load_zero cell inside its first mix)
@@ -46,9 +47,11 @@ struct Stretch { size_t tr0, tr1; int seg, canon, nio; TraceIn in[MAX_PERM_IO]; 
 // n_candidates / n_bn_left: the stretches recognised and left interpreted.
 struct Fusable { std::map<size_t, Stretch> fuse; std::vector<uint64_t> glp_meta; uint64_t glp_block_cells = 0, n_candidates = 0, n_bn_left = 0; };
 // false: err holds the message (with the entry point's name)
-bool find_fusable(const Trace *tr, int L, TemplateTable &tt, const char *const *parallel_scopes, size_t n_scopes, const h2w_poseidon_consts_t *consts, bool gl, bool bn, Fusable &F, std::string &err);
+// (split_selects: as lower_trace - the search lowers the tape once itself)
+bool find_fusable(const Trace *tr, int L, TemplateTable &tt, const char *const *parallel_scopes, size_t n_scopes, const h2w_poseidon_consts_t *consts, bool gl, bool bn, bool split_selects, Fusable &F, std::string &err);
 // segments (the instances of the parallel scopes + the root) and their tapes; F's stretches as ONE op each.  LW.err: why the trace does not lower
-void lower_trace(const Trace *tr, int L, TemplateTable &tt, const char *const *parallel_scopes, size_t n_scopes, const Fusable &F, Lowered &LW);
+// split_selects (H2W_TRACE_SPLIT_SELECTS): a DOP_FR_SELIND whose fetched operands do not fit the ring becomes consecutive parts instead of a refusal
+void lower_trace(const Trace *tr, int L, TemplateTable &tt, const char *const *parallel_scopes, size_t n_scopes, const Fusable &F, bool split_selects, Lowered &LW);
 // Shard units: the depth-1 instances in tape order (unit q: the q-th; "verify_query_round" instance q of the standard trace, where the compiled
 // plan's query block q starts: AbiBackend::query_begin).  Shardable (why_unshardable empty): the root's block [0, unit 0) and the units back to back
 // to the end of the stream and of the records, units 1.. all of one size (the compiled plan's StrandTable: query 0, a later query).
@@ -69,6 +72,7 @@ struct LoweredPlan {
     uint32_t nglp = 0; std::vector<uint32_t> glp_unit;      // fused Goldilocks-Poseidon permutations per proof; the shard unit of every list entry
     uint32_t nbnp = 0; std::vector<BnpD> bnp; std::vector<uint32_t> bnp0;      // fused PoseidonBN254 permutations per proof; the entries; per instance its first entry
     uint64_t total_slot_lanes = 0, n_segments = 0;
+    uint64_t n_select_parts = 0;             // parts of split selects in the tapes (0: the plan launches the interpreter without them)
     const uint32_t *tmpl_tape(size_t t) const { return tape.data() + tmpls[t].tape0; }      // template t's tape and its words: up to the next template's
     size_t tmpl_tape_words(size_t t) const { return (t + 1 < tmpls.size() ? tmpls[t + 1].tape0 : tape.size()) - tmpls[t].tape0; }
 };

@@ -60,14 +60,15 @@ static bool lower(h2w_ctx *ctx, uint64_t proof_words, const char *const *paralle
     if (!tr->err.empty()) { err = "h2w_plan_from_trace: " + tr->err; return false; }
     if (tr->pending.kind) { err = "h2w_plan_from_trace: a h2w_trace_input tag was never consumed"; return false; }
     const bool fusing = (flags & H2W_TRACE_FUSE_GL_PERMUTE) != 0, fusing_bn = (flags & H2W_TRACE_FUSE_BN_PERMUTE) != 0;
-    if (flags & ~(uint32_t)(H2W_TRACE_FUSE_GL_PERMUTE | H2W_TRACE_FUSE_BN_PERMUTE | H2W_TRACE_OUTPUT_FORMS)) { err = "h2w_plan_from_trace_ex: unknown flag"; return false; }
+    const bool split_selects = (flags & H2W_TRACE_SPLIT_SELECTS) != 0;
+    if (flags & ~(uint32_t)(H2W_TRACE_FUSE_GL_PERMUTE | H2W_TRACE_FUSE_BN_PERMUTE | H2W_TRACE_OUTPUT_FORMS | H2W_TRACE_SPLIT_SELECTS)) { err = "h2w_plan_from_trace_ex: unknown flag"; return false; }
     if (fusing && !consts) { err = "h2w_plan_from_trace_ex: H2W_TRACE_FUSE_GL_PERMUTE needs the Poseidon tables the permutations are claimed to use"; return false; }
     if (fusing_bn && !consts) { err = "h2w_plan_from_trace_ex: H2W_TRACE_FUSE_BN_PERMUTE needs the Poseidon tables the permutations are claimed to use"; return false; }
     const int L = ctx_lookup_bits(ctx); const uint64_t ncells = ctx_num_cells(ctx);
     TemplateTable tt(L);
     Fusable &F = W.F; LoweredPlan &LP = W.LP; VerdictTables &VT = W.VT; Lowered LW;
-    if (!find_fusable(tr, L, tt, parallel_scopes, n_scopes, consts, fusing, fusing_bn, F, err)) return false;
-    lower_trace(tr, L, tt, parallel_scopes, n_scopes, F, LW);
+    if (!find_fusable(tr, L, tt, parallel_scopes, n_scopes, consts, fusing, fusing_bn, split_selects, F, err)) return false;
+    lower_trace(tr, L, tt, parallel_scopes, n_scopes, F, split_selects, LW);
     if (!LW.err.empty()) { err = "h2w_plan_from_trace: " + LW.err; return false; }
     W.U = shard_units(LW, ncells);
     pack_glop_runs(LW, tt);
@@ -105,7 +106,7 @@ static h2w_plan *fill_handle(h2w_ctx *ctx, uint64_t proof_words, int device_id, 
     TracedPlan *tp = new TracedPlan();
     tp->tmpls = LP.tmpls; tp->total_slot_lanes = LP.total_slot_lanes; tp->h_unit = LP.unit; tp->nglp = LP.nglp; tp->h_glp_unit = LP.glp_unit; tp->nbnp = LP.nbnp; tp->h_bnp = LP.bnp; tp->h_bnp0 = LP.bnp0;
     tp->n_ops = tr->ops.size(); tp->n_segments = LP.n_segments; tp->why_unshardable = U.why_unshardable; tp->n_candidates = F.n_candidates;
-    tp->bn_flag = (flags & H2W_TRACE_FUSE_BN_PERMUTE) != 0; tp->n_bn_left = F.n_bn_left;
+    tp->bn_flag = (flags & H2W_TRACE_FUSE_BN_PERMUTE) != 0; tp->n_bn_left = F.n_bn_left; tp->select_parts = LP.n_select_parts != 0;
     tp->npool64 = (uint32_t)LP.pool64.size(); tp->npoolfr = (uint32_t)LP.poolfr.size();
     tp->op_counts.swap(W.op_counts);
     tp->why_no_verdict = W.VT.why; tp->vt = W.VT;

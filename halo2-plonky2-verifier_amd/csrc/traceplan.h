@@ -28,6 +28,7 @@ struct TracedPlan {
     uint32_t nglp = 0; uint64_t n_candidates = 0; std::vector<uint32_t> h_glp_unit; DevBuf<uint32_t> d_glp_unit;
     // fused PoseidonBN254 permutations: per proof nbnp list entries
     bool bn_flag = false; uint32_t nbnp = 0; uint64_t n_bn_left = 0; std::vector<BnpD> h_bnp; DevBuf<BnpD> d_bnp; std::vector<uint32_t> h_bnp0; DevBuf<uint32_t> d_bnp0;
+    bool select_parts = false;      // the tapes hold parts of split selects (H2W_TRACE_SPLIT_SELECTS): the plan launches the interpreter's instantiation that carries their sum
     DevEvent tev[17]; int tev_used = 0; bool timing = false;      // h2w_plan_trace_timing: around every kernel of the last call (12 depths at most, three kernels, the expansion)
     // sharding: the depth-1 instances are the units (query q = the q-th in tape order); why_unshardable empty: they tile the stream behind the root's block
     std::string why_unshardable; std::vector<uint32_t> h_unit;      // h_unit: the unit of every instance (InstD order)

@@ -233,6 +233,14 @@ h2w_plan *h2w_plan_from_trace(h2w_ctx *, uint64_t proof_words, const char *const
  * h2w_select_from_idx on 52 to 64 wide (four-word) entries, whose 4 n + n operand words cannot all be at hand - a traced PoseidonBN254 verifier
  * with cap_height 6 (64 cap entries) is such a run; up to 51 wide entries (cap_height 5) replay, and so does any
  * length up to 64 of one-word entries.
+ * H2W_TRACE_SPLIT_SELECTS (combines freely with the other flags; alone, `consts` may be null) lifts that refusal for the wide select: where its
+ * fetched operands need more than the 256 slots, the lowering cuts it at entry boundaries into as few consecutive parts as the 256 slots allow, each
+ * with its own fetches in front of it; the running sum passes from part to part in the lane's registers (no value slot, no workspace), the last part
+ * stores the result.  The cells - the leading zero, then entry, indicator, sum per entry -, the gates, the status words and the stream are those of
+ * the select as one op; h2w_plan_trace_op_counts counts every part as one wide select.  Every call that works on a traced plan works on one with
+ * parts (flat, _columns, _shard, _shard_compact, _status, the keygen metadata, H2W_OPT_OUTPUT_FORM with H2W_TRACE_OUTPUT_FORMS,
+ * h2w_trace_verdict_batch).  A plan in which nothing had to be split is the plan lowered without the flag, and runs the same kernels; any other op
+ * whose fetched operands need more than 256 slots is refused as before, and so is everything else the lowering refuses.
  * H2W_TRACE_OUTPUT_FORMS (combines freely with the fuse flags; alone, `consts` may be null): the lowering also builds, on the host, the map of the
  * plan's direct cells - the cells the expansion kernel does not write: the interpreter's own and, with H2W_TRACE_FUSE_BN_PERMUTE, the 4,032 of every
  * fused PoseidonBN254 permutation - as the complement of the record ranges, and checks that direct cells + record cells are the cells of the stream.
@@ -242,10 +250,11 @@ h2w_plan *h2w_plan_from_trace(h2w_ctx *, uint64_t proof_words, const char *const
  * PoseidonBN254 permutations' cells leave their emission kernel converted (stored once: a Montgomery instantiation of that kernel, on a Montgomery copy
  * of the plan's cell table), and one ranged kernel converts the remaining direct cells in place.  Its h2w_plan_trace_timing reports one more entry, the direct cells' conversion, between
  * the PoseidonBN254 emission's slot and the expansion (0 in canonical form).  Sizes, status words and the stream in canonical form are those of the
- * plan without the flag; a plan lowered without it is exactly as before.  (Flag value 4 is unassigned and refused.) */
+ * plan without the flag; a plan lowered without it is exactly as before.  (Flag values 4 and 16 are unassigned and refused.) */
 #define H2W_TRACE_FUSE_GL_PERMUTE 1
 #define H2W_TRACE_FUSE_BN_PERMUTE 2
 #define H2W_TRACE_OUTPUT_FORMS 8
+#define H2W_TRACE_SPLIT_SELECTS 32
 h2w_plan *h2w_plan_from_trace_ex(h2w_ctx *, uint64_t proof_words, const char *const *parallel_scopes, size_t n_scopes, int device_id,
                                  const h2w_poseidon_consts_t *consts, uint32_t flags);
 int h2w_plan_trace_info(const h2w_plan *, uint64_t out[6]);
