@@ -585,6 +585,12 @@ def bn_cases():
     tabs = [list(published()["k"]), wide]
     states = [[0] * 4, [R - 1] * 4] + [[rng.randrange(R) for _ in range(4)] for _ in range(4)]
     cases = [dict(name="%s tables, state %d" % (("published", "full-width random")[t], i), tab=t, st=st) for t in range(2) for i, st in enumerate(states)]
+    sets = lazy_sets()      # the tables the lazy walks are held to (below): the row form runs the same algebra
+    for name in ADVERSARIAL:
+        K, own = sets[name]
+        tabs.append(K)
+        more = [s for _, s in FIXED_STATES] + ([own] if own else []) + states[2:4]
+        cases += [dict(name="%s tables, state %d" % (name, i), tab=len(tabs) - 1, st=st) for i, st in enumerate(more)]
     return dict(tabs=tabs, cases=cases)
 
 
@@ -594,17 +600,22 @@ def bn_pack(c):
     return np.concatenate(parts).tobytes()
 
 
+BN_OUT = 16 + 1008 + 16             # words per case: the state, the 168 S-box values (12 dwords each), the state of the no-store form
+
+
 def bn_check(c, out):
     msgs = []
-    if len(out) != 1024 * len(c["cases"]):
-        return ["bn: %d result words, expected %d" % (len(out), 1024 * len(c["cases"]))]
+    if len(out) != BN_OUT * len(c["cases"]):
+        return ["bn: %d result words, expected %d" % (len(out), BN_OUT * len(c["cases"]))]
     for i, x in enumerate(c["cases"]):
         want, sbox = bn_permute(x["st"], c["tabs"][x["tab"]])
-        o = out[1024 * i:1024 * i + 1024]
-        got = fr_ints(o[:16])
+        o = out[BN_OUT * i:BN_OUT * i + BN_OUT]
+        got, bare = fr_ints(o[:16]), fr_ints(o[BN_OUT - 16:])
         for e in range(4):
             if got[e] != want[e]:
                 msgs.append("bn_permute_rows, %s: element %d: got 0x%x, want 0x%x" % (x["name"], e, got[e], want[e]))
+            if bare[e] != want[e]:
+                msgs.append("bn_permute_rows<false>, %s: element %d: got 0x%x, want 0x%x" % (x["name"], e, bare[e], want[e]))
         d = [int(v) for v in np.ascontiguousarray(o[16:16 + 1008]).view("<u4")]
         for v in range(168):      # x R in lazy limbs, 12 dwords each (nine used)
             t = d[12 * v:12 * v + 12]
@@ -614,8 +625,420 @@ def bn_check(c, out):
     return _first(msgs)
 
 
+# ------------------------------------------------------------------------------------------------ (e') the lazy nine-limb routines of field.h, limb for limb
+# The fr9_* routines on lists of nine Python integers.  Every routine asserts what the C++ relies on and does not check: no 32-bit limb sum wraps, no
+# 64-bit accumulator of fr9_mont reaches 2^64, at most one operand of a product has limbs of 2^29 or more and those stay below 2^30, t[8] fits, every
+# result is below 2^261, and what fr9_pack takes is below 2^256.
+N29 = limbs9(R)
+NINV29 = (-pow(R, -1, 1 << 29)) % (1 << 29)
+NINV261 = (-pow(R, -1, 1 << 261)) % (1 << 261)
+RM = (1 << 261) % R               # the form the walks read: x RM mod r
+
+
+class LazyBoundError(AssertionError):
+    """A precondition of the lazy arithmetic does not hold."""
+
+
+def _rely(ok, what):
+    if not ok:
+        raise LazyBoundError(what)
+
+
+def fr9_from(x):
+    _rely(0 <= x < 1 << 256, "fr9_from: four 64-bit words")
+    return limbs9(x)
+
+
+def fr9_pack(t):
+    _rely(max(t[:8]) <= M29, "fr9_pack: a limb is not normalised")
+    _rely(t[8] < 1 << 24, "fr9_pack: the value is not below 2^256")
+    return limbs_value(t)
+
+
+def fr9_add(a, b):
+    r = [x + y for x, y in zip(a, b)]
+    _rely(max(r) <= M32, "fr9_add: a 32-bit limb sum wraps")
+    return r
+
+
+def fr9_add_if(c, a, b):
+    return fr9_add(a, b) if c else list(a)
+
+
+def fr9_sel(c, a, b):
+    return list(a if c else b)
+
+
+def fr9_norm(a):
+    r, c = [], 0
+    for i in range(8):
+        v = a[i] + c
+        _rely(v <= M32, "fr9_norm: a 32-bit limb sum wraps")
+        r.append(v & M29)
+        c = v >> 29
+    top = a[8] + c
+    _rely(top <= M32, "fr9_norm: t[8] does not fit")
+    _rely(top <= M29, "fr9_norm: the value is not below 2^261")
+    return r + [top]
+
+
+def fr9_mont(a, b):
+    """field.h fr9_mont with its two 64-bit accumulators as written."""
+    _rely(max(a) < 1 << 30 and max(b) < 1 << 30, "fr9_mont: an operand has a limb of 2^30 or more")
+    _rely(max(a) <= M29 or max(b) <= M29, "fr9_mont: both operands have limbs of 2^29 or more")
+    m, r, acc, top = [0] * 9, [0] * 9, 0, 0
+    for k in range(9):
+        e = 0
+        for i in range(k + 1):
+            if i & 1:
+                e += a[i] * b[k - i]
+            else:
+                acc += a[i] * b[k - i]
+        for i in range(k):
+            if i & 1:
+                acc += m[i] * N29[k - i]
+            else:
+                e += m[i] * N29[k - i]
+        top = max(top, acc, e)
+        acc += e
+        top = max(top, acc)
+        m[k] = ((acc & M32) * NINV29) & M29
+        acc += m[k] * N29[0]
+        top = max(top, acc)
+        acc >>= 29
+    for k in range(9, 17):
+        e = 0
+        for i in range(k - 8, 9):
+            if i & 1:
+                e += a[i] * b[k - i]
+                acc += m[i] * N29[k - i]
+            else:
+                acc += a[i] * b[k - i]
+                e += m[i] * N29[k - i]
+        top = max(top, acc, e)
+        acc += e
+        top = max(top, acc)
+        r[k - 9] = acc & M29
+        acc >>= 29
+    _rely(top <= M64, "fr9_mont: an accumulator reaches 2^64")
+    _rely(acc <= M32, "fr9_mont: t[8] does not fit")
+    _rely(acc <= M29, "fr9_mont: the result is not below 2^261")
+    r[8] = acc
+    return r
+
+
+def mont_value(a, b):
+    """The representative fr9_mont returns, on integers: (a b + m r) / R with m = -a b / r mod R."""
+    ab = a * b
+    return (ab + (ab * NINV261 & ((1 << 261) - 1)) * R) >> 261
+
+
+# ------------------------------------------------------------------------------------------------ (e'') bnquad.h bn_values as scheduled, four lanes
+BK_C, BK_S, BK_M, BK_P, BK_ZERO, BK_ONE, BK_T = 0, 88, 480, 496, 512, 513, 514      # bntab.h
+# the sizes the comment at bn_values names, in multiples of r
+QUAD_BOUNDS = {
+    "mix + c": 5.3, "X2 (full rounds)": 1.17, "X2 (behind the partial rounds)": 24.2, "X4 (behind the partial rounds)": 4.5, "X5 (behind the partial rounds)": 2.7,
+    "s0'": 2.1, "U_k": 1.02, "W_j": 1.37, "XA": 1.04, "T0": 1.01, "s0": 6.2, "X2 (partial rounds)": 1.23, "s_k": 62.5,
+}
+
+
+class QuadTable:
+    """The nine-limb table of a constant block as bn_table_build and bn_table9_build build it: entry i < BK_T is entry i of C | S | M | P | 0 | 1 times R
+    (canonical), entry BK_T + r is S_0 c of partial round r times R.  `tr` holds the times-R values; a greedy walk writes entries before it reads them."""
+
+    def __init__(self, K):
+        self.tr = [x * RM % R for x in fr_ints(K[BO["c"]:KW])] + [0, RM]
+        assert len(self.tr) == BK_T
+
+    def k9(self, i):
+        if i < BK_T:
+            return limbs9(self.tr[i])
+        r = i - BK_T
+        return limbs9(self.tr[BK_S + 7 * r] * self.tr[BK_C + 20 + r] * RINV261 % R)
+
+    def block(self):
+        """The constant block (published Goldilocks half) that builds this table."""
+        return list(published()["k"][:GL_WORDS]) + fr_words([x * RINV261 % R for x in self.tr[:512]])
+
+
+def quad_walk(st, T, greedy=None):
+    """QuadSinkT::bn_values on the four lanes of a quad, limb for limb: the three slots of a partial round, the column update that rides in the next round,
+    the butterfly sum.  Returns (the canonical output state, the 168 S-box words as stored, {quantity: its largest value}).
+    greedy = (kind, n, rng): before an entry of the kind's part of the table is read for the first time it is replaced by the one of n seeded candidates that
+    makes the product it enters largest ("column": S'_k for U_k, and P for the mix products in front of the partial rounds; "row": S_0 for XA, T0 and T0 + S_0 c in turn, S_j for W_j, M and P for the mix products)."""
+    peak = {}
+
+    def see(name, *vs):
+        peak[name] = max([peak.get(name, 0)] + [limbs_value(v) for v in vs])
+
+    def choose(idx, other):
+        kind, n, rng = greedy
+        ov = limbs_value(other)
+        T.tr[idx] = max((rng.randrange(R) for _ in range(n)), key=lambda c: mont_value(ov, c))
+    col, row = (greedy and greedy[0] == "column"), (greedy and greedy[0] == "row")
+    chosen = set()
+    L4 = range(4)
+    lm = [0, 0, 1, 2]
+    S = [fr9_mont(fr9_from(x), fr9_from(RM * RM % R)) for x in st]
+    S = [fr9_norm(fr9_add(S[l], T.k9(BK_C + l))) for l in L4]
+    see("mix + c", *S)
+    sbox = []
+
+    def mix(mb):
+        nonlocal S
+        if (row or (col and mb == BK_P)) and mb not in chosen:
+            chosen.add(mb)
+            for l in L4:
+                for j in L4:
+                    choose(mb + 4 * j + l, S[j])
+        acc = [fr9_mont(S[0], T.k9(mb + l)) for l in L4]
+        for j in (1, 2):
+            acc = [fr9_add(fr9_mont(S[j], T.k9(mb + 4 * j + l)), acc[l]) for l in L4]
+        S = [fr9_norm(fr9_add(fr9_mont(S[3], T.k9(mb + 12 + l)), acc[l])) for l in L4]
+        see("mix + c", *S)
+    for half in (0, 1):
+        if half == 1:
+            s0p = [0] * 9
+            for r in range(56):
+                ix, ic = BK_S + 7 * r, BK_C + 20 + r
+                if col and r:
+                    for k in (1, 2, 3):
+                        choose(ix - 7 + 4 + k - 1, s0p)
+                s0b = S[0]
+                X2 = fr9_mont(S[0], S[0])
+                A = [X2] + [fr9_mont(s0p, T.k9(ix - 7 + 4 + lm[l])) for l in (1, 2, 3)]
+                sbox.append(fr9_pack(A[0]))
+                S = [S[0]] + [fr9_add(S[l], A[l]) for l in (1, 2, 3)]                  # lanes k: a sum of two until the end of the round
+                see("X2 (partial rounds)", X2)
+                if r:
+                    see("U_k", *A[1:])
+                see("s_k", *S[1:])
+                X4 = fr9_mont(X2, X2)
+                if row:
+                    if r % 3 == 0:
+                        choose(ix, s0b)
+                    else:                                                               # T0 alone, then the whole of lane 0's summand T0 + S_0 c
+                        kind, n, rng = greedy
+                        x4v, s0v, cv = limbs_value(X4), limbs_value(s0b), (T.tr[ic] if r % 3 == 2 else 0)
+                        T.tr[ix] = max((rng.randrange(R) for _ in range(n)), key=lambda c: mont_value(x4v, mont_value(s0v, c)) + c * cv * RINV261 % R)
+                    for j in (1, 2, 3):
+                        choose(ix + j, S[j])
+                B = [X4, fr9_mont(s0b, T.k9(ix))] + [fr9_mont(S[l], T.k9(ix + l)) for l in (2, 3)]
+                sbox.append(fr9_pack(B[0]))
+                see("XA", B[1])
+                Cc = [fr9_mont(X4, B[1]), fr9_mont(S[1], T.k9(ix + 1))] + [fr9_mont(X4, s0b) for l in (2, 3)]
+                sbox.append(fr9_pack(Cc[2]))
+                see("T0", Cc[0])
+                see("W_j", Cc[1], B[2], B[3])
+                s0p = fr9_add(Cc[2], T.k9(ic))                                          # a sum of two: only ever multiplied by a constant
+                see("s0'", s0p)
+                incl = [fr9_add(Cc[0], T.k9(BK_T + r)), Cc[1], B[2], B[3]]
+                incl = [fr9_add(incl[l], incl[l ^ 1]) for l in L4]                     # quad_perm [1, 0, 3, 2]
+                incl = [fr9_add(incl[l], incl[l ^ 2]) for l in L4]                     # quad_perm [2, 3, 0, 1]
+                assert incl[0] == incl[1] == incl[2] == incl[3]
+                S = [fr9_norm(incl[0])] + [fr9_norm(S[l]) for l in (1, 2, 3)]
+                see("s0", S[0])
+            if col:
+                for k in (1, 2, 3):
+                    choose(BK_S + 7 * 55 + 4 + k - 1, s0p)
+            U = [fr9_mont(s0p, T.k9(BK_S + 7 * 55 + 4 + lm[l])) for l in (1, 2, 3)]
+            see("U_k", *U)
+            S = [S[0]] + [fr9_norm(fr9_add(S[l], U[l - 1])) for l in (1, 2, 3)]
+            see("s_k", *S[1:])
+        for r in range(4):
+            last = r == 3
+            X2 = [fr9_mont(S[l], S[l]) for l in L4]
+            X4 = [fr9_mont(X2[l], X2[l]) for l in L4]
+            S = [fr9_mont(X4[l], S[l]) for l in L4]
+            if half == 1 and r == 0:
+                see("X2 (behind the partial rounds)", *X2)
+                see("X4 (behind the partial rounds)", *X4)
+                see("X5 (behind the partial rounds)", *S)
+            else:
+                see("X2 (full rounds)", *X2)
+            if not (half == 1 and last):
+                S = [fr9_add(S[l], T.k9(BK_C + (4 * (r + 1) if half == 0 else 76 + 4 * r) + l)) for l in L4]
+            mix(BK_P if half == 0 and last else BK_M)
+    one9 = [1] + [0] * 8
+    out = []
+    for l in L4:
+        s = fr9_pack(fr9_mont(S[l], one9))
+        if s >= R:
+            s -= R
+        _rely(s < R, "the output is canonical after one subtraction")
+        out.append(s)
+    return out, sbox, peak
+
+
+def peaks_in_r(peak):
+    return {k: v / R for k, v in peak.items()}
+
+
+# ---- the tables that walk is held to: a table block is data, and the walk is defined for any canonical entries
+GREEDY_N = 256
+
+
+def _random_block(rng):
+    return list(published()["k"][:GL_WORDS]) + fr_words([rng.randrange(R) for _ in range(512)])
+
+
+@functools.lru_cache(None)
+def lazy_sets():
+    """name -> (constant block, the state the set was built for or None).  The greedy sets are built by one walk of their own state over a seeded random
+    table; every other state runs on them as an ordinary case."""
+    sets = {"published": (list(published()["k"]), None)}
+    rng = random.Random(0x6C617A79)
+    sets["full-width random"] = (_random_block(rng), None)
+    for kind in ("column", "row"):
+        T = QuadTable(_random_block(rng))
+        if kind == "column":
+            for i in range(88):
+                T.tr[BK_C + i] = R - 1          # the round constants: r - 1 in the form the walk reads
+        st = [rng.randrange(R) for _ in range(4)]
+        quad_walk(st, T, greedy=(kind, GREEDY_N, rng))
+        sets[kind] = (T.block(), st)
+    one = lambda v: list(published()["k"][:GL_WORDS]) + fr_words([v] * 512)
+    sets["every entry 0"] = (one(0), None)
+    sets["every entry 1"] = (one(1), None)
+    sets["every entry r-1"] = (one(R - 1), None)
+    sets["every entry r-1 as read"] = (one((R - 1) * RINV261 % R), None)
+    return sets
+
+
+ADVERSARIAL = ("column", "row", "every entry 0", "every entry 1", "every entry r-1", "every entry r-1 as read")
+FIXED_STATES = (("all 0", [0] * 4), ("all r-1", [R - 1] * 4), ("0, 1, r-1, 2^253", [0, 1, R - 1, 1 << 253]))
+
+
+@functools.lru_cache(None)
+def _lazy_walk(name, st):
+    return quad_walk(list(st), QuadTable(lazy_sets()[name][0]))
+
+
+def lazy_walk(name, st):
+    """The model's walk of state st over the set `name` (cached: the CPU tests and the device checks share it)."""
+    return _lazy_walk(name, tuple(st))
+
+
+def lazy_cases():
+    """Every (set, state) the quad group runs, live or not: the cases of the CPU checks of the model."""
+    seen, out = set(), []
+    for x in quad_cases()["launches"]:
+        for st in x["st"]:
+            if (x["set"], tuple(st)) not in seen:
+                seen.add((x["set"], tuple(st)))
+                out.append((x["set"], st))
+    return out
+
+
+def quad_reach():
+    """({quantity: largest value in r over the ordinary cases}, the same over the cases of the adversarial sets, the column set's s_k case by case)"""
+    plain, adv, col = {}, {}, []
+    for name, st in lazy_cases():
+        pk = peaks_in_r(lazy_walk(name, st)[2])
+        into = adv if name in ADVERSARIAL else plain
+        for k, v in pk.items():
+            into[k] = max(into.get(k, 0.0), v)
+        if name == "column":
+            col.append(pk["s_k"])
+    return plain, adv, col
+
+
+# Floors of the adversarial sets' reach, in r.  s_k: 58 r is what a value-level model of the schedule measured for a greedy column set (58.9 r with 64
+# candidates per entry); it is no derivation.  Every other figure is the value test_quad_walk_cases_reach_the_stated_bounds printed on its first run with
+# GREEDY_N = 256 (the largest over all cases of the adversarial sets), cut behind its third decimal.
+QUAD_FLOORS = {
+    "mix + c": 4.016, "X2 (full rounds)": 1.083, "X2 (behind the partial rounds)": 22.222, "X4 (behind the partial rounds)": 3.799, "X5 (behind the partial rounds)": 2.001,
+    "s0'": 2.016, "U_k": 1.009, "W_j": 1.211, "XA": 1.028, "T0": 1.003, "s0": 5.37, "X2 (partial rounds)": 1.111, "s_k": 58.0,
+}
+
+
+# ------------------------------------------------------------------------------------------------ (e''') QuadSinkT::bn_values on the device, sixteen quads a wavefront
+@functools.lru_cache(None)
+def quad_cases():
+    """Launches of one wavefront: a table, sixteen states (one per quad), the quads that are live, unit_local."""
+    rng = random.Random(0x71756164)
+    sets = lazy_sets()
+    names = list(sets)
+    launches = []
+    for t, name in enumerate(names):
+        own = sets[name][1]
+        sts = [s for _, s in FIXED_STATES] + [own or [rng.randrange(R) for _ in range(4)]]
+        sts += [[rng.randrange(R) for _ in range(4)] for _ in range(12)]
+        assert len({tuple(s) for s in sts}) == 16
+        launches.append(dict(name="%s, all sixteen quads" % name, set=name, tab=t, live=0xFFFF, unit=0, st=sts))
+        if own or name == "published":
+            for q, unit in ((0, 1), (5, 0), (15, 1)):      # the set's own state, wherever its quad sits
+                moved = list(sts)
+                moved[3], moved[q] = moved[q], moved[3]
+                launches.append(dict(name="%s, quad %d alone, unit_local %d" % (name, q, unit), set=name, tab=t, live=1 << q, unit=unit, st=moved))
+    full = [x for x in launches if x["name"] == "column, all sixteen quads"][0]
+    launches.append(dict(full, name="column, all sixteen quads, unit_local 1", unit=1))
+    return dict(names=names, tabs=[sets[n][0] for n in names], launches=launches)
+
+
+QUAD_UNITS = 2                      # unit slots per quad in the result buffer
+QUAD_Q_FR = QUAD_UNITS * 4 + QUAD_UNITS * 168 + 4 + 4      # per quad: ustate [2][4], sbx [2][168], st[] after QUAD_VALUES, st[] after QUAD_VERDICT
+QUAD_L_WORDS = 16 * QUAD_Q_FR * 4
+
+
+def quad_pack(c):
+    parts = [words([len(c["tabs"]), len(c["launches"])])] + [words(K) for K in c["tabs"]]
+    parts += [words([x["tab"], x["live"], x["unit"], 0] + fr_words([v for s in x["st"] for v in s])) for x in c["launches"]]
+    return np.concatenate(parts).tobytes()
+
+
+def quad_check(c, out):
+    msgs = []
+    if len(out) != QUAD_L_WORDS * len(c["launches"]):
+        return ["quad: %d result words, expected %d" % (len(out), QUAD_L_WORDS * len(c["launches"]))]
+    seen = {}
+    for i, x in enumerate(c["launches"]):
+        for q in range(16):
+            o = [int(v) for v in out[i * QUAD_L_WORDS + q * QUAD_Q_FR * 4:i * QUAD_L_WORDS + (q + 1) * QUAD_Q_FR * 4]]
+            who = "bn_values, %s, quad %d" % (x["name"], q)
+            if not (x["live"] >> q) & 1:
+                if o != [FILL] * len(o):
+                    msgs.append("%s: a quad that returned before the call wrote" % who)
+                continue
+            u = x["unit"]
+            us, sb = o[:32], o[32:32 + 2 * 168 * 4]
+            want, sbox, _ = lazy_walk(x["set"], x["st"][q])
+            ref_out, ref_sbox = bn_permute(x["st"][q], c["tabs"][x["tab"]])
+            assert want == ref_out
+            if us[16 * (1 - u):16 * (2 - u)] != [FILL] * 16 or sb[672 * (1 - u):672 * (2 - u)] != [FILL] * 672:
+                msgs.append("%s: words outside the unit's own region were written" % who)
+            got, gsb = fr_ints(us[16 * u:16 * u + 16]), fr_ints(sb[672 * u:672 * u + 672])
+            st_values, st_verdict = fr_ints(o[-32:-16]), fr_ints(o[-16:])
+            if got != want:
+                msgs.append("%s: the stored state is %s, want %s" % (who, ["0x%x" % v for v in got], ["0x%x" % v for v in want]))
+            if st_values != want:
+                msgs.append("%s: st[] after QUAD_VALUES is %s, want %s" % (who, ["0x%x" % v for v in st_values], ["0x%x" % v for v in want]))
+            if st_verdict != st_values or st_verdict != want:
+                msgs.append("%s: st[] after QUAD_VERDICT is %s, after QUAD_VALUES %s" % (who, ["0x%x" % v for v in st_verdict], ["0x%x" % v for v in st_values]))
+            for v in range(168):
+                if gsb[v] >= 2 * R or gsb[v] * RINV261 % R != ref_sbox[v] or gsb[v] != sbox[v]:
+                    msgs.append("%s: S-box word %d (round %d, %s) is 0x%x, the model's 0x%x" % (who, v, v // 3, ("x^2", "x^4", "x^5")[v % 3], gsb[v], sbox[v]))
+                    break
+            key = (x["set"], tuple(x["st"][q]))
+            if seen.setdefault(key, (got, gsb)) != (got, gsb):
+                msgs.append("%s: the same case gave other words in another quad" % who)
+    return _first(msgs)
+
+
 # ------------------------------------------------------------------------------------------------ (f) the plain C++ routes, compiled for the device
-PLAIN_OPS = ("reduce128", "divmod", "fr_mont_mul", "fr9", "mf2", "mf3", "mf4", "mf8")
+PLAIN_OPS = ("reduce128", "divmod", "fr_mont_mul", "fr9", "mf2", "mf3", "mf4", "mf8", "canon9")
+PLAIN_HDR = 16
+CANON9_TOP = 63                     # canon9 runs on x + k r up to this k: past the largest value either lazy walk holds (bnquad.h: 62.5 r)
+
+
+def largest_sbox_words(n):
+    """The n largest S-box words the model of the quad walk stores, over every case of the quad group."""
+    ws = set()
+    for x in quad_cases()["launches"]:
+        for q in range(16):
+            if (x["live"] >> q) & 1:
+                ws.update(lazy_walk(x["set"], x["st"][q])[1])
+    return sorted(ws)[-n:]
 
 
 @functools.lru_cache(None)
@@ -629,6 +1052,20 @@ def plain_cases():
     c["reduce128"] = [(lo, hi) for lo in E64 for hi in E64] + [(r64(), r64()) for _ in range(N)]
     c["divmod"] = [(a, b, d) for a in canon for b in canon for d in (0, 1, P - 1)] + [(rng.randrange(P), rng.randrange(P), rng.randrange(P)) for _ in range(N)]      # a b + c of canonical values
     c["fr_mont_mul"] = [(a, b) for a in frs for b in frs] + [(rng.randrange(R), rng.randrange(R)) for _ in range(N)]
+    # by one, of the lazy words of [r, 2 r) the quad walk stores: what k_sbox_canon does
+    c["fr_mont_mul"] += [(x, 1) for x in [R, R + 1, 2 * R - 1, 2 * R - 2] + largest_sbox_words(48) + [rng.randrange(R, 2 * R) for _ in range(1 << 10)]]
+    # canon9: twelve dwords as the row walk leaves them - any representative below 2^261, limbs up to eight units above 2^29
+    c9 = []
+    for i in range(N):
+        k = (0, 1, 2, CANON9_TOP)[i & 3] if i < 256 else rng.randrange(CANON9_TOP + 1)
+        x = (0, 1, R - 1, R - 2)[(i >> 2) & 3] if i < 64 else rng.randrange(R)
+        t = limbs9(x + k * R)
+        if i % 4 == 3:      # as a product comes out of rf::mont: limbs of 2^29 + 0 .. 7
+            t = [(1 << 29) + rng.randrange(8) if rng.randrange(3) else rng.getrandbits(29) for _ in range(8)] + [rng.getrandbits(28)]
+        else:
+            t = _loosen(t, i % 4, rng)
+        c9.append((t + [0, 0, 0],))
+    c["canon9"] = c9
     fr9 = [(limbs9(a), limbs9(b)) for a in frs for b in frs]
     for i in range(N):      # lazy operands: one normalised, the other a sum of two (field.h)
         a, b = limbs9(rng.randrange(R) + rng.randrange(6) * R), limbs9(rng.randrange(R) + rng.randrange(2) * R)
@@ -641,25 +1078,26 @@ def plain_cases():
         vals = [x & ((1 << 32 * n) - 1) for x in edge] + [rng.getrandbits(32 * n) for _ in range(N)]
         c["mf%d" % n] = [(v,) for v in vals]
     for k in PLAIN_OPS:
-        pad = {"fr9": ([0] * 9, [0] * 9), "reduce128": (0, 0), "divmod": (0, 0, 0), "fr_mont_mul": (0, 0)}.get(k, (0,))
+        pad = {"fr9": ([0] * 9, [0] * 9), "reduce128": (0, 0), "divmod": (0, 0, 0), "fr_mont_mul": (0, 0), "canon9": ([0] * 12,)}.get(k, (0,))
         c[k] = _pad64(c[k], pad)
     return c
 
 
 def plain_pack(c):
-    parts = [words([len(c[k]) for k in PLAIN_OPS])]
+    parts = [words([len(c[k]) for k in PLAIN_OPS] + [0] * (PLAIN_HDR - len(PLAIN_OPS)))]
     parts.append(words([w for x in c["reduce128"] for w in x]))
     parts.append(words([w for x in c["divmod"] for w in x]))
     parts.append(words(fr_words([v for x in c["fr_mont_mul"] for v in x])))
     parts.append(dwords([w for a, b in c["fr9"] for w in a + b]))
     for n, pad in ((2, 2), (3, 4), (4, 4), (8, 8)):
         parts.append(dwords([(v >> (32 * i)) & M32 for (v,) in c["mf%d" % n] for i in range(pad)]))
+    parts.append(dwords([w for (t,) in c["canon9"] for w in t]))
     return np.concatenate(parts).tobytes()
 
 
 def plain_check(c, out):
     msgs, at = [], 0
-    need = sum(len(c[k]) * w for k, w in zip(PLAIN_OPS, (1, 2, 4, 5, 4, 4, 4, 4)))
+    need = sum(len(c[k]) * w for k, w in zip(PLAIN_OPS, (1, 2, 4, 5, 4, 4, 4, 4, 4)))
     if len(out) != need:
         return ["plain: %d result words, expected %d" % (len(out), need)]
 
@@ -692,6 +1130,11 @@ def plain_check(c, out):
         for i, (v,) in enumerate(cs):
             if g[i] != (v << 256) % R:
                 msgs.append("mf_convert<%d>: case %d (0x%x): got 0x%x, want 0x%x" % (n, i, v, g[i], (v << 256) % R))
+    g = fr_ints(take(4 * len(c["canon9"])))
+    for i, (t,) in enumerate(c["canon9"]):
+        want = limbs_value(t[:9]) * RINV261 % R
+        if g[i] != want:
+            msgs.append("canon9: case %d (limbs %s): got 0x%x, want 0x%x" % (i, ["0x%x" % x for x in t[:9]], g[i], want))
     if at != len(out):
         msgs.append("plain: %d result words, expected %d" % (len(out), at))
     return _first(msgs)
@@ -699,5 +1142,5 @@ def plain_check(c, out):
 
 GROUPS = {
     "glq": (glq_cases, glq_pack, glq_check), "mds": (mds_cases, mds_pack, mds_check), "perm": (perm_cases, perm_pack, perm_check),
-    "mont": (mont_cases, mont_pack, mont_check), "bn": (bn_cases, bn_pack, bn_check), "plain": (plain_cases, plain_pack, plain_check),
+    "mont": (mont_cases, mont_pack, mont_check), "bn": (bn_cases, bn_pack, bn_check), "quad": (quad_cases, quad_pack, quad_check), "plain": (plain_cases, plain_pack, plain_check),
 }

@@ -1,9 +1,9 @@
 // Device harness of tests/test_gpu_devcheck.py: runs the product's own __device__ arithmetic (csrc/glperm.h, rowfr.h, rowperm.h, field.h, montform.h)
-// on words a test wrote, and writes the raw results back.  No reference arithmetic lives here: the expected values are Python integers
+// on words a test wrote (csrc/bnquad.h bn_values too), and writes the raw results back.  No reference arithmetic lives here: the expected values are Python integers
 // (tests/devcheck_ref.py).  Files are raw little-endian 64-bit words (32-bit arrays are packed two to a word); the layout of every group is spelled out
 // at its function and mirrored by the test.
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -I halo2-plonky2-verifier_amd/csrc -I include tests/hip/devcheck.hip -o devcheck
-//   devcheck <glq|mds|perm|mont|bn|plain> <case file> <result file>
+//   devcheck <glq|mds|perm|mont|bn|quad|plain> <case file> <result file>
 // One process, one group, one device context.  Exit status 0: every kernel ran and the result file is complete; anything else: a message on stdout,
 // and nothing was launched after the first HIP error.
 #include <hip/hip_runtime.h>
@@ -183,7 +183,9 @@ static int run_mont(const std::vector<uint64_t> &in, const uint64_t *din, std::v
 }
 
 // ---------------------------------------------------------------------------------------------- (e) bn_permute_rows, one wavefront per case
-// case (20 words): table, 0, 0, 0, state[4][4]  ->  1024 words: the output state [4][4], then the 56 x 3 x SBX9_W S-box dwords
+// case (20 words): table, 0, 0, 0, state[4][4]  ->  BN_OUT words: the output state [4][4], the 56 x 3 x SBX9_W S-box dwords, then the output state [4][4] of the
+// no-store form bn_permute_rows<false> (what k_verdict_merkle_row runs) on the same input
+constexpr int BN_OUT = 16 + BN_PARTIAL_ROUNDS * 3 * rf::SBX9_W / 2 + 16;
 __global__ __launch_bounds__(64) void k_bn(const uint32_t *tab9s, const rf::RowConst *rowk, const uint64_t *cases, uint64_t *out) {
 #if defined(__HIP_DEVICE_COMPILE__)
     const uint64_t *cs = cases + (size_t)blockIdx.x * 20;
@@ -196,19 +198,19 @@ __global__ __launch_bounds__(64) void k_bn(const uint32_t *tab9s, const rf::RowC
         for (unsigned i = 0; i < sizeof(rf::RowConst) / 4; i++) dst[i] = *(const __attribute__((address_space(4))) uint32_t *)(src + i);
     }
     const rf::LaneK L = rf::lane_consts();
-    fr_t st[4];
+    fr_t st[4], bare[4];
 #pragma unroll
-    for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) st[i].l[j] = H2W_CLOAD64(cs + 4 + 4 * i + j);
-    uint64_t *o = out + (size_t)blockIdx.x * 1024;
+    for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) bare[i].l[j] = st[i].l[j] = H2W_CLOAD64(cs + 4 + 4 * i + j);
+    uint64_t *o = out + (size_t)blockIdx.x * BN_OUT;
     rf::bn_permute_rows(st, K, L, reinterpret_cast<uint32_t *>(o + 16));
+    rf::bn_permute_rows<false>(bare, K, L, nullptr);
     const unsigned lane = threadIdx.x;
 #pragma unroll
-    for (int i = 0; i < 4; i++) if (lane == (unsigned)i) g_store_fr(reinterpret_cast<fr_t *>(o) + i, st[i]);
+    for (int i = 0; i < 4; i++) if (lane == (unsigned)i) { g_store_fr(reinterpret_cast<fr_t *>(o) + i, st[i]); g_store_fr(reinterpret_cast<fr_t *>(o + BN_OUT - 16) + i, bare[i]); }
 #endif
 }
-// in: n_tab, n_case, the constant blocks (KW words each), the cases;  out: 1024 words per case
+// in: n_tab, n_case, the constant blocks (KW words each), the cases;  out: BN_OUT words per case
 static int run_bn(const std::vector<uint64_t> &in, const uint64_t *din, std::vector<uint64_t> &res, uint64_t *&dout) {
-    static_assert(16 + BN_PARTIAL_ROUNDS * 3 * rf::SBX9_W / 2 <= 1024, "a case's results fit their slot");
     if (in.size() < 2 || in.size() != 2 + in[0] * KW + in[1] * 20) { printf("case file: unexpected size\n"); return 1; }
     const size_t nt = in[0], nc = in[1];
     for (size_t i = 0; i < nc; i++) if (in[2 + nt * KW + i * 20] >= nt) { printf("case %zu: bad table\n", i); return 1; }
@@ -222,15 +224,68 @@ static int run_bn(const std::vector<uint64_t> &in, const uint64_t *din, std::vec
     uint32_t *dt; rf::RowConst *dk;
     CK(hipMalloc(&dt, tab9.size() * 4 + 16)); CK(hipMemcpy(dt, tab9.data(), tab9.size() * 4, hipMemcpyHostToDevice));
     CK(hipMalloc(&dk, sizeof rk)); CK(hipMemcpy(dk, &rk, sizeof rk, hipMemcpyHostToDevice));
-    res.assign(nc * 1024, 0); CK(hipMalloc(&dout, nc * 1024 * 8 + 8)); CK(hipMemset(dout, 0xA5, nc * 1024 * 8 + 8));
+    res.assign(nc * BN_OUT, 0); CK(hipMalloc(&dout, nc * BN_OUT * 8 + 8)); CK(hipMemset(dout, 0xA5, nc * BN_OUT * 8 + 8));
     if (nc) { hipLaunchKernelGGL(k_bn, dim3(nc), dim3(64), 0, 0, dt, dk, din + 2 + nt * KW, dout); RAN("k_bn"); }
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------- (e') QuadSinkT::bn_values, sixteen quads per wavefront, one wavefront per launch record
+// record (QL_IN words): table, live quads (bit q), unit_local, 0, state[16][4][4]
+//   ->  per quad QQ_FR field elements: ustate [QUAD_UNITS][4], sbx [QUAD_UNITS][56 * 3], st[] behind QUAD_VALUES [4], st[] behind QUAD_VERDICT [4] (lane l stores st[l]).
+// A quad that is not live returns before the call.  QUAD_VERDICT gets the same ustate / sbx pointers and must not store through them: its run comes second, and
+// the harness stores its st[] itself.
+constexpr int QUAD_UNITS = 2, QQ_FR = QUAD_UNITS * 4 + QUAD_UNITS * BN_PARTIAL_ROUNDS * 3 + 4 + 4, QL_IN = 4 + 16 * 16, QL_OUT = 16 * QQ_FR * 4;
+__global__ __launch_bounds__(64) __attribute__((flatten)) void k_quad(const uint32_t *tab9s, FrParams P, const uint64_t *recs, uint64_t *out) {
+    const uint64_t *rc = recs + (size_t)blockIdx.x * QL_IN;
+    const int tab = __builtin_amdgcn_readfirstlane((int)rc[0]), live = __builtin_amdgcn_readfirstlane((int)rc[1]), unit = __builtin_amdgcn_readfirstlane((int)rc[2]);
+    stage_bn_consts9(tab9s + (size_t)tab * (BK9_N * BK9_W), threadIdx.x, 64);      // (the barrier inside: before any quad leaves)
+    const int q = threadIdx.x >> 2, l = threadIdx.x & 3;
+    if (!((live >> q) & 1)) return;
+    fr_t *o = reinterpret_cast<fr_t *>(out + (size_t)blockIdx.x * QL_OUT) + (size_t)q * QQ_FR;
+    ValCfg cfg; cfg.P = P;
+    fr_t in[4], st[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) in[i] = g_load_fr(reinterpret_cast<const fr_t *>(rc + 4) + q * 4 + i);
+    {
+        QuadSinkT<false, QUAD_VALUES> s; s.recs = nullptr; s.nrec = 0; s.out = nullptr; s.cell_off = 0; s.ncells = nullptr; s.l4 = l;
+        s.ustate = o; s.sbx = o + QUAD_UNITS * 4; s.unit_local = unit;
+#pragma unroll
+        for (int i = 0; i < 4; i++) st[i] = in[i];
+        s.bn_values(st, cfg);
+        g_store_fr(o + QQ_FR - 8 + l, fr_sel(l < 2, fr_sel(l == 0, st[0], st[1]), fr_sel(l == 2, st[2], st[3])));
+    }
+    {
+        QuadSinkT<false, QUAD_VERDICT> s; s.recs = nullptr; s.nrec = 0; s.out = nullptr; s.cell_off = 0; s.ncells = nullptr; s.l4 = l;
+        s.ustate = o; s.sbx = o + QUAD_UNITS * 4; s.unit_local = unit;
+#pragma unroll
+        for (int i = 0; i < 4; i++) st[i] = in[i];
+        s.bn_values(st, cfg);
+        g_store_fr(o + QQ_FR - 4 + l, fr_sel(l < 2, fr_sel(l == 0, st[0], st[1]), fr_sel(l == 2, st[2], st[3])));
+    }
+}
+// in: n_tab, n_rec, the constant blocks (KW words each), the records;  out: QL_OUT words per record
+static int run_quad(const std::vector<uint64_t> &in, const uint64_t *din, std::vector<uint64_t> &res, uint64_t *&dout) {
+    if (in.size() < 2 || in.size() != 2 + in[0] * KW + in[1] * QL_IN) { printf("case file: unexpected size\n"); return 1; }
+    const size_t nt = in[0], nc = in[1];
+    for (size_t i = 0; i < nc; i++) { const uint64_t *rc = &in[2 + nt * KW + i * QL_IN]; if (rc[0] >= nt || rc[1] >> 16 || rc[2] >= (uint64_t)QUAD_UNITS) { printf("record %zu: bad table, quads or unit\n", i); return 1; } }
+    const FrParams P = fr_params_init();
+    std::vector<uint32_t> tab9(nt * BK9_N * BK9_W);
+    for (size_t t = 0; t < nt; t++) {
+        std::vector<fr_t> tab(BK_ALL);
+        bn_table_build(*reinterpret_cast<const h2w_poseidon_consts_t *>(&in[2 + t * KW]), P, tab.data());
+        bn_table9_build(tab.data(), &tab9[t * BK9_N * BK9_W]);
+    }
+    uint32_t *dt; CK(hipMalloc(&dt, tab9.size() * 4 + 16)); CK(hipMemcpy(dt, tab9.data(), tab9.size() * 4, hipMemcpyHostToDevice));
+    res.assign(nc * QL_OUT, 0); CK(hipMalloc(&dout, nc * QL_OUT * 8 + 8)); CK(hipMemset(dout, 0xA5, nc * QL_OUT * 8 + 8));
+    if (nc) { hipLaunchKernelGGL(k_quad, dim3(nc), dim3(64), 0, 0, dt, P, din + 2 + nt * KW, dout); RAN("k_quad"); }
+    return 0;
+}
+
 // ---------------------------------------------------------------------------------------------- (f) the plain C++ per-lane routes, as the device compiler builds them
-enum { PL_REDUCE128 = 0, PL_DIVMOD, PL_FRMONT, PL_FR9, PL_MF2, PL_MF3, PL_MF4, PL_MF8, PL_OPS };
+enum { PL_REDUCE128 = 0, PL_DIVMOD, PL_FRMONT, PL_FR9, PL_MF2, PL_MF3, PL_MF4, PL_MF8, PL_CANON9, PL_OPS };
+constexpr int PL_HDR = 16;      // words of the case file's header
 // words per case, in and out (fr9: 18 / 9 dwords, padded to whole words)
-__host__ __device__ constexpr int pl_in(int op) { return op == PL_REDUCE128 ? 2 : op == PL_DIVMOD ? 3 : op == PL_FRMONT ? 8 : op == PL_FR9 ? 9 : op == PL_MF2 ? 1 : op == PL_MF8 ? 4 : 2; }
+__host__ __device__ constexpr int pl_in(int op) { return op == PL_REDUCE128 ? 2 : op == PL_DIVMOD ? 3 : op == PL_FRMONT ? 8 : op == PL_FR9 ? 9 : op == PL_MF2 ? 1 : op == PL_MF8 ? 4 : op == PL_CANON9 ? 6 : 2; }
 __host__ __device__ constexpr int pl_out(int op) { return op == PL_REDUCE128 ? 1 : op == PL_DIVMOD ? 2 : op == PL_FR9 ? 5 : 4; }
 __global__ __launch_bounds__(64) void k_plain(int op, uint64_t ninv, const MontForm *mf, const uint64_t *in, uint64_t *out) {
     const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
@@ -245,22 +300,31 @@ __global__ __launch_bounds__(64) void k_plain(int op, uint64_t ninv, const MontF
         fr9_t A, B; for (int j = 0; j < 9; j++) { A.t[j] = d[j]; B.t[j] = d[9 + j]; }
         const fr9_t r = fr9_norm(fr9_mont(A, B, (uint32_t)ninv & rf::M29)); for (int j = 0; j < 9; j++) od[j] = r.t[j];
         od[9] = 0;
+    } else if (op == PL_CANON9) {      // the sequence of k_sbox_canon9 (batch.hip) on twelve dwords as the row-cooperative values pass leaves them
+        const uint32_t *t = reinterpret_cast<const uint32_t *>(c);
+        fr9_t n; uint32_t cy = 0;
+        for (int j = 0; j < 8; j++) { const uint32_t x = t[j] + cy; n.t[j] = x & rf::M29; cy = x >> 29; }
+        n.t[8] = t[8] + cy;
+        fr9_t one9; for (int j = 0; j < 9; j++) one9.t[j] = j == 0 ? 1u : 0u;
+        fr_t s = fr9_pack(fr9_mont(n, one9, (uint32_t)ninv & rf::M29));
+        if (fr_geq_mod(s)) s = fr_sub_mod_raw(s);
+        for (int j = 0; j < 4; j++) o[j] = s.l[j];
     } else {
         const uint32_t *w = reinterpret_cast<const uint32_t *>(c); uint32_t *od = reinterpret_cast<uint32_t *>(o);
         if (op == PL_MF2) mf_convert<2>(w, *mf, od); else if (op == PL_MF3) mf_convert<3>(w, *mf, od); else if (op == PL_MF4) mf_convert<4>(w, *mf, od); else mf_convert<8>(w, *mf, od);
     }
 }
-// in: n[8] (multiples of 64), then the cases of every routine: reduce128 {lo, hi} | divmod {a, b, c: a b + c} | fr_mont_mul {A[4], B[4]} | fr9 {A[9], B[9] dwords} |
-// mf_convert<2> {w[2] dwords} | <3> {w[3], 0} | <4> {w[4]} | <8> {w[8]};  out: r | q, r | [4] | [9] dwords, 0 | [8] dwords each
+// in: n[PL_HDR] (one count per routine, multiples of 64, then zeros), then the cases of every routine: reduce128 {lo, hi} | divmod {a, b, c: a b + c} | fr_mont_mul {A[4], B[4]} | fr9 {A[9], B[9] dwords} |
+// mf_convert<2> {w[2] dwords} | <3> {w[3], 0} | <4> {w[4]} | <8> {w[8]} | canon9 {t[12] dwords};  out: r | q, r | [4] | [9] dwords, 0 | [8] dwords each | [4]
 static int run_plain(const std::vector<uint64_t> &in, const uint64_t *din, std::vector<uint64_t> &res, uint64_t *&dout) {
-    if (in.size() < 8) { printf("short case file\n"); return 1; }
-    size_t need = 8, outw = 0;
+    if (in.size() < (size_t)PL_HDR) { printf("short case file\n"); return 1; }
+    size_t need = PL_HDR, outw = 0;
     for (int op = 0; op < PL_OPS; op++) { if (in[op] % 64) { printf("whole wavefronts only\n"); return 1; } need += in[op] * pl_in(op); outw += in[op] * pl_out(op); }
     if (in.size() != need) { printf("case file: %zu words, expected %zu\n", in.size(), need); return 1; }
     const FrParams P = fr_params_init(); MontForm K; montform_init(K, 64);
     MontForm *dk; CK(hipMalloc(&dk, sizeof K)); CK(hipMemcpy(dk, &K, sizeof K, hipMemcpyHostToDevice));
     res.assign(outw, 0); CK(hipMalloc(&dout, outw * 8 + 8)); CK(hipMemset(dout, 0xA5, outw * 8 + 8));
-    size_t at = 8, o = 0;
+    size_t at = PL_HDR, o = 0;
     for (int op = 0; op < PL_OPS; op++) {
         const size_t n = in[op];
         if (n) { hipLaunchKernelGGL(k_plain, dim3(n / 64), dim3(64), 0, 0, op, P.ninv, dk, din + at, dout + o); RAN("k_plain"); }
@@ -270,7 +334,7 @@ static int run_plain(const std::vector<uint64_t> &in, const uint64_t *din, std::
 }
 
 int main(int argc, char **argv) {
-    if (argc != 4) { printf("usage: devcheck <glq|mds|perm|mont|bn|plain> <case file> <result file>\n"); return 2; }
+    if (argc != 4) { printf("usage: devcheck <glq|mds|perm|mont|bn|quad|plain> <case file> <result file>\n"); return 2; }
     std::vector<uint64_t> in;
     {
         FILE *f = fopen(argv[2], "rb"); if (!f) { printf("cannot read %s\n", argv[2]); return 2; }
@@ -284,7 +348,7 @@ int main(int argc, char **argv) {
     CK(hipMalloc(&din, in.size() * 8 + 8)); CK(hipMemcpy(din, in.data(), in.size() * 8, hipMemcpyHostToDevice));
     const std::string g = argv[1]; int rc;
     if (g == "glq") rc = run_glq(in, din, res, dout); else if (g == "mds") rc = run_mds(in, din, res, dout); else if (g == "perm") rc = run_perm(in, din, res, dout);
-    else if (g == "mont") rc = run_mont(in, din, res, dout); else if (g == "bn") rc = run_bn(in, din, res, dout); else if (g == "plain") rc = run_plain(in, din, res, dout);
+    else if (g == "mont") rc = run_mont(in, din, res, dout); else if (g == "bn") rc = run_bn(in, din, res, dout); else if (g == "quad") rc = run_quad(in, din, res, dout); else if (g == "plain") rc = run_plain(in, din, res, dout);
     else { printf("unknown group %s\n", argv[1]); return 2; }
     if (rc) return rc;
     if (!res.empty()) CK(hipMemcpy(res.data(), dout, res.size() * 8, hipMemcpyDeviceToHost));

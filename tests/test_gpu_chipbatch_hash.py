@@ -13,6 +13,7 @@ import os
 import pytest
 
 import chipbatch_hash_ref as ref
+import devcheck_ref
 from chipbatch_hash_ref import BN_PERMUTE, GL_PERMUTE, HASH_NO_PAD, MERKLE_VERIFY, TWO_TO_ONE, P, R
 
 pytestmark = pytest.mark.gpu
@@ -71,10 +72,13 @@ def _device_run(h2w, h2w_api, kh, params, lookup_bits, rows, chunk=None):
     return nc, got, st[:n]
 
 
-def _check(h2w, h2w_api, oracle, tables, params, lookup_bits, n, golden=None, seed_extra=0):
-    """The case as is, then with its last row invalid.  golden: (inputs, outputs) of published known answers for the first rows."""
+def _check(h2w, h2w_api, oracle, tables, params, lookup_bits, n, golden=None, seed_extra=0, first=()):
+    """The case as is, then with its last row invalid.  golden: (inputs, outputs) of published known answers for the first rows; first: rows to put in
+    front instead of the generated ones."""
     ko, kh = tables
     rows = _rows(params, n, seed_extra)
+    for i, r in enumerate(first):
+        rows[i] = list(r)
     if golden:
         for i, (gin, _) in enumerate(golden[:n]):
             rows[i] = list(gin)
@@ -177,3 +181,18 @@ def test_chunked_run_equals_unchunked(h2w, h2w_api, oracle, consts, mode):
     nc2, got2, st2 = _device_run(h2w, h2w_api, consts[1], params, 21, rows, chunk=2)
     assert st2 == [0] * 5 and nc2 == nc
     assert got2 == got
+
+
+@pytest.mark.parametrize("name", devcheck_ref.ADVERSARIAL)
+def test_emitter_on_degenerate_and_greedy_tables(h2w, h2w_api, oracle, name):
+    """bn_emit_cells on the table blocks the lazy value walks are held to (devcheck_ref.lazy_sets: entries of 0, 1, r - 1, r - 1 times 2^-261, and the two
+    greedy sets), the oracle on the same bytes: its arithmetic is canonical, and a table block is data.  The first rows are the fixed states of those
+    checks and the state a greedy set was built for."""
+    import numpy as np
+    block, own = devcheck_ref.lazy_sets()[name]
+    raw = np.array(block, dtype="<u8").tobytes()
+    ko, kh = oracle.Consts.from_buffer_copy(raw), h2w.PoseidonConsts.from_buffer_copy(raw)
+    assert bytes(ko) == raw and bytes(kh) == raw
+    states = [st for _, st in devcheck_ref.FIXED_STATES] + ([own] if own else [])
+    _check(h2w, h2w_api, oracle, (ko, kh), (BN_PERMUTE, 0, 0, 0, 0), 21, 17, seed_extra=6, first=states)
+    _check(h2w, h2w_api, oracle, (ko, kh), (TWO_TO_ONE, 1, 0, 0, 0), 21, 17, seed_extra=6)

@@ -1,6 +1,6 @@
 """The hand-written wavefront arithmetic ON THE DEVICE, at its edge cases: tests/hip/devcheck.hip runs the product's own __device__ functions
-(csrc/glperm.h glq_*, glq_mds_small, glq_dense12, glp_permute_lanes; rowfr.h mont and the ways to build its operands; rowperm.h bn_permute_rows; the plain
-C++ routes of field.h and montform.h) on chosen words, and every result word is compared with Python integers (tests/devcheck_ref.py).  The host checks
+(csrc/glperm.h glq_*, glq_mds_small, glq_dense12, glp_permute_lanes; rowfr.h mont and the ways to build its operands; rowperm.h bn_permute_rows with and
+without its stores; bnquad.h QuadSinkT::bn_values as QUAD_VALUES and QUAD_VERDICT; the plain C++ routes of field.h and montform.h) on chosen words, and every result word is compared with Python integers (tests/devcheck_ref.py).  The host checks
 under tests/cpp/ pin the algorithms; this pins the instructions: the carry-out of v_mad_u64_u32 into a scalar pair, the vcc chains, the wait states
 behind an asm block, the DPP bank masks and bound_ctrl, the lane swaps - with lanes of one wavefront needing different corrections in one instruction.
 
@@ -71,7 +71,21 @@ def test_row_montgomery_product_and_operands(devcheck, tmp_path):
 
 def test_bn_permute_rows(devcheck, tmp_path):
     cases = run_group(devcheck, "bn", tmp_path)
-    print("  bn_permute_rows: %d tables, %d cases (one wavefront each)" % (len(cases["tabs"]), len(cases["cases"])))
+    print("  bn_permute_rows, storing and store-free: %d tables (%d of them adversarial: %s), %d cases (one wavefront each)"
+          % (len(cases["tabs"]), len(ref.ADVERSARIAL), ", ".join(ref.ADVERSARIAL), len(cases["cases"])))
+
+
+def test_bn_values_quad_walk_at_its_stated_bounds(devcheck, tmp_path):
+    """QuadSinkT::bn_values (QUAD_VALUES, then QUAD_VERDICT on the same pointers) on the tables that take its lazy values to their stated bounds
+    (devcheck_ref.lazy_sets): the stored state, the 168 S-box words and both returned states against the limb model and the integer permutation; nothing
+    outside a unit's own region written; a case gives the same words in whichever quad it sits, alone in its wavefront or with fifteen others."""
+    cases = run_group(devcheck, "quad", tmp_path)
+    ls = cases["launches"]
+    live = sum(bin(x["live"]).count("1") for x in ls)
+    print("  bn_values: %d tables, %d wavefronts (%d with all sixteen quads, %d with one; unit_local 0: %d, 1: %d), %d live quads, each as QUAD_VALUES and QUAD_VERDICT"
+          % (len(cases["tabs"]), len(ls), sum(1 for x in ls if x["live"] == 0xFFFF), sum(1 for x in ls if x["live"] != 0xFFFF), sum(1 for x in ls if x["unit"] == 0),
+             sum(1 for x in ls if x["unit"] == 1), live))
+    assert {x["live"] for x in ls} == {0xFFFF, 1 << 0, 1 << 5, 1 << 15} and {x["unit"] for x in ls} == {0, 1}
 
 
 def test_plain_routes_as_the_device_compiler_builds_them(devcheck, tmp_path):
