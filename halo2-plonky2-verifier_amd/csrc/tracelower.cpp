@@ -3,6 +3,10 @@
 // record block of a fused Goldilocks-Poseidon permutation as the emission kernel writes it.
 // Which op becomes which template is decided on STATIC widths (a value is provably below 2^64 when a Goldilocks-level op, a bit decomposition, a
 // one-word input ... produced it), never on the traced values: the layout of the records must not depend on the proof.
+// The pieces: Lowering, the pass over the trace (LowerOptions; segments, scope_op, one method per trace op kind, operand_pass and split_select behind an
+// op); LoweredOpObserver with its two readers of the lowered ops, MatcherSet (the stretch search) and RootCapture (the canonical tape's source);
+// resolve_handle, a handle's cell as a ref, for the lowering's operands and the verdict's sides alike; clear_cells, the range clear of the two cell maps.
+// A change here that is meant to change no table is held to it on the host: tools/lowering_digest.py over the dump of traceplan.cpp (H2W_LOWERING_DUMP).
 // What brings HIP into a file without a kernel: field.h marks its functions __host__ __device__ once the unit is compiled as HIP (build.sh compiles
 // every unit that way, and the annotations need the runtime header in front), and glp_block_layout instantiates ValBackend<LayoutSink> and the
 // permutation chip over it (valbackend.h; glcoop.h for GLP_RECS, bntab.h for BN_PERM_CELLS), templates shared with the device sinks.  No function of the runtime is called.
@@ -67,6 +71,34 @@ struct Matcher {
     void drop_pending() { has_pend = false; }                   // the pending CONST1 became part of the op that follows
     void boundary() { commit(); reset(); }                      // a stretch never crosses a segment boundary
 };
+// ---- the two readers of the ops as lowered (NormOp), fed while the lowering runs: nothing keeps the ops of a whole tape
+struct LoweredOpObserver {
+    virtual ~LoweredOpObserver() {}
+    virtual void op(int seg, const NormOp &o, bool replaces_previous) = 0;      // replaces_previous: the op before it in `seg`, a static CONST1, became part of this GLOP
+    virtual void boundary(int seg) = 0;                                         // a parallel child starts here in `seg`
+    virtual void end() = 0;                                                     // end of tape
+};
+// the search for permutation-shaped stretches (the first lowering of a fused plan): one Matcher per segment AND canonical tape, made when the segment's first op arrives
+struct MatcherSet final : LoweredOpObserver {
+    const std::vector<const Canon *> &cns; std::vector<Stretch> &found; std::vector<std::vector<Matcher>> of_seg;
+    MatcherSet(const std::vector<const Canon *> &cns_, std::vector<Stretch> &found_) : cns(cns_), found(found_) {}
+    std::vector<Matcher> &at(int seg) {
+        if (of_seg.size() <= (size_t)seg) of_seg.resize((size_t)seg + 1);
+        std::vector<Matcher> &ms = of_seg[(size_t)seg];
+        if (ms.empty()) for (const Canon *cn : cns) { ms.emplace_back(); ms.back().cn = cn; ms.back().found = &found; ms.back().seg = seg; }
+        return ms;
+    }
+    void op(int seg, const NormOp &o, bool replaces_previous) override { for (Matcher &m : at(seg)) { if (replaces_previous) m.drop_pending(); m.feed(o); } }
+    void boundary(int seg) override { for (Matcher &m : at(seg)) m.boundary(); }
+    void end() override { for (std::vector<Matcher> &ms : of_seg) for (Matcher &m : ms) m.commit(); }
+};
+// the lowered ops of the root segment as they are (the canonical tape is made from them)
+struct RootCapture final : LoweredOpObserver {
+    std::vector<NormOp> ops;
+    void op(int seg, const NormOp &o, bool replaces_previous) override { if (seg != 0) return; if (replaces_previous) ops.pop_back(); ops.push_back(o); }
+    void boundary(int) override {}
+    void end() override {}
+};
 static uint64_t rc_cells(int L, uint64_t bits) { if (bits == 0) return 0; const uint64_t n = (bits + L - 1) / L, rem = bits % L; return (n > 1 ? 1 + 3 * (n - 1) : 0) + (rem ? 4 : 0); }
 
 // The record block of one permutation as CoopSinkT::coop_poseidon_permute writes it (what k_glp_emit_traced runs): the sequential gadget on the
@@ -85,300 +117,365 @@ static uint64_t glp_block_layout(const TemplateTable &tt, int L, const h2w_posei
     uint64_t st[SPONGE_WIDTH] = {0}; pg.permute(st);
     return sink.ndirect == 0 && sink.nrec == (uint64_t)GLP_RECS ? sink.cell_off : 0;
 }
-// fuse: the stretches to lower as ONE op (by their first trace op), glp_meta their record block; cn: look for stretches instead (-> found);
-// capture: the lowered ops of the root segment as they are (the canonical tape is made from them)
+
+// ---- a handle's cell as an operand of something in segment s: the one map from a cell to a ref, for the lowering's operands and the verdict's sides
+static bool is_ancestor(const std::vector<SegInfo> &segs, int a, int s) { for (int x = s; x >= 0; x = segs[(size_t)x].parent) if (x == a) return true; return false; }
+struct ImportTable { std::vector<ImpD> &imps; std::map<std::pair<uint32_t, uint32_t>, uint32_t> &imp_of; };      // of the reading segment; ImpD::tmpl holds the producer SEGMENT
+enum HandleWhy { HANDLE_OK = 0, HANDLE_NOT_TRACED, HANDLE_NOT_ENCLOSING };      // no traced call's result handle; a value of a scope that does not enclose s
+// ref: a literal (a static value), a local slot, or an import through `it` (entered there when it is new).  width: the value's (W64 where there is none)
+static HandleWhy resolve_handle(const Lowered &LW, int s, uint64_t cell, ImportTable it, uint32_t &ref, int &width) {
+    ref = 0; width = W64;
+    auto f = LW.val_of.find(cell);
+    if (f == LW.val_of.end()) return HANDLE_NOT_TRACED;
+    const ValInfo &v = LW.vals[f->second]; width = v.width;
+    if (v.is_static) { ref = v.width == WFR ? mkref(RK_LITFR, WFR, v.lit) : mkref(RK_LIT64, W64, v.lit); return HANDLE_OK; }
+    if ((int)v.seg == s) { ref = mkref(RK_LOCAL, v.width, v.slot); return HANDLE_OK; }
+    if (!is_ancestor(LW.segs, (int)v.seg, s)) return HANDLE_NOT_ENCLOSING;
+    const auto key = std::make_pair(v.seg, v.slot);
+    auto im = it.imp_of.find(key);
+    if (im == it.imp_of.end()) { it.imps.push_back(ImpD{v.seg, 0, v.slot}); im = it.imp_of.emplace(key, (uint32_t)it.imps.size() - 1).first; }
+    ref = mkref(RK_IMPORT, v.width, im->second); return HANDLE_OK;
+}
+
+// ---- the lowering pass
+// fused: the stretches to lower as ONE op (by their first trace op) and the record block of a Goldilocks one
 // split_selects: a wide select whose fetched operands do not fit the ring is emitted as parts (tapefmt.h SELIND_*) instead of refused
-static void lower_pass(const Trace *tr, int L, TemplateTable &tt, const char *const *parallel_scopes, size_t n_scopes, Lowered &LW, bool split_selects,
-                        const std::map<size_t, Stretch> *fuse, const std::vector<uint64_t> *glp_meta, const std::vector<const Canon *> *cns, std::vector<Stretch> *found, std::vector<NormOp> *capture) {
-    std::string &err = LW.err;
-    auto bad = [&](const std::string &m) { if (err.empty()) err = m; };
-    // ---- pass 1: segments
-    std::vector<SegInfo> &segs = LW.segs; segs.assign(1, SegInfo());
-    std::vector<int> &op_seg = LW.op_seg; op_seg.assign(tr->ops.size(), 0);      // (kept: the verdict stage places the recorded equalities by it)
-    {
+static const Fusable NOTHING_FUSED;
+struct LowerOptions { int L; const TemplateTable &tt; const char *const *parallel_scopes = nullptr; size_t n_scopes = 0; bool split_selects = false; const Fusable &fused = NOTHING_FUSED; };
+static bool in_lds(uint32_t r, uint32_t nslots_final) {      // at hand without a fetch: in the lane's ring behind nslots_final slots, or in the LDS part of the pools
+    const int k = ref_kind(r); const uint32_t i = ref_idx(r);
+    if (k == RK_LOCAL) return (uint64_t)i + RING_K >= (uint64_t)nslots_final;
+    if (k == RK_LIT64) return i + 1 <= POOL64_CAP;
+    if (k == RK_LITFR) return i + 1 <= POOLFR_CAP;
+    return false;
+}
+static uint32_t words_of(uint32_t r) { const int k = ref_kind(r); return (uint32_t)(k == RK_LITFR ? 4 : k == RK_INPUT ? (ref_width(r) == WFR ? 4 : 1) : SLOTS_OF[ref_width(r)]); }
+
+// One pass over the trace: the segments, then every op in tape order by the method of its kind.  An op method appends the op (header, operands as mkref
+// words, result slot) to its segment's tape and returns the cells the device template has; lower_op holds that against the trace and runs the operand
+// pass behind it.  The first refusal is LW.err and ends the pass.
+struct Lowering {
+    const Trace *tr; const LowerOptions &opt; Lowered &LW; LoweredOpObserver *obs;
+    std::vector<SegInfo> &segs;
+    std::vector<int> open_child; int prev_seg = 0;      // per segment: where its parent's DOP_SKIP words are; the segment of the op before
+    // the op being lowered: its index (a fused stretch moves it to the stretch's last op), its segment and that segment's tape, its operands and result handles
+    size_t i = 0; const TraceOp *o = nullptr; int s = 0; SegInfo *S = nullptr; std::vector<uint32_t> *T = nullptr; const TraceIn *in = nullptr; const uint64_t *out = nullptr;
+    size_t op_at = 0; uint32_t slots_before = 0; bool ka_fused = false;      // where the op starts on the tape; the segment's slots in front of it; it took the CONST1 in front of it in
+
+    Lowering(const Trace *tr_, const LowerOptions &opt_, Lowered &LW_, LoweredOpObserver *obs_) : tr(tr_), opt(opt_), LW(LW_), obs(obs_), segs(LW_.segs) {}
+    void bad(const std::string &m) { if (LW.err.empty()) LW.err = m; }
+
+    // ---- pass 1: segments (the instances of the parallel scopes + the root), and one id per parallel scope name (the names compare by string)
+    void segments() {
+        segs.assign(1, SegInfo()); LW.op_seg.assign(tr->ops.size(), 0);      // (op_seg is kept: the verdict stage places the recorded equalities by it)
         std::vector<int> stack;      // per open scope: the segment it opened, or -1 (an ordinary scope)
         int cur = 0;
-        for (size_t i = 0; i < tr->ops.size(); i++) {
-            const TraceOp &o = tr->ops[i];
-            if (o.code == TR_SCOPE_PUSH) {
-                bool par = false; for (size_t k = 0; k < n_scopes; k++) if (tr->names[(size_t)o.imm] == parallel_scopes[k]) par = true;
-                if (par) { SegInfo s; s.parent = cur; s.depth = segs[(size_t)cur].depth + 1; s.name = (uint32_t)o.imm; segs.push_back(s); cur = (int)segs.size() - 1; stack.push_back(cur); }
+        for (size_t k = 0; k < tr->ops.size(); k++) {
+            const TraceOp &p = tr->ops[k];
+            if (p.code == TR_SCOPE_PUSH) {
+                bool par = false; for (size_t n = 0; n < opt.n_scopes; n++) if (tr->names[(size_t)p.imm] == opt.parallel_scopes[n]) par = true;
+                if (par) { SegInfo c; c.parent = cur; c.depth = segs[(size_t)cur].depth + 1; c.name = (uint32_t)p.imm; segs.push_back(c); cur = (int)segs.size() - 1; stack.push_back(cur); }
                 else stack.push_back(-1);
-            } else if (o.code == TR_SCOPE_POP) {
+            } else if (p.code == TR_SCOPE_POP) {
                 if (stack.empty()) { bad("unbalanced scopes in the trace"); break; }
                 if (stack.back() >= 0) cur = segs[(size_t)stack.back()].parent;
                 stack.pop_back();
             }
-            op_seg[i] = cur;
+            LW.op_seg[k] = cur;
         }
         if (!stack.empty()) bad("a scope is still open at the end of the trace");
+        std::map<std::string, uint32_t> ids;
+        for (SegInfo &c : segs) { if (c.parent < 0) continue; auto it = ids.find(tr->names[c.name]); if (it == ids.end()) it = ids.emplace(tr->names[c.name], (uint32_t)ids.size() + 1).first; c.name = it->second; }
     }
-    // scope names compare by string: give every parallel name one id
-    { std::map<std::string, uint32_t> ids; for (SegInfo &s : segs) { if (s.parent < 0) continue; auto it = ids.find(tr->names[s.name]); if (it == ids.end()) it = ids.emplace(tr->names[s.name], (uint32_t)ids.size() + 1).first; s.name = it->second; } }
-    // ---- pass 2: lowering, in tape order
-    std::unordered_map<uint64_t, uint32_t> &val_of = LW.val_of; std::vector<ValInfo> &vals = LW.vals;
-    std::vector<uint64_t> &pool64 = LW.pool64; std::map<uint64_t, uint32_t> &pool64_of = LW.pool64_of; std::vector<fr_t> &poolfr = LW.poolfr;
-    std::vector<Matcher> matchers;
-    if (cns) {
-        matchers.resize(segs.size() * cns->size());
-        for (size_t si = 0; si < segs.size(); si++) for (size_t ci = 0; ci < cns->size(); ci++) { Matcher &m = matchers[si * cns->size() + ci]; m.cn = (*cns)[ci]; m.found = found; m.seg = (int)si; segs[si].mt.push_back(&m); }
+
+    // ---- values, records, literals
+    uint32_t lit64(uint64_t v) { auto it = LW.pool64_of.find(v); if (it != LW.pool64_of.end()) return it->second; LW.pool64.push_back(v); LW.pool64_of[v] = (uint32_t)LW.pool64.size() - 1; return (uint32_t)LW.pool64.size() - 1; }
+    uint32_t litfr(const fr_t &v) { for (size_t k = 0; k < LW.poolfr.size(); k++) if (fr_eq(LW.poolfr[k], v)) return (uint32_t)k; LW.poolfr.push_back(v); return (uint32_t)LW.poolfr.size() - 1; }
+    // operand of the op: the handle's cell, or a literal
+    uint32_t ref_of(const TraceIn &x, int *width_out) {
+        if (x.lit) { if (width_out) *width_out = W64; return mkref(RK_LIT64, W64, lit64(x.v)); }
+        uint32_t r; int w; const HandleWhy why = resolve_handle(LW, s, x.v, ImportTable{S->imps, S->imp_of}, r, w);
+        if (width_out) *width_out = w;
+        if (why == HANDLE_NOT_TRACED) bad("an operand is not the result of a traced call (cell " + std::to_string(x.v) + ")");
+        if (why == HANDLE_NOT_ENCLOSING) bad("a parallel scope reads a value computed in a scope that does not enclose it: its instances are not independent (cell " + std::to_string(x.v) + ")");
+        return why == HANDLE_OK ? r : mkref(RK_LIT64, W64, lit64(0));
     }
-    auto lit64 = [&](uint64_t v) { auto it = pool64_of.find(v); if (it != pool64_of.end()) return it->second; pool64.push_back(v); pool64_of[v] = (uint32_t)pool64.size() - 1; return (uint32_t)pool64.size() - 1; };
-    auto litfr = [&](const fr_t &v) { for (size_t i = 0; i < poolfr.size(); i++) if (fr_eq(poolfr[i], v)) return (uint32_t)i; poolfr.push_back(v); return (uint32_t)poolfr.size() - 1; };
-    std::vector<uint64_t> &meta = LW.meta; uint64_t &nrec = LW.nrec;
-    auto is_ancestor = [&](int a, int s) { for (int x = s; x >= 0; x = segs[(size_t)x].parent) if (x == a) return true; return false; };
-    // operand of op in segment s: the handle's cell, or a literal
-    auto ref_of = [&](int s, const TraceIn &in, int *width_out) -> uint32_t {
-        if (in.lit) { if (width_out) *width_out = W64; return mkref(RK_LIT64, W64, lit64(in.v)); }
-        auto it = val_of.find(in.v);
-        if (it == val_of.end()) { bad("an operand is not the result of a traced call (cell " + std::to_string(in.v) + ")"); if (width_out) *width_out = W64; return mkref(RK_LIT64, W64, lit64(0)); }
-        const ValInfo &v = vals[it->second]; if (width_out) *width_out = v.width;
-        if (v.is_static) return v.width == WFR ? mkref(RK_LITFR, WFR, v.lit) : mkref(RK_LIT64, W64, v.lit);
-        if ((int)v.seg == s) return mkref(RK_LOCAL, v.width, v.slot);
-        if (!is_ancestor((int)v.seg, s)) { bad("a parallel scope reads a value computed in a scope that does not enclose it: its instances are not independent (cell " + std::to_string(in.v) + ")"); return mkref(RK_LIT64, W64, lit64(0)); }
-        SegInfo &S = segs[(size_t)s]; const auto key = std::make_pair(v.seg, v.slot);
-        auto im = S.imp_of.find(key);
-        if (im == S.imp_of.end()) { S.imps.push_back(ImpD{v.seg, 0, v.slot}); im = S.imp_of.emplace(key, (uint32_t)S.imps.size() - 1).first; }
-        return mkref(RK_IMPORT, v.width, im->second);
-    };
-    auto new_val = [&](int s, uint64_t cell, int width, bool stat, uint32_t lit) -> uint32_t {
-        SegInfo &S = segs[(size_t)s]; ValInfo v; v.seg = (uint32_t)s; v.width = (uint8_t)width; v.is_static = stat ? 1 : 0; v.lit = lit; v.slot = NO_SLOT;
-        if (!stat) { v.slot = S.nslots; S.nslots += (uint32_t)SLOTS_OF[width]; }
-        vals.push_back(v); val_of[cell] = (uint32_t)vals.size() - 1; return v.slot;
-    };
-    auto add_rec = [&](int s, int tmpl, uint64_t cell) { meta.push_back(meta_pack((uint32_t)tmpl, cell)); nrec++; segs[(size_t)s].nrecs++; };
-    std::vector<int> open_child(segs.size(), -1);
-    int prev_seg = 0;
-    for (size_t i = 0; i < tr->ops.size() && err.empty(); i++) {
-        const TraceOp &o = tr->ops[i]; const int s = op_seg[i]; SegInfo &S = segs[(size_t)s];
-        if (o.code == TR_SCOPE_PUSH || o.code == TR_SCOPE_POP) {
-            // entering a parallel child: the parent steps over its records and cells (filled in when the child ends)
-            if (o.code == TR_SCOPE_PUSH && s != prev_seg && segs[(size_t)s].parent == prev_seg) {
-                SegInfo &Pn = segs[(size_t)prev_seg]; Pn.tape.push_back(DOP_SKIP | (5u << 24)); Pn.last_const_at = -1; for (Matcher *m : Pn.mt) m->boundary(); open_child[(size_t)s] = (int)Pn.tape.size(); for (int k = 0; k < 4; k++) Pn.tape.push_back(0);
-                S.cell0 = o.cell0; S.rec0 = nrec; S.started = true;
-            }
-            if (o.code == TR_SCOPE_POP && s != prev_seg && segs[(size_t)prev_seg].parent == s) {
-                SegInfo &C = segs[(size_t)prev_seg]; C.ncells = o.cell0 - C.cell0; C.tape.push_back(DOP_END | (1u << 24));
-                // the child's totals include its own children's (they are nested in its cell and record ranges)
-                const uint64_t nr = nrec - C.rec0; uint32_t *w = S.tape.data() + open_child[(size_t)prev_seg];
-                w[0] = (uint32_t)nr; w[1] = (uint32_t)(nr >> 32); w[2] = (uint32_t)C.ncells; w[3] = (uint32_t)(C.ncells >> 32); C.all_recs = nr;
-            }
-            prev_seg = s; continue;
-        }
-        prev_seg = s;
-        const TraceIn *in = tr->ins.data() + o.first_in; const uint64_t *out = tr->outs.data() + o.first_out;
-        std::vector<uint32_t> &T = S.tape; uint64_t want_cells = 0; int w0 = 0, w1 = 0, w2 = 0;
-        size_t op_at = T.size();
-        auto head = [&](uint32_t op, uint32_t n = 0, uint32_t aux = 0) { if (aux > 255) bad("internal: op parameter too wide"); T.push_back(op | (n << 8) | (aux << 16)); };
-        const uint32_t slots_before = S.nslots; bool ka_fused = false;
-        const Stretch *fz = nullptr;
-        if (fuse) { auto f = fuse->find(i); if (f != fuse->end()) fz = &f->second; }
-        if (fz) {      // a verified permutation: one op, its results (12 one-word values; PoseidonBN254: 4 of width WFR) in fresh slots
-            const bool bn = fz->canon == CANON_BN;
-            head(bn ? DOP_BNPERM : DOP_GLPERM);
-            for (int k = 0; k < fz->nio; k++) { int w; T.push_back(ref_of(s, fz->in[k], &w)); if (!bn && w != W64) bad("internal: a wide input of a fused permutation"); }
-            const uint32_t base = S.nslots;
-            for (int k = 0; k < fz->nio; k++) new_val(s, fz->out[k], bn ? WFR : W64, false, 0);
-            T.push_back(base); T.push_back(bn ? S.nbnp++ : S.nglp++); T.push_back((uint32_t)(fz->cell1 - fz->cell0));
-            if (bn) S.bnp_cells.push_back(fz->cell0);      // no records: its cells are direct cells, the emission kernel's from where the plan lists them
-            else {                                         // its record block laid out as the emission kernel writes it
-                for (uint64_t m : *glp_meta) meta.push_back(meta_pack(meta_tmpl(m), fz->cell0 + meta_off(m)));
-                nrec += glp_meta->size(); S.nrecs += glp_meta->size();
-            }
-            S.last_const_at = -1;
-            want_cells = o.ncells; i = fz->tr1 - 1;      // (the loop goes on behind the stretch)
-        } else
-        switch (o.code) {
-            case TR_LOAD_CONSTANT: {
-                const fr_t c = tr->consts[(size_t)o.imm]; const bool small = (c.l[1] | c.l[2] | c.l[3]) == 0;
-                if (o.tag.kind == 1) {
-                    if (o.tag.n != 1) { bad("a constant that is a proof value must be one Goldilocks word"); break; }
-                    S.inputs.push_back((uint32_t)o.tag.word); head(DOP_CONST1); T.push_back(mkref(RK_INPUT, W64, (uint32_t)S.inputs.size() - 1)); T.push_back(new_val(s, out[0], W64, false, 0));
-                    add_rec(s, T_CONST1, o.cell0); want_cells = 1;
-                } else if (o.tag.kind != 0) bad("a hint tag on a constant");
-                else if (small) { const uint32_t li = lit64(c.l[0]); head(DOP_CONST1); T.push_back(mkref(RK_LIT64, W64, li)); T.push_back(NO_SLOT); new_val(s, out[0], W64, true, li); add_rec(s, T_CONST1, o.cell0); want_cells = 1;
-                                  S.last_const_at = (long)op_at; S.last_const_cell = o.cell0; S.last_const_tr = i; }
-                else { const uint32_t li = litfr(c); head(DOP_FRCELL); T.push_back(mkref(RK_LITFR, WFR, li)); T.push_back(NO_SLOT); new_val(s, out[0], WFR, true, li); want_cells = 1; }
-                break;
-            }
-            case TR_LOAD_WITNESS: {
-                if (o.tag.kind != 1) { bad("h2w_load_witness without h2w_trace_input"); break; }
-                S.inputs.push_back((uint32_t)o.tag.word);
-                if (o.tag.n == 4) { head(DOP_FRCELL); T.push_back(mkref(RK_INPUT, WFR, (uint32_t)S.inputs.size() - 1)); T.push_back(new_val(s, out[0], WFR, false, 0)); }
-                else { head(DOP_CONST1); T.push_back(mkref(RK_INPUT, W64, (uint32_t)S.inputs.size() - 1)); T.push_back(new_val(s, out[0], W64, false, 0)); add_rec(s, T_CONST1, o.cell0); }
-                want_cells = 1; break;
-            }
-            case TR_ADD: case TR_MUL: case TR_MUL_ADD: {
-                const uint32_t a = ref_of(s, in[0], &w0), b = ref_of(s, in[1], &w1), c3 = o.code == TR_MUL_ADD ? ref_of(s, in[2], &w2) : 0;
-                const bool narrow = w0 == W64 && w1 == W64 && (o.code != TR_MUL_ADD || w2 == W64);
-                if (narrow) {      // [C, A, B, A B + C] on values below 2^64: one gate record (GoldilocksChip::*_no_reduce, base.rs:240-294)
-                    head(DOP_GATE, 0, T_GATE);
-                    if (o.code == TR_ADD) { T.push_back(b); T.push_back(mkref(RK_LIT64, W64, lit64(1))); T.push_back(a); }
-                    else if (o.code == TR_MUL) { T.push_back(a); T.push_back(b); T.push_back(mkref(RK_LIT64, W64, lit64(0))); }
-                    else { T.push_back(a); T.push_back(b); T.push_back(c3); }
-                    T.push_back(new_val(s, out[0], W128, false, 0)); add_rec(s, T_GATE, o.cell0);
-                } else {
-                    head(o.code == TR_ADD ? DOP_FR_ADD : o.code == TR_MUL ? DOP_FR_MUL : DOP_FR_MULADD); T.push_back(a); T.push_back(b); if (o.code == TR_MUL_ADD) T.push_back(c3);
-                    T.push_back(new_val(s, out[0], WFR, false, 0));
-                }
-                want_cells = 4; break;
-            }
-            case TR_SELECT: {
-                const uint32_t a = ref_of(s, in[0], &w0), b = ref_of(s, in[1], &w1), sl = ref_of(s, in[2], &w2);
-                if (w2 != W64) { bad("select: the selector is not a bit"); break; }
-                const bool narrow = w0 == W64 && w1 == W64;
-                head(narrow ? DOP_SELECT : DOP_FR_SELECT); T.push_back(a); T.push_back(b); T.push_back(sl); T.push_back(new_val(s, out[0], narrow ? W64 : WFR, false, 0));
-                want_cells = 8; break;
-            }
-            case TR_IDX_TO_INDICATOR: {
-                const uint32_t n = (uint32_t)o.imm; const uint32_t a = ref_of(s, in[0], &w0);
-                if (w0 != W64 || n < 1 || n > 64) { bad("idx_to_indicator: a wide index or more than 64 entries"); break; }
-                head(DOP_IDX2IND, n); T.push_back(a); const uint32_t base = S.nslots;
-                for (uint32_t k = 0; k < n; k++) { const uint32_t sl = new_val(s, out[k], W64, false, 0); if (sl != base + k) bad("internal: slots of an array result"); }
-                T.push_back(base); want_cells = 8 + 12ull * (n - 1); break;
-            }
-            case TR_SELECT_BY_INDICATOR: {
-                const uint32_t n = (uint32_t)o.imm; if (n < 1 || n > 64) { bad("select_by_indicator: more than 64 entries"); break; }
-                std::vector<uint32_t> r(2 * n); bool narrow = true;
-                for (uint32_t k = 0; k < 2 * n; k++) { int w; r[k] = ref_of(s, in[k], &w); if (k < n && w != W64) narrow = false; if (k >= n && w != W64) bad("select_by_indicator: an indicator that is not a bit"); }
-                head(narrow ? DOP_SELIND : DOP_FR_SELIND, n); for (uint32_t x : r) T.push_back(x); T.push_back(new_val(s, out[0], narrow ? W64 : WFR, false, 0));
-                want_cells = 1 + 3ull * n; break;
-            }
-            case TR_NUM_TO_BITS: {
-                const uint32_t n = (uint32_t)o.imm; const uint32_t a = ref_of(s, in[0], &w0);
-                if (w0 != W64 || n < 1 || n > 64) { bad("num_to_bits: a wide value or more than 64 bits"); break; }
-                head(DOP_NUM2BITS, n); T.push_back(a); const uint32_t base = S.nslots;
-                for (uint32_t k = 0; k < n; k++) new_val(s, out[k], W64, false, 0);
-                T.push_back(base); want_cells = (1 + 3ull * (n - 1)) + 4ull * n; break;
-            }
-            case TR_BITS_TO_NUM: {
-                const uint32_t n = (uint32_t)o.imm; if (n > 64) { bad("bits_to_num: more than 64 bits"); break; }
-                head(DOP_BITS2NUM, n); for (uint32_t k = 0; k < n; k++) { int w; T.push_back(ref_of(s, in[k], &w)); if (w != W64) bad("bits_to_num: an operand that is not a bit"); }
-                T.push_back(new_val(s, out[0], W64, false, 0)); want_cells = n ? 1 + 3ull * (n - 1) : 1; break;
-            }
-            case TR_DECOMPOSE_LE: {
-                if ((o.imm >> 32) != 56 || (uint32_t)o.imm != 5) { bad("decompose_le: only (56 bits, 5 limbs) is replayable (HashWire::to_goldilocks_vec, hash/poseidon_bn254/hash.rs:31-43)"); break; }
-                head(DOP_DECOMP565); T.push_back(ref_of(s, in[0], &w0)); const uint32_t base = S.nslots; for (int k = 0; k < 5; k++) new_val(s, out[k], W64, false, 0); T.push_back(base);
-                want_cells = 13 + 5 * rc_cells(L, 56); break;
-            }
-            case TR_LIMBS_TO_NUM: {
-                const uint32_t n = o.n_in; if (o.imm != 64 || n < 1 || n > 4) { bad("limbs_to_num: only up to four 64-bit limbs are replayable"); break; }
-                head(DOP_LIMBS2NUM, n); for (uint32_t k = 0; k < n; k++) { int w; T.push_back(ref_of(s, in[k], &w)); if (w != W64) bad("limbs_to_num: a wide limb"); }
-                T.push_back(new_val(s, out[0], WFR, false, 0)); want_cells = 1 + 3ull * (n - 1); break;
-            }
-            case TR_RANGE_CHECK: {
-                const uint32_t a = ref_of(s, in[0], &w0); if (w0 != W64 || o.imm > 64) { bad("range_check: a wide value"); break; }
-                head(DOP_RANGE, 0, (uint32_t)o.imm); T.push_back(a); want_cells = rc_cells(L, o.imm); break;
-            }
-            case TR_CLT_SAFE: {
-                const uint32_t a = ref_of(s, in[0], &w0); if (w0 != W64 || o.imm != GL_P) { bad("check_less_than_safe: only (64-bit value, Goldilocks order) is replayable"); break; }
-                head(DOP_CLT); T.push_back(a); add_rec(s, T_CLT_SAFE, o.cell0); want_cells = (uint64_t)tt.ncells(T_CLT_SAFE); break;
-            }
-            case TR_GL_WITNESS: {
-                if (o.tag.kind == 1) { if (o.tag.n != 1) { bad("a Goldilocks witness of more than one word"); break; } S.inputs.push_back((uint32_t)o.tag.word); head(DOP_LOADW); T.push_back(mkref(RK_INPUT, W64, (uint32_t)S.inputs.size() - 1)); }
-                else if (o.tag.kind == 2) { head(DOP_LOADW_DIV); T.push_back(ref_of(s, TraceIn{o.tag.a, 0}, &w0)); T.push_back(ref_of(s, TraceIn{o.tag.b, 0}, &w1)); if (w0 != W64 || w1 != W64) bad("div: wide operands"); }
-                else if (o.tag.kind == 3 || o.tag.kind == 4) { head(DOP_LOADW_EXTINV, 0, (uint32_t)(o.tag.kind - 3)); T.push_back(ref_of(s, TraceIn{o.tag.a, 0}, &w0)); T.push_back(ref_of(s, TraceIn{o.tag.b, 0}, &w1)); if (w0 != W64 || w1 != W64) bad("ext inverse: wide operands"); }
-                else { bad("h2w_gl_load_witness without h2w_trace_input"); break; }
-                T.push_back(new_val(s, out[0], W64, false, 0)); add_rec(s, T_LOADW, o.cell0); want_cells = (uint64_t)tt.ncells(T_LOADW); break;
-            }
-            case TR_GL_REDUCE: {
-                const uint32_t a = ref_of(s, in[0], &w0); if (w0 == W64) { bad("gl_reduce of a value that is not a gate output"); break; }
-                if (ref_kind(a) != RK_LOCAL && ref_kind(a) != RK_IMPORT && ref_kind(a) != RK_RING) { bad("gl_reduce of a constant"); break; }
-                head(DOP_REDUCE); T.push_back(a); T.push_back(new_val(s, out[0], W64, false, 0)); add_rec(s, T_REDUCE, o.cell0); want_cells = (uint64_t)tt.ncells(T_REDUCE); break;
-            }
-            case TR_GLOP: {
-                const uint32_t a = ref_of(s, in[0], &w0), b = ref_of(s, in[1], &w1), c3 = ref_of(s, in[2], &w2);
-                if (w0 != W64 || w1 != W64 || w2 != W64) { bad("a Goldilocks op on a wide value"); break; }
-                if (o.sub == T_GLOP && !in[0].lit && S.last_const_at >= 0 && (size_t)S.last_const_at + 3 == T.size() && in[0].v == S.last_const_cell && S.last_const_cell + 1 == o.cell0 && ref_kind(a) == RK_LIT64) {
-                    // load_constant(K) immediately followed by the op that takes it (GoldilocksChip's constant operands, e.g. hash/poseidon/permutation.rs:55-68): ONE record [K][C, A, B, V]...
-                    op_at = (size_t)S.last_const_at; T.resize(op_at); meta.pop_back(); nrec--; S.nrecs--; ka_fused = true;
-                    T.push_back(DOP_GLOP | ((uint32_t)T_KA_GLOP << 16)); T.push_back(a); T.push_back(b); T.push_back(c3); T.push_back(new_val(s, out[0], W64, false, 0)); add_rec(s, T_KA_GLOP, o.cell0 - 1);
-                    S.last_const_at = -1; want_cells = (uint64_t)tt.ncells(T_GLOP); break;
-                }
-                head(DOP_GLOP, 0, o.sub); T.push_back(a); T.push_back(b); T.push_back(c3); T.push_back(new_val(s, out[0], W64, false, 0)); add_rec(s, o.sub, o.cell0); want_cells = (uint64_t)tt.ncells(o.sub); break;
-            }
-            default: bad("unknown op in the trace");
-        }
-        if (fz || !(o.code == TR_LOAD_CONSTANT && S.last_const_at == (long)op_at)) S.last_const_at = -1;
-        if (T.size() > op_at) {
-            if ((!S.mt.empty() || (capture && s == 0)) && err.empty()) {      // the op as lowered, its operands still as mkref words
-                uint32_t first, count; operand_span(T[op_at] & 0xff, (T[op_at] >> 8) & 0xff, first, count);
-                NormOp no; no.hdr = T[op_at] & 0xffffffu; no.nin = count <= 3 ? count : 0xffu; no.slots_before = slots_before;
-                for (uint32_t k2 = 0; k2 < count && k2 < 3; k2++) { no.ref[k2] = T[op_at + first + k2]; if (ref_kind(no.ref[k2]) == RK_LIT64) no.lit[k2] = fr_from_u64(pool64[ref_idx(no.ref[k2])]); else if (ref_kind(no.ref[k2]) == RK_LITFR) no.lit[k2] = poolfr[ref_idx(no.ref[k2])]; }
-                no.out = count <= 3 && op_at + first + count < T.size() ? T[op_at + first + count] : NO_SLOT;
-                no.tr0 = ka_fused ? S.last_const_tr : i; no.tr1 = i + 1; no.cell0 = ka_fused ? o.cell0 - 1 : o.cell0; no.cell1 = o.cell0 + o.ncells; no.out_cell = o.n_out ? out[0] : 0; no.tin = in;
-                if (!S.mt.empty()) { for (Matcher *m : S.mt) { if (ka_fused) m->drop_pending(); m->feed(no); } } else { if (ka_fused) capture->pop_back(); capture->push_back(no); }
-            }
-            const size_t len = T.size() - op_at; if (len > 255) bad("internal: op too long"); T[op_at] |= (uint32_t)len << 24;
-            // operands: those in the lane's ring or in the LDS part of the pools become fast refs; the others are fetched into fresh ring slots by DOP_FETCH
-            // ops in front of this one.  The ring holds the last RING_K slots WRITTEN, the temporaries included: decided against the slot count after them.
-            uint32_t first, count; operand_span(T[op_at] & 0xff, (T[op_at] >> 8) & 0xff, first, count);
-            auto in_lds = [&](uint32_t r, uint32_t nslots_final) {
-                const int k = ref_kind(r); const uint32_t i = ref_idx(r);
-                if (k == RK_LOCAL) return (uint64_t)i + RING_K >= (uint64_t)nslots_final;
-                if (k == RK_LIT64) return i + 1 <= POOL64_CAP;
-                if (k == RK_LITFR) return i + 1 <= POOLFR_CAP;
-                return false;
-            };
-            auto words_of = [&](uint32_t r) { const int k = ref_kind(r); return (uint32_t)(k == RK_LITFR ? 4 : k == RK_INPUT ? (ref_width(r) == WFR ? 4 : 1) : SLOTS_OF[ref_width(r)]); };
-            // the slots to fetch for the operand words R[0, m): a fixed point (the temporaries push the oldest ring slots out, which may be operands too)
-            auto fetched_slots = [&](const uint32_t *R, uint32_t m) { uint32_t t = 0; for (;;) { uint32_t need = 0; for (uint32_t k2 = 0; k2 < m; k2++) if (!in_lds(R[k2], S.nslots + t)) need += words_of(R[k2]); if (need == t) return t; t = need; } };
-            // R[0, m) become fast refs in place, the DOP_FETCH ops of those not at hand go to `fetches`; the segment's slots move behind the temporaries
-            auto to_fast_refs = [&](uint32_t *R, uint32_t m, uint32_t temps, std::vector<uint32_t> &fetches) {
-                const uint32_t nf = S.nslots + temps; uint32_t tslot = S.nslots;
-                for (uint32_t k2 = 0; k2 < m; k2++) {
-                    const uint32_t r = R[k2]; const int k = ref_kind(r), w = ref_width(r); uint32_t fr2;
-                    if (in_lds(r, nf)) fr2 = k == RK_LOCAL ? fastref_ring(w, ref_idx(r)) : k == RK_LIT64 ? fastref_pool(W64, LDS_POOL64 + ref_idx(r) * 8) : fastref_pool(WFR, LDS_POOLFR + ref_idx(r) * 32);
-                    else {
-                        const uint32_t nw = words_of(r);
-                        fetches.push_back(DOP_FETCH | (nw << 8) | (3u << 24)); fetches.push_back(r); fetches.push_back(tslot);
-                        fr2 = fastref_ring(nw == 4 ? WFR : nw == 2 ? W128 : W64, tslot); tslot += nw;
-                    }
-                    R[k2] = fr2;
-                }
-                S.nslots = nf;
-            };
-            const uint32_t temps = fetched_slots(T.data() + op_at + first, count);
-            // the ring is RING_K slots (slot mod RING_K): with more temporaries than that the later fetches overwrite the earlier ones before the op reads
-            // them.  (The op's own result slots may alias them: every op reads all its operands before it stores a result.)
-            if (temps > RING_K && split_selects && (T[op_at] & 0xff) == DOP_FR_SELIND) {
-                // The wide select walks its entries in order and carries one sum: cut at an entry boundary it is two ops that share nothing else.  Parts
-                // [e0, e1) in order, each the longest run whose own fetches fit (a shorter run never needs more: the fewest parts), each behind the slots
-                // the parts before it took - so a part fetches what their temporaries pushed out of the ring, its indicators included.  The result slot
-                // is the unsplit op's (taken above) and goes with the last part; the sum in between has no slot.
-                const uint32_t n = count / 2, res = T[op_at + first + count];
-                const std::vector<uint32_t> ops(T.begin() + (long)(op_at + first), T.begin() + (long)(op_at + first + count));
-                T.resize(op_at);
-                for (uint32_t e0 = 0; e0 < n && err.empty();) {
-                    std::vector<uint32_t> part, fetches; uint32_t e1 = n, pt = 0;
-                    for (;; e1--) {
-                        part.assign(ops.begin() + e0, ops.begin() + e1); part.insert(part.end(), ops.begin() + n + e0, ops.begin() + n + e1);
-                        pt = fetched_slots(part.data(), (uint32_t)part.size());
-                        if (pt <= RING_K || e1 == e0 + 1) break;
-                    }
-                    if (pt > RING_K) { bad("internal: one entry of a split select_by_indicator does not fit the value slots a lane keeps at hand"); break; }
-                    to_fast_refs(part.data(), (uint32_t)part.size(), pt, fetches);
-                    const uint32_t m = e1 - e0, aux = (e0 ? SELIND_CONTINUES : 0u) | (e1 < n ? SELIND_CONTINUED : 0u);
-                    T.insert(T.end(), fetches.begin(), fetches.end());
-                    T.push_back(DOP_FR_SELIND | (m << 8) | (aux << 16) | ((2 * m + 2) << 24)); T.insert(T.end(), part.begin(), part.end()); T.push_back(e1 < n ? NO_SLOT : res);
-                    LW.n_select_parts++; e0 = e1;
-                }
-            } else if (temps > RING_K) {
-                bad((o.code == TR_SELECT_BY_INDICATOR ? std::string("select_by_indicator") : "trace op " + std::to_string((int)o.code) + " (device op " + std::to_string(T[op_at] & 0xff) + ")") + " with " + std::to_string(count) + " operands: " + std::to_string(temps) + " slots of them have to be fetched (values of an enclosing scope, values computed more than " +
-                    std::to_string(RING_K) + " slots earlier, proof words, far constants), more than the " + std::to_string(RING_K) + " value slots a lane keeps at hand");
-                break;
-            } else {
-                std::vector<uint32_t> fetches; to_fast_refs(T.data() + op_at + first, count, temps, fetches);
-                if (!fetches.empty()) { T.insert(T.begin() + (long)op_at, fetches.begin(), fetches.end()); if (S.last_const_at == (long)op_at) S.last_const_at += (long)fetches.size(); }
-            }
-        }
-        if (err.empty() && want_cells != o.ncells) bad("internal: op " + std::to_string(o.code) + " appended " + std::to_string(o.ncells) + " cells on the host, the device template has " + std::to_string(want_cells));
+    uint32_t new_val(uint64_t cell, int width, bool stat = false, uint32_t lit = 0) {
+        ValInfo v; v.seg = (uint32_t)s; v.width = (uint8_t)width; v.is_static = stat ? 1 : 0; v.lit = lit; v.slot = NO_SLOT;
+        if (!stat) { v.slot = S->nslots; S->nslots += (uint32_t)SLOTS_OF[width]; }
+        LW.vals.push_back(v); LW.val_of[cell] = (uint32_t)LW.vals.size() - 1; return v.slot;
     }
-    for (Matcher &m : matchers) m.commit();
-    for (SegInfo &S : segs) S.mt.clear();
-    if (!err.empty()) return;
-    segs[0].tape.push_back(DOP_END | (1u << 24)); segs[0].cell0 = 0; segs[0].rec0 = 0;
-}
+    void add_rec(int tmpl, uint64_t cell) { LW.meta.push_back(meta_pack((uint32_t)tmpl, cell)); LW.nrec++; S->nrecs++; }
+    void head(uint32_t op, uint32_t n = 0, uint32_t aux = 0) { if (aux > 255) bad("internal: op parameter too wide"); T->push_back(op | (n << 8) | (aux << 16)); }
+    void put(std::initializer_list<uint32_t> words) { T->insert(T->end(), words.begin(), words.end()); }      // (a braced list: its entries are evaluated left to right)
+
+    // ---- scope push / pop
+    void scope_op() {
+        // entering a parallel child: the parent steps over its records and cells (filled in when the child ends)
+        if (o->code == TR_SCOPE_PUSH && s != prev_seg && segs[(size_t)s].parent == prev_seg) {
+            SegInfo &Pn = segs[(size_t)prev_seg]; Pn.tape.push_back(DOP_SKIP | (5u << 24)); Pn.last_const_at = -1; if (obs) obs->boundary(prev_seg);
+            open_child[(size_t)s] = (int)Pn.tape.size(); for (int k = 0; k < 4; k++) Pn.tape.push_back(0);
+            S->cell0 = o->cell0; S->rec0 = LW.nrec; S->started = true;
+        }
+        if (o->code == TR_SCOPE_POP && s != prev_seg && segs[(size_t)prev_seg].parent == s) {
+            SegInfo &C = segs[(size_t)prev_seg]; C.ncells = o->cell0 - C.cell0; C.tape.push_back(DOP_END | (1u << 24));
+            // the child's totals include its own children's (they are nested in its cell and record ranges)
+            const uint64_t nr = LW.nrec - C.rec0; uint32_t *w = S->tape.data() + open_child[(size_t)prev_seg];
+            w[0] = (uint32_t)nr; w[1] = (uint32_t)(nr >> 32); w[2] = (uint32_t)C.ncells; w[3] = (uint32_t)(C.ncells >> 32); C.all_recs = nr;
+        }
+    }
+
+    // ---- one method per op kind -> the cells the device template has
+    // a verified permutation: one op, its results (12 one-word values; PoseidonBN254: 4 of width WFR) in fresh slots
+    uint64_t fused_stretch(const Stretch &fz) {
+        const bool bn = fz.canon == CANON_BN;
+        head(bn ? DOP_BNPERM : DOP_GLPERM);
+        for (int k = 0; k < fz.nio; k++) { int w; T->push_back(ref_of(fz.in[k], &w)); if (!bn && w != W64) bad("internal: a wide input of a fused permutation"); }
+        const uint32_t base = S->nslots;
+        for (int k = 0; k < fz.nio; k++) new_val(fz.out[k], bn ? WFR : W64);
+        put({base, bn ? S->nbnp++ : S->nglp++, (uint32_t)(fz.cell1 - fz.cell0)});
+        if (bn) S->bnp_cells.push_back(fz.cell0);      // no records: its cells are direct cells, the emission kernel's from where the plan lists them
+        else {                                         // its record block laid out as the emission kernel writes it
+            for (uint64_t m : opt.fused.glp_meta) LW.meta.push_back(meta_pack(meta_tmpl(m), fz.cell0 + meta_off(m)));
+            LW.nrec += opt.fused.glp_meta.size(); S->nrecs += opt.fused.glp_meta.size();
+        }
+        i = fz.tr1 - 1;      // (the pass goes on behind the stretch)
+        return o->ncells;
+    }
+    uint64_t load_constant() {
+        const fr_t c = tr->consts[(size_t)o->imm]; const bool small = (c.l[1] | c.l[2] | c.l[3]) == 0;
+        if (o->tag.kind == 1) {
+            if (o->tag.n != 1) { bad("a constant that is a proof value must be one Goldilocks word"); return 0; }
+            S->inputs.push_back((uint32_t)o->tag.word); head(DOP_CONST1); put({mkref(RK_INPUT, W64, (uint32_t)S->inputs.size() - 1), new_val(out[0], W64)});
+            add_rec(T_CONST1, o->cell0); return 1;
+        }
+        if (o->tag.kind != 0) { bad("a hint tag on a constant"); return 0; }
+        if (small) {      // a static CONST1: a GLOP right behind it that takes it as operand A takes it in (glop)
+            const uint32_t li = lit64(c.l[0]); head(DOP_CONST1); put({mkref(RK_LIT64, W64, li), NO_SLOT}); new_val(out[0], W64, true, li); add_rec(T_CONST1, o->cell0);
+            S->last_const_at = (long)op_at; S->last_const_cell = o->cell0; S->last_const_tr = i; return 1;
+        }
+        const uint32_t li = litfr(c); head(DOP_FRCELL); put({mkref(RK_LITFR, WFR, li), NO_SLOT}); new_val(out[0], WFR, true, li); return 1;
+    }
+    uint64_t load_witness() {
+        if (o->tag.kind != 1) { bad("h2w_load_witness without h2w_trace_input"); return 0; }
+        S->inputs.push_back((uint32_t)o->tag.word);
+        if (o->tag.n == 4) { head(DOP_FRCELL); put({mkref(RK_INPUT, WFR, (uint32_t)S->inputs.size() - 1), new_val(out[0], WFR)}); }
+        else { head(DOP_CONST1); put({mkref(RK_INPUT, W64, (uint32_t)S->inputs.size() - 1), new_val(out[0], W64)}); add_rec(T_CONST1, o->cell0); }
+        return 1;
+    }
+    uint64_t add_mul() {      // add, mul, mul_add
+        int w0 = 0, w1 = 0, w2 = 0;
+        const uint32_t a = ref_of(in[0], &w0), b = ref_of(in[1], &w1), c3 = o->code == TR_MUL_ADD ? ref_of(in[2], &w2) : 0;
+        const bool narrow = w0 == W64 && w1 == W64 && (o->code != TR_MUL_ADD || w2 == W64);
+        if (narrow) {      // [C, A, B, A B + C] on values below 2^64: one gate record (GoldilocksChip::*_no_reduce, base.rs:240-294)
+            head(DOP_GATE, 0, T_GATE);
+            if (o->code == TR_ADD) put({b, mkref(RK_LIT64, W64, lit64(1)), a});
+            else if (o->code == TR_MUL) put({a, b, mkref(RK_LIT64, W64, lit64(0))});
+            else put({a, b, c3});
+            T->push_back(new_val(out[0], W128)); add_rec(T_GATE, o->cell0);
+        } else {
+            head(o->code == TR_ADD ? DOP_FR_ADD : o->code == TR_MUL ? DOP_FR_MUL : DOP_FR_MULADD); put({a, b}); if (o->code == TR_MUL_ADD) T->push_back(c3);
+            T->push_back(new_val(out[0], WFR));
+        }
+        return 4;
+    }
+    uint64_t select() {
+        int w0 = 0, w1 = 0, w2 = 0;
+        const uint32_t a = ref_of(in[0], &w0), b = ref_of(in[1], &w1), sl = ref_of(in[2], &w2);
+        if (w2 != W64) { bad("select: the selector is not a bit"); return 0; }
+        const bool narrow = w0 == W64 && w1 == W64;
+        head(narrow ? DOP_SELECT : DOP_FR_SELECT); put({a, b, sl, new_val(out[0], narrow ? W64 : WFR)});
+        return 8;
+    }
+    uint64_t idx_to_indicator() {
+        int w0 = 0; const uint32_t n = (uint32_t)o->imm; const uint32_t a = ref_of(in[0], &w0);
+        if (w0 != W64 || n < 1 || n > 64) { bad("idx_to_indicator: a wide index or more than 64 entries"); return 0; }
+        head(DOP_IDX2IND, n); T->push_back(a); const uint32_t base = S->nslots;
+        for (uint32_t k = 0; k < n; k++) { const uint32_t sl = new_val(out[k], W64); if (sl != base + k) bad("internal: slots of an array result"); }
+        T->push_back(base); return 8 + 12ull * (n - 1);
+    }
+    uint64_t select_by_indicator() {
+        const uint32_t n = (uint32_t)o->imm; if (n < 1 || n > 64) { bad("select_by_indicator: more than 64 entries"); return 0; }
+        std::vector<uint32_t> r(2 * n); bool narrow = true;
+        for (uint32_t k = 0; k < 2 * n; k++) { int w; r[k] = ref_of(in[k], &w); if (k < n && w != W64) narrow = false; if (k >= n && w != W64) bad("select_by_indicator: an indicator that is not a bit"); }
+        head(narrow ? DOP_SELIND : DOP_FR_SELIND, n); T->insert(T->end(), r.begin(), r.end()); T->push_back(new_val(out[0], narrow ? W64 : WFR));
+        return 1 + 3ull * n;
+    }
+    uint64_t num_to_bits() {
+        int w0 = 0; const uint32_t n = (uint32_t)o->imm; const uint32_t a = ref_of(in[0], &w0);
+        if (w0 != W64 || n < 1 || n > 64) { bad("num_to_bits: a wide value or more than 64 bits"); return 0; }
+        head(DOP_NUM2BITS, n); T->push_back(a); const uint32_t base = S->nslots;
+        for (uint32_t k = 0; k < n; k++) new_val(out[k], W64);
+        T->push_back(base); return (1 + 3ull * (n - 1)) + 4ull * n;
+    }
+    uint64_t bits_to_num() {
+        const uint32_t n = (uint32_t)o->imm; if (n > 64) { bad("bits_to_num: more than 64 bits"); return 0; }
+        head(DOP_BITS2NUM, n); for (uint32_t k = 0; k < n; k++) { int w; T->push_back(ref_of(in[k], &w)); if (w != W64) bad("bits_to_num: an operand that is not a bit"); }
+        T->push_back(new_val(out[0], W64)); return n ? 1 + 3ull * (n - 1) : 1;
+    }
+    uint64_t decompose_le() {
+        if ((o->imm >> 32) != 56 || (uint32_t)o->imm != 5) { bad("decompose_le: only (56 bits, 5 limbs) is replayable (HashWire::to_goldilocks_vec, hash/poseidon_bn254/hash.rs:31-43)"); return 0; }
+        int w0; head(DOP_DECOMP565); T->push_back(ref_of(in[0], &w0)); const uint32_t base = S->nslots; for (int k = 0; k < 5; k++) new_val(out[k], W64); T->push_back(base);
+        return 13 + 5 * rc_cells(opt.L, 56);
+    }
+    uint64_t limbs_to_num() {
+        const uint32_t n = o->n_in; if (o->imm != 64 || n < 1 || n > 4) { bad("limbs_to_num: only up to four 64-bit limbs are replayable"); return 0; }
+        head(DOP_LIMBS2NUM, n); for (uint32_t k = 0; k < n; k++) { int w; T->push_back(ref_of(in[k], &w)); if (w != W64) bad("limbs_to_num: a wide limb"); }
+        T->push_back(new_val(out[0], WFR)); return 1 + 3ull * (n - 1);
+    }
+    uint64_t range_check() {
+        int w0 = 0; const uint32_t a = ref_of(in[0], &w0); if (w0 != W64 || o->imm > 64) { bad("range_check: a wide value"); return 0; }
+        head(DOP_RANGE, 0, (uint32_t)o->imm); T->push_back(a); return rc_cells(opt.L, o->imm);
+    }
+    uint64_t clt_safe() {
+        int w0 = 0; const uint32_t a = ref_of(in[0], &w0); if (w0 != W64 || o->imm != GL_P) { bad("check_less_than_safe: only (64-bit value, Goldilocks order) is replayable"); return 0; }
+        head(DOP_CLT); T->push_back(a); add_rec(T_CLT_SAFE, o->cell0); return (uint64_t)opt.tt.ncells(T_CLT_SAFE);
+    }
+    uint64_t gl_witness() {      // a proof word, or a hint: the quotient of a division, a component of an extension inverse
+        int w0 = 0, w1 = 0;
+        if (o->tag.kind == 1) { if (o->tag.n != 1) { bad("a Goldilocks witness of more than one word"); return 0; } S->inputs.push_back((uint32_t)o->tag.word); head(DOP_LOADW); T->push_back(mkref(RK_INPUT, W64, (uint32_t)S->inputs.size() - 1)); }
+        else if (o->tag.kind == 2) { head(DOP_LOADW_DIV); put({ref_of(TraceIn{o->tag.a, 0}, &w0), ref_of(TraceIn{o->tag.b, 0}, &w1)}); if (w0 != W64 || w1 != W64) bad("div: wide operands"); }
+        else if (o->tag.kind == 3 || o->tag.kind == 4) { head(DOP_LOADW_EXTINV, 0, (uint32_t)(o->tag.kind - 3)); put({ref_of(TraceIn{o->tag.a, 0}, &w0), ref_of(TraceIn{o->tag.b, 0}, &w1)}); if (w0 != W64 || w1 != W64) bad("ext inverse: wide operands"); }
+        else { bad("h2w_gl_load_witness without h2w_trace_input"); return 0; }
+        T->push_back(new_val(out[0], W64)); add_rec(T_LOADW, o->cell0); return (uint64_t)opt.tt.ncells(T_LOADW);
+    }
+    uint64_t gl_reduce() {
+        int w0 = 0; const uint32_t a = ref_of(in[0], &w0); if (w0 == W64) { bad("gl_reduce of a value that is not a gate output"); return 0; }
+        if (ref_kind(a) != RK_LOCAL && ref_kind(a) != RK_IMPORT && ref_kind(a) != RK_RING) { bad("gl_reduce of a constant"); return 0; }
+        head(DOP_REDUCE); put({a, new_val(out[0], W64)}); add_rec(T_REDUCE, o->cell0); return (uint64_t)opt.tt.ncells(T_REDUCE);
+    }
+    uint64_t glop() {
+        int w0 = 0, w1 = 0, w2 = 0;
+        const uint32_t a = ref_of(in[0], &w0), b = ref_of(in[1], &w1), c3 = ref_of(in[2], &w2);
+        if (w0 != W64 || w1 != W64 || w2 != W64) { bad("a Goldilocks op on a wide value"); return 0; }
+        if (o->sub == T_GLOP && !in[0].lit && S->last_const_at >= 0 && (size_t)S->last_const_at + 3 == T->size() && in[0].v == S->last_const_cell && S->last_const_cell + 1 == o->cell0 && ref_kind(a) == RK_LIT64) {
+            // load_constant(K) immediately followed by the op that takes it (GoldilocksChip's constant operands, e.g. hash/poseidon/permutation.rs:55-68): ONE record [K][C, A, B, V]...
+            op_at = (size_t)S->last_const_at; T->resize(op_at); LW.meta.pop_back(); LW.nrec--; S->nrecs--; ka_fused = true;
+            T->push_back(DOP_GLOP | ((uint32_t)T_KA_GLOP << 16)); put({a, b, c3, new_val(out[0], W64)}); add_rec(T_KA_GLOP, o->cell0 - 1);
+            S->last_const_at = -1; return (uint64_t)opt.tt.ncells(T_GLOP);
+        }
+        head(DOP_GLOP, 0, o->sub); put({a, b, c3, new_val(out[0], W64)}); add_rec(o->sub, o->cell0); return (uint64_t)opt.tt.ncells(o->sub);
+    }
+    uint64_t by_kind() {
+        switch (o->code) {
+            case TR_LOAD_CONSTANT: return load_constant();
+            case TR_LOAD_WITNESS: return load_witness();
+            case TR_ADD: case TR_MUL: case TR_MUL_ADD: return add_mul();
+            case TR_SELECT: return select();
+            case TR_IDX_TO_INDICATOR: return idx_to_indicator();
+            case TR_SELECT_BY_INDICATOR: return select_by_indicator();
+            case TR_NUM_TO_BITS: return num_to_bits();
+            case TR_BITS_TO_NUM: return bits_to_num();
+            case TR_DECOMPOSE_LE: return decompose_le();
+            case TR_LIMBS_TO_NUM: return limbs_to_num();
+            case TR_RANGE_CHECK: return range_check();
+            case TR_CLT_SAFE: return clt_safe();
+            case TR_GL_WITNESS: return gl_witness();
+            case TR_GL_REDUCE: return gl_reduce();
+            case TR_GLOP: return glop();
+            default: bad("unknown op in the trace"); return 0;
+        }
+    }
+
+    // ---- behind an op
+    // the op as lowered, its operands still as mkref words, to the observer
+    void observe(uint32_t first, uint32_t count) {
+        const std::vector<uint32_t> &t = *T;
+        NormOp no; no.hdr = t[op_at] & 0xffffffu; no.nin = count <= 3 ? count : 0xffu; no.slots_before = slots_before;
+        for (uint32_t k = 0; k < count && k < 3; k++) { no.ref[k] = t[op_at + first + k]; if (ref_kind(no.ref[k]) == RK_LIT64) no.lit[k] = fr_from_u64(LW.pool64[ref_idx(no.ref[k])]); else if (ref_kind(no.ref[k]) == RK_LITFR) no.lit[k] = LW.poolfr[ref_idx(no.ref[k])]; }
+        no.out = count <= 3 && op_at + first + count < t.size() ? t[op_at + first + count] : NO_SLOT;
+        no.tr0 = ka_fused ? S->last_const_tr : i; no.tr1 = i + 1; no.cell0 = ka_fused ? o->cell0 - 1 : o->cell0; no.cell1 = o->cell0 + o->ncells; no.out_cell = o->n_out ? out[0] : 0; no.tin = in;
+        obs->op(s, no, ka_fused);
+    }
+    // the slots to fetch for the operand words R[0, m): a fixed point (the temporaries push the oldest ring slots out, which may be operands too)
+    uint32_t fetched_slots(const uint32_t *R, uint32_t m) const { uint32_t t = 0; for (;;) { uint32_t need = 0; for (uint32_t k = 0; k < m; k++) if (!in_lds(R[k], S->nslots + t)) need += words_of(R[k]); if (need == t) return t; t = need; } }
+    // R[0, m) become fast refs in place, the DOP_FETCH ops of those not at hand go to `fetches`; the segment's slots move behind the temporaries
+    void to_fast_refs(uint32_t *R, uint32_t m, uint32_t temps, std::vector<uint32_t> &fetches) {
+        const uint32_t nf = S->nslots + temps; uint32_t tslot = S->nslots;
+        for (uint32_t k2 = 0; k2 < m; k2++) {
+            const uint32_t r = R[k2]; const int k = ref_kind(r), w = ref_width(r); uint32_t fr2;
+            if (in_lds(r, nf)) fr2 = k == RK_LOCAL ? fastref_ring(w, ref_idx(r)) : k == RK_LIT64 ? fastref_pool(W64, LDS_POOL64 + ref_idx(r) * 8) : fastref_pool(WFR, LDS_POOLFR + ref_idx(r) * 32);
+            else {
+                const uint32_t nw = words_of(r);
+                fetches.insert(fetches.end(), {DOP_FETCH | (nw << 8) | (3u << 24), r, tslot});
+                fr2 = fastref_ring(nw == 4 ? WFR : nw == 2 ? W128 : W64, tslot); tslot += nw;
+            }
+            R[k2] = fr2;
+        }
+        S->nslots = nf;
+    }
+    // The wide select walks its entries in order and carries one sum: cut at an entry boundary it is two ops that share nothing else.  Parts
+    // [e0, e1) in order, each the longest run whose own fetches fit (a shorter run never needs more: the fewest parts), each behind the slots
+    // the parts before it took - so a part fetches what their temporaries pushed out of the ring, its indicators included.  The result slot
+    // is the unsplit op's (taken by its method) and goes with the last part; the sum in between has no slot.
+    void split_select(uint32_t first, uint32_t count) {
+        const uint32_t n = count / 2, res = (*T)[op_at + first + count];
+        const std::vector<uint32_t> ops(T->begin() + (long)(op_at + first), T->begin() + (long)(op_at + first + count));
+        T->resize(op_at);
+        for (uint32_t e0 = 0; e0 < n && LW.err.empty();) {
+            std::vector<uint32_t> part, fetches; uint32_t e1 = n, pt = 0;
+            for (;; e1--) {
+                part.assign(ops.begin() + e0, ops.begin() + e1); part.insert(part.end(), ops.begin() + n + e0, ops.begin() + n + e1);
+                pt = fetched_slots(part.data(), (uint32_t)part.size());
+                if (pt <= RING_K || e1 == e0 + 1) break;
+            }
+            if (pt > RING_K) { bad("internal: one entry of a split select_by_indicator does not fit the value slots a lane keeps at hand"); break; }
+            to_fast_refs(part.data(), (uint32_t)part.size(), pt, fetches);
+            const uint32_t m = e1 - e0, aux = (e0 ? SELIND_CONTINUES : 0u) | (e1 < n ? SELIND_CONTINUED : 0u);
+            T->insert(T->end(), fetches.begin(), fetches.end());
+            T->push_back(DOP_FR_SELIND | (m << 8) | (aux << 16) | ((2 * m + 2) << 24)); T->insert(T->end(), part.begin(), part.end()); T->push_back(e1 < n ? NO_SLOT : res);
+            LW.n_select_parts++; e0 = e1;
+        }
+    }
+    // The op's length byte and its operands: those in the lane's ring or in the LDS part of the pools become fast refs; the others are fetched into fresh
+    // ring slots by DOP_FETCH ops in front of this one.  The ring holds the last RING_K slots WRITTEN, the temporaries included: decided against the slot
+    // count after them.  false: refused - more slots to fetch than the ring has
+    bool operand_pass() {
+        std::vector<uint32_t> &t = *T;
+        uint32_t first, count; operand_span(t[op_at] & 0xff, (t[op_at] >> 8) & 0xff, first, count);
+        if (obs && LW.err.empty()) observe(first, count);
+        const size_t len = t.size() - op_at; if (len > 255) bad("internal: op too long"); t[op_at] |= (uint32_t)len << 24;
+        const uint32_t temps = fetched_slots(t.data() + op_at + first, count);
+        // the ring is RING_K slots (slot mod RING_K): with more temporaries than that the later fetches overwrite the earlier ones before the op reads
+        // them.  (The op's own result slots may alias them: every op reads all its operands before it stores a result.)
+        if (temps > RING_K && opt.split_selects && (t[op_at] & 0xff) == DOP_FR_SELIND) split_select(first, count);
+        else if (temps > RING_K) {
+            bad((o->code == TR_SELECT_BY_INDICATOR ? std::string("select_by_indicator") : "trace op " + std::to_string((int)o->code) + " (device op " + std::to_string(t[op_at] & 0xff) + ")") + " with " + std::to_string(count) + " operands: " + std::to_string(temps) + " slots of them have to be fetched (values of an enclosing scope, values computed more than " +
+                std::to_string(RING_K) + " slots earlier, proof words, far constants), more than the " + std::to_string(RING_K) + " value slots a lane keeps at hand");
+            return false;
+        } else {
+            std::vector<uint32_t> fetches; to_fast_refs(t.data() + op_at + first, count, temps, fetches);
+            if (!fetches.empty()) { t.insert(t.begin() + (long)op_at, fetches.begin(), fetches.end()); if (S->last_const_at == (long)op_at) S->last_const_at += (long)fetches.size(); }
+        }
+        return true;
+    }
+
+    // ---- pass 2: the ops in tape order
+    bool lower_op() {      // false: the pass ends here
+        in = tr->ins.data() + o->first_in; out = tr->outs.data() + o->first_out;
+        op_at = T->size(); slots_before = S->nslots; ka_fused = false;
+        auto f = opt.fused.fuse.find(i); const bool fz = f != opt.fused.fuse.end();
+        const uint64_t want_cells = fz ? fused_stretch(f->second) : by_kind();
+        if (fz || !(o->code == TR_LOAD_CONSTANT && S->last_const_at == (long)op_at)) S->last_const_at = -1;
+        if (T->size() > op_at && !operand_pass()) return false;
+        if (LW.err.empty() && want_cells != o->ncells) bad("internal: op " + std::to_string(o->code) + " appended " + std::to_string(o->ncells) + " cells on the host, the device template has " + std::to_string(want_cells));
+        return true;
+    }
+    void run() {
+        segments();
+        open_child.assign(segs.size(), -1);
+        for (i = 0; i < tr->ops.size() && LW.err.empty(); i++) {
+            o = &tr->ops[i]; s = LW.op_seg[i]; S = &segs[(size_t)s]; T = &S->tape;
+            if (o->code == TR_SCOPE_PUSH || o->code == TR_SCOPE_POP) scope_op();
+            else if (!lower_op()) break;
+            prev_seg = s;
+        }
+        if (obs) obs->end();
+        if (!LW.err.empty()) return;
+        segs[0].tape.push_back(DOP_END | (1u << 24)); segs[0].cell0 = 0; segs[0].rec0 = 0;
+    }
+};
+static void lower_pass(const Trace *tr, const LowerOptions &opt, Lowered &LW, LoweredOpObserver *obs = nullptr) { Lowering(tr, opt, LW, obs).run(); }
 
 // The canonical tape of ONE permutation on `consts`: the library's own PoseidonChip::permute / PoseidonBN254PermutationChip::permute (what
 // h2w_chip_gl_poseidon_permute / h2w_chip_bn_poseidon_permute run) recorded on abstract inputs and lowered by lower_trace like any tape; its operands
@@ -399,8 +496,8 @@ static bool canonical_tape(int id, int L, TemplateTable &tt, const h2w_poseidon_
     if (rc == 0) rc = bn ? h2w_chip_bn_poseidon_permute(c, consts, in, out) : h2w_chip_gl_poseidon_permute(c, consts, in, out);
     const Trace *tr = ctx_trace(c);
     if (rc != 0 || !tr || !tr->err.empty()) { err = "cannot record the canonical permutation"; h2w_ctx_free(c); return false; }
-    Lowered LW; std::vector<NormOp> ops;
-    lower_pass(tr, L, tt, nullptr, 0, LW, false, nullptr, nullptr, nullptr, nullptr, &ops);
+    Lowered LW; RootCapture root; const std::vector<NormOp> &ops = root.ops;
+    lower_pass(tr, LowerOptions{L, tt}, LW, &root);
     const size_t first = lead + (size_t)nio;
     bool ok = LW.err.empty() && ops.size() > first;
     if (!ok) err = "the canonical permutation does not lower: " + LW.err;
@@ -436,7 +533,7 @@ static bool canonical_tape(int id, int L, TemplateTable &tt, const h2w_poseidon_
 }
 
 void lower_trace(const Trace *tr, int L, TemplateTable &tt, const char *const *parallel_scopes, size_t n_scopes, const Fusable &F, bool split_selects, Lowered &LW) {
-    lower_pass(tr, L, tt, parallel_scopes, n_scopes, LW, split_selects, F.fuse.empty() ? nullptr : &F.fuse, &F.glp_meta, nullptr, nullptr, nullptr);
+    lower_pass(tr, LowerOptions{L, tt, parallel_scopes, n_scopes, split_selects, F}, LW);
 }
 
 // The stretches that equal a canonical tape word for word, found on a first lowering; those nothing outside reads into are lowered as one op
@@ -455,7 +552,7 @@ bool find_fusable(const Trace *tr, int L, TemplateTable &tt, const char *const *
         if (cnb.ncells != (uint64_t)BN_PERM_CELLS || cnz.ncells != (uint64_t)BN_PERM_CELLS + 1) { err = ex + "a PoseidonBN254 permutation has " + std::to_string(cnb.ncells) + " traced cells, the emission kernel writes " + std::to_string(BN_PERM_CELLS); return false; }
         cns.push_back(&cnb); cns.push_back(&cnz);
     }
-    { Lowered first; lower_pass(tr, L, tt, parallel_scopes, n_scopes, first, split_selects, nullptr, nullptr, &cns, &found, nullptr); if (!first.err.empty()) { err = "h2w_plan_from_trace: " + first.err; return false; } }
+    { Lowered first; MatcherSet search(cns, found); lower_pass(tr, LowerOptions{L, tt, parallel_scopes, n_scopes, split_selects}, first, &search); if (!first.err.empty()) { err = "h2w_plan_from_trace: " + first.err; return false; } }
     std::sort(found.begin(), found.end(), [](const Stretch &a, const Stretch &b) { return a.cell0 < b.cell0; });
     // an interior value read outside its stretch: every operand handle of the trace (the hints' operands too) against the stretches' cell ranges
     auto reads = [&](size_t op, uint64_t cell) {
@@ -567,30 +664,26 @@ bool group_templates(Lowered &LW, const ShardUnits &U, LoweredPlan &P, std::stri
     return true;
 }
 
+// ---- the verdict stage: a segment's entries with the verdict's own import table; the first reason why there is no verdict stays
+struct SegV { std::vector<VEntD> ents; std::vector<ImpD> imps; std::map<std::pair<uint32_t, uint32_t>, uint32_t> imp_of; };
+static void no_verdict(VerdictTables &V, const std::string &m) { if (V.why.empty()) V.why = "the traced plan has no verdict: " + m; }
+static void share_verdict_entries(const std::vector<SegV> &sv, const std::vector<SegInfo> &segs, const LoweredPlan &P, VerdictTables &V);
 VerdictTables verdict_tables(const Trace *tr, const Lowered &LW, const Fusable &F, const LoweredPlan &P) {
     VerdictTables V; V.n_asserts = tr->asserts.size();
     const std::vector<SegInfo> &segs = LW.segs;
-    struct SegV { std::vector<VEntD> ents; std::vector<ImpD> imps; std::map<std::pair<uint32_t, uint32_t>, uint32_t> imp_of; };
     std::vector<SegV> sv(segs.size());
-    auto unavailable = [&](const std::string &m) { if (V.why.empty()) V.why = "the traced plan has no verdict: " + m; };
-    auto is_ancestor = [&](int a, int s) { for (int x = s; x >= 0; x = segs[(size_t)x].parent) if (x == a) return true; return false; };
-    // a handle's cell as an operand of a check in segment s (lower_pass ref_of, on the finished maps and with the verdict's own imports)
+    auto unavailable = [&](const std::string &m) { no_verdict(V, m); };
+    // a handle's cell as an operand of a check in segment s (resolve_handle on the finished maps, with the verdict's own imports)
     auto vref = [&](int s, uint64_t cell, bool has_cell, const char *what, uint32_t &r) -> bool {
         r = 0;
         if (!has_cell) { unavailable(std::string(what) + " compares a handle that is no cell of the traced context"); return false; }
-        auto it = LW.val_of.find(cell);
-        if (it == LW.val_of.end()) {
+        int width; const HandleWhy why = resolve_handle(LW, s, cell, ImportTable{sv[(size_t)s].imps, sv[(size_t)s].imp_of}, r, width);
+        if (why == HANDLE_NOT_TRACED) {
             for (const auto &kv : F.fuse) if (cell >= kv.second.cell0 && cell < kv.second.cell1) { unavailable(std::string(what) + " reads a value interior to a fused permutation, which the value store no longer has (cell " + std::to_string(cell) + "): lower the trace without the fuse flag for a verdict"); return false; }
-            unavailable(std::string(what) + " reads a cell that is no traced call's result handle (cell " + std::to_string(cell) + ")"); return false;
+            unavailable(std::string(what) + " reads a cell that is no traced call's result handle (cell " + std::to_string(cell) + ")");
         }
-        const ValInfo &v = LW.vals[it->second];
-        if (v.is_static) { r = v.width == WFR ? mkref(RK_LITFR, WFR, v.lit) : mkref(RK_LIT64, W64, v.lit); return true; }
-        if ((int)v.seg == s) { r = mkref(RK_LOCAL, v.width, v.slot); return true; }
-        if (!is_ancestor((int)v.seg, s)) { unavailable(std::string(what) + " reads a value computed in a scope that does not enclose it (cell " + std::to_string(cell) + ")"); return false; }
-        SegV &S = sv[(size_t)s]; const auto key = std::make_pair(v.seg, v.slot);
-        auto im = S.imp_of.find(key);
-        if (im == S.imp_of.end()) { S.imps.push_back(ImpD{v.seg, 0, v.slot}); im = S.imp_of.emplace(key, (uint32_t)S.imps.size() - 1).first; }
-        r = mkref(RK_IMPORT, v.width, im->second); return true;
+        if (why == HANDLE_NOT_ENCLOSING) unavailable(std::string(what) + " reads a value computed in a scope that does not enclose it (cell " + std::to_string(cell) + ")");
+        return why == HANDLE_OK;
     };
     for (const TraceAssert &e : tr->asserts) {
         if (e.at > LW.op_seg.size()) { unavailable("internal: an equality beyond the tape"); break; }
@@ -609,7 +702,13 @@ VerdictTables verdict_tables(const Trace *tr, const Lowered &LW, const Fusable &
         if (vref_words(d.a) != 1) { unavailable("internal: a range check of a wide value"); break; }
         sv[(size_t)s].ents.push_back(d);
     }
-    // the instances of a template share one table (their import tables, one per instance, make it concrete): InstD order
+    share_verdict_entries(sv, segs, P, V);
+    if (!V.why.empty()) { V.ents.clear(); V.ent0.clear(); V.vimps.clear(); V.vimp0.clear(); V.nvimp.clear(); V.sites.clear(); V.site0.clear(); V.n_eq_lanes = V.n_range = V.n_tmpl = 0; }
+    return V;
+}
+// the instances of a template share one table (their import tables, one per instance, make it concrete): InstD order
+static void share_verdict_entries(const std::vector<SegV> &sv, const std::vector<SegInfo> &segs, const LoweredPlan &P, VerdictTables &V) {
+    auto unavailable = [&](const std::string &m) { no_verdict(V, m); };
     std::vector<std::vector<int>> members(P.tmpls.size());
     for (size_t si = 0; si < segs.size(); si++) {
         const SegInfo &S = segs[si];
@@ -642,10 +741,18 @@ VerdictTables verdict_tables(const Trace *tr, const Lowered &LW, const Fusable &
         if (!M.ents.empty()) V.n_tmpl++;
     }
     V.ent0.push_back((uint32_t)V.ents.size());
-    if (!V.why.empty()) { V.ents.clear(); V.ent0.clear(); V.vimps.clear(); V.vimp0.clear(); V.nvimp.clear(); V.sites.clear(); V.site0.clear(); V.n_eq_lanes = V.n_range = V.n_tmpl = 0; }
-    return V;
 }
 
+// clears the bits of the cells [c0, c0 + n) of a one-bit-per-cell map, word by word; false: one of them was clear already (the map is left as far as it got)
+static bool clear_cells(std::vector<uint64_t> &bits, uint64_t c0, uint64_t n) {
+    for (uint64_t c = c0; c < c0 + n;) {
+        const uint64_t k = c & 63, take = std::min<uint64_t>(64 - k, c0 + n - c), mask = (take == 64 ? ~0ull : ((1ull << take) - 1)) << k;
+        uint64_t &w = bits[(size_t)(c / 64)];
+        if ((w & mask) != mask) return false;
+        w &= ~mask; c += take;
+    }
+    return true;
+}
 bool direct_cell_map(const LoweredPlan &P, const TemplateTable &tt, uint64_t ncells, std::vector<uint64_t> &direct, uint64_t &n_direct, std::string &err) {
     direct.assign((size_t)(((ncells + 63) / 64 + 63) / 64 * 64), 0);
     for (uint64_t w = 0; w < ncells / 64; w++) direct[(size_t)w] = ~0ull;
@@ -654,12 +761,7 @@ bool direct_cell_map(const LoweredPlan &P, const TemplateTable &tt, uint64_t nce
     for (size_t i = 0; i < P.meta.size(); i++) {
         const uint64_t c0 = meta_off(P.meta[i]), n = (uint64_t)tt.ncells((int)meta_tmpl(P.meta[i]));
         if (c0 + n > ncells) { err = "h2w_plan_from_trace_ex: internal: record " + std::to_string(i) + " lies beyond the stream"; return false; }
-        for (uint64_t c = c0; c < c0 + n;) {      // word by word
-            const uint64_t k = c & 63, take = std::min<uint64_t>(64 - k, c0 + n - c), mask = (take == 64 ? ~0ull : ((1ull << take) - 1)) << k;
-            uint64_t &w = direct[(size_t)(c / 64)];
-            if ((w & mask) != mask) { err = "h2w_plan_from_trace_ex: internal: record " + std::to_string(i) + " overlaps another record"; return false; }
-            w &= ~mask; c += take;
-        }
+        if (!clear_cells(direct, c0, n)) { err = "h2w_plan_from_trace_ex: internal: record " + std::to_string(i) + " overlaps another record"; return false; }
         rec_cells += n;
     }
     n_direct = 0;
@@ -671,12 +773,7 @@ bool direct_cell_map(const LoweredPlan &P, const TemplateTable &tt, uint64_t nce
 bool ranged_cell_map(const LoweredPlan &P, uint64_t perm_cells, const std::vector<uint64_t> &direct, std::vector<uint64_t> &ranged, std::string &err) {
     ranged = direct;
     for (const BnpD &b : P.bnp)
-        for (uint64_t c = b.cell0; c < b.cell0 + perm_cells;) {
-            const uint64_t k = c & 63, take = std::min<uint64_t>(64 - k, b.cell0 + perm_cells - c), mask = (take == 64 ? ~0ull : ((1ull << take) - 1)) << k;
-            uint64_t &w = ranged[(size_t)(c / 64)];
-            if ((w & mask) != mask) { err = "h2w_plan_from_trace_ex: internal: a fused permutation's cell is a record's cell, or two permutations overlap"; return false; }
-            w &= ~mask; c += take;
-        }
+        if (!clear_cells(ranged, b.cell0, perm_cells)) { err = "h2w_plan_from_trace_ex: internal: a fused permutation's cell is a record's cell, or two permutations overlap"; return false; }
     return true;
 }
 

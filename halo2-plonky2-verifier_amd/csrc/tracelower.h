@@ -24,7 +24,6 @@ struct SegInfo {
     uint32_t unit = NO_SLOT;      // the depth-1 instance (shard unit) this segment is or lies in
     int tmpl = -1; uint32_t inst = 0;
     long last_const_at = -1; uint64_t last_const_cell = 0; size_t last_const_tr = 0;      // the op emitted last is a static CONST1 (its tape position, its cell): a GLOP right behind it that takes it as operand A fuses with it
-    std::vector<struct Matcher *> mt; // the searches for permutation-shaped stretches (first lowering of a fused plan): one per canonical tape
     uint32_t nglp = 0;                // fused permutations (DOP_GLPERM) of this segment
     uint32_t nbnp = 0; std::vector<uint64_t> bnp_cells;      // fused PoseidonBN254 permutations (DOP_BNPERM) of this segment: their first cells
 };

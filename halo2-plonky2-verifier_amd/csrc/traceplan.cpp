@@ -8,6 +8,7 @@
 #include <string>
 #include <cstring>
 #include <cstdlib>
+#include <cstdio>
 #include "traceplan.h"
 #include "keygen.h"
 
@@ -53,6 +54,31 @@ int traced_mont_tables(const h2w_plan *p, DevBuf<fr_t> &bn_tab_mont, DevBuf<uint
 
 // ---- h2w_plan_from_trace
 struct LoweredTrace { Fusable F; ShardUnits U; LoweredPlan LP; VerdictTables VT; std::vector<uint64_t> op_counts; };
+#ifdef H2W_LOWERING_DUMP
+// What the lowering produced, every item as a count and its raw bytes, to the file H2W_LOWERING_DUMP_FILE names (tools/lowering_digest.py hashes it: a
+// change of tracelower.cpp that is meant to change nothing is held to equal files).  A variant build only: the product library has no such switch.
+struct LoweringDump {
+    FILE *f;
+    explicit LoweringDump(const char *mode) { const char *path = getenv("H2W_LOWERING_DUMP_FILE"); f = path ? fopen(path, mode) : nullptr; }
+    ~LoweringDump() { if (f) fclose(f); }
+    void raw(const void *p, size_t count, size_t size) { if (!f) return; const uint64_t n = count; fwrite(&n, 8, 1, f); if (count) fwrite(p, size, count, f); }
+    template <class T> void vec(const std::vector<T> &v) { raw(v.data(), v.size(), sizeof(T)); }
+    void num(uint64_t v) { if (f) fwrite(&v, 8, 1, f); }
+    void text(const std::string &s) { raw(s.data(), s.size(), 1); }
+};
+static void dump_lowering(const LoweredTrace &W, uint64_t ncells) {
+    LoweringDump D("wb"); const LoweredPlan &LP = W.LP; const ShardUnits &U = W.U; const VerdictTables &VT = W.VT;
+    D.vec(LP.tape); D.vec(LP.insts); D.vec(LP.imps); D.vec(LP.inputs); D.vec(LP.pool64); D.vec(LP.poolfr); D.vec(LP.meta); D.vec(LP.tmpls);
+    D.vec(LP.unit); D.vec(LP.glp_unit); D.vec(LP.bnp); D.vec(LP.bnp0);
+    D.num(LP.nrec); D.num(ncells); D.num(U.num_queries); D.num(U.pro_ncell); D.num(U.pro_nrec);
+    for (int k = 0; k < 2; k++) { D.num(U.q_cell0[k]); D.num(U.q_rec0[k]); D.num(U.q_ncell[k]); D.num(U.q_nrec[k]); }
+    D.vec(U.units); D.text(U.why_unshardable);
+    D.num(W.F.fuse.size()); D.num(W.F.glp_meta.size()); D.num(W.F.glp_block_cells); D.num(W.F.n_candidates); D.num(W.F.n_bn_left); D.num(LP.nglp); D.num(LP.nbnp);
+    D.num(LP.total_slot_lanes); D.num(LP.n_segments); D.num(LP.n_select_parts); D.vec(W.op_counts);
+    D.vec(VT.ents); D.vec(VT.ent0); D.vec(VT.vimps); D.vec(VT.vimp0); D.vec(VT.nvimp); D.vec(VT.sites); D.vec(VT.site0);
+    D.num(VT.n_asserts); D.num(VT.n_eq_lanes); D.num(VT.n_range); D.num(VT.n_tmpl); D.text(VT.why);
+}
+#endif
 // Host only.  false: err is the message
 static bool lower(h2w_ctx *ctx, uint64_t proof_words, const char *const *parallel_scopes, size_t n_scopes, const h2w_poseidon_consts_t *consts, uint32_t flags, LoweredTrace &W, std::string &err) {
     const Trace *tr = ctx_trace(ctx);
@@ -95,6 +121,9 @@ static bool lower(h2w_ctx *ctx, uint64_t proof_words, const char *const *paralle
     for (size_t t = 0; t < LP.tmpls.size(); t++) tape_op_counts(LP.tmpl_tape(t), LP.tmpl_tape_words(t), W.op_counts.data());
     for (uint32_t w : LP.inputs) if (w >= proof_words) { err = "h2w_plan_from_trace: an input tag beyond proof_words"; return false; }
     for (const BnpD &b : LP.bnp) if (b.cell0 + (uint64_t)BN_PERM_CELLS > ncells) { err = "h2w_plan_from_trace_ex: internal: a fused permutation's cells lie beyond the stream"; return false; }
+#ifdef H2W_LOWERING_DUMP
+    dump_lowering(W, ncells);
+#endif
     return true;
 }
 // The plan handle and its TracedPlan, host members only.  null: the last error says why
@@ -118,6 +147,9 @@ static h2w_plan *fill_handle(h2w_ctx *ctx, uint64_t proof_words, int device_id, 
         std::string err;
         if (!direct_cell_map(LP, pl->tt, ncells, pl->direct_bits, pl->n_direct, err) || !ranged_cell_map(LP, (uint64_t)BN_PERM_CELLS, pl->direct_bits, pl->ranged_bits, err)) { set_error(err); h2w_plan_free(pl); return nullptr; }
         pl->trace_forms = true; pl->trace_bn_ranged = getenv("H2W_TRACE_BN_RANGED") != nullptr;
+#ifdef H2W_LOWERING_DUMP
+        { LoweringDump D("ab"); D.vec(pl->direct_bits); D.vec(pl->ranged_bits); D.num(pl->n_direct); }
+#endif
     }
     if (consts) pl->h_consts = *consts;
     for (uint64_t m : LP.meta) pl->rec_cells += (uint64_t)pl->tt.ncells((int)meta_tmpl(m));

@@ -246,4 +246,5 @@ def test_product_library_has_no_experiment_switches(h2w):
     and bench.py load reads no such environment variable."""
     blob = open(h2w.LIB_PATH, "rb").read()
     assert b"H2W_DBG" not in blob and b"H2W_EXPAND_VARIANT" not in blob and b"H2W_BN_UNITS" not in blob
+    assert b"H2W_LOWERING_DUMP" not in blob      # (csrc/traceplan.cpp's dump of the lowering: a variant build's, tools/lowering_digest.py)
     assert os.path.basename(h2w.LIB_PATH) == "libh2w.so" or os.environ.get("H2W_LIB")

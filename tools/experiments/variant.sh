@@ -4,6 +4,8 @@
 #   variant.sh NAME "EXTRA_CXX_FLAGS" -- COMMAND...
 #       builds halo2-plonky2-verifier_amd/libh2w_NAME.so with the extra compiler flags (compile-time knobs of the kernels: -DH2W_FAST_T=8,
 #       -DH2W_QUAD_BLOCK=512, -DH2W_QUAD_EU=1, -DH2W_FAST_K=2 ...) and runs COMMAND with H2W_LIB pointing at it.  NAME "" = the product library.
+#   H2W_UNITS="traceplan.cpp tracelower.cpp" variant.sh lowdump "-DH2W_LOWERING_DUMP" -- python3 tools/lowering_digest.py
+#       H2W_UNITS: the units the flags go to (tools/build_debug_variant.sh; default the three kernel units).  This one is the lowering dump: host only, no GPU.
 #   variant.sh - "" -- python bench.py --steps 12 --warmup 4 --no-cpu-baseline --no-extras [--chain-passes 1|2] [--streams N] [--batch B] [--no-fork] ...
 #       run-time knobs need no build: they are bench.py flags / h2w_plan_configure options.
 #   variant.sh pmc "" -- rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_VMEM_WR \
