@@ -93,6 +93,10 @@ HD uint64_t gl_primitive_root_of_unity(int n_log) {
     return g;
 }
 struct gle_t { uint64_t c[2]; };
+HD gle_t gle_of(uint64_t a) { gle_t r; r.c[0] = a; r.c[1] = 0; return r; }
+HD gle_t gle_add(gle_t a, gle_t b) { gle_t r; r.c[0] = gl_add(a.c[0], b.c[0]); r.c[1] = gl_add(a.c[1], b.c[1]); return r; }
+HD gle_t gle_sub(gle_t a, gle_t b) { gle_t r; r.c[0] = gl_sub(a.c[0], b.c[0]); r.c[1] = gl_sub(a.c[1], b.c[1]); return r; }
+HD gle_t gle_scale(gle_t a, uint64_t b) { gle_t r; r.c[0] = gl_mul(a.c[0], b); r.c[1] = gl_mul(a.c[1], b); return r; }
 HD gle_t gle_mul(gle_t a, gle_t b) {
     gle_t r;
     r.c[0] = gl_add(gl_mul(a.c[0], b.c[0]), gl_mul(7, gl_mul(a.c[1], b.c[1])));
@@ -105,6 +109,7 @@ HD gle_t gle_inv(gle_t a) {
     gle_t r; r.c[0] = gl_mul(a.c[0], ni); r.c[1] = gl_mul(gl_sub(0, a.c[1]), ni);
     return r;
 }
+HD gle_t gle_pow(gle_t a, uint64_t e) { gle_t acc = gle_of(1); while (e) { if (e & 1) acc = gle_mul(acc, a); a = gle_mul(a, a); e >>= 1; } return acc; }
 
 // ---------------------------------------------------------------- BN254 Fr
 // r = 0x30644e72e131a029b85045b68181585d2833e84879b9709143e1f593f0000001

@@ -17,226 +17,12 @@
 #include <cstring>
 #include <string>
 #include <vector>
-#include "chips.h"
 #include "common.h"
+#include "proverhash.h"
 #include "verifier.h"
 
 namespace h2w {
 namespace {
-
-struct BnMont { fr_t c[88], s[392], m[4][4], p[4][4]; };                 // PoseidonBN254 tables in Montgomery form (x * 2^261)
-struct ProverConsts { h2w_poseidon_consts_t k; BnMont bn; fr_t r2; uint64_t ninv; };
-struct H4 { uint64_t w[4]; };
-
-HD gle_t gle_add(gle_t a, gle_t b) { gle_t r; r.c[0] = gl_add(a.c[0], b.c[0]); r.c[1] = gl_add(a.c[1], b.c[1]); return r; }
-HD gle_t gle_sub(gle_t a, gle_t b) { gle_t r; r.c[0] = gl_sub(a.c[0], b.c[0]); r.c[1] = gl_sub(a.c[1], b.c[1]); return r; }
-HD gle_t gle_scale(gle_t a, uint64_t b) { gle_t r; r.c[0] = gl_mul(a.c[0], b); r.c[1] = gl_mul(a.c[1], b); return r; }
-HD gle_t gle_of(uint64_t a) { gle_t r; r.c[0] = a; r.c[1] = 0; return r; }
-HD gle_t gle_pow(gle_t a, uint64_t e) { gle_t acc = gle_of(1); while (e) { if (e & 1) acc = gle_mul(acc, a); a = gle_mul(a, a); e >>= 1; } return acc; }
-
-// ---------------------------------------------------------------- Goldilocks Poseidon, plonky2 "fast" layout (hash/poseidon/permutation.rs:43-314)
-// dot products of full-width words: 128-bit accumulator + overflow count, reduced once (2^128 = -2^32 mod p)
-struct GlAcc { u128 lo; uint32_t carries; };
-HD void glacc_mul(GlAcc &a, uint64_t x, uint64_t y) { const u128 pr = (u128)x * y; a.lo += pr; a.carries += a.lo < pr; }
-HD uint64_t glacc_reduce(const GlAcc &a) { return gl_sub(gl_reduce128(a.lo), (uint64_t)a.carries << 32); }
-// SMALL_MDS: every MDS_MATRIX_CIRC / _DIAG entry is below 2^28 (plonky2's are <= 41): a row is then two 64-bit accumulations over the
-// 32-bit halves of the state (13 terms < 2^32 * 2^28 each) and ONE reduction, instead of 13 reduced 64x64 products - the full
-// rounds' MDS layers are two thirds of a permutation's instructions otherwise.  Same values either way (exact arithmetic).
-template <bool SMALL_MDS> HDN inline void gl_permute_t(const h2w_poseidon_consts_t *k, uint64_t *st) {
-    int rc = 0;
-    for (int half = 0; half < 2; half++) {
-        if (half == 1) {
-#pragma unroll
-            for (int i = 0; i < 12; i++) st[i] = gl_add(st[i], k->fast_partial_first_round_constant[i]);
-            uint64_t res[12];
-            res[0] = st[0];
-#pragma unroll
-            for (int c = 1; c < 12; c++) {
-                GlAcc a; a.lo = 0; a.carries = 0;
-#pragma unroll
-                for (int r = 1; r < 12; r++) glacc_mul(a, k->fast_partial_round_initial_matrix[r - 1][c - 1], st[r]);
-                res[c] = glacc_reduce(a);
-            }
-#pragma unroll
-            for (int c = 0; c < 12; c++) st[c] = res[c];
-            const uint64_t m00 = gl_add(k->mds_circ[0], k->mds_diag[0]);
-#pragma unroll 1
-            for (int r = 0; r < N_PARTIAL_ROUNDS; r++) {
-                uint64_t x = st[0], x2 = gl_mul(x, x), x4 = gl_mul(x2, x2), x6 = gl_mul(x4, x2);
-                const uint64_t s0 = gl_add(gl_mul(x6, x), k->fast_partial_round_constants[r]);
-                GlAcc a; a.lo = (u128)m00 * s0; a.carries = 0;
-#pragma unroll
-                for (int i = 1; i < 12; i++) glacc_mul(a, k->fast_partial_round_w_hats[r][i - 1], st[i]);
-#pragma unroll
-                for (int i = 1; i < 12; i++) st[i] = gl_muladd(k->fast_partial_round_vs[r][i - 1], s0, st[i]);
-                st[0] = glacc_reduce(a);
-            }
-            rc += N_PARTIAL_ROUNDS;
-        }
-#pragma unroll 1
-        for (int f = 0; f < HALF_N_FULL_ROUNDS; f++) {
-#pragma unroll
-            for (int i = 0; i < 12; i++) {
-                uint64_t x = gl_add(st[i], k->all_round_constants[i + 12 * rc]);
-                uint64_t x2 = gl_mul(x, x), x4 = gl_mul(x2, x2), x6 = gl_mul(x4, x2); st[i] = gl_mul(x6, x);
-            }
-            uint64_t res[12];
-            if (SMALL_MDS) {
-                uint32_t lo32[12], hi32[12];
-#pragma unroll
-                for (int i = 0; i < 12; i++) { lo32[i] = (uint32_t)st[i]; hi32[i] = (uint32_t)(st[i] >> 32); }
-#pragma unroll
-                for (int r = 0; r < 12; r++) {
-                    const uint32_t dg = (uint32_t)k->mds_diag[r];
-                    uint64_t lo = (uint64_t)lo32[r] * dg, hi = (uint64_t)hi32[r] * dg;
-#pragma unroll
-                    for (int i = 0; i < 12; i++) { const uint32_t c = (uint32_t)k->mds_circ[i]; lo += (uint64_t)lo32[(i + r) % 12] * c; hi += (uint64_t)hi32[(i + r) % 12] * c; }
-                    res[r] = gl_reduce128((u128)lo + ((u128)hi << 32));
-                }
-            } else {
-#pragma unroll
-                for (int r = 0; r < 12; r++) {
-                    uint64_t acc = 0;
-#pragma unroll
-                    for (int i = 0; i < 12; i++) acc = gl_muladd(k->mds_circ[i], st[(i + r) % 12], acc);
-                    res[r] = gl_muladd(k->mds_diag[r], st[r], acc);
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < 12; r++) st[r] = res[r];
-            rc++;
-        }
-    }
-}
-
-HDN inline bool gl_mds_is_small(const h2w_poseidon_consts_t *k) {
-    bool small = true;
-    for (int i = 0; i < 12; i++) small = small && k->mds_circ[i] < (1ull << 28) && k->mds_diag[i] < (1ull << 28);
-    return small;
-}
-HDN inline void gl_permute(const h2w_poseidon_consts_t *k, uint64_t *st) { if (gl_mds_is_small(k)) gl_permute_t<true>(k, st); else gl_permute_t<false>(k, st); }
-
-// ---------------------------------------------------------------- PoseidonBN254 (hash/poseidon_bn254/permutation.rs:48-203), Montgomery-form state
-HNI fr_t mmul(fr_t a, fr_t b, uint64_t ninv) { return fr_mont_mul(a, b, ninv); }
-HDN inline fr_t bn_pow5(fr_t x, uint64_t ni) { fr_t x2 = mmul(x, x, ni), x4 = mmul(x2, x2, ni); return mmul(x4, x, ni); }
-HDN inline void bn_mix(fr_t *st, const fr_t m[4][4], uint64_t ni) {
-    fr_t ns[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        ns[i] = mmul(m[0][i], st[0], ni);
-#pragma unroll
-        for (int j = 1; j < 4; j++) ns[i] = fr_add(ns[i], mmul(m[j][i], st[j], ni));
-    }
-#pragma unroll
-    for (int i = 0; i < 4; i++) st[i] = ns[i];
-}
-HDN inline void bn_permute_m(const ProverConsts *K, fr_t *st) {
-    const uint64_t ni = K->ninv; const BnMont &B = K->bn;
-#pragma unroll
-    for (int j = 0; j < 4; j++) st[j] = fr_add(st[j], B.c[j]);
-    for (int half = 0; half < 2; half++) {
-        if (half == 1) {
-#pragma unroll 1
-            for (int r = 0; r < BN_PARTIAL_ROUNDS; r++) {
-                st[0] = fr_add(bn_pow5(st[0], ni), B.c[bn_c_partial(r)]);
-                fr_t ns0 = mmul(B.s[bn_s_row(r)], st[0], ni);
-#pragma unroll
-                for (int j = 1; j < 4; j++) ns0 = fr_add(ns0, mmul(B.s[bn_s_row(r) + j], st[j], ni));
-#pragma unroll
-                for (int kk = 1; kk < 4; kk++) st[kk] = fr_add(st[kk], mmul(B.s[bn_s_row(r) + BN_WIDTH + kk - 1], st[0], ni));
-                st[0] = ns0;
-            }
-        }
-#pragma unroll 1
-        for (int i = 0; i < BN_FULL_ROUNDS / 2 - 1; i++) {
-            const int it = bn_c_full(half, i);
-#pragma unroll
-            for (int j = 0; j < 4; j++) st[j] = fr_add(bn_pow5(st[j], ni), B.c[it + j]);
-            bn_mix(st, B.m, ni);
-        }
-#pragma unroll
-        for (int j = 0; j < 4; j++) st[j] = bn_pow5(st[j], ni);
-        if (half == 0) {
-#pragma unroll
-            for (int j = 0; j < 4; j++) st[j] = fr_add(st[j], B.c[(BN_FULL_ROUNDS / 2) * BN_WIDTH + j]);
-            bn_mix(st, B.p, ni);
-        } else bn_mix(st, B.m, ni);
-    }
-}
-HDN inline fr_t to_mont(const ProverConsts *K, fr_t x) { return mmul(x, K->r2, K->ninv); }
-HDN inline fr_t from_mont(const ProverConsts *K, fr_t x) { return mmul(x, fr_from_u64(1), K->ninv); }
-
-// ---------------------------------------------------------------- hashers (hash/poseidon/hash.rs:63-215, hash/poseidon_bn254/hash.rs:67-210): a hash is 4 words
-template <int MAXN> HDN inline H4 hash_no_pad(const ProverConsts *K, int mode, const uint64_t (&in)[MAXN], int n) {
-    H4 h;
-    if (mode == 0) {
-        uint64_t st[12];
-#pragma unroll
-        for (int i = 0; i < 12; i++) st[i] = 0;
-#pragma unroll
-        for (int off = 0; off < MAXN; off += SPONGE_RATE) {
-            if (off < n) {
-#pragma unroll
-                for (int i = 0; i < SPONGE_RATE; i++) if (off + i < MAXN && off + i < n) st[i] = in[off + i];
-                gl_permute(&K->k, st);
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 4; i++) h.w[i] = st[i];
-    } else {
-        fr_t st[4];
-#pragma unroll
-        for (int i = 0; i < 4; i++) st[i] = fr_zero();
-#pragma unroll
-        for (int off = 0; off < MAXN; off += 9) {
-            if (off < n) {
-#pragma unroll
-                for (int j = 0; j < 3; j++) {
-                    const int o = off + 3 * j;
-                    if (o < MAXN && o < n) {
-                        fr_t v = fr_zero();
-#pragma unroll
-                        for (int l = 0; l < 3; l++) if (o + l < MAXN && o + l < n) v.l[l] = in[o + l];
-                        st[j + 1] = to_mont(K, v);
-                    }
-                }
-                bn_permute_m(K, st);
-            }
-        }
-        const fr_t o = from_mont(K, st[0]);
-#pragma unroll
-        for (int i = 0; i < 4; i++) h.w[i] = o.l[i];
-    }
-    return h;
-}
-template <int MAXN> HDN inline H4 hash_or_noop(const ProverConsts *K, int mode, const uint64_t (&in)[MAXN], int n) {
-    if (n > (mode == 0 ? 4 : 3)) return hash_no_pad<MAXN>(K, mode, in, n);
-    H4 h;
-#pragma unroll
-    for (int i = 0; i < 4; i++) h.w[i] = (i < MAXN && i < n) ? in[i < MAXN ? i : 0] : 0;
-    return h;
-}
-HDN inline H4 two_to_one(const ProverConsts *K, int mode, const H4 &l, const H4 &r) {
-    H4 h;
-    if (mode == 0) {
-        uint64_t st[12];
-#pragma unroll
-        for (int i = 0; i < 4; i++) { st[i] = l.w[i]; st[4 + i] = r.w[i]; st[8 + i] = 0; }
-        gl_permute(&K->k, st);
-#pragma unroll
-        for (int i = 0; i < 4; i++) h.w[i] = st[i];
-    } else {
-        fr_t st[4], a, b;
-#pragma unroll
-        for (int i = 0; i < 4; i++) { a.l[i] = l.w[i]; b.l[i] = r.w[i]; }
-        st[0] = fr_zero(); st[1] = fr_zero(); st[2] = to_mont(K, a); st[3] = to_mont(K, b);
-        bn_permute_m(K, st);
-        const fr_t o = from_mont(K, st[0]);
-#pragma unroll
-        for (int i = 0; i < 4; i++) h.w[i] = o.l[i];
-    }
-    return h;
-}
 
 // ================================================================= kernels
 __global__ void k_twiddles(uint64_t *tw, uint64_t half_n, uint64_t w) {
@@ -305,6 +91,11 @@ __global__ void k_tree_level(const ProverConsts *K, int mode, const H4 *in, H4 *
     in += blockIdx.y * tree_stride; out += blockIdx.y * tree_stride;
     out[i] = two_to_one(K, mode, in[2 * i], in[2 * i + 1]);
 }
+// red[0] <- the sum of red[0 .. 255], by a block of 256 threads that have each stored their own term
+__device__ __forceinline__ void block_sum_256(gle_t *red) {
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) { if ((int)threadIdx.x < s) red[threadIdx.x] = gle_add(red[threadIdx.x], red[threadIdx.x + s]); __syncthreads(); }
+}
 // partial[proof][p][block] = sum over the block's coefficients c_i x^i (blocked Horner, then a block reduction); x = xs[proof]
 constexpr int EVAL_PER_THREAD = 16;
 __global__ __launch_bounds__(256) void k_eval_partial(const uint64_t *coef, uint64_t N, const gle_t *xs, gle_t *partial, uint64_t coef_stride, uint64_t partial_stride) {
@@ -317,8 +108,7 @@ __global__ __launch_bounds__(256) void k_eval_partial(const uint64_t *coef, uint
         for (int i = EVAL_PER_THREAD - 1; i >= 0; i--) acc = gle_add(gle_mul(acc, x), gle_of(base + i < N ? c[i] : 0));
         acc = gle_mul(acc, gle_pow(x, base));
     }
-    red[threadIdx.x] = acc; __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) { if ((int)threadIdx.x < s) red[threadIdx.x] = gle_add(red[threadIdx.x], red[threadIdx.x + s]); __syncthreads(); }
+    red[threadIdx.x] = acc; block_sum_256(red);
     if (threadIdx.x == 0) partial[blockIdx.z * partial_stride + p * gridDim.x + blockIdx.x] = red[0];
 }
 // batched quotient, step 1: T[m] = G[m] z^m with G = sum_i alpha^i f_i (minus G(z) at m = 0); block sums.  One QuotArgs per proof.
@@ -340,8 +130,7 @@ __global__ __launch_bounds__(256) void k_quot_terms(const QuotArgs *Av, gle_t *T
             T[m] = t; sum = gle_add(sum, t); zp = gle_mul(zp, z);
         }
     }
-    red[threadIdx.x] = sum; __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) { if ((int)threadIdx.x < s) red[threadIdx.x] = gle_add(red[threadIdx.x], red[threadIdx.x + s]); __syncthreads(); }
+    red[threadIdx.x] = sum; block_sum_256(red);
     if (threadIdx.x == 0) totals[blockIdx.x] = red[0];
 }
 // step 2: carry[b] = sum of the totals of the blocks after b (one block per proof)
@@ -413,6 +202,13 @@ struct GatherArgs {
     uint64_t *proof; uint64_t proof_stride, q_base, q_words, init_off[3], step_off[MAX_STEPS]; const uint64_t *x_index;
 };
 HD uint64_t level_off(int bits, int l) { return (2ull << bits) - (2ull << (bits - l)); }     // hashes before level l of a tree with 2^bits leaves
+// the sibling hashes of the path of leaf idx through the first nlev levels of a tree with 2^bits leaves -> out[at + 4 l ..], by the block's threads
+__device__ __forceinline__ void copy_path(const H4 *tree, int bits, int nlev, uint64_t idx, uint64_t *out, int at) {
+    for (int l = threadIdx.x; l < nlev; l += blockDim.x) {
+        const H4 h = tree[level_off(bits, l) + ((idx >> l) ^ 1)];
+        for (int i = 0; i < 4; i++) out[at + 4 * l + i] = h.w[i];
+    }
+}
 __global__ void k_gather(GatherArgs G) {
     const uint64_t pr = blockIdx.y;
     uint64_t *w = G.proof + pr * G.proof_stride + G.q_base + (uint64_t)blockIdx.x * G.q_words;
@@ -421,10 +217,7 @@ __global__ void k_gather(GatherArgs G) {
         uint64_t *wo = w + G.init_off[o];
         const H4 *tree = G.tree + (pr * G.no + o) * G.tree_stride;
         for (int p = threadIdx.x; p < G.npoly[o]; p += blockDim.x) wo[p] = G.lde[pr * G.lde_stride + (uint64_t)(G.poly0[o] + p) * G.L + x];
-        for (int l = threadIdx.x; l < G.lb - G.capb; l += blockDim.x) {
-            const H4 h = tree[level_off(G.lb, l) + ((x >> l) ^ 1)];
-            for (int i = 0; i < 4; i++) wo[G.npoly[o] + 4 * l + i] = h.w[i];
-        }
+        copy_path(tree, G.lb, G.lb - G.capb, x, wo, G.npoly[o]);
     }
     uint64_t idx = x; int bits = G.lb;
     for (int st = 0; st < G.n_steps; st++) {
@@ -432,10 +225,7 @@ __global__ void k_gather(GatherArgs G) {
         uint64_t *ws = w + G.step_off[st];
         const uint64_t *fv = G.fv[st] + pr * 2 * G.fn[st]; const H4 *ft = G.ftree[st] + pr * 2 * (G.fn[st] >> ab);
         for (int t = threadIdx.x; t < ar; t += blockDim.x) { ws[2 * t] = fv[(coset << ab) + t]; ws[2 * t + 1] = fv[G.fn[st] + (coset << ab) + t]; }
-        for (int l = threadIdx.x; l < bits - G.capb; l += blockDim.x) {
-            const H4 h = ft[level_off(bits, l) + ((coset >> l) ^ 1)];
-            for (int i = 0; i < 4; i++) ws[2 * ar + 4 * l + i] = h.w[i];
-        }
+        copy_path(ft, bits, bits - G.capb, coset, ws, 2 * ar);
         idx = coset;
     }
 }
@@ -451,12 +241,16 @@ struct HostChallenger {
         for (int i = 0; i < 5; i++) observe(fr_bits(v, 56 * i, 56));                       // hash/poseidon_bn254/hash.rs:31-43
     }
     void observe_ext(const gle_t &e) { observe(e.c[0]); observe(e.c[1]); }
+    // the complete rate blocks of the pending input into st (the state, or a copy of it); returns the words they hold
+    size_t absorb_blocks(uint64_t *st) const {
+        const size_t full = in.size() - in.size() % SPONGE_RATE;
+        for (size_t off = 0; off < full; off += SPONGE_RATE) { memcpy(st, in.data() + off, SPONGE_RATE * 8); gl_permute(k, st); }
+        return full;
+    }
     void absorb() {
         if (in.empty()) return;
-        for (size_t off = 0; off < in.size(); off += SPONGE_RATE) {
-            const size_t len = in.size() - off < (size_t)SPONGE_RATE ? in.size() - off : (size_t)SPONGE_RATE;
-            memcpy(state, in.data() + off, len * 8); gl_permute(k, state);
-        }
+        const size_t full = absorb_blocks(state);
+        if (full < in.size()) { memcpy(state, in.data() + full, (in.size() - full) * 8); gl_permute(k, state); }
         memcpy(out, state, sizeof(out)); n_out = SPONGE_RATE; in.clear();
     }
     uint64_t challenge() {
@@ -489,6 +283,7 @@ struct h2w_prover {
     DevEvent ev[8];
     float ms[7] = {0, 0, 0, 0, 0, 0, 0};
     int eval_blocks = 0, scan_blocks = 0;
+    size_t query_slots() const { return shape.num_queries ? (size_t)shape.num_queries : 1; }      // query indices per proof, as their buffers are sized (never empty)
 };
 
 namespace {
@@ -506,6 +301,12 @@ void build_trees(const h2w_prover *p, H4 *base, int bits, uint64_t count, uint64
         hipLaunchKernelGGL(k_tree_level, dim3(blocks(m, 64), (unsigned)count), dim3(64), 0, s, p->dk.get(), p->shape.hash_mode, base + level_off(bits, l - 1), base + level_off(bits, l), m, tree_stride);
     }
 }
+// the caps (level bits - cap_height) of `count` trees tree_stride hashes apart -> out[tree][cap_size], on the stream
+int read_caps(const h2w_prover *p, const H4 *base, int bits, uint64_t count, uint64_t tree_stride, H4 *out, hipStream_t s) {
+    const size_t row = (size_t)p->d.cap_size * sizeof(H4);
+    H2W_HIP(hipMemcpy2DAsync(out, row, base + level_off(bits, bits - p->shape.cap_height), tree_stride * sizeof(H4), row, count, hipMemcpyDeviceToHost, s));
+    return 0;
+}
 // device buffers of a batch of n proofs.  Only grows; a failed growth leaves every buffer empty and cap == 0, so that the next call starts over
 int ensure_capacity(h2w_prover *p, uint64_t n) {
     if (n <= p->cap) return 0;
@@ -514,7 +315,7 @@ int ensure_capacity(h2w_prover *p, uint64_t n) {
     bool ok = b.lde.alloc(n * p->np * L) == 0 && b.tree.alloc(n * d.n_oracles * 2 * L) == 0 && b.Fa.alloc(n * L) == 0 && b.Fb.alloc(n * L) == 0 && b.T.alloc(n * N) == 0 &&
               b.totals.alloc(n * p->scan_blocks) == 0 && b.carry.alloc(n * p->scan_blocks) == 0 && b.partial.alloc(n * 2 * p->np * p->eval_blocks) == 0 &&
               b.pts.alloc(n * 3) == 0 && b.qargs.alloc(n) == 0 && b.pargs.alloc(n) == 0 &&
-              b.x_index.alloc(n * (size_t)(p->shape.num_queries ? p->shape.num_queries : 1)) == 0 && b.best.alloc(n) == 0;
+              b.x_index.alloc(n * p->query_slots()) == 0 && b.best.alloc(n) == 0;
     { uint64_t m = L; for (int st = 0; st < d.n_steps && ok; st++) { ok = b.fv[st].alloc(n * 2 * m) == 0 && b.ftree[st].alloc(n * 2 * (m >> d.arity[st])) == 0; m >>= d.arity[st]; } }
     if (!ok) {
         p->b = BatchBufs(); (void)hipGetLastError();
@@ -534,6 +335,189 @@ int prover_upload(h2w_prover *p) {
     }
     return 0;
 }
+// one proof's batch of the quotient: sum_i alpha^i (f_i - f_i(z)) / (X - z) over the first npoly polynomials at coef, open[i] = f_i(z)
+void fill_quot_args(QuotArgs &A, const uint64_t *coef, uint64_t N, int npoly, gle_t z, gle_t alpha, const gle_t *open) {
+    A.coef = coef; A.N = N; A.npoly = npoly; A.z = z; A.zinv = gle_inv(A.z);
+    gle_t ap = gle_of(1); A.gz = gle_of(0);
+    for (int i = 0; i < npoly; i++) { A.ap[i] = ap; A.gz = gle_add(A.gz, gle_mul(ap, open[i])); ap = gle_mul(ap, alpha); }
+    A.an = ap;
+}
+// where k_gather finds the oracles and the commit-phase steps of a batch, and where their words go in the proofs
+GatherArgs gather_args(const h2w_prover *p, uint64_t *proofs_dev) {
+    const Derived &d = p->d; const ProofLayout &pl = p->pl; const BatchBufs &B = p->b; const uint64_t L = p->L;
+    GatherArgs G; G.lde = B.lde.get(); G.L = L; G.lde_stride = (uint64_t)p->np * L; G.lb = d.lde_bits; G.capb = p->shape.cap_height; G.no = d.n_oracles; G.tree = B.tree.get(); G.tree_stride = 2 * L;
+    for (int o = 0; o < 3; o++) { G.npoly[o] = o < d.n_oracles ? d.oracle_polys[o] : 0; G.poly0[o] = p->poly0[o]; G.init_off[o] = pl.init_off[o]; }
+    G.n_steps = d.n_steps;
+    { uint64_t m = L; for (int st = 0; st < MAX_STEPS; st++) { G.ab[st] = st < d.n_steps ? d.arity[st] : 0; G.fv[st] = B.fv[st].get(); G.fn[st] = m; G.ftree[st] = B.ftree[st].get(); G.step_off[st] = pl.step_off[st]; if (st < d.n_steps) m >>= d.arity[st]; } }
+    G.proof = proofs_dev; G.proof_stride = pl.total; G.q_base = pl.queries; G.q_words = pl.query_words; G.x_index = B.x_index.get();
+    return G;
+}
+
+// One h2w_prove_fri_batch call: the state that outlives a phase, and one method per phase in transcript order.  A method is what one timing value
+// measures (ms[i]: ev[i] to ev[i + 1]; ms[2] is three methods) and ends by recording the closing mark.  caps and fin are members because their
+// read-backs are issued in front of a mark and read behind the synchronisation after it; every other buffer of a phase is a local of its method.
+struct Proving {
+    h2w_prover *const p; const uint64_t *const coeffs_dev; const uint64_t n; const hipStream_t s;
+    const h2w_shape_t &sh; const Derived &d; const ProofLayout &pl; const BatchBufs &B;
+    const int mode, lb, cs, no, np, nz, nzn; const uint64_t N, L; const unsigned nb;      // nz: polynomials opened at zeta (all), nzn: at g zeta (all but the quotient's)
+    std::vector<uint64_t> head;                                 // per proof: the words before the per-query blocks
+    std::vector<HostChallenger> chs;
+    std::vector<gle_t> pts, opens, alphas;                      // pts: [zeta of every proof | g zeta of every proof | beta of every proof]; opens: [proof][batch][MAX_BATCH_POLYS]
+    std::vector<H4> caps; std::vector<gle_t> fin;               // the oracle caps [proof][oracle][cs]; the final polynomials [proof][final_poly_len]
+    gle_t *F, *Fo;                                              // the polynomial being committed / folded, and the buffer the next fold writes
+    std::vector<unsigned long long> wit;
+
+    Proving(h2w_prover *p_, const uint64_t *coeffs, uint64_t n_, hipStream_t s_)
+        : p(p_), coeffs_dev(coeffs), n(n_), s(s_), sh(p_->shape), d(p_->d), pl(p_->pl), B(p_->b), mode(sh.hash_mode), lb(d.lde_bits), cs(d.cap_size), no(d.n_oracles),
+          np(p_->np), nz(np), nzn(np - d.oracle_polys[no - 1]), N(p_->N), L(p_->L), nb((unsigned)n_), head(n_ * pl.queries, 0), chs(n_, HostChallenger(&p_->hk.k)), pts(3 * n_),
+          opens(n_ * 2 * MAX_BATCH_POLYS), alphas(n_), caps(n_ * no * cs), fin(n_ * d.final_poly_len), F(B.Fa.get()), Fo(B.Fb.get()), wit(n_, ~0ull) {}
+    int mark(int i) { H2W_HIP(hipEventRecord(p->ev[i], s)); return 0; }
+    // a cap into the head of proof b at word `at`, and into its transcript
+    void take_cap(uint64_t b, const H4 *cap, uint64_t at) {
+        memcpy(&head[b * pl.queries + at], cap, (size_t)cs * 32);
+        for (int i = 0; i < cs; i++) chs[b].observe_hash(mode, cap[i]);
+    }
+
+    // ---- ms[0]: lde[proof][poly][j] = f(7 w^bitrev(j))
+    int lde() {
+        if (mark(0)) return -1;
+        hipLaunchKernelGGL(k_scale_pad, dim3(blocks(L, 256), (unsigned)(n * np)), dim3(256), 0, s, coeffs_dev, N, (uint64_t)7, L, B.lde.get());
+        ntt_dif(p, B.lde.get(), lb, n * np, s);
+        return mark(1);
+    }
+    // ---- ms[1]: Merkle commitments of the oracles, tree[proof][oracle]
+    int commit_oracles() {
+        const uint64_t tstride = 2 * L;
+        for (int o = 0; o < no; o++)
+            hipLaunchKernelGGL(k_leaves_initial, dim3(blocks(L, 64), nb), dim3(64), 0, s, p->dk.get(), mode, B.lde.get() + (uint64_t)p->poly0[o] * L, d.oracle_polys[o], L, B.tree.get() + o * tstride, (uint64_t)np * L, no * tstride);
+        build_trees(p, B.tree.get(), lb, n * no, tstride, s);
+        if (read_caps(p, B.tree.get(), lb, n * no, tstride, caps.data(), s)) return -1;
+        return mark(2);
+    }
+    // ---- ms[2], first part: the transcript up to zeta (challenger/mod.rs:168-222 in stark/mod.rs order)
+    int draw_zeta() {
+        H2W_HIP(hipStreamSynchronize(s));                          // the caps
+        const int o_trace = 0, o_perm = sh.n_perm_z > 0 ? 1 : -1, o_quot = no - 1;
+        for (uint64_t b = 0; b < n; b++) {
+            HostChallenger &ch = chs[b]; const H4 *cp = &caps[b * no * cs];
+            take_cap(b, cp + (size_t)o_trace * cs, pl.trace_cap);
+            if (o_perm >= 0) {
+                for (int set = 0; set < sh.perm_batch_size; set++) for (int i = 0; i < sh.num_challenges; i++) { ch.challenge(); ch.challenge(); }
+                take_cap(b, cp + (size_t)o_perm * cs, pl.perm_cap);
+            }
+            for (int i = 0; i < sh.num_challenges; i++) ch.challenge();
+            take_cap(b, cp + (size_t)o_quot * cs, pl.quotient_cap);
+            pts[b] = ch.ext_challenge(); pts[n + b] = gle_mul(gle_of(gl_primitive_root_of_unity(sh.degree_bits)), pts[b]);
+        }
+        return 0;
+    }
+    // ---- ms[2], second part: the openings (batch 0 = every polynomial at zeta, batch 1 = trace and permutation Zs at g zeta) and alpha
+    int open_polys() {
+        const int eb = p->eval_blocks; const uint64_t pstride = (uint64_t)(nz + nzn) * eb;
+        H2W_HIP(hipMemcpyAsync(B.pts.get(), pts.data(), 2 * n * sizeof(gle_t), hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_eval_partial, dim3((unsigned)eb, (unsigned)nz, nb), dim3(256), 0, s, coeffs_dev, N, B.pts.get(), B.partial.get(), (uint64_t)np * N, pstride);
+        if (nzn > 0) hipLaunchKernelGGL(k_eval_partial, dim3((unsigned)eb, (unsigned)nzn, nb), dim3(256), 0, s, coeffs_dev, N, B.pts.get() + n, B.partial.get() + (size_t)nz * eb, (uint64_t)np * N, pstride);
+        std::vector<gle_t> part(n * pstride);
+        H2W_HIP(hipMemcpyAsync(part.data(), B.partial.get(), part.size() * sizeof(gle_t), hipMemcpyDeviceToHost, s));
+        H2W_HIP(hipStreamSynchronize(s));
+        for (uint64_t b = 0; b < n; b++) {
+            HostChallenger &ch = chs[b]; gle_t *open0 = &opens[b * 2 * MAX_BATCH_POLYS], *open1 = open0 + MAX_BATCH_POLYS;
+            for (int i = 0; i < nz + nzn; i++) { gle_t a = gle_of(0); for (int e = 0; e < eb; e++) a = gle_add(a, part[b * pstride + (size_t)i * eb + e]); if (i < nz) open0[i] = a; else open1[i - nz] = a; }
+            for (int i = 0; i < nz; i++) ch.observe_ext(open0[i]);
+            for (int i = 0; i < nzn; i++) ch.observe_ext(open1[i]);
+            alphas[b] = ch.ext_challenge();
+            // local_values, next_values, permutation_zs, permutation_zs_next, quotient_polys (witness/mod.rs:236-266 order)
+            uint64_t *w = &head[b * pl.queries + pl.openings]; const int nc = sh.n_cols, npz = sh.n_perm_z, nq = sh.n_quotient;
+            auto put = [&w](const gle_t *o, int cnt) { for (int i = 0; i < cnt; i++) { *w++ = o[i].c[0]; *w++ = o[i].c[1]; } };
+            put(open0, nc); put(open1, nc); put(open0 + nc, npz); put(open1 + nc, npz); put(open0 + nc + npz, nq);
+        }
+        return 0;
+    }
+    // ---- ms[2], third part: F = (G_0 - G_0(zeta)) / (X - zeta) * alpha^{n_1} + (G_1 - G_1(g zeta)) / (X - g zeta)
+    int batch_quotients() {
+        H2W_HIP(hipMemsetAsync(F, 0, n * L * sizeof(gle_t), s));
+        std::vector<QuotArgs> qa(n);
+        for (int bt = 0; bt < 2; bt++) {
+            const int nbp = bt == 0 ? nz : nzn; if (nbp == 0) continue;
+            for (uint64_t b = 0; b < n; b++) fill_quot_args(qa[b], coeffs_dev + b * np * N, N, nbp, pts[bt * n + b], alphas[b], &opens[b * 2 * MAX_BATCH_POLYS + (size_t)bt * MAX_BATCH_POLYS]);
+            H2W_HIP(hipMemcpyAsync(B.qargs.get(), qa.data(), n * sizeof(QuotArgs), hipMemcpyHostToDevice, s));
+            hipLaunchKernelGGL(k_quot_terms, dim3((unsigned)p->scan_blocks, nb), dim3(256), 0, s, B.qargs.get(), B.T.get(), B.totals.get());
+            hipLaunchKernelGGL(k_suffix_totals, dim3(nb), dim3(64), 0, s, B.totals.get(), B.carry.get(), p->scan_blocks);
+            hipLaunchKernelGGL(k_quot_finish, dim3((unsigned)p->scan_blocks, nb), dim3(256), 0, s, B.qargs.get(), B.T.get(), B.carry.get(), F, L);
+            H2W_HIP(hipStreamSynchronize(s));                      // qa is reused by the second batch
+        }
+        return mark(3);
+    }
+    // ---- ms[3]: the commit phase (a tree, its cap and a beta per step; fold; shift <- shift^arity) and the final polynomial
+    int commit_phase() {
+        uint64_t shift = 7; int cur = lb;
+        std::vector<H4> fcap(n * cs);
+        for (int st = 0; st < d.n_steps; st++) {
+            const int ab = d.arity[st]; const uint64_t m = 1ull << cur, nl = m >> ab;
+            hipLaunchKernelGGL(k_split_scale, dim3(blocks(m, 256), nb), dim3(256), 0, s, F, m, shift, B.fv[st].get(), L);
+            ntt_dif(p, B.fv[st].get(), cur, 2 * n, s);
+            hipLaunchKernelGGL(k_leaves_fri, dim3(blocks(nl, 64), nb), dim3(64), 0, s, p->dk.get(), mode, B.fv[st].get(), ab, m, B.ftree[st].get(), 2 * nl);
+            build_trees(p, B.ftree[st].get(), cur - ab, n, 2 * nl, s);
+            if (read_caps(p, B.ftree[st].get(), cur - ab, n, 2 * nl, fcap.data(), s)) return -1;
+            H2W_HIP(hipStreamSynchronize(s));
+            for (uint64_t b = 0; b < n; b++) { take_cap(b, &fcap[b * cs], pl.commit_caps + (uint64_t)st * cs * 4); pts[2 * n + b] = chs[b].ext_challenge(); }
+            H2W_HIP(hipMemcpyAsync(B.pts.get() + 2 * n, &pts[2 * n], n * sizeof(gle_t), hipMemcpyHostToDevice, s));
+            hipLaunchKernelGGL(k_fold, dim3(blocks(nl, 256), nb), dim3(256), 0, s, F, Fo, nl, ab, B.pts.get() + 2 * n, L);
+            H2W_HIP(hipStreamSynchronize(s));                      // the betas are overwritten by the next step
+            gle_t *t = F; F = Fo; Fo = t;
+            shift = gl_exp(shift, 1ull << ab); cur -= ab;
+        }
+        const int fl = d.final_poly_len;
+        H2W_HIP(hipMemcpy2DAsync(fin.data(), (size_t)fl * sizeof(gle_t), F, L * sizeof(gle_t), (size_t)fl * sizeof(gle_t), n, hipMemcpyDeviceToHost, s));
+        return mark(4);
+    }
+    // ---- ms[4]: proof of work.  The complete rate blocks of the pending inputs are absorbed once; the witnesses are searched on the device
+    int proof_of_work() {
+        H2W_HIP(hipStreamSynchronize(s));                          // the final polynomials
+        const int fl = d.final_poly_len; std::vector<PowArgs> pa(n);
+        for (uint64_t b = 0; b < n; b++) {
+            HostChallenger &ch = chs[b]; uint64_t *hd = &head[b * pl.queries];
+            for (int i = 0; i < fl; i++) { hd[pl.final_poly + 2 * i] = fin[b * fl + i].c[0]; hd[pl.final_poly + 2 * i + 1] = fin[b * fl + i].c[1]; ch.observe_ext(fin[b * fl + i]); }
+            PowArgs &PA = pa[b]; PA.pow_bits = sh.pow_bits;
+            memcpy(PA.state, ch.state, sizeof(PA.state));
+            const size_t full = ch.absorb_blocks(PA.state);
+            PA.ntail = (int)(ch.in.size() - full);
+            for (int i = 0; i < SPONGE_RATE; i++) PA.tail[i] = i < PA.ntail ? ch.in[full + i] : 0;
+        }
+        H2W_HIP(hipMemcpyAsync(B.pargs.get(), pa.data(), n * sizeof(PowArgs), hipMemcpyHostToDevice, s));
+        H2W_HIP(hipMemcpyAsync(B.best.get(), wit.data(), n * 8, hipMemcpyHostToDevice, s));
+        // 2^pow_bits candidates per round (63 % of the proofs finish in each; finished proofs' blocks exit at once)
+        const int round_bits = sh.pow_bits < 8 ? 8 : sh.pow_bits > 22 ? 22 : sh.pow_bits;
+        for (uint64_t first = 0;; first += 1ull << round_bits) {
+            if (first >> 40) { set_error("h2w_prove_fri_batch: no proof-of-work witness found"); return -1; }
+            hipLaunchKernelGGL(k_pow, dim3(1u << (round_bits - 6), nb), dim3(64), 0, s, p->dk.get(), B.pargs.get(), first, B.best.get());
+            H2W_HIP(hipMemcpyAsync(wit.data(), B.best.get(), n * 8, hipMemcpyDeviceToHost, s));
+            H2W_HIP(hipStreamSynchronize(s));
+            bool all = true; for (uint64_t b = 0; b < n; b++) all = all && wit[b] != ~0ull;
+            if (all) break;
+        }
+        return mark(5);
+    }
+    // ---- ms[5]: the query indices, their openings, and the heads and public inputs into the proofs
+    int answer_queries(const uint64_t *public_inputs, uint64_t *proofs_dev) {
+        const int nq = sh.num_queries;
+        std::vector<uint64_t> xs(n * p->query_slots());
+        for (uint64_t b = 0; b < n; b++) {
+            HostChallenger &ch = chs[b];
+            head[b * pl.queries + pl.pow_witness] = wit[b];
+            ch.observe(wit[b]); (void)ch.challenge();
+            for (int q = 0; q < nq; q++) xs[b * nq + q] = ch.challenge() & (L - 1);
+        }
+        H2W_HIP(hipMemcpyAsync(B.x_index.get(), xs.data(), xs.size() * 8, hipMemcpyHostToDevice, s));
+        if (nq > 0) hipLaunchKernelGGL(k_gather, dim3((unsigned)nq, nb), dim3(64), 0, s, gather_args(p, proofs_dev));
+        H2W_HIP(hipMemcpy2DAsync(proofs_dev, pl.total * 8, head.data(), pl.queries * 8, pl.queries * 8, n, hipMemcpyHostToDevice, s));
+        if (sh.n_pis > 0) H2W_HIP(hipMemcpy2DAsync(proofs_dev + pl.pis, pl.total * 8, public_inputs, (size_t)sh.n_pis * 8, (size_t)sh.n_pis * 8, n, hipMemcpyHostToDevice, s));
+        if (mark(6)) return -1;
+        H2W_HIP(hipStreamSynchronize(s));
+        H2W_HIP(hipGetLastError());
+        return 0;
+    }
+};
 }  // namespace
 
 extern "C" {
@@ -553,12 +537,7 @@ h2w_prover *h2w_prover_new(const h2w_shape_t *shape, const h2w_poseidon_consts_t
     p->N = 1ull << shape->degree_bits; p->L = 1ull << d.lde_bits;
     for (int o = 0; o < d.n_oracles; o++) { p->poly0[o] = p->np; p->np += d.oracle_polys[o]; }
     p->scan_blocks = (int)blocks(p->N, SCAN_TILE); p->eval_blocks = (int)blocks(p->N, 256 * EVAL_PER_THREAD);
-    // constants: caller's tables + PoseidonBN254 tables in Montgomery form
-    const FrParams P = fr_params_init();
-    p->hk.k = *consts; p->hk.r2 = P.r2; p->hk.ninv = P.ninv;
-    for (int i = 0; i < 88; i++) p->hk.bn.c[i] = fr_mont_mul(consts->bn_c[i], P.r2, P.ninv);
-    for (int i = 0; i < 392; i++) p->hk.bn.s[i] = fr_mont_mul(consts->bn_s[i], P.r2, P.ninv);
-    for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) { p->hk.bn.m[i][j] = fr_mont_mul(consts->bn_m[i][j], P.r2, P.ninv); p->hk.bn.p[i][j] = fr_mont_mul(consts->bn_p[i][j], P.r2, P.ninv); }
+    prover_consts_init(p->hk, *consts);      // the caller's tables + the PoseidonBN254 ones in Montgomery form
     DeviceGuard dg(device_id);
     if (prover_upload(p) != 0) { set_error("h2w_prover_new: " + g_last_error); h2w_prover_free(p); return nullptr; }
     return p;
@@ -576,162 +555,17 @@ int h2w_prove_fri_batch(h2w_prover *p, const uint64_t *coeffs_dev, const uint64_
     if (n == 0) return 0;
     if (n > 2048) { set_error("h2w_prove_fri_batch: at most 2048 proofs per call"); return -1; }
     const auto t_begin = std::chrono::steady_clock::now();
-    hipStream_t s = (hipStream_t)stream_;
-    const h2w_shape_t &sh = p->shape; const Derived &d = p->d; const ProofLayout &pl = p->pl;
-    const int mode = sh.hash_mode, lb = d.lde_bits, capb = sh.cap_height, cs = d.cap_size, no = d.n_oracles, np = p->np;
-    const uint64_t N = p->N, L = p->L; const unsigned nb = (unsigned)n;
     DeviceGuard dg(p->device);
     if (ensure_capacity(p, n)) return -1;
-    const BatchBufs &B = p->b;
-    std::vector<uint64_t> head(n * pl.queries, 0);             // per proof: the words before the per-query blocks
-    // ---- LDE: lde[proof][poly][j] = f(7 w^bitrev(j))
-    H2W_HIP(hipEventRecord(p->ev[0], s));
-    hipLaunchKernelGGL(k_scale_pad, dim3(blocks(L, 256), (unsigned)(n * np)), dim3(256), 0, s, coeffs_dev, N, (uint64_t)7, L, B.lde.get());
-    ntt_dif(p, B.lde.get(), lb, n * np, s);
-    H2W_HIP(hipEventRecord(p->ev[1], s));
-    // ---- Merkle commitments of the oracles: tree[proof][oracle]
-    const uint64_t tstride = 2 * L;
-    for (int o = 0; o < no; o++)
-        hipLaunchKernelGGL(k_leaves_initial, dim3(blocks(L, 64), nb), dim3(64), 0, s, p->dk.get(), mode, B.lde.get() + (uint64_t)p->poly0[o] * L, d.oracle_polys[o], L, B.tree.get() + o * tstride, (uint64_t)np * L, no * tstride);
-    build_trees(p, B.tree.get(), lb, n * no, tstride, s);
-    std::vector<H4> caps(n * no * cs);
-    H2W_HIP(hipMemcpy2DAsync(caps.data(), (size_t)cs * sizeof(H4), B.tree.get() + level_off(lb, lb - capb), tstride * sizeof(H4), (size_t)cs * sizeof(H4), n * no, hipMemcpyDeviceToHost, s));
-    H2W_HIP(hipEventRecord(p->ev[2], s));
-    H2W_HIP(hipStreamSynchronize(s));
-    const int o_trace = 0, o_perm = sh.n_perm_z > 0 ? 1 : -1, o_quot = no - 1;
-    // ---- transcript up to zeta (challenger/mod.rs:168-222 in stark/mod.rs order)
-    std::vector<HostChallenger> chs(n, HostChallenger(&p->hk.k));
-    std::vector<gle_t> pts(3 * n);                              // [zeta of every proof | g zeta of every proof | beta of every proof]
-    for (uint64_t b = 0; b < n; b++) {
-        HostChallenger &ch = chs[b]; const H4 *cp = &caps[b * no * cs]; uint64_t *hd = &head[b * pl.queries];
-        memcpy(hd + pl.trace_cap, cp + (size_t)o_trace * cs, (size_t)cs * 32);
-        memcpy(hd + pl.quotient_cap, cp + (size_t)o_quot * cs, (size_t)cs * 32);
-        if (o_perm >= 0) memcpy(hd + pl.perm_cap, cp + (size_t)o_perm * cs, (size_t)cs * 32);
-        for (int i = 0; i < cs; i++) ch.observe_hash(mode, cp[(size_t)o_trace * cs + i]);
-        if (o_perm >= 0) {
-            for (int set = 0; set < sh.perm_batch_size; set++) for (int i = 0; i < sh.num_challenges; i++) { ch.challenge(); ch.challenge(); }
-            for (int i = 0; i < cs; i++) ch.observe_hash(mode, cp[(size_t)o_perm * cs + i]);
-        }
-        for (int i = 0; i < sh.num_challenges; i++) ch.challenge();
-        for (int i = 0; i < cs; i++) ch.observe_hash(mode, cp[(size_t)o_quot * cs + i]);
-        pts[b] = ch.ext_challenge(); pts[n + b] = gle_mul(gle_of(gl_primitive_root_of_unity(sh.degree_bits)), pts[b]);
-    }
-    // ---- openings: batch 0 = every polynomial at zeta, batch 1 = trace and permutation Zs at g zeta
-    const int nz = np, nzn = np - d.oracle_polys[o_quot], eb = p->eval_blocks; const uint64_t pstride = (uint64_t)(nz + nzn) * eb;
-    H2W_HIP(hipMemcpyAsync(B.pts.get(), pts.data(), 2 * n * sizeof(gle_t), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_eval_partial, dim3((unsigned)eb, (unsigned)nz, nb), dim3(256), 0, s, coeffs_dev, N, B.pts.get(), B.partial.get(), (uint64_t)np * N, pstride);
-    if (nzn > 0) hipLaunchKernelGGL(k_eval_partial, dim3((unsigned)eb, (unsigned)nzn, nb), dim3(256), 0, s, coeffs_dev, N, B.pts.get() + n, B.partial.get() + (size_t)nz * eb, (uint64_t)np * N, pstride);
-    std::vector<gle_t> part(n * pstride);
-    H2W_HIP(hipMemcpyAsync(part.data(), B.partial.get(), part.size() * sizeof(gle_t), hipMemcpyDeviceToHost, s));
-    H2W_HIP(hipStreamSynchronize(s));
-    std::vector<gle_t> opens(n * 2 * MAX_BATCH_POLYS), alphas(n);
-    for (uint64_t b = 0; b < n; b++) {
-        HostChallenger &ch = chs[b]; gle_t *open0 = &opens[b * 2 * MAX_BATCH_POLYS], *open1 = open0 + MAX_BATCH_POLYS;
-        for (int i = 0; i < nz + nzn; i++) { gle_t a = gle_of(0); for (int e = 0; e < eb; e++) a = gle_add(a, part[b * pstride + (size_t)i * eb + e]); if (i < nz) open0[i] = a; else open1[i - nz] = a; }
-        for (int i = 0; i < nz; i++) ch.observe_ext(open0[i]);
-        for (int i = 0; i < nzn; i++) ch.observe_ext(open1[i]);
-        alphas[b] = ch.ext_challenge();
-        // local_values, next_values, permutation_zs, permutation_zs_next, quotient_polys (witness/mod.rs:236-266 order)
-        uint64_t *w = &head[b * pl.queries + pl.openings]; const int nc = sh.n_cols, npz = sh.n_perm_z, nq = sh.n_quotient;
-        for (int i = 0; i < nc; i++) { *w++ = open0[i].c[0]; *w++ = open0[i].c[1]; }
-        for (int i = 0; i < nc; i++) { *w++ = open1[i].c[0]; *w++ = open1[i].c[1]; }
-        for (int i = 0; i < npz; i++) { *w++ = open0[nc + i].c[0]; *w++ = open0[nc + i].c[1]; }
-        for (int i = 0; i < npz; i++) { *w++ = open1[nc + i].c[0]; *w++ = open1[nc + i].c[1]; }
-        for (int i = 0; i < nq; i++) { *w++ = open0[nc + npz + i].c[0]; *w++ = open0[nc + npz + i].c[1]; }
-    }
-    // ---- F = (G_0 - G_0(zeta)) / (X - zeta) * alpha^{n_1} + (G_1 - G_1(g zeta)) / (X - g zeta)
-    gle_t *F = B.Fa.get(), *Fo = B.Fb.get();
-    H2W_HIP(hipMemsetAsync(F, 0, n * L * sizeof(gle_t), s));
-    std::vector<QuotArgs> qa(n);
-    for (int bt = 0; bt < 2; bt++) {
-        const int nbp = bt == 0 ? nz : nzn; if (nbp == 0) continue;
-        for (uint64_t b = 0; b < n; b++) {
-            QuotArgs &A = qa[b]; const gle_t *open = &opens[b * 2 * MAX_BATCH_POLYS + (size_t)bt * MAX_BATCH_POLYS];
-            A.coef = coeffs_dev + b * np * N; A.N = N; A.npoly = nbp; A.z = pts[bt * n + b]; A.zinv = gle_inv(A.z);
-            gle_t ap = gle_of(1); A.gz = gle_of(0);
-            for (int i = 0; i < nbp; i++) { A.ap[i] = ap; A.gz = gle_add(A.gz, gle_mul(ap, open[i])); ap = gle_mul(ap, alphas[b]); }
-            A.an = ap;
-        }
-        H2W_HIP(hipMemcpyAsync(B.qargs.get(), qa.data(), n * sizeof(QuotArgs), hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_quot_terms, dim3((unsigned)p->scan_blocks, nb), dim3(256), 0, s, B.qargs.get(), B.T.get(), B.totals.get());
-        hipLaunchKernelGGL(k_suffix_totals, dim3(nb), dim3(64), 0, s, B.totals.get(), B.carry.get(), p->scan_blocks);
-        hipLaunchKernelGGL(k_quot_finish, dim3((unsigned)p->scan_blocks, nb), dim3(256), 0, s, B.qargs.get(), B.T.get(), B.carry.get(), F, L);
-        H2W_HIP(hipStreamSynchronize(s));                      // qa is reused by the second batch
-    }
-    H2W_HIP(hipEventRecord(p->ev[3], s));
-    // ---- commit phase
-    uint64_t shift = 7; int cur = lb;
-    std::vector<H4> fcap(n * cs);
-    for (int st = 0; st < d.n_steps; st++) {
-        const int ab = d.arity[st]; const uint64_t m = 1ull << cur, nl = m >> ab;
-        hipLaunchKernelGGL(k_split_scale, dim3(blocks(m, 256), nb), dim3(256), 0, s, F, m, shift, B.fv[st].get(), L);
-        ntt_dif(p, B.fv[st].get(), cur, 2 * n, s);
-        hipLaunchKernelGGL(k_leaves_fri, dim3(blocks(nl, 64), nb), dim3(64), 0, s, p->dk.get(), mode, B.fv[st].get(), ab, m, B.ftree[st].get(), 2 * nl);
-        build_trees(p, B.ftree[st].get(), cur - ab, n, 2 * nl, s);
-        H2W_HIP(hipMemcpy2DAsync(fcap.data(), (size_t)cs * sizeof(H4), B.ftree[st].get() + level_off(cur - ab, cur - ab - capb), 2 * nl * sizeof(H4), (size_t)cs * sizeof(H4), n, hipMemcpyDeviceToHost, s));
-        H2W_HIP(hipStreamSynchronize(s));
-        for (uint64_t b = 0; b < n; b++) {
-            memcpy(&head[b * pl.queries + pl.commit_caps + (uint64_t)st * cs * 4], &fcap[b * cs], (size_t)cs * 32);
-            for (int i = 0; i < cs; i++) chs[b].observe_hash(mode, fcap[b * cs + i]);
-            pts[2 * n + b] = chs[b].ext_challenge();
-        }
-        H2W_HIP(hipMemcpyAsync(B.pts.get() + 2 * n, &pts[2 * n], n * sizeof(gle_t), hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_fold, dim3(blocks(nl, 256), nb), dim3(256), 0, s, F, Fo, nl, ab, B.pts.get() + 2 * n, L);
-        H2W_HIP(hipStreamSynchronize(s));                      // the betas are overwritten by the next step
-        gle_t *t = F; F = Fo; Fo = t;
-        shift = gl_exp(shift, 1ull << ab); cur -= ab;
-    }
-    const int fl = d.final_poly_len;
-    std::vector<gle_t> fin(n * fl);
-    H2W_HIP(hipMemcpy2DAsync(fin.data(), (size_t)fl * sizeof(gle_t), F, L * sizeof(gle_t), (size_t)fl * sizeof(gle_t), n, hipMemcpyDeviceToHost, s));
-    H2W_HIP(hipEventRecord(p->ev[4], s));
-    H2W_HIP(hipStreamSynchronize(s));
-    // ---- proof of work: absorb the complete rate blocks of the pending inputs once, search the witnesses on the device
-    std::vector<PowArgs> pa(n); std::vector<unsigned long long> wit(n, ~0ull);
-    for (uint64_t b = 0; b < n; b++) {
-        HostChallenger &ch = chs[b]; uint64_t *hd = &head[b * pl.queries];
-        for (int i = 0; i < fl; i++) { hd[pl.final_poly + 2 * i] = fin[b * fl + i].c[0]; hd[pl.final_poly + 2 * i + 1] = fin[b * fl + i].c[1]; ch.observe_ext(fin[b * fl + i]); }
-        PowArgs &PA = pa[b]; PA.pow_bits = sh.pow_bits; PA.ntail = (int)(ch.in.size() % SPONGE_RATE);
-        uint64_t st[12]; memcpy(st, ch.state, sizeof(st));
-        const size_t full = ch.in.size() - (size_t)PA.ntail;
-        for (size_t off = 0; off < full; off += SPONGE_RATE) { memcpy(st, ch.in.data() + off, SPONGE_RATE * 8); gl_permute(&p->hk.k, st); }
-        memcpy(PA.state, st, sizeof(st));
-        for (int i = 0; i < SPONGE_RATE; i++) PA.tail[i] = i < PA.ntail ? ch.in[full + i] : 0;
-    }
-    H2W_HIP(hipMemcpyAsync(B.pargs.get(), pa.data(), n * sizeof(PowArgs), hipMemcpyHostToDevice, s));
-    H2W_HIP(hipMemcpyAsync(B.best.get(), wit.data(), n * 8, hipMemcpyHostToDevice, s));
-    // 2^pow_bits candidates per round (63 % of the proofs finish in each; finished proofs' blocks exit at once)
-    const int round_bits = sh.pow_bits < 8 ? 8 : sh.pow_bits > 22 ? 22 : sh.pow_bits;
-    for (uint64_t first = 0;; first += 1ull << round_bits) {
-        if (first >> 40) { set_error("h2w_prove_fri_batch: no proof-of-work witness found"); return -1; }
-        hipLaunchKernelGGL(k_pow, dim3(1u << (round_bits - 6), nb), dim3(64), 0, s, p->dk.get(), B.pargs.get(), first, B.best.get());
-        H2W_HIP(hipMemcpyAsync(wit.data(), B.best.get(), n * 8, hipMemcpyDeviceToHost, s));
-        H2W_HIP(hipStreamSynchronize(s));
-        bool all = true; for (uint64_t b = 0; b < n; b++) all = all && wit[b] != ~0ull;
-        if (all) break;
-    }
-    H2W_HIP(hipEventRecord(p->ev[5], s));
-    // ---- query openings
-    const int nq = sh.num_queries;
-    std::vector<uint64_t> xs(n * (size_t)(nq ? nq : 1));
-    for (uint64_t b = 0; b < n; b++) {
-        HostChallenger &ch = chs[b];
-        head[b * pl.queries + pl.pow_witness] = wit[b];
-        ch.observe(wit[b]); (void)ch.challenge();
-        for (int q = 0; q < nq; q++) xs[b * nq + q] = ch.challenge() & (L - 1);
-    }
-    H2W_HIP(hipMemcpyAsync(B.x_index.get(), xs.data(), xs.size() * 8, hipMemcpyHostToDevice, s));
-    GatherArgs G; G.lde = B.lde.get(); G.L = L; G.lde_stride = (uint64_t)np * L; G.lb = lb; G.capb = capb; G.no = no; G.tree = B.tree.get(); G.tree_stride = tstride;
-    for (int o = 0; o < 3; o++) { G.npoly[o] = o < no ? d.oracle_polys[o] : 0; G.poly0[o] = p->poly0[o]; G.init_off[o] = pl.init_off[o]; }
-    G.n_steps = d.n_steps;
-    { uint64_t m = L; for (int st = 0; st < MAX_STEPS; st++) { G.ab[st] = st < d.n_steps ? d.arity[st] : 0; G.fv[st] = B.fv[st].get(); G.fn[st] = m; G.ftree[st] = B.ftree[st].get(); G.step_off[st] = pl.step_off[st]; if (st < d.n_steps) m >>= d.arity[st]; } }
-    G.proof = proofs_dev; G.proof_stride = pl.total; G.q_base = pl.queries; G.q_words = pl.query_words; G.x_index = B.x_index.get();
-    if (nq > 0) hipLaunchKernelGGL(k_gather, dim3((unsigned)nq, nb), dim3(64), 0, s, G);
-    H2W_HIP(hipMemcpy2DAsync(proofs_dev, pl.total * 8, head.data(), pl.queries * 8, pl.queries * 8, n, hipMemcpyHostToDevice, s));
-    if (sh.n_pis > 0) H2W_HIP(hipMemcpy2DAsync(proofs_dev + pl.pis, pl.total * 8, public_inputs, (size_t)sh.n_pis * 8, (size_t)sh.n_pis * 8, n, hipMemcpyHostToDevice, s));
-    H2W_HIP(hipEventRecord(p->ev[6], s));
-    H2W_HIP(hipStreamSynchronize(s));
-    H2W_HIP(hipGetLastError());
+    Proving c(p, coeffs_dev, n, (hipStream_t)stream_);
+    if (c.lde()) return -1;
+    if (c.commit_oracles()) return -1;
+    if (c.draw_zeta()) return -1;
+    if (c.open_polys()) return -1;
+    if (c.batch_quotients()) return -1;
+    if (c.commit_phase()) return -1;
+    if (c.proof_of_work()) return -1;
+    if (c.answer_queries(public_inputs, proofs_dev)) return -1;
     for (int i = 0; i < 6; i++) { float t = 0; H2W_HIP(hipEventElapsedTime(&t, p->ev[i], p->ev[i + 1])); p->ms[i] = t; }
     p->ms[6] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
     return 0;
