@@ -44,6 +44,11 @@ class Shape(C.Structure):
         "perm_batch_size", "hash_mode", "lookup_bits", "witness_load_range_check")]
 
 
+class ChipBatchVerdict(C.Structure):
+    """h2w_chipbatch_verdict_t: one instance's words of h2w_chipbatch_values."""
+    _fields_ = [("status", C.c_uint32), ("n_failed", C.c_uint32)]
+
+
 class PoseidonConsts(C.Structure):
     _fields_ = [
         ("all_round_constants", C.c_uint64 * 360),
@@ -82,6 +87,7 @@ H2W_TRACE_SPLIT_SELECTS = 32       # (16 is unassigned)
 H2W_OP_GL_PERMUTE, H2W_OP_BN_PERMUTE, H2W_OP_HASH_NO_PAD, H2W_OP_TWO_TO_ONE, H2W_OP_MERKLE_VERIFY = 9, 10, 11, 12, 13
 H2W_CHIPBATCH_MAX_N_IN = 4096
 H2W_CHIPBATCH_OPT_CHUNK = 1
+H2W_CHIPBATCH_FORM_AUTO, H2W_CHIPBATCH_FORM_QUAD, H2W_CHIPBATCH_FORM_ROW = 0, 1, 2      # form of h2w_chipbatch_values
 # flags of h2w_verdict_t (include/h2w.h 3b)
 (H2W_VERDICT_POW, H2W_VERDICT_MERKLE_TRACE, H2W_VERDICT_MERKLE_PERM_Z, H2W_VERDICT_MERKLE_QUOTIENT, H2W_VERDICT_MERKLE_STEP, H2W_VERDICT_FOLD,
  H2W_VERDICT_FINAL) = 1, 2, 4, 8, 16, 32, 64
@@ -199,6 +205,8 @@ SYMBOLS = {
     "h2w_chipbatch_run": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, _vp]),
     "h2w_chipbatch_new_hash": (_vp, [C.c_int, C.POINTER(PoseidonConsts), C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int]),
     "h2w_chipbatch_configure": (C.c_int, [_vp, C.c_int, C.c_uint64]),
+    "h2w_chipbatch_num_results": (C.c_uint64, [_vp]),
+    "h2w_chipbatch_values": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, C.c_uint, _vp]),
     "h2w_comm_unique_id": (C.c_int, [_vp]),
     "h2w_comm_init": (_vp, [_vp, C.c_int, C.c_int, C.c_int]),
     "h2w_comm_free": (None, [_vp]),

@@ -698,3 +698,12 @@ class ChipBatch:
     def run(self, operands_ptr, n, advice_ptr, status_ptr, stream=0):
         """h2w_chipbatch_run: device pointers; status_ptr: n u32 words (0, 1 / 2 where the reference panics, 4: an operand outside its field)."""
         _ck(self.L.h2w_chipbatch_run(self.p, operands_ptr, n, advice_ptr, status_ptr, stream), "h2w_chipbatch_run")
+
+    def num_results(self):
+        """u64 words per instance of results_dev[n][num_results] (h2w_chipbatch_values): 12 / 16 / 4 / 4 / 0 for ops 9-13.  Needs no device."""
+        return int(self.L.h2w_chipbatch_num_results(self.p))
+
+    def values(self, operands_ptr, n, results_ptr, verdict_ptr, form=0, stream=0):
+        """h2w_chipbatch_values: the op's output wires (results_ptr: n x num_results u64, device; may be 0 for MERKLE_VERIFY) and one
+        h2w_chipbatch_verdict_t {status, n_failed} per instance (verdict_ptr: n x 2 u32, device) - no advice stream.  form: H2W_CHIPBATCH_FORM_*."""
+        _ck(self.L.h2w_chipbatch_values(self.p, operands_ptr, n, results_ptr, verdict_ptr, form, stream), "h2w_chipbatch_values")

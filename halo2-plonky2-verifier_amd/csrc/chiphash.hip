@@ -2,7 +2,7 @@
 //   PoseidonPermutationChip::permute / PoseidonBN254PermutationChip::permute   hash/poseidon/permutation.rs:270-284, poseidon_bn254/permutation.rs:190-203
 //   HasherChip::hash_no_pad / two_to_one                                       hash/poseidon/hash.rs:161-214, hash/poseidon_bn254/hash.rs:156-209
 //   MerkleTreeChip::verify_proof_to_cap                                        merkle/mod.rs:80-102
-// each in a fresh Context, its operands loaded the way the verifier's WitnessChip loads them (hash_program below), the shape of the reference's own chip
+// each in a fresh Context, its operands loaded the way the verifier's WitnessChip loads them (chiphash.h hash_program), the shape of the reference's own chip
 // tests (permutation.rs:325-347, poseidon_bn254/permutation.rs:266-301, hash.rs test_hash_no_pad / test_hash_two_to_one, merkle/mod.rs:136-265).
 // The single-source chips (chips.h) on the device sinks the batched verifier runs them on, behind a front end that knows no proof shape:
 //   Goldilocks-Poseidon (hash_mode 0, GL_PERMUTE)   k_chiphash_gl: one wavefront per instance walks the op wave-uniformly on the values-phase sink
@@ -13,87 +13,18 @@
 //       (bnquad.h QuadSinkT<false, QUAD_FUSED>::bn_emit_cells<false>, as k_merkle_bn_fused); lane 0 of the quad stores the Goldilocks-level records (leaf
 //       loads) and the other direct cells.  The quads of a wavefront run the same program in lockstep; tail quads redo the last instance.
 //   k_chiphash_check                                one lane per (instance, operand item): status 4 for a word outside its field / an index >= 2^depth.
+//                                                   (also launched for h2w_chipbatch_values: chiphash_launch_check, the verdicts' status words two words apart)
 // The layout of an instance (record metas, cells, listed permutations) is one host replay of the same program on the sequential gadgets.
+// The program, its parameters and operand layout and the handle's part live in chiphash.h: chipvalues.hip runs the same program for results and verdicts.
 #define H2W_FLATTEN_CHIPS 1      // the gadget stack inlined into the two value kernels (field.h HNI): the sinks below exist in this unit alone
 #include <hip/hip_runtime.h>
 #include <vector>
-#include "batchargs.h"
-#include "chipbatch.h"
+#include "chiphash.h"
 
 namespace h2w {
 
-struct HashParams { int op, mode; uint32_t n_in, depth, cap_height; };
 constexpr uint64_t CHIPHASH_WS_BYTES = 512ull << 20;      // default bound of a call's internal workspace (records, permutation lists): instances per launch = this / bytes per instance
 constexpr uint64_t CHIPHASH_MAX_CHUNK = 32768;            // instances per launch at most (grid.y of the expansion kernel)
-
-// operand words of an instance and what the status check makes of them: [n_gl Goldilocks words][the leaf index, if has_idx][n_hash hashes x 4 words]
-struct OperandLayout { uint32_t nw, n_gl, has_idx, n_hash, fr_hashes; };
-inline OperandLayout operand_layout(const HashParams &hp) {
-    OperandLayout o{0, 0, 0, 0, hp.mode == 1 ? 1u : 0u};
-    switch (hp.op) {
-        case H2W_OP_GL_PERMUTE: o.n_gl = SPONGE_WIDTH; break;
-        case H2W_OP_BN_PERMUTE: o.n_hash = BN_WIDTH; o.fr_hashes = 1; break;
-        case H2W_OP_HASH_NO_PAD: o.n_gl = hp.n_in; break;
-        case H2W_OP_TWO_TO_ONE: o.n_hash = 2; break;
-        default: o.n_gl = hp.n_in; o.has_idx = 1; o.n_hash = (1u << hp.cap_height) + (hp.depth - hp.cap_height); break;
-    }
-    o.nw = o.n_gl + o.has_idx + 4 * o.n_hash;
-    return o;
-}
-
-// operand words as wires: on the value backends a wire IS its value, so a loaded operand is read again where the op uses it
-struct WordView { const uint64_t *w; HF uint64_t operator[](int i) const { return g_load_u64(w + i); } };
-template <class B> HF HashW<B> hash_words(int mode, const uint64_t *w) {
-    HashW<B> h; h.f = fr_zero();
-    for (int i = 0; i < 4; i++) { const uint64_t x = g_load_u64(w + i); h.e[i] = mode == 0 ? x : 0; if (mode != 0) h.f.l[i] = x; }
-    return h;
-}
-// FAM: the ops a backend is instantiated for - 0: Goldilocks-Poseidon (GL_PERMUTE, hash_mode 0), 1: PoseidonBN254 (BN_PERMUTE, hash_mode 1), -1: all (host)
-template <int FAM, class B> HF void hash_program(B &be, const HashParams &hp, const h2w_poseidon_consts_t *k, const uint64_t *w) {
-    typedef typename B::Gl Gl; typedef typename B::Bool Bool; typedef typename B::Fr Fr; typedef HashW<B> H;
-    GoldilocksChip<B> gl(be);
-    if (hp.op == H2W_OP_GL_PERMUTE) {
-        if constexpr (FAM != 1) {
-            PoseidonPermutationChip<B> pg(be, k); Gl st[SPONGE_WIDTH];
-            for (int i = 0; i < SPONGE_WIDTH; i++) st[i] = gl.load_witness(g_load_u64(w + i));
-            pg.permute(st);
-        }
-        return;
-    }
-    if (hp.op == H2W_OP_BN_PERMUTE) {
-        if constexpr (FAM != 0) {
-            PoseidonBN254PermutationChip<B> pb(be, k); Fr st[BN_WIDTH];
-            for (int i = 0; i < BN_WIDTH; i++) st[i] = be.fr_witness(hash_words<B>(1, w + 4 * i).f);      // NativeChip::load_witness
-            pb.permute(st);
-        }
-        return;
-    }
-    const int mode = hp.mode;
-    auto load_hash = [&](const uint64_t *p) { uint64_t t[4]; for (int i = 0; i < 4; i++) t[i] = g_load_u64(p + i); HasherChip<B> hs(be, mode, k); return hs.load_witness(t); };
-    if (hp.op == H2W_OP_HASH_NO_PAD) {
-        const WordView in{w};
-        for (uint32_t i = 0; i < hp.n_in; i++) gl.load_witness(in[(int)i]);
-        HasherChip<B> hs(be, mode, k); hs.hash_no_pad(in, (int)hp.n_in);
-        return;
-    }
-    if (hp.op == H2W_OP_TWO_TO_ONE) {
-        const H l = load_hash(w), r = load_hash(w + 4);
-        HasherChip<B> hs(be, mode, k); hs.two_to_one(l, r);
-        return;
-    }
-    // MERKLE_VERIFY: leaf, index -> bits, cap, siblings, cap_index, the path
-    const int depth = (int)hp.depth, ch = (int)hp.cap_height, n_cap = 1 << ch, n_sib = depth - ch;
-    const WordView leaf{w}; const uint64_t *cap0 = w + hp.n_in + 1, *sib0 = cap0 + 4 * n_cap;
-    for (uint32_t i = 0; i < hp.n_in; i++) gl.load_witness(leaf[(int)i]);
-    const Gl idx = gl.load_witness(g_load_u64(w + hp.n_in));
-    Bool bits[32]; gl.num_to_bits(idx, depth, bits);
-    for (int i = 0; i < n_cap; i++) load_hash(cap0 + 4 * i);
-    for (int i = 0; i < n_sib; i++) load_hash(sib0 + 4 * i);
-    const Gl cap_index = gl.bits_to_num(bits + n_sib, ch);
-    MerkleTreeChip<B> mk(be, mode, k);
-    mk.verify_proof_to_cap_with_cap_index(leaf, (int)hp.n_in, bits, depth, cap_index, n_cap,
-                                          [&](int i) { return hash_words<B>(mode, cap0 + 4 * i); }, n_sib, [&](int i) { return hash_words<B>(mode, sib0 + 4 * i); });
-}
 
 // host: lays out the instance (record metas, cell count, listed Goldilocks-Poseidon permutations) - the sequential gadgets: a permutation's record block
 // is the GLP_RECS records coop_poseidon_permute writes
@@ -104,12 +35,6 @@ struct HashLayoutSink : SinkBase {
     void skip(uint64_t, uint64_t) {}
     void glp_note() { nglp++; }
 };
-
-HF ValCfg chiphash_cfg(int mode, int L, const FrParams &P, const fr_t *inv, bool split_bn) {
-    ValCfg cfg; cfg.fri = nullptr; cfg.proof = nullptr; cfg.mode = mode; cfg.L = L; cfg.P = P; cfg.inv_pos = inv; cfg.inv_neg = inv + INV_TAB; cfg.st = nullptr; cfg.split = false; cfg.split_bn = split_bn;
-    cfg.load_items = nullptr; cfg.n_load_items = 0; cfg.load_nrec = cfg.load_ncell = 0; cfg.n_cap_items = 0;
-    return cfg;
-}
 
 struct HashArgs {
     HashParams hp; int L; FrParams P; const uint64_t *operands; uint32_t nw; rec_t *recs; uint64_t nrec, ncells, n; fr_t *out; const uint16_t *tmpl_cells; const fr_t *inv;
@@ -129,7 +54,7 @@ __global__ __launch_bounds__(64) __attribute__((flatten)) void k_chiphash_gl(Has
     sink.nrec = 0; sink.cell_off = 0; sink.glp_slot = 0; sink.emit = true;
     CoopB be(sink, chiphash_cfg(0, A.L, A.P, A.inv, false), false);
     const HashParams hp = A.hp;
-    hash_program<0>(be, hp, A.consts, A.operands + i * (uint64_t)A.nw);
+    hash_program<0>(be, hp, A.consts, A.operands + i * (uint64_t)A.nw, NoHashOut());
 }
 
 // one wavefront per listed permutation of the launch: its GLP_RECS records from the entry {first record, input state} (replay.hip k_glp_emit_traced)
@@ -160,11 +85,10 @@ __global__ __launch_bounds__(QUAD_BLOCK) H2W_QUAD_ATTR __attribute__((flatten)) 
     sink.cc.init(flat_cols()); sink.ustate = nullptr; sink.sbx = nullptr;
     QuadB be(sink, chiphash_cfg(1, A.L, A.P, A.inv, true), false);      // a fresh Context: its first permutation holds the cached load_zero cell
     const HashParams hp = A.hp;
-    hash_program<1>(be, hp, nullptr, A.operands + i * (uint64_t)A.nw);
+    hash_program<1>(be, hp, nullptr, A.operands + i * (uint64_t)A.nw, NoHashOut());
 }
 
-// status 4: one lane per (instance, item) - a Goldilocks word, the leaf index, a hash (four Goldilocks words or one Fr)
-struct CheckArgs { const uint64_t *operands; OperandLayout o; uint32_t depth; uint64_t n; uint32_t *status; };
+// status 4: one lane per (instance, item) - a Goldilocks word, the leaf index, a hash (four Goldilocks words or one Fr); the argument block: chiphash.h
 __global__ __launch_bounds__(256) void k_chiphash_check(CheckArgs C) {
     const uint32_t items = C.o.n_gl + C.o.has_idx + C.o.n_hash;
     const uint64_t g = (uint64_t)blockIdx.x * 256 + threadIdx.x, i = g / items; const uint32_t j = (uint32_t)(g % items);
@@ -178,14 +102,12 @@ __global__ __launch_bounds__(256) void k_chiphash_check(CheckArgs C) {
         fr_t v; for (int t = 0; t < 4; t++) v.l[t] = g_load_u64(h + t);
         bad = C.o.fr_hashes ? fr_geq_mod(v) : (v.l[0] >= GL_P || v.l[1] >= GL_P || v.l[2] >= GL_P || v.l[3] >= GL_P);
     }
-    if (bad) atomicOr(&C.status[i], 4u);
+    if (bad) atomicOr(&C.status[i * C.stride], 4u);
 }
-
-struct ChipHash {
-    HashParams hp; OperandLayout o; bool bn; uint32_t nglp = 0; int small_mds = 0; uint64_t chunk = 0;      // chunk 0: by CHIPHASH_WS_BYTES
-    DevBuf<GlpConsts> d_consts; DevBuf<fr_t> d_bn_tab, d_inv;
-};
-
+void chiphash_launch_check(const CheckArgs &K, hipStream_t stream) {
+    const uint64_t items = (uint64_t)(K.o.n_gl + K.o.has_idx + K.o.n_hash) * K.n;
+    hipLaunchKernelGGL(k_chiphash_check, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, stream, K);
+}
 
 void chiphash_free(h2w_chipbatch *h) { delete h->hash; h->hash = nullptr; }
 
@@ -206,9 +128,8 @@ int chiphash_run(h2w_chipbatch *h, const uint64_t *operands_dev, uint64_t n, voi
             A.consts = c->d_consts.get(); A.glist = (uint64_t *)(ws + b_recs); A.nglp = c->nglp; A.small_mds = c->small_mds; A.bn_tab = c->d_bn_tab.get();
             uint32_t *const status = status_dev + first;
             H2W_HIP(hipMemsetAsync(status, 0, m * sizeof(uint32_t), stream));
-            CheckArgs K; K.operands = A.operands; K.o = c->o; K.depth = c->hp.depth; K.n = m; K.status = status;
-            const uint64_t items = (uint64_t)(c->o.n_gl + c->o.has_idx + c->o.n_hash) * m;
-            hipLaunchKernelGGL(k_chiphash_check, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, stream, K);
+            CheckArgs K; K.operands = A.operands; K.o = c->o; K.depth = c->hp.depth; K.n = m; K.status = status; K.stride = 1;
+            chiphash_launch_check(K, stream);
             if (c->bn) hipLaunchKernelGGL(k_chiphash_bn, dim3((unsigned)((m * 4 + QUAD_BLOCK - 1) / QUAD_BLOCK)), dim3(QUAD_BLOCK), 0, stream, A);
             else {
                 hipLaunchKernelGGL(k_chiphash_gl, dim3((unsigned)m), dim3(64), 0, stream, A);
@@ -263,16 +184,17 @@ h2w_chipbatch *h2w_chipbatch_new_hash(int op, const h2w_poseidon_consts_t *const
     {   // layout of one instance: replay on harmless operands (all zero: in every field, index 0)
         ValBackend<HashLayoutSink> be(ls, chiphash_cfg(c->hp.mode, lookup_bits, h->P, inv.data(), false), false);
         const std::vector<uint64_t> zeros(c->o.nw, 0);
-        hash_program<-1>(be, c->hp, consts, zeros.data());
+        hash_program<-1>(be, c->hp, consts, zeros.data(), NoHashOut());
     }
     h->nrec = ls.meta.size(); h->ncells = ls.cell_off; c->nglp = ls.nglp;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { h->device = -1; return h; }      // layout queries still work; h2w_chipbatch_run fails
     if (device_id < 0 || device_id >= ndev) { set_error("h2w_chipbatch_new_hash: device_id out of range"); h->device = -1; h2w_chipbatch_free(h); return nullptr; }
     DeviceGuard dg(device_id);
-    // the tables of the op's hash: PoseidonBN254's, or the Goldilocks-Poseidon constants (handletabs.h)
+    // the tables of the op's hash: PoseidonBN254's (with the limb-form copy and the row constants of the values call), or the Goldilocks-Poseidon constants (handletabs.h)
+    rf::RowConst rk; rf::rowconst_init(rk, h->P);
     if (h->dt.upload(h->tt) != 0 || h->d_meta.upload(ls.meta) != 0 || upload_tmpl_cells(h->d_tmpl_cells, h->tt) != 0 || c->d_inv.upload(inv) != 0 ||
-        (c->bn ? upload_bn_tab(c->d_bn_tab, *consts, h->P) : upload_glp_consts(c->d_consts, *consts)) != 0) { h2w_chipbatch_free(h); return nullptr; }
+        (c->bn ? (upload_bn_tab(c->d_bn_tab, *consts, h->P, &c->d_bn_tab9) != 0 || c->d_rowk.upload(&rk, 1) != 0) : upload_glp_consts(c->d_consts, *consts) != 0)) { h2w_chipbatch_free(h); return nullptr; }
     return h;
 }
 

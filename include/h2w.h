@@ -612,8 +612,8 @@ int            h2w_chipbatch_run(h2w_chipbatch *, const uint64_t *operands_dev, 
  * 1 <= depth <= 32; cap_height <= min(depth, 6).
  * status_dev[i]: 0, or 4 where an operand word is outside its field (a Goldilocks word >= p, an Fr >= r: the cells are still produced,
  * from the raw value, as h2w_plan_status defines 4) or the leaf index is >= 2^depth (the cells of that instance are unspecified).
- * The chips' assert_equal emits no cells: a Merkle verdict is not part of this (h2w_check_equalities is the check; for whole proofs,
- * h2w_fri_verdict_batch).
+ * The chips' assert_equal emits no cells: a Merkle verdict is not part of the stream (h2w_chipbatch_values below gives it, and the op's
+ * results; for whole proofs, h2w_fri_verdict_batch).
  * hash_mode 0 and GL_PERMUTE: one wavefront per instance, its permutations' records written by one wavefront per permutation;
  * hash_mode 1 and BN_PERMUTE: four lanes per instance, which emit every permutation's 4,032 cells themselves. */
 #define H2W_OP_GL_PERMUTE     9   /* PoseidonPermutationChip::permute           hash/poseidon/permutation.rs:270-284 */
@@ -628,6 +628,34 @@ h2w_chipbatch *h2w_chipbatch_new_hash(int op, const h2w_poseidon_consts_t *, int
  * call's internal workspace - records, permutation lists - under a fixed number of bytes). */
 #define H2W_CHIPBATCH_OPT_CHUNK 1
 int            h2w_chipbatch_configure(h2w_chipbatch *, int option, uint64_t value);
+/* The same ops on VALUES (csrc/chipvalues.hip): what the op computed and, for MERKLE_VERIFY, whether the opening holds - without the advice stream.
+ * A handle of h2w_chipbatch_new_hash only; a handle of h2w_chipbatch_new is refused.  operands_dev as for h2w_chipbatch_run.
+ *   results_dev[n][num_results]   the op's output wires as canonical values:
+ *       GL_PERMUTE               12 Goldilocks words (the permuted state)
+ *       BN_PERMUTE               16 words: four little-endian Fr, each below r
+ *       HASH_NO_PAD, TWO_TO_ONE  4 words: the four Goldilocks words of the hash (hash_mode 0), one little-endian Fr (hash_mode 1)
+ *       MERKLE_VERIFY            0 words (results_dev may be null): the computed cap-level node is not handed out by MerkleTreeChip
+ *   verdict_dev[n]   status    the word h2w_chipbatch_run stores for the same operands: 0, or 4 from the same item check
+ *                    n_failed  chip-level assert_equal / assert_equal_fr calls of the op whose two sides differ, counted as h2w_verdict_t.n_failed
+ *                              counts them: the root check of MERKLE_VERIFY is four comparisons with Goldilocks hashes, one with PoseidonBN254; ops 9-12
+ *                              hold none (0).  An opening holds iff status == 0 && n_failed == 0.
+ * An instance with status 4 has unspecified results and n_failed; it changes no other instance.
+ * form: with hash_mode 1 and BN_PERMUTE, which kernel walks the instances - FORM_QUAD four lanes per instance, FORM_ROW one wavefront per instance
+ * (a permutation in under half the time on sixteen times the lanes: for few instances); FORM_AUTO is FORM_ROW while n is at most the crossover the
+ * library keeps (2,048 instances: measured, a call alone on the chip, on MERKLE_VERIFY at depth 20) and FORM_QUAD beyond it.  With hash_mode 0 and GL_PERMUTE there is one kernel (a wavefront per instance): FORM_QUAD and FORM_AUTO name it, FORM_ROW is
+ * refused.  The words stored do not depend on the form, on lookup_bits or on any option.
+ * Stream-ordered, no synchronisation, no device allocation: the kernels keep no records and no lists, so the call has no workspace and runs its n
+ * instances as ONE launch - H2W_CHIPBATCH_OPT_CHUNK is not looked at.  n == 0: 0.  n above 2^26: -1 ("batch too large").
+ * -1 before any device work, the reason in h2w_last_error(): a null handle, a handle of h2w_chipbatch_new, a form above FORM_ROW, FORM_ROW without
+ * PoseidonBN254, a null operands_dev / verdict_dev (results_dev: null only where num_results is 0).  Without a device: -1 ("no HIP device"). */
+typedef struct { uint32_t status, n_failed; } h2w_chipbatch_verdict_t;   /* 8 bytes */
+uint64_t       h2w_chipbatch_num_results(const h2w_chipbatch *);   /* u64 words per instance of results_dev; needs no device (0 and an error for a handle of h2w_chipbatch_new) */
+#define H2W_CHIPBATCH_FORM_AUTO 0
+#define H2W_CHIPBATCH_FORM_QUAD 1   /* hash_mode 1: four lanes per instance;  hash_mode 0: its one kernel */
+#define H2W_CHIPBATCH_FORM_ROW  2   /* hash_mode 1 / BN_PERMUTE only: one wavefront per instance (rowfr.h / rowperm.h) */
+int            h2w_chipbatch_values(h2w_chipbatch *, const uint64_t *operands_dev, uint64_t n,
+                                    uint64_t *results_dev, h2w_chipbatch_verdict_t *verdict_dev,
+                                    unsigned form, void *stream);
 
 /* ------------------------------------------------------------------ the step BEFORE the path
  * Synthetic VALID FRI instances generated on the GPU (SURVEY 8(d) variant (A)): low-degree extension (Goldilocks NTT on the coset
