@@ -102,9 +102,10 @@
         if (op == DOP_FR_SELIND && aux != 0) {      // (in front of the switch, as DOP_BNPERM)  A part of a split select (tapefmt.h SELIND_*): the cells of its entries, where the
             // whole op puts them - the zero cell with the first part, a gate before every sum cell but the select's last.  The sum arrives from and leaves to the neighbouring
             // part in `carry`: only DOP_FETCH ops run in between, which touch the ring alone.  The result (the last part's: the others carry NO_SLOT) is stored behind the last read.
-            fr_t sum = carry;
+            fr_t sum = carry; uint64_t any = 0;
             if (!(aux & SELIND_CONTINUES)) { sum = fr_zero(); be.G(); be.cell64(0); }
-            for (uint32_t i = 0; i < n; i++) { const fr_t a = getfr(tw(tape, pc + 1 + i)); const uint64_t ind = get64(tw(tape, pc + 1 + n + i), 0); if (ind) sum = h2w::fr_add(sum, a); be.cell(a); be.cell64(ind); if (i + 1 < n || (aux & SELIND_CONTINUED)) be.G(); be.cell(sum); }
+            for (uint32_t i = 0; i < n; i++) { const fr_t a = getfr(tw(tape, pc + 1 + i)); const uint64_t ind = get64(tw(tape, pc + 1 + n + i), 0); any |= ind; if (ind) sum = h2w::fr_add(sum, a); be.cell(a); be.cell64(ind); if (i + 1 < n || (aux & SELIND_CONTINUED)) be.G(); be.cell(sum); }
+            if (any > 1) be.fail(5);      // an indicator that is no bit, in this part (status 5, below)
             carry = sum; putfr(tw(tape, pc + 1 + 2 * n), sum);
             pc = pcn; w0 = n0; w1 = n1; w2 = n2; w3 = n3; w4 = n4;
             continue;
@@ -112,6 +113,10 @@
 #endif
         // Every case reads ALL its operands (into registers, ta / tb) before its first st1 / putfr: the lowering lets an op's result slots alias the ring
         // slots of its fetched operands (tracelower.cpp bounds the fetched slots alone by RING_K; tape_check the same).  A case that stores before its last read breaks that.
+        // Status 5 (include/h2w.h 2d): an operand outside the domain its op was lowered for - a selector, an indicator or a bit above 1, a second indicator set
+        // where the sum is kept in one word, 2^128 or more in front of a reduce.  The eager call of proof A did the field's arithmetic on such a value or refused
+        // it; the templates of the value backend (shared with the compiled plan's kernels, where these are bits by construction) do neither.  Decided on the
+        // operand, once per op (the words ORed), whether or not the result happens to come out right; the op's cells are written as before and are unspecified.
         switch (op) {
             case DOP_SKIP: { const uint64_t nr = ((uint64_t)w2 << 32) | w1, nc = ((uint64_t)w4 << 32) | w3; sink.skip(nr, nc); break; }
             case DOP_CONST1: { const uint64_t v = get64(w1, 0); sink.rec(T_CONST1, v, 0, 0, 0); put64(w2, v); break; }
@@ -130,23 +135,28 @@
             case DOP_GLOP: { const uint64_t A = get64(w1, 0), B = get64(w2, 0), C = get64(w3, 0); sink.rec((int)aux, A, B, C, 0); put64(w4, gl_reduce128((u128)A * B + C)); break; }
             case DOP_GATE: { const uint64_t A = get64(w1, 0), B = get64(w2, 0), C = get64(w3, 0); sink.rec((int)aux, A, B, C, 0);
                              const u128 v = (u128)A * B + C; const uint32_t o = w4; if (o != NO_SLOT) { st1(o, (uint64_t)v); st1(o + 1, (uint64_t)(v >> 64)); } break; }
-            case DOP_REDUCE: { const uint32_t r = w1; const uint64_t lo = get64(r, 0), hi = get64(r, 1); sink.rec(T_REDUCE, lo, hi, 0, 0); put64(w2, gl_reduce128(((u128)hi << 64) | lo)); break; }
+            case DOP_REDUCE: { const uint32_t r = w1; const uint64_t lo = get64(r, 0), hi = get64(r, 1);
+                               if (((r >> 27) & 3u) == WFR && (get64(r, 2) | get64(r, 3)) != 0) be.fail(5);      // a four-slot operand (mul_sub: a b + c (p - 1)): beyond the range of GoldilocksChip::reduce, where h2w_gl_reduce fails
+                               sink.rec(T_REDUCE, lo, hi, 0, 0); put64(w2, gl_reduce128(((u128)hi << 64) | lo)); break; }
             case DOP_CLT: { sink.rec(T_CLT_SAFE, get64(w1, 0), 0, 0, 0); break; }
             case DOP_FR_ADD: { const fr_t v = be.fr_add(getfr(w1), getfr(w2)); putfr(w3, v); break; }
             case DOP_FR_MUL: { const fr_t v = be.fr_mul(getfr(w1), getfr(w2)); putfr(w3, v); break; }
             case DOP_FR_MULADD: { const fr_t v = be.fr_mul_add(getfr(w1), getfr(w2), getfr(w3)); putfr(w4, v); break; }
-            case DOP_SELECT: { const uint64_t v = be.select(get64(w1, 0), get64(w2, 0), get64(w3, 0)); put64(w4, v); break; }
-            case DOP_FR_SELECT: { const fr_t v = be.fr_select(getfr(w1), getfr(w2), get64(w3, 0)); putfr(w4, v); break; }
+            case DOP_SELECT: { const uint64_t sel = get64(w3, 0); if (sel > 1) be.fail(5); const uint64_t v = be.select(get64(w1, 0), get64(w2, 0), sel); put64(w4, v); break; }
+            case DOP_FR_SELECT: { const uint64_t sel = get64(w3, 0); if (sel > 1) be.fail(5); const fr_t v = be.fr_select(getfr(w1), getfr(w2), sel); putfr(w4, v); break; }
             case DOP_IDX2IND: { be.idx_to_indicator(get64(w1, 0), (int)n, ta); const uint32_t o = w2; for (uint32_t i = 0; i < n; i++) st1(o + i, ta[i]); break; }
-            case DOP_SELIND: { for (uint32_t i = 0; i < n; i++) { ta[i] = get64(tw(tape, pc + 1 + i), 0); tb[i] = get64(tw(tape, pc + 1 + n + i), 0); }
+            case DOP_SELIND: { uint64_t any = 0, set = 0;      // (set: exact while every indicator is a bit; two entries of one word need not sum to one word)
+                               for (uint32_t i = 0; i < n; i++) { ta[i] = get64(tw(tape, pc + 1 + i), 0); tb[i] = get64(tw(tape, pc + 1 + n + i), 0); any |= tb[i]; set += tb[i]; }
+                               if ((any | set) > 1) be.fail(5);
                                put64(tw(tape, pc + 1 + 2 * n), be.select_by_indicator(ta, 1, tb, (int)n)); break; }
             case DOP_FR_SELIND: {      // GateChip::select_by_indicator on native values: [0, a0, ind0, s0, a1, ind1, s1, ...] (gates at 3 i)
-                fr_t sum = fr_zero(); if (n > 0) be.G(); be.cell64(0);
-                for (uint32_t i = 0; i < n; i++) { const fr_t a = getfr(tw(tape, pc + 1 + i)); const uint64_t ind = get64(tw(tape, pc + 1 + n + i), 0); if (ind) sum = h2w::fr_add(sum, a); be.cell(a); be.cell64(ind); if (i + 1 < n) be.G(); be.cell(sum); }
+                fr_t sum = fr_zero(); uint64_t any = 0; if (n > 0) be.G(); be.cell64(0);
+                for (uint32_t i = 0; i < n; i++) { const fr_t a = getfr(tw(tape, pc + 1 + i)); const uint64_t ind = get64(tw(tape, pc + 1 + n + i), 0); any |= ind; if (ind) sum = h2w::fr_add(sum, a); be.cell(a); be.cell64(ind); if (i + 1 < n) be.G(); be.cell(sum); }
+                if (any > 1) be.fail(5);
                 putfr(tw(tape, pc + 1 + 2 * n), sum); break;
             }
             case DOP_NUM2BITS: { be.num_to_bits(get64(w1, 0), (int)n, ta); const uint32_t o = w2; for (uint32_t i = 0; i < n; i++) st1(o + i, ta[i]); break; }
-            case DOP_BITS2NUM: { for (uint32_t i = 0; i < n; i++) ta[i] = get64(tw(tape, pc + 1 + i), 0); put64(tw(tape, pc + 1 + n), be.bits_to_num(ta, (int)n)); break; }
+            case DOP_BITS2NUM: { uint64_t any = 0; for (uint32_t i = 0; i < n; i++) { ta[i] = get64(tw(tape, pc + 1 + i), 0); any |= ta[i]; } if (any > 1) be.fail(5); put64(tw(tape, pc + 1 + n), be.bits_to_num(ta, (int)n)); break; }
             case DOP_DECOMP565: { be.decompose_le_56_5(getfr(w1), ta); const uint32_t o = w2; for (int i = 0; i < 5; i++) st1(o + i, ta[i]); break; }
             case DOP_LIMBS2NUM: { for (uint32_t i = 0; i < n; i++) ta[i] = get64(tw(tape, pc + 1 + i), 0); putfr(tw(tape, pc + 1 + n), n == 4 ? be.limbs_to_num4(ta) : be.limbs_to_num(ta, (int)n)); break; }
             case DOP_RANGE: { be.range_check(get64(w1, 0), (int)aux); break; }

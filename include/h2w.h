@@ -169,7 +169,13 @@ int h2w_chip_verify_stark(h2w_ctx *, const h2w_shape_t *, const h2w_poseidon_con
 /* ------------------------------------------------------------------ 2d. record and replay: the operator API served at GPU speed
  * A context in trace mode records the tape of ONE run driven through nothing but the level-1 / level-2 calls above (for the reference: its unchanged
  * chips over the NativeChip shim); h2w_plan_from_trace lowers the tape to a device program, and h2w_fri_witness_batch replays it on any batch of proofs
- * of the same shape - bit-identical to running the calls on each of them.  What makes a run replayable:
+ * of the same shape - bit-identical to running the calls on each of them, for every proof whose status is 0.  The replay works at the widths the
+ * lowering assigned on the traced proof and has no host call that could refuse a value: a proof in which a selector of h2w_select, an indicator of
+ * h2w_select_array_by_indicator - in every part of a split one - or an operand of h2w_bits_to_num is above 1, in which more than one indicator of a
+ * select on one-word entries is set (their sum need not be one word), or in which the operand of h2w_gl_reduce - the one inside
+ * h2w_gl_mul_sub too - is 2^128 or more (where the eager calls fail) has status 5: decided on the operand, whether or not the result would come out
+ * right.  Among 1, 2 and 5 the first op in program order wins, and all win over 4.  The cells in front of the first cell of the first such op are
+ * those of the calls; the cells from there on are unspecified; no other proof of the batch changes.  What makes a run replayable:
  *   - control flow does not depend on values (true of the reference's gadgets: SURVEY 7);
  *   - a value that depends on the proof enters as a TAGGED proof word: h2w_trace_input(ctx, word, n) just before the h2w_load_witness /
  *     h2w_gl_load_witness / h2w_load_constant / h2w_gl_load_constant that loads it (n = 1: a Goldilocks element, 4: a BN254 hash);
@@ -279,7 +285,7 @@ int h2w_plan_trace_timing(h2w_plan *, float *ms, uint32_t cap);
  *                range_check(a, n limbs) and range_check(a + 2^(n lookup_bits) - b, n limbs): a >= b breaks the second limb sum (+ 1 with n > 1)
  *   first_query  the lowest shard unit (the depth-1 parallel instance an equality's scope is or lies in) that owns a failing equality; 0xFFFFFFFF: none
  *                fails, or only the root's, or the plan has no units.  Range sites do not count here
- *   status       the word h2w_plan_status reports after a witness call of the plan on the same proofs (1, 2: the hint ops; 4: a proof word outside its field)
+ *   status       the word h2w_plan_status reports after a witness call of the plan on the same proofs (1, 2: the hint ops; 5: a value outside its op's domain; 4: a proof word outside its field)
  * A proof is accepted iff flags == 0 && n_failed == 0 && status == 0.  On a trace of h2w_chip_verify_stark the first three words are those of 3b's call
  * on the compiled plan of the shape (the hint checks in the prologue, which 3b's kernels do not judge, can only fail beside status 1 / 2).
  * workspace_dev: h2w_plan_workspace_bytes(n_proofs) bytes, the witness call's (the value store and the status words live there; whoever runs next on it
@@ -414,8 +420,10 @@ int h2w_check_equalities(const void *advice_dev, uint64_t n_cells, uint64_t proo
 /* Per-proof device status words.  0 = ok.  1 = GoldilocksChip::div by zero (reference asserts, base.rs:379), 2 = extension
  * inverse of zero (extension.rs:327), 3 = challenger input buffer overflow, 4 = the proof holds a word outside its field's
  * canonical range (a Goldilocks word >= p or a BN254 hash >= r: not representable by the reference's types; the cells are
- * still produced — identical to the reference's arithmetic for Goldilocks words, unreduced for the hash).  The first
- * condition met wins. */
+ * still produced — identical to the reference's arithmetic for Goldilocks words, unreduced for the hash), 5 = a traced
+ * plan only (2d): a replayed value left the domain its op was lowered for (a selector, indicator or bit above 1, a second
+ * indicator set on one-word entries, 2^128 or more in front of GoldilocksChip::reduce); the cells from that op on are
+ * unspecified.  The first condition met wins. */
 int h2w_plan_status(h2w_plan *, const void *workspace_dev, uint64_t n_proofs, uint32_t *host_status, void *stream);
 /* 32-byte checksum of n_cells cells (for streamed configurations, whose advice buffers are re-used before anything could read them
  * back): digest[j] = sum over cells i of limb_j(cell i) * ((((i + 1) * 0x9E3779B97F4A7C15) | 1) + 2 j)  mod 2^64 - position-dependent,

@@ -6,7 +6,7 @@ A program is a function prog(b) written once against the small backend interface
   IntBackend     Python integers only, no cells: the value of every handle ((a * b + c) % P, % R, bit lists ...) and the status word
 lower() turns the traced run into a plan; check_on_device() replays it on a batch and holds every proof's stream to the oracle's bytes, its
 status word and the cells at the returned handles to the Int backend's values (and the oracle's values to the Int backend's: a bug the oracle
-and the device share still shows).  The programs themselves (PROGRAMS) are shared by tests/test_replay_programs_lowering.py (no GPU) and
+and the device share still shows); a proof the Int backend gives status 5 (include/h2w.h 2d) is held to the cells in front of the offending op.  The programs themselves (PROGRAMS) are shared by tests/test_replay_programs_lowering.py (no GPU) and
 tests/test_gpu_replay_programs.py."""
 import contextlib
 import ctypes as C
@@ -142,7 +142,9 @@ class OracleBackend(_Base):
     def __init__(self, oracle, words, lookup_bits):
         self.O, self.L, self.w = oracle, oracle.lib(), words
         self.ctx = oracle.Ctx(lookup_bits); self.p = self.ctx.p
+        self.entries = []      # the cell count at the entry of every op that can raise status 5, in program order (IntBackend.off indexes it)
 
+    def _enter(self): self.entries.append(self.ctx.num_cells())
     def _arr(self, xs): return (self.O.AV * max(len(xs), 1))(*xs)
     def _fr(self, v): return self.O.Fr.from_int(v)
     def gl_in(self, word): return self.L.orc_gl_load_witness(self.p, self.w[word])
@@ -154,20 +156,20 @@ class OracleBackend(_Base):
     def add(self, a, b): return self.L.orc_add(self.p, a, b)
     def mul(self, a, b): return self.L.orc_mul(self.p, a, b)
     def mul_add(self, a, b, c): return self.L.orc_mul_add(self.p, a, b, c)
-    def select(self, a, b, s): return self.L.orc_select(self.p, a, b, s)
+    def select(self, a, b, s): self._enter(); return self.L.orc_select(self.p, a, b, s)
     def select_from_idx(self, arr, idx): return self.L.orc_select_from_idx(self.p, self._arr(arr), len(arr), idx)
 
     def idx_to_indicator(self, idx, n):
         out = (self.O.AV * n)(); self.L.orc_idx_to_indicator(self.p, idx, n, out); return list(out)
 
     def select_array_by_indicator(self, arr2d, ind):
-        ln, w = len(arr2d), len(arr2d[0]); out = (self.O.AV * w)()
+        self._enter(); ln, w = len(arr2d), len(arr2d[0]); out = (self.O.AV * w)()
         self.L.orc_select_array_by_indicator(self.p, self._arr([x for row in arr2d for x in row]), ln, w, self._arr(ind), out); return list(out)
 
     def num_to_bits(self, a, n):
         out = (self.O.AV * n)(); self.L.orc_num_to_bits(self.p, a, n, out); return list(out)
 
-    def bits_to_num(self, bits): return self.L.orc_bits_to_num(self.p, self._arr(bits), len(bits))
+    def bits_to_num(self, bits): self._enter(); return self.L.orc_bits_to_num(self.p, self._arr(bits), len(bits))
 
     def decompose_le(self, a, limb_bits, n):
         out = (self.O.AV * n)(); self.L.orc_decompose_le(self.p, a, limb_bits, n, out); return list(out)
@@ -179,11 +181,11 @@ class OracleBackend(_Base):
     def gl_sub(self, a, b): return self.L.orc_gl_sub(self.p, a, b)
     def gl_mul(self, a, b): return self.L.orc_gl_mul(self.p, a, b)
     def gl_mul_add(self, a, b, c): return self.L.orc_gl_mul_add(self.p, a, b, c)
-    def gl_mul_sub(self, a, b, c): return self.L.orc_gl_mul_sub(self.p, a, b, c)
+    def gl_mul_sub(self, a, b, c): self._enter(); return self.L.orc_gl_mul_sub(self.p, a, b, c)
     def gl_neg(self, a): k = self.L.orc_gl_load_constant(self.p, P - 1); return self.L.orc_gl_mul(self.p, a, k)      # load_neg_one, mul (base.rs:234-238)
     def gl_square(self, a): return self.L.orc_gl_mul(self.p, a, a)
     def gl_exp_power_of_2(self, a, k): return self.L.orc_gl_exp_power_of_2(self.p, a, k)
-    def gl_reduce(self, a): return self.L.orc_gl_reduce(self.p, a)
+    def gl_reduce(self, a): self._enter(); return self.L.orc_gl_reduce(self.p, a)
     def gl_div(self, a, b): return self.L.orc_gl_div(self.p, a, b)
     def gl_inv(self, a): return self.L.orc_gl_inv(self.p, a)
 
@@ -202,11 +204,24 @@ def _ext_mul(a, b):      # F_p[X] / (X^2 - 7)
 
 
 class IntBackend(_Base):
-    """Values only.  chip: the status of the first op of the run the reference would panic in (1: a zero divisor, 2: a zero extension element);
-    flagged: a proof word outside its field (one word >= p, four words >= r); unspecified: a four-word one, whose cells h2w.h leaves open."""
+    """Values only, exact in the field.  chip: the status of the first op of the run that raises one (1: a zero divisor, 2: a zero extension element -
+    the reference would panic; 5: an operand outside the domain its op is lowered for, include/h2w.h 2d: a selector, an indicator or a bit above 1,
+    more than one indicator set in a select_by_indicator on one-word entries, GoldilocksChip::reduce of 2^128 or more); off: which of the ops that can
+    raise 5 - select, select_array_by_indicator, bits_to_num, gl_mul_sub, gl_reduce, counted in program order as OracleBackend.entries lists them - was
+    the first to, n_off: how many did; flagged: a proof word outside its field (one word >= p, four words >= r); unspecified: a four-word one, whose
+    cells h2w.h leaves open."""
 
     def __init__(self, words):
         self.w, self.chip, self.flagged, self.unspecified = words, 0, False, False
+        self.k, self.off, self.n_off = 0, None, 0
+
+    def _domain(self, left):
+        """the entry of an op that can raise 5; left: its operands are outside the domain"""
+        if left:
+            self.chip = self.chip or 5; self.n_off += 1
+            if self.off is None:
+                self.off = self.k
+        self.k += 1
 
     def status(self):
         return self.chip or (4 if self.flagged else 0)
@@ -231,12 +246,17 @@ class IntBackend(_Base):
     def add(self, a, b): return (a + b) % R
     def mul(self, a, b): return a * b % R
     def mul_add(self, a, b, c): return (a * b + c) % R
-    def select(self, a, b, s): return a if s else b
+    def select(self, a, b, s): self._domain(s > 1); return ((a - b) * s + b) % R
     def select_from_idx(self, arr, idx): return arr[idx] if idx < len(arr) else 0
     def idx_to_indicator(self, idx, n): return [1 if i == idx else 0 for i in range(n)]
-    def select_array_by_indicator(self, arr2d, ind): return [sum(row[j] * s for row, s in zip(arr2d, ind)) % R for j in range(len(arr2d[0]))]
+    def select_array_by_indicator(self, arr2d, ind):
+        # a column of one-word entries is one narrow op.  (The lowering goes by the static width and the model sees values: the programs that set more
+        # than one indicator keep an entry of 2^64 or more in every four-word column.)
+        narrow = any(all(row[j] < 2**64 for row in arr2d) for j in range(len(arr2d[0])))
+        self._domain(any(s > 1 for s in ind) or (narrow and sum(1 for s in ind if s) > 1))
+        return [sum(row[j] * s for row, s in zip(arr2d, ind)) % R for j in range(len(arr2d[0]))]
     def num_to_bits(self, a, n): return [(a >> i) & 1 for i in range(n)]
-    def bits_to_num(self, bits): return sum(x << i for i, x in enumerate(bits)) % R
+    def bits_to_num(self, bits): self._domain(any(x > 1 for x in bits)); return sum(x << i for i, x in enumerate(bits)) % R
     def decompose_le(self, a, limb_bits, n): return [(a >> (limb_bits * i)) & ((1 << limb_bits) - 1) for i in range(n)]
     def limbs_to_num(self, limbs, limb_bits): return sum(x << (limb_bits * i) for i, x in enumerate(limbs)) % R
     def check_less_than_safe(self, a, bound): pass
@@ -245,11 +265,11 @@ class IntBackend(_Base):
     def gl_sub(self, a, b): return (a - b) % P
     def gl_mul(self, a, b): return a * b % P
     def gl_mul_add(self, a, b, c): return (a * b + c) % P
-    def gl_mul_sub(self, a, b, c): return (a * b - c) % P
+    def gl_mul_sub(self, a, b, c): v = a * b + c * (P - 1); self._domain(v >= 2**128); return v % P      # mul_no_reduce, sub_no_reduce (a + b (p - 1), base.rs:262-272), reduce
     def gl_neg(self, a): return -a % P
     def gl_square(self, a): return a * a % P
     def gl_exp_power_of_2(self, a, k): return pow(a, 2**k, P)
-    def gl_reduce(self, a): return a % P
+    def gl_reduce(self, a): self._domain(a >= 2**128); return a % P
 
     def gl_div(self, a, b):
         if b % P == 0:
@@ -287,13 +307,35 @@ def lower(h2w, api, prog, proof_a, lookup_bits=21, parallel_scopes=()):
         tb.ctx.close()
 
 
-def oracle_run(oracle, prog, proof, lookup_bits=21):
-    """(stream bytes, cells of the returned handles, their values) of prog on the oracle"""
+def oracle_run(oracle, prog, proof, lookup_bits=21, entries=False):
+    """(stream bytes, cells of the returned handles, their values) of prog on the oracle; entries: and OracleBackend.entries"""
     ob = OracleBackend(oracle, proof, lookup_bits)
     hs = flatten(prog(ob))
     out = ob.ctx.advice_bytes(), [int(h.cell) for h in hs], [h.v.to_int() for h in hs]
     ob.ctx.close()
-    return out
+    return out + (ob.entries,) if entries else out
+
+
+def held_cells(ib, entries, num_cells):
+    """How many cells of a proof's stream are the oracle's (include/h2w.h 2d): all of them, or - an op of the run raised 5 - those in front of the
+    first cell of the first such op.  ib: the proof's IntBackend after the run; entries: its OracleBackend's."""
+    assert len(entries) == ib.k
+    return num_cells if ib.off is None else entries[ib.off]
+
+
+def compare_on_device(i, got, status, want_status, ib, stream, entries, offsets, want_vals):
+    """Proof i of a replayed batch against the oracle's stream and the integer model (check_on_device; tests/test_gpu_replay_split_selects.py).
+    got: its cells, [num_cells, 4] u64"""
+    import numpy as np
+    assert status == want_status, f"proof {i}: status {status}, expected {want_status}"
+    want = np.frombuffer(stream, dtype=np.uint64).reshape(-1, 4)
+    cut = held_cells(ib, entries, len(want))
+    if not np.array_equal(got[:cut], want[:cut]):
+        bad = np.nonzero((got[:cut] != want[:cut]).any(axis=1))[0]
+        raise AssertionError(f"proof {i} (status {status}, {cut} of {len(want)} cells held): {len(bad)} cells differ, first at {bad[:8]}: got {got[bad[0]]} want {want[bad[0]]}")
+    for k, (c, v) in enumerate(zip(offsets, want_vals)):
+        if c < cut:
+            assert [int(x) for x in got[c]] == fr_words(v), f"proof {i}: handle {k} (cell {c}) is not the integer model's value {v:#x}"
 
 
 def int_run(prog, proof):
@@ -302,7 +344,8 @@ def int_run(prog, proof):
 
 
 def check_on_device(h2w, api, oracle, prog, proof_a, proofs, lookup_bits=21, parallel_scopes=()):
-    """Traces prog on proof A, replays the plan on `proofs` in one batch, and holds every proof to the oracle and to the Int backend.  -> the status words"""
+    """Traces prog on proof A, replays the plan on `proofs` in one batch, and holds every proof to the oracle and to the Int backend: the status word
+    is the model's; the whole stream and every handle where no op raised 5, else the cells in front of the first op that did.  -> the status words"""
     import numpy as np
     import torch
     lw = lower(h2w, api, prog, proof_a, lookup_bits, parallel_scopes)
@@ -323,15 +366,10 @@ def check_on_device(h2w, api, oracle, prog, proof_a, proofs, lookup_bits=21, par
         assert status[i] == ib.status(), f"proof {i}: status {status[i]}, expected {ib.status()}"
         if ib.unspecified:
             continue
-        stream, cells, vals = oracle_run(oracle, prog, p, lookup_bits)
+        stream, cells, vals, entries = oracle_run(oracle, prog, p, lookup_bits, entries=True)
         assert cells == lw.offsets and len(stream) == plan.num_cells * 32
         assert vals == want_vals, f"proof {i}: the oracle's values differ from the integer model at handles {[k for k in range(len(vals)) if vals[k] != want_vals[k]][:8]}"
-        want = np.frombuffer(stream, dtype=np.uint64).reshape(-1, 4)
-        if not np.array_equal(got[i], want):
-            bad = np.nonzero((got[i] != want).any(axis=1))[0]
-            raise AssertionError(f"proof {i}: {len(bad)} cells differ, first at {bad[:8]}: got {got[i][bad[0]]} want {want[bad[0]]}")
-        for k, (c, v) in enumerate(zip(lw.offsets, want_vals)):
-            assert [int(x) for x in got[i][c]] == fr_words(v), f"proof {i}: handle {k} (cell {c}) is not the integer model's value {v:#x}"
+        compare_on_device(i, got[i], status[i], ib.status(), ib, stream, entries, lw.offsets, want_vals)
     return status
 
 
@@ -352,11 +390,15 @@ class Program:
     """name; fn(b); words of a proof; lookup_bits; parallel_scopes; make(i) -> proof i of a batch; sizes: the batch sizes of the device test;
     expect(counts, E): what the op counts of the lowered plan must show (E: tape_enums())"""
 
-    def __init__(self, name, fn, nwords, make, lookup_bits=21, scopes=(), sizes=(1, 130), expect=None):
+    def __init__(self, name, fn, nwords, make, lookup_bits=21, scopes=(), sizes=(1, 130), expect=None, off=None, fix_a=None):
         self.name, self.fn, self.nwords, self.make, self.lookup_bits, self.scopes, self.sizes, self.expect = name, fn, nwords, make, lookup_bits, tuple(scopes), sizes, expect
+        self.off, self.fix_a = off, fix_a      # off: the OffDomain of a program whose batch leaves proof A's domain; fix_a(p): what the eager calls need of proof A
 
     def proof_a(self):
-        return safe_proof(self.nwords)
+        p = safe_proof(self.nwords)
+        if self.fix_a:
+            self.fix_a(p)
+        return p
 
     def batch(self, n):
         return [self.make(i) for i in range(n)]
@@ -621,6 +663,216 @@ def make_far_operands(n):
     return make
 
 
+# ---- 9. proofs that leave proof A's value domain (include/h2w.h 2d, status 5).  Proof A's eager calls validated what proof A holds; the interpreter
+# works at the widths the lowering assigned and has no host call that could refuse: a selector, an indicator or a bit above 1, a second indicator set
+# where the entries are one word, a value of 2^128 or more in front of GoldilocksChip::reduce.  Every program starts and ends with a division
+# (words 0 1 and 2 3: x, divisor), so that a zero divisor can stand in front of and behind the offence.
+OFF_POOL = [2, 2**32, P - 1]
+
+
+class OffDomain:
+    """The batch of such a program.  base(i): proof i, in domain (canonical words: status 0); kinds: [(name, put(p))] - put writes ONE offence into a proof.
+    Proof i is in domain where i % 4 == 0; the others take the kinds in turn.  i % 16 == 5: the last divisor is zero as well (the 5 comes first and
+    wins), i % 16 == 11: the first one is (status 1; the cells in front of the offending op are still the oracle's)."""
+
+    def __init__(self, base, kinds):
+        self.base, self.kinds = base, kinds
+
+    def kind(self, i):
+        j = i - i // 4 - 1      # the off-domain proofs in front of proof i; every run of len(kinds) of them holds every kind, rotated by one from run to run, so
+        return None if i % 4 == 0 else self.kinds[(j + j // len(self.kinds)) % len(self.kinds)]      # that a kind meets the zero divisors of i % 16 in some proofs only
+
+    def expected_status(self, i):
+        return 0 if i % 4 == 0 else 1 if i % 16 == 11 else 5
+
+    def make(self, i):
+        p = self.base(i); k = self.kind(i)
+        if k:
+            k[1](p)
+        if i % 16 == 5:
+            p[3] = 0
+        if i % 16 == 11:
+            p[1] = 0
+        return p
+
+
+def _put(word, v):
+    return lambda p: p.__setitem__(word, v)
+
+
+def _div(b, w):
+    x, d = b.gl_in(w), b.gl_in(w + 1)
+    return [x, d, b.gl_div(x, d)]
+
+
+def _div_words(i):
+    return [pick(GL_EDGES, i, 0), pick(GL_EDGES[1:], i, 1), pick(GL_EDGES, i, 2), pick(GL_EDGES[1:], i, 3)]
+
+
+# 9a. select.  words: 4 n0, 5 n1, 6.. h0, 10.. h1, 14 .. 17 the selectors of the narrow, the wide, the wide-and-narrow select and of select(n0, n0, .)
+def prog_off_select(b):
+    out = _div(b, 0)
+    n0, n1, h0, h1 = b.nat_in(4), b.nat_in(5), b.hash_in(6), b.hash_in(10)
+    sels = [b.nat_in(14 + k) for k in range(4)]
+    for (x, y), s in zip(((n0, n1), (h0, h1), (h0, n1), (n0, n0)), sels):      # (a == b: the result would come out right, the selector is still no bit)
+        r = b.select(x, y, s); out += [r, b.add(r, n1)]
+    return out + _div(b, 2) + [n0, n1, h0, h1] + sels
+
+
+def base_off_select(i):
+    p = _div_words(i) + [pick(GL_EDGES, i, 4), pick(GL_EDGES, i, 5)] + [0] * 8 + [(i >> k) & 1 for k in (2, 3, 4, 5)]
+    _put_fr(p, 6, pick(FR_EDGES, i, 6)); _put_fr(p, 10, pick(FR_EDGES, i, 7))
+    return p
+
+
+OFF_SELECT = OffDomain(base_off_select, [(f"{name}-{v:#x}", _put(14 + k, v)) for k, name in enumerate(("narrow", "wide", "mixed", "equal")) for v in OFF_POOL])
+
+
+# 9b. bits.  words: 4 5 the bits of bits_to_num at n = 2, 6 .. 69 at n = 64; 70, 71 the numbers of num_to_bits at 2 and 8 bits; 72 .. 77 range-checked
+# words; 78 check_less_than_safe.  The words from 70 on are beyond their ranges in most proofs of the batch, in-domain ones included: those values fit,
+# the stream is the oracle's and the status stays 0.
+def prog_off_bits(L):
+    def prog(b):
+        out = _div(b, 0)
+        for bits in ([b.nat_in(4 + k) for k in range(2)], [b.nat_in(6 + k) for k in range(64)]):
+            r = b.bits_to_num(bits); out += [r, b.add(r, r)]
+        out += [b.num_to_bits(b.nat_in(70), 2), b.num_to_bits(b.nat_in(71), 8)]
+        for k, bits in enumerate(rc_bits(L)):
+            b.range_check(b.nat_in(72 + k), bits)
+        b.check_less_than_safe(b.nat_in(78), P)
+        return out + _div(b, 2)
+    return prog
+
+
+def base_off_bits(L):
+    def base(i):
+        rnd = random.Random(1000 + i)
+        p = _div_words(i) + [rnd.randrange(2) for _ in range(66)] + [pick([3, 4, 2**32, P - 1, 1], i, 70), pick([255, 256, 2**63, P - 1, 2**8 + 1], i, 71)]
+        if i % 8 == 0:
+            p[6:70] = [1] * 64                                          # 2^64 - 1: the largest sum of bits
+        for k, bits in enumerate(rc_bits(L)):
+            n = (bits + L - 1) // L
+            p.append(pick([v for v in (2**bits - 1, 2**bits, 2**bits + 1, 2**(n * L) - 1, 2**(n * L), 2**63, P - 1) if v < P], i, 72 + k))
+        return p + [pick([P - 1, P - 2, 0, 2**32], i, 78)]
+    return base
+
+
+def _two_high_bits(p):
+    p[4] = p[5] = 2**63      # 2^63 + 2^64: wraps to 2^63 in 64 bits
+
+
+OFF_BITS_KINDS = [(f"n2-bit{k}-{v:#x}", _put(4 + k, v)) for k in (0, 1) for v in OFF_POOL] + [(f"n64-bit{k}-{v:#x}", _put(6 + k, v)) for k in (0, 1, 63) for v in OFF_POOL] + [("n2-both-2^63", _two_high_bits)]
+
+
+# 9c. select_by_indicator.  words: 4 5 / 6 7 two one-word entries and their indicators; 8.. 12.. / 16 17 two four-word entries; 18 .. 81 / 82 .. 145 64 one-word
+# entries; 146 .. 177 / 178 .. 241 eight four-word entries, in front of 56 four-word constants (64 four-word values loaded by the program would have
+# to be fetched into more slots than a lane has, h2w.h 2d).  An indicator list in domain is all zero or has one entry set; where the entries are four
+# words it may have several set: the sum is the field's.
+SI = {"narrow2": (4, 6, 2), "wide2": (8, 16, 2), "narrow64": (18, 82, 64), "wide64": (146, 178, 64)}      # name -> (first entry word, first indicator word, n)
+SI_CONSTS = [2**200 + 2**64 * 7 + k for k in range(56)]
+SI_BIG = [2**64, 2**128 - 1, 2**128, 2**253, R - 1]
+
+
+def prog_off_selind(b):
+    out = _div(b, 0)
+    ks = [b.const(v) for v in SI_CONSTS]
+    use = b.nat_in(4)
+    for name, (e0, i0, n) in SI.items():
+        wide = name.startswith("wide")
+        arr = [b.hash_in(e0 + 4 * k) for k in range(min(n, 8))] + (ks if n == 64 else []) if wide else [b.nat_in(e0 + k) for k in range(n)]
+        ind = [b.nat_in(i0 + k) for k in range(n)]
+        r = b.select_array_by_indicator([[x] for x in arr], ind); out += [r, b.add(r[0], use)]      # (the result is used: a sum cut to 64 bits would show)
+    return out + _div(b, 2)
+
+
+def base_off_selind(i):
+    p = _div_words(i) + [0] * 238
+    j = i // 4
+    for name, (e0, i0, n) in SI.items():
+        wide = name.startswith("wide")
+        for k in range(min(n, 8) if wide else n):
+            if wide:
+                _put_fr(p, e0 + 4 * k, pick(SI_BIG, i, k) if k == 0 else pick(FR_EDGES, i, k, off=2))      # (entry 0: two words or more, IntBackend.select_array_by_indicator)
+            else:
+                p[e0 + k] = pick(GL_EDGES, i, e0 + k)
+        if j % 5 != 4:
+            p[i0 + (j * 7 + 3) % n] = 1
+        if wide and j % 3 == 1:
+            p[i0 + (j * 5) % n] = 1; p[i0 + n - 1] = 1
+    return p
+
+
+def _several_set(e0, i0, n):
+    def put(p):
+        p[i0:i0 + n] = [0] * n; p[i0] = p[i0 + n - 1] = 1
+        p[e0], p[e0 + n - 1] = 2**63, P - 1      # their sum is more than one word
+    return put
+
+
+def _the_issues_case(p):
+    p[4:8] = [5, 9, 2, P - 1]      # 5 * 2 + 9 * (p - 1) = 0x8fffffff70000000a
+
+
+OFF_SELIND_KINDS = [(f"{name}-ind{k}-{v:#x}", _put(i0 + k, v)) for name, (e0, i0, n) in SI.items() for k in sorted({0, n // 2 - 1, n - 1}) for v in OFF_POOL]
+OFF_SELIND_KINDS += [(f"{name}-two-set", _several_set(*SI[name])) for name in ("narrow2", "narrow64")] + [("narrow2-5-9-by-2-p-1", _the_issues_case)]
+
+
+# 9d. GoldilocksChip::reduce.  words: 4 x, 5 y, 6 c of mul_sub (x y + c (p - 1) in front of its reduce); 7.. h0, 11.. h1, 15.. h2 of reduce(h0 h1 + h2)
+def prog_off_reduce(b):
+    out = _div(b, 0)
+    x, y, c = b.gl_in(4), b.gl_in(5), b.gl_in(6)
+    ms = b.gl_mul_sub(x, y, c); out += [x, y, c, ms, b.gl_add(ms, x)]
+    h = [b.hash_in(7 + 4 * k) for k in range(3)]
+    g = b.mul_add(h[0], h[1], h[2]); rd = b.gl_reduce(g); out += h + [g, rd, b.gl_mul(rd, y)]
+    return out + _div(b, 2)
+
+
+def fix_a_off_reduce(p):
+    for k in range(3):
+        p[8 + 4 * k:11 + 4 * k] = [0, 0, 0]      # h0 h1 + h2 below 2^128 on proof A: the eager reduce takes it; the lowering goes by the static width
+
+
+MS_X = -(-2**128 // (P - 1)) - (P - 1)      # the least x with (x + p - 1) (p - 1) >= 2^128
+_MS = [(P - 1, P - 1, P - 1), (MS_X, P - 1, P - 1), (MS_X - 1, P - 1, P - 1), (P - 1, P - 1, 0), (P - 1, P - 1, 2**33), (2**63, 2**63, P - 1), (0, 0, P - 1), (2**32 + 1, P - 2, P - 1),
+       (P - 1, 2**32, P - 1), (0, 0, 0), (1, P - 1, 2**63), (P - 2, P - 1, 2**32 + 1), (P - 1, P - 1, MS_X), (P - 1, P - 1, MS_X - 1), (P - 1, P - 2, P - 1), (2**63, P - 1, 2**63)]
+MS_IN = [t for t in _MS if t[0] * t[1] + t[2] * (P - 1) < 2**128]
+MS_OFF = [t for t in _MS if t not in MS_IN]
+# (A, B, C) with A B + C in the field: 2^128 - 1 and 2^128 exactly, 1 by way of (r - 1)^2, values with only word 2 or only word 3 set
+_RD = [(2**64, 2**64 - 1, 2**64 - 1), (2**64, 2**64, 0), (R - 1, R - 1, 0), (0, 0, 0), (2**127, 1, 2**127 - 1), (2**127, 2, 0), (2**200, 1, 0), (2**128, 1, 2**64), (R - 1, 1, 0), (2**253, 3, 5),
+       (P, P, 0), (R - 1, 2**128, 2**128 - 1), (2**64 - 1, 2**64 - 1, 2**65 - 2), (2**192, 1, 7)]
+RD_IN = [t for t in _RD if (t[0] * t[1] + t[2]) % R < 2**128]
+RD_OFF = [t for t in _RD if t not in RD_IN]
+assert (2**64, 2**64, 0) in RD_OFF and (2**64, 2**64 - 1, 2**64 - 1) in RD_IN and (P - 1, P - 1, P - 1) in MS_OFF and (MS_X - 1, P - 1, P - 1) in MS_IN and len(MS_OFF) >= 4 and len(RD_IN) >= 5
+
+
+def _put_rd(p, t):
+    for k in range(3):
+        _put_fr(p, 7 + 4 * k, t[k])
+
+
+def base_off_reduce(i):
+    p = _div_words(i) + list(pick(MS_IN, i, 4)) + [0] * 12
+    _put_rd(p, pick(RD_IN, i, 7))
+    return p
+
+
+OFF_REDUCE_KINDS = [(f"mul_sub-{t[0]:#x}-{t[1]:#x}-{t[2]:#x}", lambda p, t=t: p.__setitem__(slice(4, 7), list(t))) for t in MS_OFF]
+OFF_REDUCE_KINDS += [(f"reduce-{t[0]:#x}-{t[1]:#x}-{t[2]:#x}", lambda p, t=t: _put_rd(p, t)) for t in RD_OFF]
+
+
+# 9e. a wide select on n far entries, as 8., with the indicators proof words: at 64 entries refused without H2W_TRACE_SPLIT_SELECTS, replayed in parts
+# with it (tests/test_trace_split_selects.py).  words: 4 k .. entry k, 4 n + k: indicator k
+def prog_ind_words_select(n, scoped):
+    def prog(b):
+        arr = [b.hash_in(4 * k) for k in range(n)]
+        with (b.scope("sel") if scoped else contextlib.nullcontext()):
+            ind = [b.nat_in(4 * n + k) for k in range(n)]
+            r = b.select_array_by_indicator([[x] for x in arr], ind)
+            use = b.add(r[0], arr[0])
+        return [arr, ind, r, use]
+    return prog
+
+
 def _need(counts, E, ops=(), fetch=()):
     for name in ops:
         assert counts[E[name]] > 0, f"no {name} in the lowered program"
@@ -640,6 +892,12 @@ def _expect_gl(c, E): _need(c, E, ("DOP_LOADW", "DOP_LOADW_DIV", "DOP_LOADW_EXTI
 def _expect_native(c, E): _need(c, E, ("DOP_FRCELL", "DOP_GATE", "DOP_FR_ADD", "DOP_FR_MUL", "DOP_FR_MULADD", "DOP_SELECT", "DOP_FR_SELECT", "DOP_LIMBS2NUM", "DOP_DECOMP565", "DOP_CLT"))
 def _expect_lists(c, E): _need(c, E, ("DOP_IDX2IND", "DOP_SELIND", "DOP_NUM2BITS", "DOP_BITS2NUM", "DOP_RANGE"))
 def _expect_lists_wide(c, E): _expect_lists(c, E); _need(c, E, ("DOP_FR_SELIND",))
+
+
+def _expect_off_select(c, E): _need(c, E, ("DOP_SELECT", "DOP_FR_SELECT", "DOP_LOADW_DIV"))
+def _expect_off_bits(c, E): _need(c, E, ("DOP_BITS2NUM", "DOP_NUM2BITS", "DOP_RANGE", "DOP_CLT", "DOP_LOADW_DIV"))
+def _expect_off_selind(c, E): _need(c, E, ("DOP_SELIND", "DOP_FR_SELIND", "DOP_LOADW_DIV"))
+def _expect_off_reduce(c, E): _need(c, E, ("DOP_GATE", "DOP_FR_MULADD", "DOP_REDUCE", "DOP_LOADW_DIV"))
 
 
 def _expect_ring(dist):
@@ -688,7 +946,13 @@ def programs(empty_bits=True):
         ps.append(Program(f"scopes-{ninst}", prog_scopes(ninst), 12 + max(ninst, 2), make_scopes(ninst), 13, SCOPE_NAMES, sizes=(1, 70) if ninst == 1 else (1, 5), expect=_expect_scopes))
     for scoped in (True, False):
         ps.append(Program(f"far_operands-51-{'scoped' if scoped else 'flat'}", prog_far_operands(51, scoped), 205, make_far_operands(51), 21, ("sel",) if scoped else (), sizes=(1, 70), expect=_expect_far_operands(51, scoped)))
+    off = [("off_select", prog_off_select, 18, OFF_SELECT, 21, _expect_off_select, None), ("off_selind", prog_off_selind, 242, OffDomain(base_off_selind, OFF_SELIND_KINDS), 21, _expect_off_selind, None),
+           ("off_reduce", prog_off_reduce, 19, OffDomain(base_off_reduce, OFF_REDUCE_KINDS), 21, _expect_off_reduce, fix_a_off_reduce)]
+    off += [(f"off_bits-L{L}", prog_off_bits(L), 79, OffDomain(base_off_bits(L), OFF_BITS_KINDS), L, _expect_off_bits, None) for L in (21, 13, 8)]
+    for name, fn, nwords, od, L, expect, fix_a in off:
+        ps.append(Program(name, fn, nwords, od.make, L, expect=expect, off=od, fix_a=fix_a))
     return ps
 
 
 PROGRAMS = programs()
+OFF_PROGRAMS = [p for p in PROGRAMS if p.off]

@@ -4,7 +4,9 @@ operands (0, p - 1, 2^32 +- 1, quotient edges, r - 1, non-canonical words, wide 
 lowering: operands exactly 255 / 256 / 257 slots back, constants at the end of the LDS part of the pools, runs of 255 Goldilocks ops, 1 / 63 / 64 / 65
 instances of a parallel scope, several templates in one launch, imports into depth 2, an op with 255 fetched operand slots.  Per proof: the whole stream
 equals the oracle's bytes, the status word is the expected one, the cells at the program's handles hold the values of a plain integer model (to which
-the oracle's values are held too).  tests/test_replay_programs_lowering.py shows, without a GPU, that each program reaches what it was written for."""
+the oracle's values are held too).  The off_* programs leave the value domain proof A's eager calls validated - selectors, indicators and bits above 1,
+2^128 or more in front of a reduce: such a proof has status 5 and the oracle's cells in front of the offending op, its in-domain neighbours the whole
+stream; values beyond a range that do fit (num_to_bits, range_check) keep status 0.  tests/test_replay_programs_lowering.py shows, without a GPU, that each program reaches what it was written for."""
 import pytest
 
 import replay_prog as rp

@@ -16,7 +16,7 @@ import pytest
 
 import replay_prog as rp
 import verdict_ref as VR
-from test_trace_split_selects import SPLIT, SPLIT_PROGRAMS, VERIFIER_SCOPES, lower, plan_ex
+from test_trace_split_selects import IND_PROGRAM, SPLIT, SPLIT_PROGRAMS, VERIFIER_SCOPES, lower, plan_ex
 
 pytestmark = pytest.mark.gpu
 
@@ -65,17 +65,12 @@ def check_on_device(h2w, api, oracle, prog, proofs, flags=SPLIT):
     plan.close()
     for i, p in enumerate(proofs):
         want_vals, ib = rp.int_run(prog.fn, p)
-        assert status[i] == ib.status(), f"proof {i}: status {status[i]}, expected {ib.status()}"
         assert not ib.unspecified
-        stream, cells, vals = rp.oracle_run(oracle, prog.fn, p, prog.lookup_bits)
+        stream, cells, vals, entries = rp.oracle_run(oracle, prog.fn, p, prog.lookup_bits, entries=True)
         assert cells == lw.offsets and len(stream) == lw.num_cells * 32
         assert vals == want_vals, f"proof {i}: the oracle's values differ from the integer model"
-        want = np.frombuffer(stream, dtype=np.uint64).reshape(-1, 4)
-        if not np.array_equal(got[i], want):
-            bad = np.nonzero((got[i] != want).any(axis=1))[0]
-            raise AssertionError(f"proof {i} (selects entry {i}): {len(bad)} cells differ, first at {bad[:8]}: got {got[i][bad[0]]} want {want[bad[0]]}")
-        for k, (c, v) in enumerate(zip(lw.offsets, want_vals)):
-            assert [int(x) for x in got[i][c]] == rp.fr_words(v), f"proof {i}: handle {k} (cell {c}) is not the integer model's value {v:#x}"
+        rp.compare_on_device(i, got[i], status[i], ib.status(), ib, stream, entries, lw.offsets, want_vals)
+    return status
 
 
 @pytest.mark.parametrize("case", SPLIT_PROGRAMS, ids=lambda c: c[0].name)
@@ -83,6 +78,28 @@ def test_a_program_with_a_split_select_replays_to_the_oracles_stream(h2w, h2w_ap
     prog = case[0]
     for n in (1, 70):      # one proof; a batch with a partial second wavefront in which every entry (n <= 64) is selected once
         check_on_device(h2w, h2w_api, oracle, prog, make_batch(prog, n))
+
+
+def test_an_indicator_that_is_no_bit_in_any_part_of_a_split_select_is_status_5(h2w, h2w_api, oracle):
+    """The select on 64 wide entries with its indicators read from the proof (tests/test_trace_split_selects.py IND_PROGRAM: two parts - 64 entries
+    are never more).  Proof i with i % 4 != 0 has one entry set and one indicator of 2, 2^32 or p - 1, at position 0, 1, .. 63 in turn: in the first
+    part, on either side of the cut wherever the lowering makes it, in the last part.  Status 5, and the cells in front of the select - the loads of
+    the entries and of the indicators - are the oracle's.  Its neighbours (i % 4 == 0: one entry set, or three) have status 0 and the whole stream."""
+    prog = IND_PROGRAM; n = 64; proofs = []; positions = set()
+    for i in range(87):
+        p = [0] * prog.nwords
+        for k, v in enumerate(distinct_entries(i, n)):
+            rp._put_fr(p, 4 * k, v)
+        p[4 * n + (7 * i) % n] = 1
+        if i % 4 == 0 and i % 8:
+            p[4 * n + (7 * i + 20) % n] = p[4 * n + n - 1] = 1      # several entries set: the sum is the field's
+        if i % 4:
+            pos = (i - i // 4 - 1) % n; positions.add(pos)
+            p[4 * n + pos] = rp.OFF_POOL[i % 3]
+        proofs.append(p)
+    assert positions == set(range(n))
+    status = check_on_device(h2w, h2w_api, oracle, prog, proofs)
+    assert status == [5 if i % 4 else 0 for i in range(len(proofs))]
 
 
 # ---------------------------------------------------------------- the PoseidonBN254 verifier at cap_height 6

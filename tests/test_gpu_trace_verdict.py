@@ -333,6 +333,28 @@ def test_status_1_and_2_beside_a_failing_equality(h2w, h2w_api):
     assert got == [(0, 0, NO, 0), (0xA, 2, NO, 1), (0xC, 2, NO, 2), (0x6, 2, NO, 1), (0, 0, NO, 1)]
 
 
+def test_status_5_of_the_off_domain_select_batch_is_the_witness_calls(h2w, h2w_api):
+    """The batch of tests/replay_prog.py's off_select (selectors above 1 on either side of a zero divisor): the verdict call runs the same interpreter on
+    values only, and its status word is h2w_plan_status after a witness call on the same buffer - 0, 1 or 5 as the integer model says, per proof."""
+    prog = next(p for p in RP.PROGRAMS if p.name == "off_select")
+    proofs = prog.batch(130); n = len(proofs)
+    tb = VTrace(h2w, h2w_api, prog.proof_a(), prog.lookup_bits)
+    try:
+        prog.fn(tb)
+        plan = h2w_api.Plan.from_trace(tb.ctx, prog.nwords)
+    finally:
+        tb.ctx.close()
+    assert plan.trace_verdict_info()["available"] == 1
+    d = _upload(proofs); ws = _ws(plan, n)
+    got = plan.trace_verdict(d.data_ptr(), n, ws.data_ptr())
+    status, _ = _witness_status(plan, d, n)
+    plan.close()
+    want = [RP.int_run(prog.fn, p)[1].status() for p in proofs]
+    print(want, [g[3] for g in got], status)
+    assert set(want) == {0, 1, 5} and want == [prog.off.expected_status(i) for i in range(n)]
+    assert [g[3] for g in got] == want and status == want
+
+
 # ---------------------------------------------------------------- the call among others
 def test_the_call_among_witness_calls_on_one_workspace(h2w, h2w_api, oracle, consts):
     """verdict, sharded witness calls (world 2, both ranks), verdict again on one plan and one workspace: equal verdicts, shard streams byte-equal to

@@ -83,6 +83,62 @@ def test_the_status_cases_of_the_goldilocks_program_are_all_there():
     assert not any(p[8] == 0 and p[11] == 0 and p[12] == 0 for p in proofs)
 
 
+# ---- batches that leave proof A's value domain (status 5)
+def test_the_off_domain_programs_together_show_the_ops_that_can_raise_5(h2w, h2w_api, oracle):
+    total = [0] * (E["DOP_COUNT"] + E["RK_RING"] + 1)
+    for prog in rp.OFF_PROGRAMS:
+        total = [a + b for a, b in zip(total, _lowered_counts(h2w, h2w_api, oracle, prog)[0])]
+    ops = ("DOP_SELECT", "DOP_FR_SELECT", "DOP_SELIND", "DOP_FR_SELIND", "DOP_BITS2NUM", "DOP_NUM2BITS", "DOP_RANGE", "DOP_FR_MULADD", "DOP_REDUCE")
+    assert not [op for op in ops if total[E[op]] == 0]
+    assert {p.name for p in rp.OFF_PROGRAMS} == {"off_select", "off_selind", "off_reduce", "off_bits-L21", "off_bits-L13", "off_bits-L8"}
+
+
+@pytest.mark.parametrize("prog", rp.OFF_PROGRAMS, ids=lambda p: p.name)
+def test_an_off_domain_batch_holds_what_it_is_built_for(oracle, prog):
+    """Per proof of every batch the device test replays: the oracle (total on these inputs) and the integer model agree on every handle; the model's
+    status is the batch's stated one - 0 for the proofs in domain, 5 for one offence, 5 where the offence stands in front of a zero divisor, 1 where
+    the zero divisor stands in front; an off-domain proof has exactly one offending op, and the cells in front of it are fewer than the stream.  At
+    least a quarter of every batch is in domain, proof 0 is, and the batch of 130 holds every kind of offence."""
+    od = prog.off
+    assert prog.sizes == (1, 130) and len(od.kinds) == len({k[0] for k in od.kinds})
+    for n in prog.sizes:
+        proofs = prog.batch(n); in_domain = 0; kinds = set()
+        for i, p in enumerate(proofs):
+            assert len(p) == prog.nwords and all(0 <= w < 2**64 for w in p)
+            want_vals, ib = rp.int_run(prog.fn, p)
+            stream, cells, vals, entries = rp.oracle_run(oracle, prog.fn, p, prog.lookup_bits, entries=True)
+            assert vals == want_vals, (i, od.kind(i) and od.kind(i)[0], [k for k in range(len(vals)) if vals[k] != want_vals[k]][:8])
+            assert ib.status() == od.expected_status(i), (i, ib.status(), od.kind(i) and od.kind(i)[0])
+            held = rp.held_cells(ib, entries, len(stream) // 32)
+            if od.kind(i) is None:
+                assert ib.status() == 0 and ib.off is None and not ib.flagged and held == len(stream) // 32
+                in_domain += 1
+            else:
+                assert ib.n_off == 1 and 0 < held < len(stream) // 32, (i, od.kind(i)[0], ib.n_off)
+                kinds.add(od.kind(i)[0])
+        assert 4 * in_domain >= n and od.kind(0) is None
+        if n == 130:
+            assert kinds == {k[0] for k in od.kinds}
+            assert {od.expected_status(i) for i in range(n)} == {0, 1, 5} and any(i % 16 == 5 for i in range(n))
+
+
+def test_the_integer_model_states_the_cases_of_the_status_5_rule():
+    """select(5, 9, 2) = 1; bits_to_num([2^63, 2^63]) = 3 * 2^63; entries (5, 9) by indicators (2, p - 1); mul_sub(p - 1, p - 1, p - 1) = 2: the field's
+    values, each under status 5; the same ops on bits: status 0."""
+    P = rp.P
+    for run, want in ((lambda b: b.select(5, 9, 2), 1), (lambda b: b.bits_to_num([2**63, 2**63]), 0x18000000000000000),
+                      (lambda b: b.select_array_by_indicator([[5], [9]], [2, P - 1])[0], 0x8fffffff70000000a), (lambda b: b.gl_mul_sub(P - 1, P - 1, P - 1), 2),
+                      (lambda b: b.gl_reduce(2**128), 2**128 % P), (lambda b: b.select_array_by_indicator([[2**63], [2**63]], [1, 1])[0], 2**64)):
+        ib = rp.IntBackend([]); assert run(ib) == want and ib.status() == 5 and ib.off == 0
+    for run, want in ((lambda b: b.select(5, 9, 1), 5), (lambda b: b.select(5, 9, 0), 9), (lambda b: b.bits_to_num([1] * 64), 2**64 - 1), (lambda b: b.gl_reduce(2**128 - 1), (2**128 - 1) % P),
+                      (lambda b: b.select_array_by_indicator([[2**64], [2**253]], [1, 1])[0], 2**64 + 2**253), (lambda b: b.gl_mul_sub(P - 1, P - 1, 0), 1)):
+        ib = rp.IntBackend([]); assert run(ib) == want and ib.status() == 0 and ib.off is None
+    ib = rp.IntBackend([]); ib.gl_div(3, 0); ib.select(1, 2, 3)
+    assert ib.status() == 1 and ib.off == 0      # the first condition wins; the offending op is still remembered
+    ib = rp.IntBackend([2**64 - 1]); ib.nat_in(0); ib.select(1, 2, 3)
+    assert ib.status() == 5 and ib.flagged      # ... and 5 wins over 4
+
+
 # ---- what cannot be replayed
 def _refused(h2w, h2w_api, fn, nwords, match, scopes=()):
     proof = rp.safe_proof(nwords)

@@ -119,6 +119,21 @@ def test_a_refused_program_lowers_with_the_flag(h2w, h2w_api, oracle, case):
             assert local <= 2 * n and 4 * max(local - n, 0) + min(local, n) <= RING_K * parts, local
 
 
+# the same select with its indicators read from the proof (tests/test_gpu_replay_split_selects.py puts indicators that are no bits into every part)
+IND_PROGRAM = rp.Program("ind_words_select-64-scoped", rp.prog_ind_words_select(64, True), 5 * 64, None, 21, ("sel",))
+
+
+def test_a_select_by_indicators_from_the_proof_is_refused_without_the_flag_and_split_with_it(h2w, h2w_api, oracle):
+    prog = IND_PROGRAM
+    with pytest.raises(h2w.H2WError, match="more than the 256 value slots"):
+        lower(h2w, h2w_api, prog.fn, prog.proof_a(), 0, prog.lookup_bits, prog.scopes)
+    lw = lower(h2w, h2w_api, prog.fn, prog.proof_a(), SPLIT, prog.lookup_bits, prog.scopes)
+    stream, cells, _ = rp.oracle_run(oracle, prog.fn, prog.proof_a(), prog.lookup_bits)
+    parts = lw.plan.trace_op_counts()[E["DOP_FR_SELIND"]]; lw.plan.close()
+    assert lw.num_cells == len(stream) // 32 and lw.offsets == cells
+    assert parts >= 2, parts
+
+
 @pytest.mark.parametrize("n", [52, 64])
 def test_the_public_keyword_routes_the_flag(h2w, h2w_api, n):
     tb = rp.TraceBackend(h2w, h2w_api, rp.safe_proof(4 * n + 1), 21)
