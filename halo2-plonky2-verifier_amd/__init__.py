@@ -88,6 +88,9 @@ H2W_OP_GL_PERMUTE, H2W_OP_BN_PERMUTE, H2W_OP_HASH_NO_PAD, H2W_OP_TWO_TO_ONE, H2W
 H2W_CHIPBATCH_MAX_N_IN = 4096
 H2W_CHIPBATCH_OPT_CHUNK = 1
 H2W_CHIPBATCH_FORM_AUTO, H2W_CHIPBATCH_FORM_QUAD, H2W_CHIPBATCH_FORM_ROW = 0, 1, 2      # form of h2w_chipbatch_values
+# Merkle trees on the device (include/h2w.h 2e): the option of h2w_merkle_configure and its two named values
+H2W_MERKLE_OPT_CROWN_BITS = 1
+H2W_MERKLE_CROWN_NONE, H2W_MERKLE_CROWN_AUTO = 254, 255
 # flags of h2w_verdict_t (include/h2w.h 3b)
 (H2W_VERDICT_POW, H2W_VERDICT_MERKLE_TRACE, H2W_VERDICT_MERKLE_PERM_Z, H2W_VERDICT_MERKLE_QUOTIENT, H2W_VERDICT_MERKLE_STEP, H2W_VERDICT_FOLD,
  H2W_VERDICT_FINAL) = 1, 2, 4, 8, 16, 32, 64
@@ -207,6 +210,14 @@ SYMBOLS = {
     "h2w_chipbatch_configure": (C.c_int, [_vp, C.c_int, C.c_uint64]),
     "h2w_chipbatch_num_results": (C.c_uint64, [_vp]),
     "h2w_chipbatch_values": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, C.c_uint, _vp]),
+    "h2w_merkle_new": (_vp, [C.POINTER(PoseidonConsts), C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int]),
+    "h2w_merkle_free": (None, [_vp]),
+    "h2w_merkle_tree_words": (C.c_uint64, [_vp]),
+    "h2w_merkle_layout": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.c_size_t]),
+    "h2w_merkle_build": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, _vp]),
+    "h2w_merkle_open": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp]),
+    "h2w_merkle_configure": (C.c_int, [_vp, C.c_int, C.c_uint64]),
+    "h2w_merkle_crown_bits": (C.c_int, [_vp, C.c_uint64]),
     "h2w_comm_unique_id": (C.c_int, [_vp]),
     "h2w_comm_init": (_vp, [_vp, C.c_int, C.c_int, C.c_int]),
     "h2w_comm_free": (None, [_vp]),

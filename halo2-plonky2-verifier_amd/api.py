@@ -707,3 +707,65 @@ class ChipBatch:
         """h2w_chipbatch_values: the op's output wires (results_ptr: n x num_results u64, device; may be 0 for MERKLE_VERIFY) and one
         h2w_chipbatch_verdict_t {status, n_failed} per instance (verdict_ptr: n x 2 u32, device) - no advice stream.  form: H2W_CHIPBATCH_FORM_*."""
         _ck(self.L.h2w_chipbatch_values(self.p, operands_ptr, n, results_ptr, verdict_ptr, form, stream), "h2w_chipbatch_values")
+
+
+class MerkleTree:
+    """Merkle trees on the device (h2w_merkle_*, include/h2w.h 2e): plonky2's MerkleTree::new(leaves, cap_height) and tree.prove(i) in both hash
+    modes; an opening row is the operand row of a ChipBatch MERKLE_VERIFY handle with the same parameters."""
+
+    def __init__(self, consts, hash_mode=0, n_in=1, depth=1, cap_height=0, device_id=0):
+        self.L = lib()
+        self.p = self.L.h2w_merkle_new(C.byref(consts) if consts is not None else None, hash_mode, n_in, depth, cap_height, device_id)
+        if not self.p:
+            raise H2WError("h2w_merkle_new: " + last_error())
+        self.consts = consts
+        self.hash_mode, self.n_in, self.depth, self.cap_height = hash_mode, n_in, depth, cap_height
+
+    @classmethod
+    def new(cls, consts, hash_mode=0, n_in=1, depth=1, cap_height=0, device_id=0):
+        return cls(consts, hash_mode, n_in, depth, cap_height, device_id)
+
+    def close(self):
+        if getattr(self, "p", None):
+            self.L.h2w_merkle_free(self.p)
+            self.p = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def tree_words(self):
+        """u64 words of one tree's hash store: 4 (2^(depth+1) - 2^cap_height)."""
+        return int(self.L.h2w_merkle_tree_words(self.p))
+
+    def layout(self):
+        """{"level_offsets": word offset of levels 0 .. depth - cap_height, "cap_offset", "num_operands": words of an opening row}.  Needs no device."""
+        n = self.L.h2w_merkle_layout(self.p, None, 0)
+        if n < 0:
+            raise H2WError("h2w_merkle_layout: " + last_error())
+        out = (C.c_uint64 * n)()
+        if self.L.h2w_merkle_layout(self.p, out, n) != n:
+            raise H2WError("h2w_merkle_layout: " + last_error())
+        nl = int(out[0])
+        return {"level_offsets": [int(out[1 + i]) for i in range(nl)], "cap_offset": int(out[1 + nl]), "num_operands": int(out[2 + nl])}
+
+    def build(self, leaves_ptr, n_trees, trees_ptr, status_ptr, stream=0):
+        """h2w_merkle_build: leaves [n_trees][2^depth][n_in] u64 -> trees [n_trees][tree_words] u64, status [n_trees] u32 (0, or 4: a leaf word >= p)."""
+        _ck(self.L.h2w_merkle_build(self.p, leaves_ptr, n_trees, trees_ptr, status_ptr, stream), "h2w_merkle_build")
+
+    def open(self, leaves_ptr, trees_ptr, n_trees, queries_ptr, n, operands_ptr, status_ptr, stream=0):
+        """h2w_merkle_open: queries [n][2] u64 = {tree, leaf index} -> operands [n][num_operands] u64, status [n] u32 (0, or 4: an index out of range)."""
+        _ck(self.L.h2w_merkle_open(self.p, leaves_ptr, trees_ptr, n_trees, queries_ptr, n, operands_ptr, status_ptr, stream), "h2w_merkle_open")
+
+    def configure(self, option, value):
+        """h2w_merkle_configure (H2W_MERKLE_OPT_CROWN_BITS: 0 .. depth, H2W_MERKLE_CROWN_NONE or H2W_MERKLE_CROWN_AUTO)."""
+        _ck(self.L.h2w_merkle_configure(self.p, option, value), "h2w_merkle_configure")
+
+    def crown_bits(self, n_trees):
+        """What a build of n_trees trees runs with: 0 .. depth or H2W_MERKLE_CROWN_NONE.  Needs no device."""
+        r = self.L.h2w_merkle_crown_bits(self.p, n_trees)
+        if r < 0:
+            raise H2WError("h2w_merkle_crown_bits: " + last_error())
+        return int(r)

@@ -665,6 +665,55 @@ int            h2w_chipbatch_values(h2w_chipbatch *, const uint64_t *operands_de
                                     uint64_t *results_dev, h2w_chipbatch_verdict_t *verdict_dev,
                                     unsigned form, void *stream);
 
+/* ------------------------------------------------------------------ 2e. Merkle trees on the device: build, caps and openings
+ * The producer side of H2W_OP_MERKLE_VERIFY (csrc/merkletree.hip): plonky2's MerkleTree::new(leaves, cap_height) and tree.prove(i) in both hash
+ * modes, so that the reference's own chip test (merkle/mod.rs:137-230: build a tree, open a leaf, verify_proof_to_cap) runs on the device end to end.
+ *   leaf digest   hash_or_noop(leaf): hash_mode 0 copies up to four words (zero-padded) and hashes longer leaves with the Goldilocks sponge at rate 8;
+ *                 hash_mode 1 copies up to three words as the limbs of one Fr and hashes longer leaves nine words a PoseidonBN254 permutation
+ *                 (three Fr of three words each)
+ *   inner node    two_to_one(left, right); a hash is four words in both modes
+ *   levels        0 (the 2^depth leaf digests) .. depth - cap_height (the cap, 2^cap_height hashes); nothing above the cap is computed
+ *   hash store    one tree = tree_words = 4 (2^(depth+1) - 2^cap_height) u64 words, the levels from the leaves upward: level l starts at word
+ *                 4 (2^(depth+1) - 2^(depth-l+1)), node i of it at 4 i behind that; the cap is the last 4 2^cap_height words.  The layout is public:
+ *                 a caller reads caps and nodes out of trees_dev without a further call
+ *   opening row   leaf[n_in], leaf_index, cap[2^cap_height][4], siblings[depth - cap_height][4], sibling j = node (index >> j) ^ 1 of level j:
+ *                 the operand words of a MERKLE_VERIFY instance (2c), num_operands = h2w_chipbatch_num_operands of such a handle with the same
+ *                 parameters - the rows of h2w_merkle_open go into h2w_chipbatch_run / h2w_chipbatch_values as they are
+ * Limits: 1 <= n_in <= H2W_CHIPBATCH_MAX_N_IN, 1 <= depth <= 24 (the prover's LDE bound), cap_height <= min(depth, 6), hash_mode 0 or 1 - every tree
+ * that can be built can be verified by the chip.  h2w_merkle_new names the reason of a refusal before it looks for a device; without a device it
+ * returns a handle whose layout queries work and whose compute calls fail ("no HIP device").  The handle carries its device like every other.
+ * h2w_merkle_layout: out[0] = n_levels = depth - cap_height + 1, out[1 .. n_levels] = the word offset of levels 0 .. n_levels - 1, then the cap's
+ * word offset (the last level's), then num_operands of an opening row.  Returns the number of words (n_levels + 3); out == NULL: that number alone;
+ * n_out below it: -1.
+ * h2w_merkle_build: leaves_dev [n_trees][2^depth][n_in] canonical Goldilocks words -> trees_dev [n_trees][tree_words].  status_dev[t] = 0, or 4
+ * when a leaf word of tree t is >= p (that tree's hashes are then unspecified; no other tree changes).
+ * h2w_merkle_open: queries_dev [n][2] = {tree, leaf index} -> operands_dev [n][num_operands], from the leaves and the trees of a build.
+ * status_dev[i] = 0, or 4 when the tree index is >= n_trees or the leaf index >= 2^depth (that row is then unspecified: it is not written).
+ * Both calls are stream-ordered, synchronise nothing, allocate nothing on the device and touch nothing outside the caller's buffers.  n_trees == 0
+ * and n == 0: 0.  A call of more than 2^30 leaves in all, more than 65,535 trees or more than 2^26 queries: -1 ("batch too large").
+ * H2W_MERKLE_OPT_CROWN_BITS: the levels of at most 2^value nodes per tree (the crown; the leaf digests aside, which are always the leaf kernel's)
+ * are built by one wavefront per node - the wavefront-cooperative permutations of the values calls, four levels a launch, handed over inside a
+ * workgroup through LDS - instead of one lane per node and one launch per level.  value: 0 .. depth, H2W_MERKLE_CROWN_NONE (every level one lane per
+ * node) or H2W_MERKLE_CROWN_AUTO (the default): the largest value with n_trees x 2^value at most the crossover the library keeps per hash mode.
+ * The crossover: 16,384 nodes with hash_mode 0, 8,192 with hash_mode 1 - measured, a call alone on the chip: the build time falls with every level the
+ * crown takes up to these counts and rises beyond them, at depth 12, 16 and 20, leaves of 5 and 20 words, 1, 8 and 64 trees (tools/bench_merkle.py
+ * --crossover, profiles/merkle_tree_forms.jsonl).  A caller that keeps other launches in flight names its value itself.
+ * h2w_merkle_crown_bits reports what a build of n_trees trees runs with: 0 .. depth or H2W_MERKLE_CROWN_NONE; no device needed.  The words stored do
+ * not depend on the option. */
+typedef struct h2w_merkle h2w_merkle;
+#define H2W_MERKLE_OPT_CROWN_BITS 1
+#define H2W_MERKLE_CROWN_NONE 254
+#define H2W_MERKLE_CROWN_AUTO 255
+h2w_merkle *h2w_merkle_new(const h2w_poseidon_consts_t *, int hash_mode, uint32_t n_in, uint32_t depth, uint32_t cap_height, int device_id);
+void        h2w_merkle_free(h2w_merkle *);
+uint64_t    h2w_merkle_tree_words(const h2w_merkle *);      /* u64 words of one tree's hash store */
+int         h2w_merkle_layout(const h2w_merkle *, uint64_t *out, size_t n_out);
+int         h2w_merkle_build(h2w_merkle *, const uint64_t *leaves_dev, uint64_t n_trees, uint64_t *trees_dev, uint32_t *status_dev, void *stream);
+int         h2w_merkle_open(h2w_merkle *, const uint64_t *leaves_dev, const uint64_t *trees_dev, uint64_t n_trees,
+                            const uint64_t *queries_dev, uint64_t n, uint64_t *operands_dev, uint32_t *status_dev, void *stream);
+int         h2w_merkle_configure(h2w_merkle *, int option, uint64_t value);
+int         h2w_merkle_crown_bits(const h2w_merkle *, uint64_t n_trees);
+
 /* ------------------------------------------------------------------ the step BEFORE the path
  * Synthetic VALID FRI instances generated on the GPU (SURVEY 8(d) variant (A)): low-degree extension (Goldilocks NTT on the coset
  * 7<w>), Merkle commitments with the selected hash, the starky / plonky2 Fiat-Shamir transcript (stark/mod.rs:167-222 order, as

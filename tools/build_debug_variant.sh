@@ -12,7 +12,7 @@ units=${H2W_UNITS:-batch.hip glue.hip expand.hip}
 mkdir -p ../build_$name
 for f in $units; do hipcc $FLAGS -c $f -o ../build_$name/${f%.*}.o; done
 objs=""
-for u in expand eager plancompile batch advicetools glue chipbatch chiphash abi_backend prover comm replay traceplan bnemit_mont tracelower verdict traceverdict; do
+for u in expand eager plancompile batch advicetools glue chipbatch chiphash chipvalues abi_backend prover comm replay traceplan bnemit_mont tracelower verdict traceverdict merkletree; do
   case " $units " in *" $u.hip "*|*" $u.cpp "*) objs="$objs ../build_$name/$u.o";; *) objs="$objs ../build/$u.o";; esac
 done
 hipcc --offload-arch=gfx950 -shared -fPIC $objs -ldl -o ../libh2w_$name.so
