@@ -220,3 +220,88 @@ def test_batched_chip_ops_and_device_status_words(h2w, oracle, op, lookup_bits):
         ctx.close()
     assert any(st) == (op in ("div", "inv", "ext_inv", "ext_div"))
     L.h2w_chipbatch_free(h)
+
+
+def oracle_chip_instance(oracle, op, lookup_bits, w):
+    """One instance of a batched field op on the oracle: (its advice bytes, the status word the device must store for it)."""
+    OL = oracle.lib()
+    ctx = oracle.Ctx(lookup_bits)
+    av = [OL.orc_gl_load_witness(ctx.p, x) for x in w]
+    if op in ("add", "sub", "mul", "div"):
+        getattr(OL, "orc_gl_" + op)(ctx.p, av[0], av[1])
+    elif op == "mul_add":
+        OL.orc_gl_mul_add(ctx.p, av[0], av[1], av[2])
+    elif op == "inv":
+        OL.orc_gl_inv(ctx.p, av[0])
+    else:
+        a = (oracle.AV * 2)(av[0], av[1]); out = (oracle.AV * 2)()
+        if op == "ext_inv":
+            OL.orc_ext_inv(ctx.p, a, out)
+        else:
+            b = (oracle.AV * 2)(av[2], av[3])
+            (OL.orc_ext_mul if op == "ext_mul" else OL.orc_ext_div)(ctx.p, a, b, out)
+    zero_gl = (op == "div" and w[1] == 0) or (op == "inv" and w[0] == 0)
+    zero_ext = (op == "ext_inv" and w[0] == 0 and w[1] == 0) or (op == "ext_div" and w[2] == 0 and w[3] == 0)
+    assert bool(ctx.error()) == (zero_gl or zero_ext), (op, w, ctx.error())
+    cells = ctx.advice_bytes(); ctx.close()
+    return cells, 1 if zero_gl else 2 if zero_ext else 0
+
+
+CHUNK = 32768      # csrc/chipbatch.hip: instances per internal launch of a handle of h2w_chipbatch_new
+N_ROWS = 67        # distinct operand rows, cycled: coprime to 64 (a wavefront) and to the chunk, so every row meets every lane and both chunks
+
+
+@pytest.mark.parametrize("op", ["mul_add", "ext_div"])
+def test_batched_chip_ops_across_the_chunk_boundary(h2w, oracle, op):
+    """n = 32768 + 65: h2w_chipbatch_run splits at 32768 instances, and the second launch - its operand, advice and status offsets, the record workspace
+    it takes over from the first - runs 65 instances (a second wavefront with one live lane).  67 distinct rows, cycled, the all-zero row among them
+    (EXT_DIV: status 2); the oracle runs once per row; every instance's cells and status word are compared with its row's block.  One spare instance
+    behind the advice and behind the status buffer keeps its sentinel.  Then the same call behind a delayed producer on a side stream
+    (tests/stream_order.py): the whole chunk loop runs in its place on the caller's stream."""
+    import numpy as np
+    import torch
+    import stream_order as SO
+    L = h2w.lib()
+    lookup_bits, n = 13, CHUNK + 65
+    h = L.h2w_chipbatch_new(OPS[op], lookup_bits, 0)
+    assert h, h2w.last_error()
+    nw, nc = int(L.h2w_chipbatch_num_operands(h)), int(L.h2w_chipbatch_num_cells(h))
+    rnd = random.Random(67 + sum(map(ord, op)))
+    rows = [[rnd.randrange(P) for _ in range(nw)] for _ in range(N_ROWS)]
+    rows[0] = [0] * nw; rows[1] = [P - 1] * nw; rows[2] = [1] * nw
+    if op == "ext_div":
+        rows[3] = [rnd.randrange(1, P) for _ in range(nw // 2)] + [0] * (nw // 2)
+    assert len(set(map(tuple, rows))) == N_ROWS
+    ref = [oracle_chip_instance(oracle, op, lookup_bits, w) for w in rows]      # the reference: once per distinct row, shared by both runs
+    blocks = np.stack([np.frombuffer(c, dtype=np.uint8) for c, _ in ref]); stat = np.array([s for _, s in ref], dtype=np.uint32)
+    assert blocks.shape == (N_ROWS, nc * 32) and len({c for c, _ in ref}) == N_ROWS
+    assert (stat != 0).any() == (op == "ext_div") and stat[0] == (2 if op == "ext_div" else 0)
+    words = np.array(rows, dtype=np.uint64)
+
+    def staged(shift):      # instance i runs row (i + shift) % 67
+        return torch.from_numpy(words[(np.arange(n) + shift) % N_ROWS].view(np.int64).reshape(-1).copy()).cuda()
+
+    def hold(adv, st, shift, what):
+        adv = adv.reshape(n + 1, nc * 32); st = st.view(np.uint32)
+        assert (adv[n] == SO.SENTINEL).all(), what + ": the spare instance behind the advice buffer was written"
+        assert st[n] == 0xA5A5A5A5, what + ": the spare word behind the status buffer was written"
+        want_st = stat[(np.arange(n) + shift) % N_ROWS]
+        bad = np.nonzero(st[:n] != want_st)[0]
+        assert bad.size == 0, (what, "status words differ", bad.size, "first at", int(bad[0]), int(st[bad[0]]), int(want_st[bad[0]]))
+        for r in range(N_ROWS):      # the instances that ran row r: first at (r - shift) % 67, then every 67th
+            first = (r - shift) % N_ROWS
+            wrong = np.nonzero((adv[first:n:N_ROWS] != blocks[r]).any(axis=1))[0]
+            assert wrong.size == 0, (what, "row", r, "instances with other cells", wrong.size, "first", first + N_ROWS * int(wrong[0]))
+
+    d_ops, d_a, d_b = staged(0), staged(0), staged(1)
+    advice = torch.full(((n + 1) * nc * 32,), SO.SENTINEL, dtype=torch.uint8, device="cuda")
+    status = torch.full((n + 1,), 0, dtype=torch.int32, device="cuda"); SO.as_bytes(status).fill_(SO.SENTINEL)
+    call = lambda s: L.h2w_chipbatch_run(h, d_ops.data_ptr(), n, advice.data_ptr(), status.data_ptr(), s) == 0 or pytest.fail(h2w.last_error())
+    idle_s = SO.timed_warm_up(call)      # the plain call on the null stream (and the first stream-ordered allocation of this size)
+    hold(advice.cpu().numpy(), status.cpu().numpy(), 0, "null stream")
+    info = {}
+    (adv, st), blocked = SO.run_ordered(call, [(d_ops, d_a, d_b)], [advice, status], delay_ms=SO.delay_for(idle_s), info=info)
+    print(f"{op}: n = {n}, {nc} cells an instance; idle call {idle_s * 1e3:.2f} ms, enqueue {info['enqueue_s'] * 1e3:.2f} ms, delay {info['delay_ms']:.1f} ms, blocked {blocked}")
+    SO.assert_delay_covers(info, idle_s, "h2w_chipbatch_run")
+    hold(adv, st, 0, "behind the delayed producer")      # (with the operands of B, every instance would hold its neighbour row's block: all distinct)
+    L.h2w_chipbatch_free(h)
