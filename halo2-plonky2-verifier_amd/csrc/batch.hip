@@ -13,8 +13,8 @@
 // Data layout in HBM (per batch): proofs [n][proof_words] u64 ; records [n][n_records] 32 B ; challenge blocks [n] ; unit states
 // [n][units][4] 32 B ; permutation list [n][perms][13] u64 ; advice [n][n_cells] 32 B canonical-LE Fr.  Record metas / templates /
 // Poseidon constants are per-shape and shared.
-// Here: the kernels of a call (k_prologue_load, k_glp_emit, k_sbox_canon*, k_merkle_bn_fused, k_direct_to_montgomery, k_columns_fixup), ws_layout and
-// run_batch, the h2w_fri_witness_batch* entry points and the shard queries, h2w_fri_expand_records, h2w_plan_status, the timing calls, h2w_plan_configure.
+// Here: the kernels of a call (k_prologue_load, k_glp_emit, k_sbox_canon*, k_merkle_bn_fused, k_direct_to_montgomery, k_columns_fixup), ws_layout, WitnessCall
+// (a call's phases) and run_batch, the h2w_fri_witness_batch* entry points and the shard queries, h2w_fri_expand_records, h2w_plan_status, the timing calls, h2w_plan_configure.
 #include <hip/hip_runtime.h>
 #include <vector>
 #include <string>
@@ -178,6 +178,8 @@ extern "C" __global__ void k_columns_fixup(ulonglong2 *cols, const uint64_t *len
 }
 
 namespace h2w {
+static bool bad_shard(int rank, int world) { return world < 1 || rank < 0 || rank >= world; }
+static ShardSpec shard_spec(int rank, int world, int compact = 0) { ShardSpec sh; sh.rank = rank; sh.world = world; sh.compact = compact; return sh; }
 static uint64_t own_count(uint64_t total, int rank, int world) { return total > (uint64_t)rank ? (total - (uint64_t)rank + (uint64_t)world - 1) / (uint64_t)world : 0; }
 static uint32_t unit_slot_of(const h2w_plan *p) { return (uint32_t)(p->st.q_nunit[0] > p->st.q_nunit[1] ? p->st.q_nunit[0] : p->st.q_nunit[1]); }
 static uint64_t shard_q_slot(const h2w_plan *p) { return p->st.q_ncell[0] > p->st.q_ncell[1] ? p->st.q_ncell[0] : p->st.q_ncell[1]; }      // a query block's slot in the packed layout (ShardMap)
@@ -230,6 +232,152 @@ int launch_plan_direct(const h2w_plan *p, const uint64_t *bits, uint64_t n_proof
     launch_cols(cm.starts != nullptr, k_direct_to_montgomery<true>, k_direct_to_montgomery<false>, dim3((unsigned)((nwaves + 3) / 4), (unsigned)n_proofs), dim3(256), 0, stream, D);
     return 0;
 }
+// A workspace as typed pointers, by ws_layout's offsets
+struct WsPtrs {
+    rec_t *recs; DevCB *cbs; uint32_t *status, *load_flag, *ctr; fr_t *unit_state, *unit_sbox; uint32_t *unit_sbox9; uint64_t *glp_list;
+    void fill(BatchArgs &A) const { A.recs = recs; A.cbs = cbs; A.status = status; A.load_flag = load_flag; A.unit_state = unit_state; A.unit_sbox = unit_sbox; A.unit_sbox9 = unit_sbox9; A.glp_list = glp_list; }
+};
+static WsPtrs ws_ptrs(void *workspace_dev, const WsLayout &wl) {
+    char *ws = (char *)workspace_dev;
+    return {(rec_t *)(ws + wl.recs), (DevCB *)(ws + wl.cbs), (uint32_t *)(ws + wl.status), (uint32_t *)(ws + wl.lflag), (uint32_t *)(ws + wl.ctr),
+            (fr_t *)(ws + wl.units), (fr_t *)(ws + wl.sbox), (uint32_t *)(ws + wl.sbox9), (uint64_t *)(ws + wl.glp)};
+}
+// One witness call of a compiled plan (run_batch): what outlives a phase, and one method per phase, cut at the public event marks (include/h2w.h H2W_EV_*)
+// and called in this order.  Every method enqueues and returns 0, or -1 with the reason in the last error; a call that leaves early waits for its side
+// stream (plan.h SideFork).
+struct WitnessCall {
+    h2w_plan *const p; const uint64_t n_proofs; BatchArgs A; const WsLayout wl; const WsPtrs wp;
+    const hipStream_t stream, estream, cstream;      // the caller's, the expansion kernel's, the chain kernels' (either may be the caller's)
+    const DevEvent *const prev_ev, *const ev;        // the event rows of the previous call (null: none) and of this one
+    const ColMap cm; const uint64_t cell_stride; const ShardSpec sh;
+    unsigned nunits, nkinds, n_pro_perms, n_mk_perms;
+    SideFork fork; int side_end = H2W_EV_CHAINS_END;      // side_end: the event that closes the work on the side stream, named by the method that opened the fork
+
+    WitnessCall(h2w_plan *p_, const uint64_t *proofs_dev, uint64_t n, void *advice_dev, void *workspace_dev, hipStream_t s, hipStream_t es, hipStream_t cs, ColMap cm_, uint64_t cell_stride_, const ShardSpec &sh_)
+        : p(p_), n_proofs(n), A(plan_batch_args(p_, proofs_dev, n)), wl(ws_layout(p_, n, sh_)), wp(ws_ptrs(workspace_dev, wl)), stream(s), estream(es), cstream(cs),
+          prev_ev((p_->n_batches && p_->ev_recorded) ? p_->evr[(p_->n_batches - 1) % h2w_plan::EV_RING] : nullptr), ev(p_->evr[p_->n_batches % h2w_plan::EV_RING]),
+          cm(cm_), cell_stride(cell_stride_), sh(sh_), fork(s, cs) {
+        wp.fill(A); A.rec_stride = p->nrec; A.out = (fr_t *)advice_dev; A.cell_stride = cell_stride; A.cm = cm;
+        A.sh.rank = sh.rank; A.sh.world = sh.world; A.sh.compact = sh.compact; A.sh.q_slot = shard_q_slot(p); A.sh.unit_slot = unit_slot_of(p);
+        A.sh.n_own_units = (uint32_t)own_count(n_proofs * (uint64_t)p->shape.num_queries, sh.rank, sh.world);
+        A.sh.n_own_proofs = (uint32_t)own_count(n_proofs, sh.rank, sh.world);
+        nunits = A.sh.n_own_units; nkinds = (unsigned)(p->d.n_oracles + p->d.n_steps);
+        n_pro_perms = A.sh.n_own_proofs * p->st.pro_nglp; n_mk_perms = nunits * p->st.q_nglp;
+    }
+    // ---- H2W_EV_CALL_START .. H2W_EV_PROLOGUE_END
+    int prologue() {
+        H2W_HIP(hipEventRecord(ev[H2W_EV_CALL_START], stream));
+        // prologue strands, values: one wavefront per proof (witness load, Fiat-Shamir sponge, PoW, reduced openings) -> challenge blocks.  FIRST: everything
+        // else of the launch waits for the challenges, nothing for the load cells
+        launch_prologue_values(A, stream);
+        H2W_HIP(hipEventRecord(ev[h2w_plan::EV_PROLOGUE_VALUES_END], stream));
+        // witness load + cap-hash limb decompositions: one lane per (proof, item).  Cells and a flag word only (nobody's input): behind the prologue, beside the
+        // Merkle chains that fork off at this point
+        H2W_HIP(hipMemsetAsync(A.load_flag, 0, n_proofs * sizeof(uint32_t), stream));
+        if (p->n_items + p->n_cap_items) {
+            const dim3 lgrid((p->n_items + p->n_cap_items + 255) / 256, (unsigned)n_proofs);
+            launch_cols(cm.starts != nullptr, k_prologue_load<true>, k_prologue_load<false>, lgrid, dim3(256), 0, stream, A);
+        }
+        if (p->shape.hash_mode == 1) { if (glp_emit(n_pro_perms) != 0) return -1; }
+        H2W_HIP(hipEventRecord(ev[H2W_EV_PROLOGUE_END], stream));
+        return 0;
+    }
+    // the records of n listed Goldilocks-Poseidon permutations, once per call: with PoseidonBN254 caps the prologues' (prologue); with Goldilocks caps
+    // together with the Merkle strands' (glue).  (Defined behind prologue: the kernel templates appear in the device code in the order of their first use.)
+    int glp_emit(unsigned n) {
+        H2W_HIP(hipEventRecord(ev[h2w_plan::EV_GLP_START], stream));
+        if (n) launch_cols(cm.starts != nullptr, k_glp_emit<true>, k_glp_emit<false>, dim3(n), dim3(64), 0, stream, A);
+        H2W_HIP(hipEventRecord(ev[h2w_plan::EV_GLP_END], stream));
+        return 0;
+    }
+    // ---- PoseidonBN254 Merkle chains (hash_mode 1), the fork .. H2W_EV_CHAINS_END: values, then one quad per permutation unit.  They write their cells
+    // themselves and no block records, so nothing but the challenge blocks orders them against the other kernels of the batch: they run on a side
+    // stream of the plan and rejoin at the end of the call.
+    int bn_chains() {
+        if (p->shape.hash_mode != 1) return 0;
+        if (fork.fork_at(ev[h2w_plan::EV_PROLOGUE_VALUES_END]) != 0) return -1;
+        side_end = H2W_EV_CHAINS_END;
+        H2W_HIP(hipEventRecord(ev[H2W_EV_CHAINS_START], cstream));
+        const dim3 sgrid((nunits * 4 + QUAD_BLOCK - 1) / QUAD_BLOCK, nkinds);
+        // one pass or two (include/h2w.h H2W_OPT_CHAIN_PASSES): a launch whose paths do not fill the chip is bound by the depth of a path - split it
+        const int passes = p->chain_passes ? p->chain_passes : (nunits <= 512 ? 2 : 1);
+        p->passes_of[p->n_batches % h2w_plan::EV_RING] = passes;
+        if (nunits && passes == 1) launch_cols(cm.starts != nullptr, k_merkle_bn_fused<true>, k_merkle_bn_fused<false>, sgrid, dim3(QUAD_BLOCK), 0, cstream, A);
+        if (nunits && passes != 1) {
+            // the values of the paths: one wavefront per path (rowperm.h: a path's 18 permutations in 1.3 ms instead of 2.6) for a launch of a few proofs - the form for
+            // one proof's latency; four lanes per path (bnquad.h bn_values: a sixth of the instructions per path) beyond that: alone on the chip the wavefront form
+            // wins up to ~2,500 paths (profiles/r04_values_forms.jsonl), but a caller with several launches in flight pays for its instructions (cfg 1 pipelined,
+            // 1,024 paths per launch: 160 G cells/s against 175-190), so the default switches early and H2W_OPT_VALUES_FORM = 2 is the caller's to set
+            const bool rows = p->values_form ? p->values_form == 2 : (uint64_t)nunits * nkinds <= 784;
+            const uint32_t upq = unit_slot_of(p);
+            const uint64_t nval = (uint64_t)nunits * upq * (BN_PARTIAL_ROUNDS * 3);
+            if (rows) {
+                launch_merkle_bn_values_row(A, nkinds, cstream);
+                if (nval) hipLaunchKernelGGL(k_sbox_canon9, dim3((unsigned)((nval + 255) / 256)), dim3(256), 0, cstream, A, upq);
+            } else {
+                launch_merkle_bn_values(A, sgrid, cstream);
+                if (nval) hipLaunchKernelGGL(k_sbox_canon, dim3((unsigned)((nval + 255) / 256)), dim3(256), 0, cstream, A, upq);
+            }
+        }
+        H2W_HIP(hipEventRecord(ev[h2w_plan::EV_CHAIN_VALUES_END], cstream));
+        const unsigned long long items = passes == 1 ? 0ull : (unsigned long long)((nunits + 15u) & ~15u) * p->st.mk_item0[MK_KINDS];
+        if (items) launch_merkle_bn_emit(A, dim3((unsigned)((items * 4 + QUAD_BLOCK - 1) / QUAD_BLOCK)), cstream);
+        H2W_HIP(hipEventRecord(ev[H2W_EV_CHAINS_END], cstream));
+        return 0;
+    }
+    // ---- H2W_EV_GLUE_START .. H2W_EV_GLUE_END: query glue strands (FriChip::verify_query_round minus its Merkle proofs), one lane per owned (proof, query);
+    // Goldilocks-Poseidon Merkle strands (hash_mode 0), values: one cooperating wavefront per (proof, query, tree).  The two read the challenge blocks and
+    // write disjoint records (and list entries): with Goldilocks caps the Merkle strands run on the plan's side stream beside the glue strands and rejoin
+    // before the permutations' records are emitted.
+    int glue() {
+        H2W_HIP(hipEventRecord(ev[H2W_EV_GLUE_START], stream));
+        if (p->shape.hash_mode == 0) {
+            if (fork.fork_at(ev[h2w_plan::EV_PROLOGUE_VALUES_END]) != 0) return -1;
+            side_end = H2W_EV_CHAINS_END;
+            H2W_HIP(hipEventRecord(ev[H2W_EV_CHAINS_START], cstream));
+            if (nunits) launch_merkle_gl_values(A, nunits, nkinds, cstream);
+            H2W_HIP(hipEventRecord(ev[h2w_plan::EV_CHAIN_VALUES_END], cstream)); H2W_HIP(hipEventRecord(ev[H2W_EV_CHAINS_END], cstream));
+        }
+        if (nunits) launch_glue_strands(A, stream);
+        if (p->shape.hash_mode == 0) {
+            if (fork.join_at(ev[H2W_EV_CHAINS_END]) != 0) return -1;
+            if (glp_emit(n_pro_perms + n_mk_perms) != 0) return -1;
+        }
+        H2W_HIP(hipEventRecord(ev[H2W_EV_GLUE_END], stream));
+        return 0;
+    }
+    // ---- H2W_EV_EXPAND_START .. H2W_EV_EXPAND_END: expansion of the block records (HBM-write-bound)
+    int expand() {
+        if (estream != stream) H2W_HIP(hipStreamWaitEvent(estream, ev[H2W_EV_GLUE_END], 0));    // value strands done -> expansion on the emit stream
+        // One expansion kernel at a time over all the streams a plan is driven on: its blocks are persistent and hold their CUs until the
+        // launch is written, so two of them side by side keep the latency-bound strands of the other launches in flight off the chip
+        // (measured: +8..12 % for the whole job with PoseidonBN254 caps, profiles/r02_sweep5.txt; +5 % with Goldilocks caps since that kernel
+        // runs on a grid of resident blocks there and reaches its rate alone, profiles/r02_expand_grid.txt).
+        if (p->serial_expand != 0 && prev_ev) H2W_HIP(hipStreamWaitEvent(estream, prev_ev[H2W_EV_EXPAND_END], 0));
+        H2W_HIP(hipEventRecord(ev[H2W_EV_EXPAND_START], estream));
+        if (launch_plan_expand(p, n_proofs, A.recs, wp.ctr, A.out, cell_stride, cm, &sh, plan_roam_per_cu(p), estream) != 0) return -1;
+        H2W_HIP(hipEventRecord(ev[H2W_EV_EXPAND_END], estream));
+        return 0;
+    }
+    // ---- Montgomery form: the direct cells, behind the chain kernels on the stream they ran on, beside the expansion kernel (which converts its own cells
+    // as it writes them).  The glue strands' and the prologue's direct cells were written on the caller's stream: the side stream waits for them.
+    int direct_cells() {
+        if (p->output_form != H2W_FORM_MONTGOMERY) return 0;
+        if (fork.fork_at(ev[H2W_EV_GLUE_END]) != 0) return -1;
+        side_end = h2w_plan::EV_DIRECT_END;
+        if (launch_plan_direct(p, p->d_direct_bits.get(), n_proofs, A.out, A.cell_stride, A.cm, sh, cstream) != 0) return -1;
+        if (cstream != stream) H2W_HIP(hipEventRecord(ev[h2w_plan::EV_DIRECT_END], cstream));
+        return 0;
+    }
+    // ---- .. H2W_EV_CALL_END: the caller's stream completes when the advice is complete
+    int finish() {
+        if (estream != stream) H2W_HIP(hipStreamWaitEvent(stream, ev[H2W_EV_EXPAND_END], 0));
+        if (fork.join_at(ev[side_end]) != 0) return -1;
+        H2W_HIP(hipEventRecord(ev[H2W_EV_CALL_END], stream));
+        H2W_HIP(hipGetLastError());
+        return 0;
+    }
+};
 static int run_batch(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void *advice_dev, void *workspace_dev, void *stream_, void *emit_stream_, ColMap cm, uint64_t cell_stride, const ShardSpec &sh) {
     if (!p) { set_error("h2w_fri_witness_batch: null plan"); return -1; }
     if (p->device < 0) { set_error("h2w_fri_witness_batch: no HIP device — the hot path only runs on the GPU (no CPU fallback)"); return -1; }
@@ -242,133 +390,15 @@ static int run_batch(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs,
     if (n_proofs * (uint64_t)p->shape.num_queries * (p->st.mk_item0[MK_KINDS] ? p->st.mk_item0[MK_KINDS] : 1) > 0x3fffffffull) { set_error("h2w_fri_witness_batch: batch too large"); return -1; }
     if (n_proofs > 65535) { set_error("h2w_fri_witness_batch: more than 65535 proofs per call (the proof index is a grid dimension of the load and expansion kernels); split the batch"); return -1; }
     DeviceGuard dg(p->device);
-    hipStream_t stream = (hipStream_t)stream_, estream = (hipStream_t)emit_stream_;
-    const WsLayout wl = ws_layout(p, n_proofs, sh);
-    char *ws = (char *)workspace_dev;
-    BatchArgs A = plan_batch_args(p, proofs_dev, n_proofs);
-    A.recs = (rec_t *)(ws + wl.recs); A.rec_stride = p->nrec; A.out = (fr_t *)advice_dev; A.cell_stride = cell_stride; A.cm = cm;
-    A.cbs = (DevCB *)(ws + wl.cbs); A.status = (uint32_t *)(ws + wl.status); A.load_flag = (uint32_t *)(ws + wl.lflag);
-    A.unit_state = (fr_t *)(ws + wl.units); A.unit_sbox = (fr_t *)(ws + wl.sbox); A.unit_sbox9 = (uint32_t *)(ws + wl.sbox9); A.glp_list = (uint64_t *)(ws + wl.glp);
-    A.sh.rank = sh.rank; A.sh.world = sh.world; A.sh.compact = sh.compact; A.sh.q_slot = shard_q_slot(p); A.sh.unit_slot = unit_slot_of(p);
-    A.sh.n_own_units = (uint32_t)own_count(n_proofs * (uint64_t)p->shape.num_queries, sh.rank, sh.world);
-    A.sh.n_own_proofs = (uint32_t)own_count(n_proofs, sh.rank, sh.world);
-    hipStream_t cstream = stream;      // chain kernels' stream
-    if (p->fork_chains) {
-        const int k = plan_side_slot(p, stream);
-        if (k == -2) return -1;
-        if (k >= 0) cstream = p->side[k];      // (more caller streams than side streams: the extra ones do not fork)
-    }
-    const DevEvent *prev_ev = (p->n_batches && p->ev_recorded) ? p->evr[(p->n_batches - 1) % h2w_plan::EV_RING] : nullptr;
-    const DevEvent *ev = p->evr[p->n_batches % h2w_plan::EV_RING];
-    const unsigned nunits = A.sh.n_own_units;
-    const unsigned nkinds = (unsigned)(p->d.n_oracles + p->d.n_steps);
-    bool forked = false;
-    auto body = [&]() -> int {
-        H2W_HIP(hipEventRecord(ev[H2W_EV_CALL_START], stream));
-        // 1. prologue strands, values: one wavefront per proof (witness load, Fiat-Shamir sponge, PoW, reduced openings) -> challenge blocks.  FIRST: everything
-        //    else of the launch waits for the challenges, nothing for the load cells
-        launch_prologue_values(A, stream);
-        H2W_HIP(hipEventRecord(ev[h2w_plan::EV_PROLOGUE_VALUES_END], stream));
-        // 0. witness load + cap-hash limb decompositions: one lane per (proof, item).  Cells and a flag word only (nobody's input): behind the prologue, beside the
-        //    Merkle chains that fork off at this point
-        H2W_HIP(hipMemsetAsync(A.load_flag, 0, n_proofs * sizeof(uint32_t), stream));
-        if (p->n_items + p->n_cap_items) {
-            const dim3 lgrid((p->n_items + p->n_cap_items + 255) / 256, (unsigned)n_proofs);
-            launch_cols(cm.starts != nullptr, k_prologue_load<true>, k_prologue_load<false>, lgrid, dim3(256), 0, stream, A);
-        }
-        // 2. the records of the listed Goldilocks-Poseidon permutations: with PoseidonBN254 caps the prologues' (now); with Goldilocks caps
-        //    together with the Merkle strands' (below)
-        const unsigned n_pro_perms = A.sh.n_own_proofs * p->st.pro_nglp, n_mk_perms = nunits * p->st.q_nglp;
-        auto glp_emit = [&](unsigned n) -> int {
-            H2W_HIP(hipEventRecord(ev[h2w_plan::EV_GLP_START], stream));
-            if (n) launch_cols(cm.starts != nullptr, k_glp_emit<true>, k_glp_emit<false>, dim3(n), dim3(64), 0, stream, A);
-            H2W_HIP(hipEventRecord(ev[h2w_plan::EV_GLP_END], stream));
-            return 0;
-        };
-        if (p->shape.hash_mode == 1) { if (glp_emit(n_pro_perms) != 0) return -1; }
-        H2W_HIP(hipEventRecord(ev[H2W_EV_PROLOGUE_END], stream));
-        // 3. PoseidonBN254 Merkle chains (hash_mode 1): values, then one quad per permutation unit.  They write their cells themselves and no
-        //    block records, so nothing but the challenge blocks orders them against the other kernels of the batch: they run on a side
-        //    stream of the plan and rejoin at the end of the call.
-        if (p->shape.hash_mode == 1) {
-            if (cstream != stream) { H2W_HIP(hipStreamWaitEvent(cstream, ev[h2w_plan::EV_PROLOGUE_VALUES_END], 0)); forked = true; }
-            H2W_HIP(hipEventRecord(ev[H2W_EV_CHAINS_START], cstream));
-            const dim3 sgrid((nunits * 4 + QUAD_BLOCK - 1) / QUAD_BLOCK, nkinds);
-            // one pass or two (include/h2w.h H2W_OPT_CHAIN_PASSES): a launch whose paths do not fill the chip is bound by the depth of a path - split it
-            const int passes = p->chain_passes ? p->chain_passes : (nunits <= 512 ? 2 : 1);
-            p->passes_of[p->n_batches % h2w_plan::EV_RING] = passes;
-            if (nunits && passes == 1) launch_cols(cm.starts != nullptr, k_merkle_bn_fused<true>, k_merkle_bn_fused<false>, sgrid, dim3(QUAD_BLOCK), 0, cstream, A);
-            if (nunits && passes != 1) {
-                // the values of the paths: one wavefront per path (rowperm.h: a path's 18 permutations in 1.3 ms instead of 2.6) for a launch of a few proofs - the form for
-                // one proof's latency; four lanes per path (bnquad.h bn_values: a sixth of the instructions per path) beyond that: alone on the chip the wavefront form
-                // wins up to ~2,500 paths (profiles/r04_values_forms.jsonl), but a caller with several launches in flight pays for its instructions (cfg 1 pipelined,
-                // 1,024 paths per launch: 160 G cells/s against 175-190), so the default switches early and H2W_OPT_VALUES_FORM = 2 is the caller's to set
-                const bool rows = p->values_form ? p->values_form == 2 : (uint64_t)nunits * nkinds <= 784;
-                const uint32_t upq = unit_slot_of(p);
-                const uint64_t nval = (uint64_t)nunits * upq * (BN_PARTIAL_ROUNDS * 3);
-                if (rows) {
-                    launch_merkle_bn_values_row(A, nkinds, cstream);
-                    if (nval) hipLaunchKernelGGL(k_sbox_canon9, dim3((unsigned)((nval + 255) / 256)), dim3(256), 0, cstream, A, upq);
-                } else {
-                    launch_merkle_bn_values(A, sgrid, cstream);
-                    if (nval) hipLaunchKernelGGL(k_sbox_canon, dim3((unsigned)((nval + 255) / 256)), dim3(256), 0, cstream, A, upq);
-                }
-            }
-            H2W_HIP(hipEventRecord(ev[h2w_plan::EV_CHAIN_VALUES_END], cstream));
-            const unsigned long long items = passes == 1 ? 0ull : (unsigned long long)((nunits + 15u) & ~15u) * p->st.mk_item0[MK_KINDS];
-            if (items) {
-                const dim3 egrid((unsigned)((items * 4 + QUAD_BLOCK - 1) / QUAD_BLOCK));
-                launch_merkle_bn_emit(A, egrid, cstream);
-            }
-            H2W_HIP(hipEventRecord(ev[H2W_EV_CHAINS_END], cstream));
-        }
-        // 4. query glue strands (FriChip::verify_query_round minus its Merkle proofs): one lane per owned (proof, query);
-        //    Goldilocks-Poseidon Merkle strands (hash_mode 0), values: one cooperating wavefront per (proof, query, tree)
-        //    The two read the challenge blocks and write disjoint records (and list entries): with Goldilocks caps the Merkle strands run on the
-        //    plan's side stream beside the glue strands and rejoin before the permutations' records are emitted.
-        H2W_HIP(hipEventRecord(ev[H2W_EV_GLUE_START], stream));
-        if (p->shape.hash_mode == 0) {
-            if (cstream != stream) { H2W_HIP(hipStreamWaitEvent(cstream, ev[h2w_plan::EV_PROLOGUE_VALUES_END], 0)); forked = true; }
-            H2W_HIP(hipEventRecord(ev[H2W_EV_CHAINS_START], cstream));
-            if (nunits) launch_merkle_gl_values(A, nunits, nkinds, cstream);
-            H2W_HIP(hipEventRecord(ev[h2w_plan::EV_CHAIN_VALUES_END], cstream)); H2W_HIP(hipEventRecord(ev[H2W_EV_CHAINS_END], cstream));
-        }
-        if (nunits) launch_glue_strands(A, stream);
-        if (p->shape.hash_mode == 0) {
-            if (forked) { H2W_HIP(hipStreamWaitEvent(stream, ev[H2W_EV_CHAINS_END], 0)); forked = false; }
-            if (glp_emit(n_pro_perms + n_mk_perms) != 0) return -1;
-        }
-        H2W_HIP(hipEventRecord(ev[H2W_EV_GLUE_END], stream));
-        // 5. expansion of the block records (HBM-write-bound)
-        if (estream != stream) H2W_HIP(hipStreamWaitEvent(estream, ev[H2W_EV_GLUE_END], 0));    // value strands done -> expansion on the emit stream
-        // One expansion kernel at a time over all the streams a plan is driven on: its blocks are persistent and hold their CUs until the
-        // launch is written, so two of them side by side keep the latency-bound strands of the other launches in flight off the chip
-        // (measured: +8..12 % for the whole job with PoseidonBN254 caps, profiles/r02_sweep5.txt; +5 % with Goldilocks caps since that kernel
-        // runs on a grid of resident blocks there and reaches its rate alone, profiles/r02_expand_grid.txt).
-        if (p->serial_expand != 0 && prev_ev) H2W_HIP(hipStreamWaitEvent(estream, prev_ev[H2W_EV_EXPAND_END], 0));
-        H2W_HIP(hipEventRecord(ev[H2W_EV_EXPAND_START], estream));
-        if (launch_plan_expand(p, n_proofs, A.recs, (uint32_t *)(ws + wl.ctr), A.out, cell_stride, cm, &sh, plan_roam_per_cu(p), estream) != 0) return -1;
-        H2W_HIP(hipEventRecord(ev[H2W_EV_EXPAND_END], estream));
-        // 6. Montgomery form: the direct cells, behind the chain kernels on the stream they ran on, beside the expansion kernel (which converts its own cells
-        //    as it writes them).  The glue strands' and the prologue's direct cells were written on the caller's stream: the side stream waits for them.
-        const bool mont = p->output_form == H2W_FORM_MONTGOMERY;
-        if (mont) {
-            if (cstream != stream) { H2W_HIP(hipStreamWaitEvent(cstream, ev[H2W_EV_GLUE_END], 0)); forked = true; }
-            if (launch_plan_direct(p, p->d_direct_bits.get(), n_proofs, A.out, A.cell_stride, A.cm, sh, cstream) != 0) return -1;
-            if (cstream != stream) H2W_HIP(hipEventRecord(ev[h2w_plan::EV_DIRECT_END], cstream));
-        }
-        if (estream != stream) H2W_HIP(hipStreamWaitEvent(stream, ev[H2W_EV_EXPAND_END], 0));    // the caller's stream completes when the advice is complete
-        if (forked) { H2W_HIP(hipStreamWaitEvent(stream, ev[mont ? (int)h2w_plan::EV_DIRECT_END : (int)H2W_EV_CHAINS_END], 0)); forked = false; }
-        H2W_HIP(hipEventRecord(ev[H2W_EV_CALL_END], stream));
-        H2W_HIP(hipGetLastError());
-        return 0;
-    };
-    if (body() != 0) {
-        // a failed enqueue after the fork: the chain kernels may still be writing advice / workspace on the side stream and nothing orders the
-        // caller's stream behind them any more - wait for them here, so that the caller may release the buffers when it sees the error
-        if (forked) (void)hipStreamSynchronize(cstream);
-        return -1;
-    }
+    hipStream_t stream = (hipStream_t)stream_, cstream;      // cstream: the chain kernels' (more caller streams than side streams: the extra ones do not fork)
+    if (plan_side_stream(p, stream, p->fork_chains, &cstream) != 0) return -1;
+    WitnessCall c(p, proofs_dev, n_proofs, advice_dev, workspace_dev, stream, (hipStream_t)emit_stream_, cstream, cm, cell_stride, sh);
+    if (c.prologue()) return -1;
+    if (c.bn_chains()) return -1;
+    if (c.glue()) return -1;
+    if (c.expand()) return -1;
+    if (c.direct_cells()) return -1;
+    if (c.finish()) return -1;
     p->n_batches++; p->ev_recorded = true;
     return 0;
 }
@@ -384,11 +414,10 @@ extern "C" {
 
 uint64_t h2w_plan_workspace_bytes(const h2w_plan *p, uint64_t n_proofs) { return !p ? 0 : p->traced ? traced_workspace_bytes(p, n_proofs) : ws_layout(p, n_proofs).total; }
 uint64_t h2w_plan_shard_workspace_bytes(const h2w_plan *p, uint64_t n_proofs, int rank, int world) {
-    if (!p || world < 1 || rank < 0 || rank >= world) return 0;
+    if (!p || bad_shard(rank, world)) return 0;
     if (const char *why = traced_shard_refusal(p)) { set_error(std::string("h2w_plan_shard_workspace_bytes: ") + why); return 0; }
     if (p->traced) return traced_workspace_bytes(p, n_proofs);      // (value store and records per proof: the unsharded size)
-    ShardSpec sh; sh.rank = rank; sh.world = world;
-    return ws_layout(p, n_proofs, sh).total;
+    return ws_layout(p, n_proofs, shard_spec(rank, world)).total;
 }
 int h2w_fri_witness_batch(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void *advice_dev, void *workspace_dev, void *stream_) {
     return run_batch(p, proofs_dev, n_proofs, advice_dev, workspace_dev, stream_, stream_, flat_cols(), p ? p->ncells : 0, ShardSpec());
@@ -428,19 +457,18 @@ int h2w_fri_witness_batch_columns(h2w_plan *p, const uint64_t *proofs_dev, uint6
 // query blocks of the units (proof * num_queries + query) % world == rank (every rank runs every prologue's values: it needs the
 // challenges) - at their global offsets in advice_dev[n_proofs][num_cells]; the other blocks are left untouched.
 int h2w_fri_witness_batch_shard(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void *advice_dev, void *workspace_dev, void *stream_, int rank, int world) {
-    if (world < 1 || rank < 0 || rank >= world) { set_error("h2w_fri_witness_batch_shard: bad rank / world"); return -1; }
+    if (bad_shard(rank, world)) { set_error("h2w_fri_witness_batch_shard: bad rank / world"); return -1; }
     if (const char *why = p ? traced_shard_refusal(p) : nullptr) { set_error(std::string("h2w_fri_witness_batch_shard: ") + why); return -1; }
-    ShardSpec sh; sh.rank = rank; sh.world = world;
-    return run_batch(p, proofs_dev, n_proofs, advice_dev, workspace_dev, stream_, stream_, flat_cols(), p ? p->ncells : 0, sh);
+    return run_batch(p, proofs_dev, n_proofs, advice_dev, workspace_dev, stream_, stream_, flat_cols(), p ? p->ncells : 0, shard_spec(rank, world));
 }
 // The same blocks packed into a buffer of h2w_plan_shard_cells cells: the rank's owned blocks back to back in (proof, block) order.
 uint64_t h2w_plan_shard_cells(const h2w_plan *p, uint64_t n_proofs, int rank, int world) {
-    if (!p || world < 1 || rank < 0 || rank >= world) return 0;
+    if (!p || bad_shard(rank, world)) return 0;
     if (const char *why = traced_shard_refusal(p)) { set_error(std::string("h2w_plan_shard_cells: ") + why); return 0; }
     return own_count(n_proofs, rank, world) * p->st.pro_ncell + own_count(n_proofs * (uint64_t)p->shape.num_queries, rank, world) * shard_q_slot(p);
 }
 int h2w_plan_shard_block(const h2w_plan *p, int rank, int world, uint64_t proof, int query, uint64_t *local_cell, uint64_t *n_cells, uint64_t *global_cell) {
-    if (!p || world < 1 || rank < 0 || rank >= world || query >= p->shape.num_queries) { set_error("h2w_plan_shard_block: bad argument"); return -1; }
+    if (!p || bad_shard(rank, world) || query >= p->shape.num_queries) { set_error("h2w_plan_shard_block: bad argument"); return -1; }
     if (const char *why = traced_shard_refusal(p)) { set_error(std::string("h2w_plan_shard_block: ") + why); return -1; }
     const uint64_t W = (uint64_t)world, r = (uint64_t)rank, nq = (uint64_t)p->shape.num_queries;
     if (!shard_owns(W, r, nq, proof, query)) return 1;
@@ -451,11 +479,10 @@ int h2w_plan_shard_block(const h2w_plan *p, int rank, int world, uint64_t proof,
     return 0;
 }
 int h2w_fri_witness_batch_shard_compact(h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, void *shard_advice_dev, void *workspace_dev, void *stream_, int rank, int world) {
-    if (world < 1 || rank < 0 || rank >= world) { set_error("h2w_fri_witness_batch_shard_compact: bad rank / world"); return -1; }
+    if (bad_shard(rank, world)) { set_error("h2w_fri_witness_batch_shard_compact: bad rank / world"); return -1; }
     if (const char *why = p ? traced_shard_refusal(p) : nullptr) { set_error(std::string("h2w_fri_witness_batch_shard_compact: ") + why); return -1; }
     if (p && !(p->shape.lookup_bits == 21 || p->shape.lookup_bits == 13 || p->shape.lookup_bits == 8)) { set_error("h2w_fri_witness_batch_shard_compact: lookup_bits must be 21, 13 or 8 (the packed layout is written by expand_fast)"); return -1; }
-    ShardSpec sh; sh.rank = rank; sh.world = world; sh.compact = 1;
-    return run_batch(p, proofs_dev, n_proofs, shard_advice_dev, workspace_dev, stream_, stream_, flat_cols(), 0, sh);
+    return run_batch(p, proofs_dev, n_proofs, shard_advice_dev, workspace_dev, stream_, stream_, flat_cols(), 0, shard_spec(rank, world, 1));
 }
 // Re-expands the block records a previous h2w_fri_witness_batch* call left in `workspace_dev` (same n_proofs) into advice_dev: the
 // expansion kernel alone, for measuring its streaming rate (bench.py roofline).  Cells written by the value kernels are not touched.
@@ -466,10 +493,9 @@ int h2w_fri_expand_records(h2w_plan *p, uint64_t n_proofs, void *advice_dev, voi
     if (n_proofs == 0) return 0;
     DeviceGuard dg(p->device);
     hipStream_t stream = (hipStream_t)stream_;
-    const WsLayout wl = ws_layout(p, n_proofs);
-    char *ws = (char *)workspace_dev;
+    const WsPtrs wp = ws_ptrs(workspace_dev, ws_layout(p, n_proofs));
     const ShardSpec one_rank{};
-    if (launch_plan_expand(p, n_proofs, (rec_t *)(ws + wl.recs), (uint32_t *)(ws + wl.ctr), (fr_t *)advice_dev, p->ncells, flat_cols(), &one_rank, plan_roam_per_cu(p), stream) != 0) return -1;
+    if (launch_plan_expand(p, n_proofs, wp.recs, wp.ctr, (fr_t *)advice_dev, p->ncells, flat_cols(), &one_rank, plan_roam_per_cu(p), stream) != 0) return -1;
     H2W_HIP(hipGetLastError());
     return 0;
 }

@@ -52,9 +52,9 @@ struct h2w_plan {
 };
 extern "C" int h2w_plan_metadata(h2w_plan *pl);      // plancompile.cpp: the keygen-metadata replay, once per plan (the selector / lookup queries and advicetools.hip call it)
 namespace h2w {
-// The plan's side stream for the caller's stream `s` (batch.hip run_batch: the chain kernels; verdict.hip: the forked glue kernel - a witness call and a
-// forked verdict call on one caller stream share it, in order): slot k of side[] / side_of[], created when `s` is first seen.  -1: every side stream is
-// another caller stream's (the call does not fork); -2: the stream could not be created (the reason is in the last error).
+// The plan's side stream for the caller's stream `s` (batch.hip WitnessCall: the chain kernels; verdict.hip: the glue kernel of a H2W_VERDICT_FORK call - a
+// witness call and such a verdict call on one caller stream share it, in order): slot k of side[] / side_of[], created when `s` is first seen.  -1: every side
+// stream is another caller stream's (the call does not fork); -2: the stream could not be created (the reason is in the last error).
 inline int plan_side_slot(h2w_plan *p, hipStream_t s) {
     int k = 0; while (k < p->n_side && p->side_of[k] != s) k++;
     if (k < p->n_side) return k;
@@ -64,6 +64,31 @@ inline int plan_side_slot(h2w_plan *p, hipStream_t s) {
     p->side_of[k] = s; p->n_side++;
     return k;
 }
+// plan_side_slot's codes resolved for a call on `s` that asks for a fork or not: *side is the plan's side stream for `s`, or `s` itself where the call does not
+// fork (then *slot, where asked for, is -1).  -1: error.
+inline int plan_side_stream(h2w_plan *p, hipStream_t s, bool fork, hipStream_t *side, int *slot = nullptr) {
+    const int k = fork ? plan_side_slot(p, s) : -1;
+    if (k == -2) return -1;
+    *side = k >= 0 ? (hipStream_t)p->side[k] : s;
+    if (slot) *slot = k;
+    return 0;
+}
+// The owner of a call's fork onto that stream: `caller` the caller's stream, `side` the side stream (the same: the call does not fork), `open` while work
+// enqueued on `side` is not yet ordered in front of `caller`.  The events are the call's own and it records them itself, where its timing marks belong
+// (h2w_plan_timing*, h2w_plan_event_gap); the owner only waits.
+// A call that leaves with the fork open - an enqueue failed behind fork_at - has kernels on the side stream that may still read and write its buffers, and
+// nothing orders the caller's stream behind them any more: the destructor waits for them.  So the owner lives inside whatever releases the call's workspace,
+// and the caller sees the error, and may release its buffers, only after the wait.
+struct SideFork {
+    const hipStream_t caller, side; bool open = false;
+    SideFork(hipStream_t caller_, hipStream_t side_) : caller(caller_), side(side_) {}
+    SideFork(const SideFork &) = delete; SideFork &operator=(const SideFork &) = delete;
+    ~SideFork() { if (open) (void)hipStreamSynchronize(side); }
+    // `side` waits for `e`, which the call has recorded on `caller`; nothing to do for a call that does not fork
+    int fork_at(hipEvent_t e) { if (side == caller) return 0; H2W_HIP(hipStreamWaitEvent(side, e, 0)); open = true; return 0; }
+    // `caller` waits for `e`, which the call has recorded on `side`; nothing to do where no fork is open
+    int join_at(hipEvent_t e) { if (!open) return 0; H2W_HIP(hipStreamWaitEvent(caller, e, 0)); open = false; return 0; }
+};
 // The plan's part of a call's kernel arguments (batch.hip run_batch, verdict.hip verdict_call): the shape, its device tables, the proofs.  What belongs to
 // the call - workspace pointers, the output buffer and its stride, cm, sh - is value-initialised here and the caller's to set.
 inline BatchArgs plan_batch_args(const h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs) {

@@ -196,6 +196,37 @@ static unsigned verdict_form_of(const h2w_plan *p, uint64_t n_proofs) {
     return per_proof == 0 || n_proofs <= VERDICT_ROW_MAX_PATHS / per_proof ? H2W_VERDICT_FORM_ROW : H2W_VERDICT_FORM_QUAD;
 }
 
+// The launches of a verdict call on its arguments V (workspace pointers set).  gstream: the glue kernel's stream - the caller's, or the plan's side stream
+// with `vev`, that side stream's two events (null: the call does not fork).  The SideFork lives in here, inside verdict_call's release of the workspace.
+static int verdict_enqueue(const h2w_plan *p, VerdictArgs &V, uint64_t n_proofs, hipStream_t stream, hipStream_t gstream, const DevEvent *vev, unsigned form) {
+    BatchArgs &A = V.A;
+    SideFork fork(stream, gstream);
+    H2W_HIP(hipMemsetAsync(V.lflag, 0, n_proofs * sizeof(uint32_t), stream));
+    // the prologue on values: a world in which this rank owns no proof's block (own_prologue: p % world == rank never holds below 2^30 proofs)
+    A.sh.world = 0x40000000; A.sh.rank = 0x3fffffff;
+    launch_prologue_values(A, stream);
+    // every (proof, query) unit is this call's
+    A.sh.world = 1; A.sh.rank = 0; A.sh.n_own_units = (uint32_t)(n_proofs * (uint64_t)p->shape.num_queries); A.sh.n_own_proofs = (uint32_t)n_proofs;
+    const unsigned pgrid = (unsigned)((n_proofs + 255) / 256), nunits = A.sh.n_own_units, nkinds = (unsigned)(p->d.n_oracles + p->d.n_steps);
+    hipLaunchKernelGGL(k_verdict_init, dim3(pgrid), dim3(256), 0, stream, V);
+    if (p->n_items) hipLaunchKernelGGL(k_verdict_check, dim3((unsigned)((n_proofs * p->n_items + 255) / 256)), dim3(256), 0, stream, V);
+    // the glue kernel and the Merkle kernel read the challenge blocks and meet in the verdict words' atomics alone: with H2W_VERDICT_FORK the glue kernel runs on
+    // the plan's side stream beside the Merkle kernel and the caller's stream waits for it before k_verdict_finish and before the workspace is released
+    if (vev) {
+        H2W_HIP(hipEventRecord(vev[0], stream));
+        if (fork.fork_at(vev[0]) != 0) return -1;
+    }
+    hipLaunchKernelGGL(k_verdict_glue, dim3((nunits + 63) / 64), dim3(64), 0, gstream, V);
+    if (vev) H2W_HIP(hipEventRecord(vev[1], gstream));
+    if (p->shape.hash_mode == 0) hipLaunchKernelGGL(k_verdict_merkle_gl, dim3(nunits, nkinds), dim3(64), 0, stream, V);
+    else if (form == H2W_VERDICT_FORM_ROW) hipLaunchKernelGGL(k_verdict_merkle_row, dim3((nunits + QUAD_WAVES - 1) / QUAD_WAVES, nkinds), dim3(QUAD_BLOCK), 0, stream, V);
+    else hipLaunchKernelGGL(k_verdict_merkle_bn, dim3((nunits * 4 + QUAD_BLOCK - 1) / QUAD_BLOCK, nkinds), dim3(QUAD_BLOCK), 0, stream, V);
+    if (vev && fork.join_at(vev[1]) != 0) return -1;
+    hipLaunchKernelGGL(k_verdict_finish, dim3(pgrid), dim3(256), 0, stream, V);
+    H2W_HIP(hipGetLastError());
+    return 0;
+}
+
 // the checks both entry points share, in h2w_fri_verdict_batch's order, and the call itself.  form: H2W_VERDICT_FORM_QUAD or _ROW
 static int verdict_call(const char *who, h2w_plan *p, const uint64_t *proofs_dev, uint64_t n_proofs, h2w_verdict_t *verdict_dev, void *stream_, unsigned form, bool fork) {
     const std::string w(who);
@@ -205,55 +236,19 @@ static int verdict_call(const char *who, h2w_plan *p, const uint64_t *proofs_dev
     const uint64_t nq = (uint64_t)p->shape.num_queries;
     if (n_proofs > 0x3fffffffull / (4 * nq)) { set_error(w + ": batch too large; split the batch"); return -1; }
     DeviceGuard dg(p->device);
-    hipStream_t stream = (hipStream_t)stream_, gstream = stream;      // gstream: the glue kernel's
-    int slot = -1;
-    if (fork) {
-        slot = plan_side_slot(p, stream);      // (-1: every side stream is another caller stream's - this one does not fork)
-        if (slot == -2) return -1;
-        if (slot >= 0) {
-            for (DevEvent &e : p->vev[slot]) if (!(hipEvent_t)e && e.create() != 0) return -1;
-            gstream = p->side[slot];
-        }
-    }
+    hipStream_t stream = (hipStream_t)stream_, gstream;      // gstream: the glue kernel's
+    int slot;      // (-1: no fork asked for, or every side stream is another caller stream's - this call does not fork)
+    if (plan_side_stream(p, stream, fork, &gstream, &slot) != 0) return -1;
+    if (slot >= 0) for (DevEvent &e : p->vev[slot]) if (!(hipEvent_t)e && e.create() != 0) return -1;
     // the call's workspace: challenge blocks, the prologue's status words, the range flags
     const size_t o_status = align_up((size_t)n_proofs * sizeof(DevCB), 256), o_lflag = o_status + align_up((size_t)n_proofs * sizeof(uint32_t), 256), total = o_lflag + align_up((size_t)n_proofs * sizeof(uint32_t), 256);
     char *ws = nullptr;
     H2W_HIP(hipMallocAsync((void **)&ws, total, stream));
-    bool forked = false;
-    auto run = [&]() -> int {
-        VerdictArgs V; BatchArgs &A = V.A;
-        A = plan_batch_args(p, proofs_dev, n_proofs);      // (no records, no advice, no unit buffers, no permutation list: those stay null)
-        A.cm = flat_cols(); A.cbs = (DevCB *)ws; A.status = (uint32_t *)(ws + o_status); A.load_flag = (uint32_t *)(ws + o_lflag);
-        V.verdict = verdict_dev; V.lflag = A.load_flag;
-        H2W_HIP(hipMemsetAsync(V.lflag, 0, n_proofs * sizeof(uint32_t), stream));
-        // the prologue on values: a world in which this rank owns no proof's block (own_prologue: p % world == rank never holds below 2^30 proofs)
-        A.sh.world = 0x40000000; A.sh.rank = 0x3fffffff;
-        launch_prologue_values(A, stream);
-        // every (proof, query) unit is this call's
-        A.sh.world = 1; A.sh.rank = 0; A.sh.n_own_units = (uint32_t)(n_proofs * nq); A.sh.n_own_proofs = (uint32_t)n_proofs;
-        const unsigned pgrid = (unsigned)((n_proofs + 255) / 256), nunits = A.sh.n_own_units, nkinds = (unsigned)(p->d.n_oracles + p->d.n_steps);
-        hipLaunchKernelGGL(k_verdict_init, dim3(pgrid), dim3(256), 0, stream, V);
-        if (p->n_items) hipLaunchKernelGGL(k_verdict_check, dim3((unsigned)((n_proofs * p->n_items + 255) / 256)), dim3(256), 0, stream, V);
-        // the glue kernel and the Merkle kernel read the challenge blocks and meet in the verdict words' atomics alone: forked, the glue kernel runs on the
-        // plan's side stream beside the Merkle kernel and the caller's stream waits for it before k_verdict_finish and before the workspace is released
-        if (gstream != stream) {
-            H2W_HIP(hipEventRecord(p->vev[slot][0], stream));
-            H2W_HIP(hipStreamWaitEvent(gstream, p->vev[slot][0], 0)); forked = true;
-        }
-        hipLaunchKernelGGL(k_verdict_glue, dim3((nunits + 63) / 64), dim3(64), 0, gstream, V);
-        if (forked) H2W_HIP(hipEventRecord(p->vev[slot][1], gstream));
-        if (p->shape.hash_mode == 0) hipLaunchKernelGGL(k_verdict_merkle_gl, dim3(nunits, nkinds), dim3(64), 0, stream, V);
-        else if (form == H2W_VERDICT_FORM_ROW) hipLaunchKernelGGL(k_verdict_merkle_row, dim3((nunits + QUAD_WAVES - 1) / QUAD_WAVES, nkinds), dim3(QUAD_BLOCK), 0, stream, V);
-        else hipLaunchKernelGGL(k_verdict_merkle_bn, dim3((nunits * 4 + QUAD_BLOCK - 1) / QUAD_BLOCK, nkinds), dim3(QUAD_BLOCK), 0, stream, V);
-        if (forked) { H2W_HIP(hipStreamWaitEvent(stream, p->vev[slot][1], 0)); forked = false; }
-        hipLaunchKernelGGL(k_verdict_finish, dim3(pgrid), dim3(256), 0, stream, V);
-        H2W_HIP(hipGetLastError());
-        return 0;
-    };
-    const int rc = run();
-    // a failed enqueue after the fork: the glue kernel may still read the workspace on the side stream and nothing orders the caller's stream behind it
-    // any more - wait for it here (as h2w_fri_witness_batch does), before the workspace is released and the caller sees the error
-    if (forked) (void)hipStreamSynchronize(gstream);
+    VerdictArgs V; BatchArgs &A = V.A;
+    A = plan_batch_args(p, proofs_dev, n_proofs);      // (no records, no advice, no unit buffers, no permutation list: those stay null)
+    A.cm = flat_cols(); A.cbs = (DevCB *)ws; A.status = (uint32_t *)(ws + o_status); A.load_flag = (uint32_t *)(ws + o_lflag);
+    V.verdict = verdict_dev; V.lflag = A.load_flag;
+    const int rc = verdict_enqueue(p, V, n_proofs, stream, gstream, slot >= 0 ? p->vev[slot] : nullptr, form);      // (failed behind its fork: it has waited for the side stream)
     (void)hipFreeAsync(ws, stream);
     return rc;
 }

@@ -9,6 +9,7 @@ First the harness on stand-ins of torch ops (it reports each fault class under t
    h2w_chipbatch_values                                                        in, out, no sync
    h2w_chipbatch_run (field op, hash op with three internal launches)          in, out; blocked printed (the header is silent)
    h2w_fri_witness_batch / _batch2 under the scheduling options                in, out (advice, status words), no sync ("returns after enqueueing")
+   h2w_fri_witness_batch_shard, one rank of two                                in, out (its blocks; sentinels elsewhere), no sync
    h2w_fri_verdict_batch / _ex in every form, forked and not                   in, out, no sync
    a traced plan's witness call, then h2w_trace_verdict_batch                  in, out; the verdict call: no sync
    witness -> h2w_advice_digest -> h2w_advice_to_montgomery                    in, out
@@ -414,13 +415,20 @@ def _montgomery_of(h2w, stream_words):
     return out
 
 
-# (fork chains, an emit stream, Montgomery form, chain passes - a PoseidonBN254 option; 0: the library's choice, two for a launch this small)
+# (fork chains, an emit stream, Montgomery form, chain passes and values form - PoseidonBN254 options; 0: the library's choice, two passes and one wavefront
+# per path for a launch this small).  Montgomery form without an emit stream: the direct cells run on the caller's stream (fork 0) or on the side stream,
+# and with Goldilocks caps and fork 1 the fork is closed behind the glue strands and opened again for them.
 WITNESS_CONFIGS = [(0, False, False, 0), (1, False, False, 0), (0, True, False, 0), (1, True, False, 0), (1, True, True, 0)]
-WITNESS_CASES = [(m,) + c for m in (0, 1) for c in WITNESS_CONFIGS] + [(1, 1, False, False, 1), (1, 1, False, False, 2)]
+WITNESS_CASES = [(m,) + c + (0,) for m in (0, 1) for c in WITNESS_CONFIGS] + [(1, 1, False, False, 1, 0), (1, 1, False, False, 2, 0)]
+WITNESS_CASES += [(m, fork, False, True, 0, 0) for m in (0, 1) for fork in (1, 0)] + [(1, 1, False, False, 2, 1), (1, 1, False, False, 2, 2)]
 
 
-@pytest.mark.parametrize("mode,fork,emit,mont,passes", WITNESS_CASES)
-def test_witness_batch(h2w, h2w_api, oracle, consts, mode, fork, emit, mont, passes):
+def _witness_id(case):
+    return "-".join(str(x) for x in case[:5]) + (f"-form{case[5]}" if case[5] else "")
+
+
+@pytest.mark.parametrize("mode,fork,emit,mont,passes,form", WITNESS_CASES, ids=[_witness_id(c) for c in WITNESS_CASES])
+def test_witness_batch(h2w, h2w_api, oracle, consts, mode, fork, emit, mont, passes, form):
     """fibonacci_shape(8, 3, rate_bits=1, cap_height=2), two proofs: every launch of the call - prologue, load, permutation records, Merkle chains or
     strands (forked to the plan's side stream or not), glue, expansion (on an emit stream or not), the direct cells' conversion."""
     import torch
@@ -430,6 +438,8 @@ def test_witness_batch(h2w, h2w_api, oracle, consts, mode, fork, emit, mont, pas
     plan.configure(h2w_api.OPT_FORK_CHAINS, fork)
     if passes:
         plan.configure(h2w_api.OPT_CHAIN_PASSES, passes)
+    if form:
+        plan.configure(h2w_api.OPT_VALUES_FORM, form)
     if mont:
         plan.set_output_form(h2w_api.FORM_MONTGOMERY)
         want = _montgomery_of(h2w, want)
@@ -442,9 +452,38 @@ def test_witness_batch(h2w, h2w_api, oracle, consts, mode, fork, emit, mont, pas
     assert plan.status(ws.data_ptr(), n) == status_b
     info = {}
     (adv, wsn), blocked = SO.run_ordered(call, [(d_proofs, p_a, p_b)], [advice, (ws, 0)], expect_no_sync=True, info=info)
-    _report(f"h2w_fri_witness_batch{'2' if emit else ''} mode {mode} fork {fork} montgomery {mont} passes {passes}", info)
+    _report(f"h2w_fri_witness_batch{'2' if emit else ''} mode {mode} fork {fork} montgomery {mont} passes {passes} values form {form}", info)
     assert _status_of(plan, wsn, n) == [0] * n
     _same(adv.view(np.uint64), want, "advice")
+    plan.close()
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+def test_witness_batch_shard(h2w, h2w_api, oracle, consts, mode):
+    """h2w_fri_witness_batch_shard as rank 1 of 2 with FORK_CHAINS 1, the same shape and proofs: the rank launches three of the six (proof, query) units
+    and proof 1's prologue.  Its blocks hold the oracle's words for A; every other word of the buffer is still the sentinel."""
+    n, rank, world = 2, 1, 2
+    sh, osh, pa, pb, want, status_b = _witness_case(h2w, oracle, consts, mode, n)
+    plan = h2w_api.Plan(sh, consts[1])
+    plan.configure(h2w_api.OPT_FORK_CHAINS, 1)
+    blocks = [(p_, plan.shard_block(rank, world, p_, q)) for p_ in range(n) for q in range(-1, sh.num_queries)]
+    own = [(p_, b) for p_, b in blocks if b is not None]
+    assert len(own) == 4 and [p_ for p_, b in own if b[2] == 0] == [1]      # (three units of proofs x queries = 6, and the prologue of proof 1)
+    expect = np.full(n * plan.num_cells * 4, SENT64, dtype=np.uint64)
+    for p_, (_, cnt, g) in own:
+        lo = 4 * (p_ * plan.num_cells + g)
+        expect[lo:lo + 4 * cnt] = want[lo:lo + 4 * cnt]
+    p_a, p_b = _dev_u64(pa), _dev_u64(pb)
+    d_proofs = p_b.clone()
+    advice = _out(n * plan.num_cells * 32, "uint8"); ws = _out(plan.shard_workspace_bytes(n, rank, world), "uint8")
+    call = lambda s: plan.run_shard(d_proofs.data_ptr(), n, advice.data_ptr(), ws.data_ptr(), rank, world, s)
+    SO.timed_warm_up(call)
+    assert plan.status(ws.data_ptr(), n) == status_b      # (every rank checks every proof's words)
+    info = {}
+    (adv, wsn), blocked = SO.run_ordered(call, [(d_proofs, p_a, p_b)], [advice, (ws, 0)], expect_no_sync=True, info=info)
+    _report(f"h2w_fri_witness_batch_shard mode {mode} rank {rank} of {world}", info)
+    assert _status_of(plan, wsn, n) == [0] * n
+    _same(adv.view(np.uint64), expect, "advice: this rank's blocks, sentinels elsewhere")
     plan.close()
 
 
